@@ -20,10 +20,19 @@ every rank) three times — (A) ground-truth flat shard + k-means sample, (B) ne
 round-robin to the ranks, labels summed over RCCL), (C) list fill (every rank keeps the rows of the lists it owns).
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the list scan, timed with HIP events
-on its launch stream inside the library) and `cpu_baseline` (kind "reference": the reference's OWN IVFSearcher /
-FlatSearcher — oracle/_ref/libzvec_ref_core.so, its core library compiled in place — on the host cores, same index /
-queries; N=1 only; kind "port" = the oracle's restated loops when that library did not travel).  oracle/ is used ONLY
-for that baseline and the parity cross-check — never on the timed GPU path.
+on its launch stream inside the library).  A plain run does only what that line needs: set up (corpus, index, and for
+IVF the ground truth and recall sweep that choose the timed nprobe), warm up, time the K steps, print.
+
+--full adds every other measurement, each outside the timed region: `cpu_baseline` (kind "reference": the reference's
+OWN IVFSearcher / FlatSearcher — oracle/_ref/libzvec_ref_core.so, its core library compiled in place — on the host
+cores, same index / queries; N=1 only; kind "port" = the oracle's restated loops when that library is absent), the
+host-pointer entry (`host_pointer_qps`), the half-width pre-selection (`certified_half_scan`), the QPS at the BASELINE
+nprobe when the recall sweep widened it, and the box calibration (`roofline.box_*`).  oracle/ is used ONLY for that
+baseline and the parity cross-check — never on the timed GPU path.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (top-k keys, scores, valid counts) as
+DIR/keys.npy (float64), DIR/scores.npy (float32) and DIR/counts.npy (float64).  The corpus and queries are seeded, so the
+same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -112,6 +121,11 @@ def parse_args():
     ap.add_argument("--cpu-port", action="store_true", help="time the oracle's restated loops (kind \"port\") even when the reference's own classes are available")
     ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive host-pointer measurement")
     ap.add_argument("--cpu-queries", type=int, default=0, help="0 = one whole batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the host-pointer entry, the half-width "
+                         "pre-selection leg, the QPS at the BASELINE nprobe and the box calibration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the keys / scores / counts of the last timed step as DIR/<name>.npy (float64 / float32)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, form the process group (backend: $ZVEC_BENCH_BACKEND, default nccl = RCCL), "
                          "all-gather the rank ids and print the JSON line; no GPU work (the CPU test of the launcher path)")
@@ -297,7 +311,7 @@ def main():
         lo, hi = flat_row_range(n, rank, world)
         flat = zvec_amd.HipFlatSearcher(dim, flat_metric, device=local_rank, dtype=dtype)
         base = None
-        keep_base = world == 1 and n <= 2_000_000 and not args.no_cpu_baseline
+        keep_base = args.full and world == 1 and n <= 2_000_000 and not args.no_cpu_baseline
         parts = []
         for o, x in corpus_chunks(torch, n, dim, dev, SEED, proj, tdtype):
             a, b = max(o, lo), min(o + x.shape[0], hi)
@@ -437,7 +451,7 @@ def main():
                 scanned.mean(), 100.0 * scanned.mean() / n, probes.mean()))
 
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             gk, gs, gc = sh.search(q, topk, nprobe, max_scan, stream_ptr)
             torch.cuda.synchronize()
             cpu = cpu_baseline_ivf(torch, ivf, q, topk, nprobe, max_scan, args, dtype,
@@ -465,12 +479,12 @@ def main():
             sh_i, sp, ts = lanes[i % len(lanes)]
             qi = qpool[i % qpool_n]
             if ts is None:
-                sh_i.search(qi, topk, np_, max_scan, sp)
-            else:
-                with torch.cuda.stream(ts):
-                    sh_i.search(qi, topk, np_, max_scan, sp)
+                return sh_i.search(qi, topk, np_, max_scan, sp)
+            with torch.cuda.stream(ts):
+                return sh_i.search(qi, topk, np_, max_scan, sp)
 
         host_issue = [0.0]
+        last_out = [None]       # what the last timed step returned (the lane's result buffers: read before that lane searches again)
 
         def timed(np_, steps, warmup):
             for i in range(warmup * len(lanes)):
@@ -488,8 +502,9 @@ def main():
             torch.cuda.synchronize()
             t_start = time.perf_counter()
             for i in range(steps):
-                run_step(i, np_)
+                out = run_step(i, np_)
             host_issue[0] = (time.perf_counter() - t_start) / steps * 1e3      # ms of host time to ISSUE one step
+            last_out[0] = out
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -508,16 +523,18 @@ def main():
                 pr["per_lane_ms"].append(p1["scan_ms"] / max(p1["launches"], 1))
             return el, pr
         elapsed, prof = timed(nprobe, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, *last_out[0])
         extra_cfg["host_issue_ms_per_step"] = host_issue[0]
         qps_base = None
-        if nprobe != nprobe_base:      # the BASELINE nprobe as well (outside the reported region)
+        if args.full and nprobe != nprobe_base:      # the BASELINE nprobe as well (outside the reported region)
             el32, _ = timed(nprobe_base, max(3, min(args.steps, 10)), 1)
             qps_base = batch * max(3, min(args.steps, 10)) / el32
         # the boundary's HOST-pointer entry (what IndexRunner::search_impl hands over: queries in host memory, results
         # back into host buffers) on the same batch: H2D of the queries + D2H of the lists per call.  Reported next to
         # `value`, never as it.
         host_qps = None
-        if world == 1 and not args.no_host_path:
+        if args.full and world == 1 and not args.no_host_path:
             hctx = ivf.create_context()
             qhs = [np.ascontiguousarray(x.cpu().numpy()) for x in qpool]      # (small batches: a different batch every call)
             hcall = [0]
@@ -545,7 +562,7 @@ def main():
         # fp32 rows, the k best are CERTIFIED against the measured rounding, uncertified queries are re-run on the fp32 lists —
         # inside the timed region.  Same answer, about half the bytes.  Reported as `certified_half_scan`, never as `value`.)
         shadow_leg = None
-        if dtype == "fp32" and world == 1 and batch > 8 and not args.no_shadow_leg:
+        if args.full and dtype == "fp32" and world == 1 and batch > 8 and not args.no_shadow_leg:
             try:
                 # the fp32 route's answers on every batch of the pool first (the parity reference of this leg)
                 ref32 = []
@@ -678,7 +695,7 @@ def main():
             # duration in a kernel trace — includes that wait; the step time is then the honest per-launch figure: it cannot understate)
             frac_ms, frac_basis = ms_per_step, "ms_per_step (overlapping lanes: kernel_ms > ms_per_step, see kernel_ms_per_lane)"
         achieved = bytes_per_launch / (frac_ms * 1e-3) / 1e9 if frac_ms > 0 else 0.0
-        box = box_calibration(zvec_amd, local_rank)
+        box = box_calibration(zvec_amd, local_rank) if args.full else {}
         result = {
             "value": batch * args.steps / elapsed,
             "ms_per_step": ms_per_step,
@@ -738,6 +755,29 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, keys, scores, counts):
+    """--dump-outputs: the last timed step's results as the caller receives them, written as DIR/keys.npy (float64: row ids are
+    exact), DIR/scores.npy (float32) and DIR/counts.npy (float64).  A batch whose dump would pass 64 MB is cut to a fixed, seeded
+    sample of its queries, and the sampled query rows go to DIR/query_rows.npy."""
+    k, s, c = keys.cpu().numpy(), scores.cpu().numpy(), counts.cpu().numpy()
+    per_query = k.shape[1] * 8 + s.shape[1] * 4 + 8
+    rows = None
+    budget = DUMP_BYTES_MAX - 4096          # (room for the four .npy headers)
+    if k.shape[0] * per_query > budget:
+        rows = np.sort(np.random.default_rng(SEED).choice(k.shape[0], budget // (per_query + 8), replace=False))
+        k, s, c = k[rows], s[rows], c[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "keys.npy"), k.astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), s.astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), c.astype(np.float64))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    log("outputs of the last timed step (%d queries x k=%d) written to %s" % (k.shape[0], k.shape[1], out_dir))
 
 
 def committed_traffic(args, world, shard_mode):
@@ -892,7 +932,7 @@ def run_flat(torch, dist, zvec_amd, sharded, flat, fctx, q, n, n_local, dim, top
             return sh_i.search(q, topk, sp, d_exclude=excl.data_ptr() if excl is not None else None, threshold=thr)
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and doc_filter is None and base is not None:
+    if args.full and not args.no_cpu_baseline and world == 1 and doc_filter is None and base is not None:
         ok, os_, oc = step()
         torch.cuda.synchronize()
         cpu = cpu_baseline_flat(torch, base, q, topk, metric_name, args, gpu=(ok.cpu().numpy(), os_.cpu().numpy(), oc.cpu().numpy()))
@@ -910,12 +950,14 @@ def run_flat(torch, dist, zvec_amd, sharded, flat, fctx, q, n, n_local, dim, top
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # (the lane's result buffers: read before that lane searches again)
+        dump_outputs(args.dump_outputs, *out)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         coll(dist.all_reduce, t, op=dist.ReduceOp.MAX)
@@ -941,7 +983,7 @@ def run_flat(torch, dist, zvec_amd, sharded, flat, fctx, q, n, n_local, dim, top
     f16 = args.workload.endswith("fp16")
     small = batch <= 16         # a handful of queries: the scan streams the base once => HBM-bound
     peak = MFMA_F16_PEAK_TF if f16 else MFMA_F32_PEAK_TF
-    box = box_calibration(zvec_amd, torch.cuda.current_device())
+    box = box_calibration(zvec_amd, torch.cuda.current_device()) if args.full else {}
     # which wide kernel the dispatch takes (api_flat_scan.inc.h: fp16 rows, >= 256 queries, k <= 11, unfiltered, option scan256 on)
     import ctypes as C
     opt256 = C.c_int(0)
@@ -960,7 +1002,7 @@ def run_flat(torch, dist, zvec_amd, sharded, flat, fctx, q, n, n_local, dim, top
                      "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "mfma_tflops": tf})
     # ---------------- second measurement: the same steps through the half-width pre-selection (zvec_hip_flat_set_shadow) ----------------
     shadow_leg = None
-    if not f16 and world == 1 and thr is None and not args.no_shadow_leg:
+    if args.full and not f16 and world == 1 and thr is None and not args.no_shadow_leg:
         try:
             ex_ptr = excl.data_ptr() if excl is not None else None      # (filter workloads: the exclude set every step materialises)
             if doc_filter is not None:

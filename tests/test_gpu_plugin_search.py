@@ -3,7 +3,7 @@
 oracle/_ref/libzvec_ref_core.so   = the reference's whole core library compiled in place (oracle/Makefile `ref_core`; incl.
                                     ailego::BufferHandle from its own buffer_manager.cc against the image's real Arrow —
                                     nothing stubbed) + the by-name driver oracle/ref_core_shim.cc
-plugin/build/libzvec_hip_plugin.so = plugin/hip_plugin.cc + hip_ivf_builder.cc linked to it and to zvec_amd/libzvec_hip.so,
+oracle/_ref/libzvec_hip_plugin.so = plugin/hip_plugin.cc + hip_ivf_builder.cc linked to it and to zvec_amd/libzvec_hip.so,
                                     brought in through the reference's IndexPluginBroker::emplace (dlopen + static registrars)
 Every case opens the SAME index file with the reference's class ("FlatSearcher", "IVFSearcher", "IVFStreamer", "FlatStreamer")
 and with the plugin's ("HipFlatSearcher", "HipIVFSearcher", "HipIVFStreamer", "HipFlatStreamer") created by their registered names

@@ -10,7 +10,7 @@ O=$R/gpurun_out/profiles_new
 mkdir -p $O
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/sht_$c
-  timeout -k 10 280 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/sht_$c -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-host-path --streams 1 > $O/sht_$c.json 2> $O/sht_$c.log || exit 1
+  timeout -k 10 280 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/sht_$c -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-host-path --streams 1 > $O/sht_$c.json 2> $O/sht_$c.log || exit 1
 done
 python3 - <<PY
 import csv, glob, json

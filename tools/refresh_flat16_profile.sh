@@ -16,11 +16,11 @@ O=$R/gpurun_out/profiles_new
 mkdir -p $O
 for b in 256 1024; do
   v=""; [ $b != 256 ] && v="_b$b"
-  python3 $R/bench.py --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline > $O/${tag}_flat1m_fp16${v}_bench.json 2> $O/f16$v.log
-  python3 $R/bench.py --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_streams1_bench.json 2>> $O/f16$v.log
-  ZVEC_HIP_SCAN256=0 python3 $R/bench.py --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_scan8_bench.json 2>> $O/f16$v.log
+  python3 $R/bench.py --full --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline > $O/${tag}_flat1m_fp16${v}_bench.json 2> $O/f16$v.log
+  python3 $R/bench.py --full --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_streams1_bench.json 2>> $O/f16$v.log
+  ZVEC_HIP_SCAN256=0 python3 $R/bench.py --full --workload flat1m_fp16 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_scan8_bench.json 2>> $O/f16$v.log
   rm -rf $O/f16prof
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/f16prof -- python3 $R/bench.py --workload flat1m_fp16 --batch $b --steps 10 --warmup 2 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_bench_under_rocprof.json 2>> $O/f16$v.log
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/f16prof -- python3 $R/bench.py --full --workload flat1m_fp16 --batch $b --steps 10 --warmup 2 --no-cpu-baseline --streams 1 > $O/${tag}_flat1m_fp16${v}_bench_under_rocprof.json 2>> $O/f16$v.log
   python3 - <<PY
 import csv, glob, shutil
 O, tag, v = "$O", "$tag", "$v"

@@ -12,7 +12,7 @@ mkdir -p $O && rm -rf $O/stats
 for v in "" "_streams1"; do
   extra=""; [ -n "$v" ] && extra="--streams 1"
   rm -rf $O/stats
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline $extra > $O/${tag}_ivf10m${v}_bench_under_rocprof.json 2> $O/stats$v.log
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $extra > $O/${tag}_ivf10m${v}_bench_under_rocprof.json 2> $O/stats$v.log
   python3 - <<PY
 import csv, glob, shutil
 O, tag, v = "$O", "$tag", "$v"
