@@ -370,12 +370,14 @@ int flat_dense_scores(zvec_hip_ctx_s *ctx, const Store &st, uint32_t q0, uint32_
   return 0;
 }
 
-// `user_facing`: a search whose lists go back to the caller (profiled, L2-refined); false for the IVF
-// coarse pass and the k-means labelling, which only need the ranking
+// Who reads a scan's lists: `user` a search whose lists go back to the caller (profiled, gated, L2-refined); `shadow` the scan over
+// an index's twin (the search's dominant scan: profiled and gated like a user-facing one, its lists are re-scored instead of refined);
+// `internal` the IVF coarse pass, the k-means labelling and the seeding pre-pass, which only need the ranking
+enum class ScanRole { internal, shadow, user };
+
 int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uint32_t topk, float threshold,
-                       const uint64_t *d_exclude, const SearchOut &out_in, hipStream_t stream, bool user_facing) {
-  const bool profile_it = user_facing || ctx->shadow_scan;      // (the scan over a shadow store IS the search's dominant scan)
-  ctx->shadow_scan = false;                                     // (... its nested seeding pre-pass is not)
+                       const uint64_t *d_exclude, const SearchOut &out_in, hipStream_t stream, ScanRole role) {
+  const bool user_facing = role == ScanRole::user, profile_it = role != ScanRole::internal;
   SearchOut out = out_in;
   if (user_facing && st.metric == ZVEC_HIP_METRIC_L2 && out.idx == nullptr) {
     ZRET(ctx->ridx.ensure((size_t)count * topk * sizeof(uint32_t)));
@@ -436,7 +438,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
       tmp.base = ctx->cmp_base.as<float>(); tmp.bnorm = ctx->cmp_norm.as<float>();
       tmp.extra = st.extra ? ctx->cmp_extra.as<float>() : nullptr; tmp.keys = ctx->cmp_keys.as<uint64_t>();
       tmp.n = kept; tmp.cap_tiles = ktiles;
-      int rc = flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, user_facing);
+      int rc = flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, role);
       tmp.base = nullptr; tmp.bnorm = nullptr; tmp.extra = nullptr; tmp.keys = nullptr;   // the view owns nothing
       return rc;
     }
@@ -517,7 +519,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
       ZCHK(hipGetLastError());
     } else {
       SearchOut so{ctx->seed_keys.as<uint64_t>(), ctx->seed_scores.as<float>(), ctx->seed_idx.as<uint32_t>(), ctx->seed_counts.as<uint32_t>()};
-      rc = flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, false);
+      rc = flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal);
       view.base = nullptr; view.bnorm = nullptr; view.extra = nullptr; view.keys = nullptr;   // the view owns nothing
       ZRET(rc);
       hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
@@ -634,6 +636,124 @@ int prep_queries(zvec_hip_ctx_s *ctx, const Store &st, const void *d_queries, ui
   return 0;
 }
 
+// ---- half-width pre-selection (zvk_shadow.hip.h): the steps the flat and the IVF search share ----------------------------------
+
+// the fp16 query rows of a search through `twin` and their rounding facts (ctx->sh.q16 / qn16 / qinfo)
+int shadow_prep_queries(zvec_hip_ctx_s *ctx, const Store &twin, const void *d_queries, uint32_t count, hipStream_t stream) {
+  ShadowScratch &sh = ctx->sh;
+  ZRET(sh.q16.ensure((size_t)count * twin.dpad * sizeof(float)));
+  ZRET(sh.qn16.ensure((size_t)count * sizeof(float)));
+  ZRET(sh.qinfo.ensure((size_t)count * sizeof(f32x2)));
+  hipLaunchKernelGGL(shadow_prep_queries_kernel, dim3((count + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const float *>(d_queries),
+                     count, twin.dim_in, twin.dscan, twin.dpad, sh.q16.as<float>(), sh.qn16.as<float>(), sh.qinfo.as<f32x2>());
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+// where the k' pre-selected rows of every query go (the output of the flat scan over the twin, of the IVF merge), sized for this search
+int shadow_lists(zvec_hip_ctx_s *ctx, uint32_t count, uint32_t kp, SearchOut *pre) {
+  ShadowScratch &sh = ctx->sh;
+  const size_t ck = (size_t)count * kp;
+  ZRET(sh.keys.ensure(ck * sizeof(uint64_t)));
+  ZRET(sh.scores.ensure(ck * sizeof(float)));
+  ZRET(sh.rescored.ensure(ck * sizeof(float)));
+  ZRET(sh.idx.ensure(ck * sizeof(uint32_t)));
+  ZRET(sh.counts.ensure((size_t)count * sizeof(uint32_t)));
+  ZRET(sh.flags.ensure(((size_t)count + 4) * sizeof(uint32_t)));
+  *pre = SearchOut{sh.keys.as<uint64_t>(), sh.scores.as<float>(), sh.idx.as<uint32_t>(), sh.counts.as<uint32_t>()};
+  return 0;
+}
+
+// the k' pre-selected rows of every query (shadow_lists, in shadow-score order) -> their true scores on the fp32 rows `rows` (ctx->qpad
+// holds the prepared fp32 queries) -> the k best into `out` + the certificate, which the certify step reads back
+int shadow_rescore_select(zvec_hip_ctx_s *ctx, const Store &rows, const ShadowTwin &twin, uint32_t count, uint32_t kp, uint32_t topk,
+                          const SearchOut &out, hipStream_t stream) {
+  ShadowScratch &sh = ctx->sh;
+  const size_t ck = (size_t)count * kp;
+  hipLaunchKernelGGL(shadow_rescore_kernel<false>, dim3((unsigned)((ck + 3) / 4)), dim3(256), 0, stream, rows.base, ctx->qpad.as<float>(),
+                     rows.dpad, rows.metric, sh.idx.as<uint32_t>(), sh.counts.as<uint32_t>(), count, kp, sh.rescored.as<float>());
+  ZCHK(hipMemsetAsync(sh.flags.as<uint32_t>() + count, 0, sizeof(uint32_t), stream));
+  ShadowSelectArgs sa{};
+  sa.c_keys = sh.keys.as<uint64_t>(); sa.c_shadow = sh.scores.as<float>(); sa.c_true = sh.rescored.as<float>();
+  sa.c_idx = sh.idx.as<uint32_t>(); sa.c_counts = sh.counts.as<uint32_t>(); sa.qinfo = sh.qinfo.as<f32x2>(); sa.facts = twin.facts;
+  sa.kp = kp; sa.k = topk; sa.dscan = rows.dscan; sa.metric = rows.metric;
+  sa.out_keys = out.keys; sa.out_scores = out.scores; sa.out_idx = out.idx; sa.out_counts = out.counts;
+  sa.flags = sh.flags.as<uint32_t>(); sa.nflag = sa.flags + count;
+  hipLaunchKernelGGL(shadow_select_kernel, dim3(count), dim3(64), 0, stream, sa);
+  ZCHK(hipGetLastError());
+  sh.count = count;
+  sh.kp = kp;
+  return 0;
+}
+
+// The second half of a search through the twin: waits for it, reads how many queries could not be certified and answers those again,
+// their results replacing the uncertified ones.  `search(mode, queries, coarse_queries, m, keys, scores, counts)` searches m gathered
+// query rows the way the index searched the batch (same probe rule, same exclude set).  `d_coarse`: the batch's coarse-space rows
+// of `crb` bytes (an IVF index with a coarse space of its own; nullptr otherwise).  `tier` 1: inside the second pass, whose own flagged
+// queries go to the fp32 rows.  The caller holds c->mu (and whatever lock its search needs).
+template <typename Search>
+int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, size_t rb, const void *d_coarse, size_t crb,
+                   uint32_t count, uint32_t topk, uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, hipStream_t s,
+                   uint32_t *rerun_out, int tier, const Search &search) {
+  if (rerun_out) *rerun_out = 0;
+  if (c->sh.count == 0) return 0;                      // the last search on this context did not use the twin
+  if (c->sh.count != count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  c->sh.count = 0;
+  uint32_t nflag = 0;
+  ZCHK(hipMemcpyAsync(&nflag, c->sh.flags.as<uint32_t>() + count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  ZCHK(hipStreamSynchronize(s));
+  const uint32_t used_kp = c->sh.kp;
+  if (tier == 0) {
+    twin.gov.report(nflag, count);
+    if (twin.kp == 0) twin.gov.report_width(nflag, count);
+  }
+  if (nflag == 0) return 0;
+  std::vector<uint32_t> flags(count);
+  ZCHK(hipMemcpyAsync(flags.data(), c->sh.flags.p, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  ZCHK(hipStreamSynchronize(s));
+  std::vector<uint32_t> which;
+  for (uint32_t q = 0; q < count; ++q) if (flags[q]) which.push_back(q);
+  const uint32_t m = (uint32_t)which.size();
+  if (m == 0) return 0;
+  Scoped<char> tq, tcq;
+  Scoped<uint64_t> tk;
+  Scoped<float> ts;
+  Scoped<uint32_t> tc;
+  ZRET(tq.alloc((size_t)m * rb));
+  ZRET(tk.alloc((size_t)m * topk));
+  ZRET(ts.alloc((size_t)m * topk));
+  ZRET(tc.alloc(m));
+  if (d_coarse) ZRET(tcq.alloc((size_t)m * crb));
+  for (uint32_t i = 0; i < m; ++i) {
+    ZCHK(hipMemcpyAsync(tq.p + (size_t)i * rb, static_cast<const char *>(d_queries) + (size_t)which[i] * rb, rb, hipMemcpyDeviceToDevice, s));
+    if (d_coarse)
+      ZCHK(hipMemcpyAsync(tcq.p + (size_t)i * crb, static_cast<const char *>(d_coarse) + (size_t)which[i] * crb, crb, hipMemcpyDeviceToDevice, s));
+  }
+  // A failed certificate first costs a SECOND half-width pass over the flagged queries alone, at twice the pre-selection (32 .. 64 rows:
+  // what separates the k-th row from the rest may simply lie beyond the first k'), and only what that pass cannot certify either is
+  // answered by the fp32 rows.  (A handful of flagged IVF queries take the small-batch route, which reads the fp32 lists anyway.)
+  uint32_t answered_by_fp32 = m;
+  int rc;
+  if (tier == 0 && used_kp < 64) {
+    const ShadowMode wide{ShadowMode::forced, std::min<uint32_t>(64, std::max<uint32_t>(32, 2 * used_kp))};   // (wide lists are dear to keep: twice the first pass)
+    rc = search(wide, tq.p, tcq.p, m, tk.p, ts.p, tc.p);
+    if (rc == 0 && c->sh.count)
+      rc = shadow_certify(c, twin, tq.p, rb, tcq.p, crb, m, topk, tk.p, ts.p, tc.p, s, &answered_by_fp32, 1, search);
+  } else {
+    rc = search(ShadowMode{ShadowMode::fp32_only}, tq.p, tcq.p, m, tk.p, ts.p, tc.p);
+  }
+  ZRET(rc);
+  for (uint32_t i = 0; i < m; ++i) {
+    const size_t o = (size_t)which[i] * topk;
+    ZCHK(hipMemcpyAsync(d_out_keys + o, tk.p + (size_t)i * topk, (size_t)topk * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    ZCHK(hipMemcpyAsync(d_out_scores + o, ts.p + (size_t)i * topk, (size_t)topk * sizeof(float), hipMemcpyDeviceToDevice, s));
+    ZCHK(hipMemcpyAsync(d_out_counts + which[i], tc.p + i, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  }
+  ZCHK(hipStreamSynchronize(s));                       // (the temporaries are freed on return)
+  if (rerun_out) *rerun_out = answered_by_fp32;        // queries that ended on the fp32 rows
+  return 0;
+}
+
 int launch_pack(const Store &st, const void *d_rows, uint64_t n, const uint64_t *d_src, uint64_t pos0,
                 const uint64_t *d_dst, hipStream_t stream, uint64_t *keys_out = nullptr, const uint64_t *key_src = nullptr) {
   if (st.f16)
@@ -711,7 +831,7 @@ void ctx_free(zvec_hip_ctx_s *c) {
   c->gtau.release(); c->ridx.release(); c->seed_keys.release(); c->seed_scores.release(); c->seed_counts.release(); c->seed_idx.release(); c->cmp_base.release(); c->cmp_norm.release(); c->cmp_extra.release(); c->cmp_keys.release(); c->cmp_pos.release(); c->cmp_cnt.release(); c->qpad.release(); c->qnorm.release(); c->part_s.release(); c->part_i.release();
   c->coarse_keys.release(); c->coarse_scores.release(); c->coarse_idx.release(); c->coarse_cnt.release();
   c->plan.release(); c->io_q.release(); c->io_ex.release(); c->io_out.release(); c->io_cq.release();
-  c->grp_ws.release(); c->grp_of.release(); c->grp_out.release(); c->grp_tab.release(); c->holes_ex.release(); c->direct_pos.release(); c->direct_keys.release(); c->direct_scores.release(); c->direct_idx.release(); c->direct_cnt.release(); c->stats.release(); c->sh_q16.release(); c->sh_qn16.release(); c->sh_qinfo.release(); c->sh_keys.release(); c->sh_scores.release(); c->sh_true.release(); c->sh_idx.release(); c->sh_counts.release(); c->sh_flags.release(); c->pin_in.release(); c->pin_out.release(); c->done_word.release();
+  c->grp_ws.release(); c->grp_of.release(); c->grp_out.release(); c->grp_tab.release(); c->holes_ex.release(); c->direct_pos.release(); c->direct_keys.release(); c->direct_scores.release(); c->direct_idx.release(); c->direct_cnt.release(); c->stats.release(); c->sh.release(); c->pin_in.release(); c->pin_out.release(); c->done_word.release();
   if (c->block_ev) (void)hipEventDestroy(c->block_ev);
   for (auto e : c->ev0) (void)hipEventDestroy(e);
   for (auto e : c->ev1) (void)hipEventDestroy(e);

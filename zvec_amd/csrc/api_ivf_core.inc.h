@@ -19,7 +19,7 @@ struct CoarseSplit {
 int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_queries, uint32_t count, uint32_t topk,
                     float threshold, uint32_t nprobe, uint32_t max_scan_count, int brute_force,
                     const uint64_t *d_exclude, const SearchOut &out, hipStream_t stream, const void *d_coarse_queries = nullptr,
-                    const CoarseSplit &coarse = CoarseSplit()) {
+                    const CoarseSplit &coarse = CoarseSplit(), ShadowMode mode = ShadowMode()) {
   const bool given = coarse.given_idx != nullptr, coarse_only = coarse.out_idx != nullptr;
   if ((given || coarse_only) && brute_force) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (h->coarse_sep && !brute_force && !given && d_coarse_queries == nullptr) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -105,7 +105,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(256), (size_t)nprobe * 12 + 16, stream, m);     // four waves share the row
       ZCHK(hipGetLastError());
     } else {
-      ZRET(flat_scan_prepared(ctx, h->cent, count, nprobe, FLT_MAX, nullptr, co, stream, false));
+      ZRET(flat_scan_prepared(ctx, h->cent, count, nprobe, FLT_MAX, nullptr, co, stream, ScanRole::internal));
     }
     if (coarse_only) return 0;
   }
@@ -256,15 +256,15 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   // Half-width pre-selection (zvk_shadow.hip.h): the scan reads the fp16 twin of the lists and keeps k' > k rows per query, which
   // are re-scored on the fp32 rows and certified below.  Not with an RNN radius (it would have to be widened by the rounding bound),
   // not for search_bf, not on the certify step's own re-run.
+  ShadowTwin &tw = h->shadow;
   uint32_t kp = 0;
-  if (h->shadow_on && h->shadow.base && !ctx->shadow_skip && !brute_force && !(threshold < FLT_MAX) && topk <= 32 && h->shadow_gov.allow()) {
-    kp = ctx->shadow_force_kp ? ctx->shadow_force_kp : h->shadow_kp ? h->shadow_kp : h->shadow_gov.kp_auto(topk);
-    kp = std::min<uint32_t>(kp, 64);                                     // (shadow_select_kernel: one candidate per lane)
+  if (tw.on && tw.st.base && mode.kind != ShadowMode::fp32_only && !brute_force && !(threshold < FLT_MAX) && topk <= 32 && tw.gov.allow()) {
+    kp = tw.pick_kp(mode.kp, topk);
     if (kp <= topk || scan_lds_bytes(1, kp, true) > LDS_LIMIT - 1024) kp = 0;
   }
   const bool use_shadow = kp != 0;
   const uint32_t ks = use_shadow ? kp : topk;                            // k of the list scan and of its merge
-  ctx->sh_count = 0;
+  ctx->sh.count = 0;
   const uint32_t rows_per_group = 32;
   const uint64_t npairs = (uint64_t)count * (brute_force ? nlist : nprobe);
   // layout of the plan buffer (u32 words)
@@ -344,19 +344,13 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   ZRET(ctx->part_s.ensure(slots_bound * ks * sizeof(float)));
   ZRET(ctx->part_i.ensure(slots_bound * ks * sizeof(uint32_t)));
 
-  const Store &sst = use_shadow ? h->shadow : h->lists;                  // the store the list scan streams
+  const Store &sst = use_shadow ? tw.st : h->lists;                      // the store the list scan streams
   ScanArgs a{};
   a.base = sst.base; a.bnorm = sst.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
   a.queries = ctx->qpad.as<float>(); a.qnorm = ctx->qnorm.as<float>();
   if (use_shadow) {
-    ZRET(ctx->sh_q16.ensure((size_t)count * sst.dpad * sizeof(float)));
-    ZRET(ctx->sh_qn16.ensure((size_t)count * sizeof(float)));
-    ZRET(ctx->sh_qinfo.ensure((size_t)count * sizeof(f32x2)));
-    hipLaunchKernelGGL(shadow_prep_queries_kernel, dim3((count + 3) / 4), dim3(256), 0, stream, reinterpret_cast<const float *>(d_queries),
-                       count, h->lists.dim_in, sst.dscan, sst.dpad, ctx->sh_q16.as<float>(), ctx->sh_qn16.as<float>(),
-                       ctx->sh_qinfo.as<f32x2>());
-    ZCHK(hipGetLastError());
-    a.queries = ctx->sh_q16.as<float>(); a.qnorm = ctx->sh_qn16.as<float>();
+    ZRET(shadow_prep_queries(ctx, sst, d_queries, count, stream));
+    a.queries = ctx->sh.q16.as<float>(); a.qnorm = ctx->sh.qn16.as<float>();
   }
   a.dpad = sst.dpad; a.nks = sst.dpad / TILE_K; a.metric = h->metric; a.k = ks; a.threshold = threshold;
   a.gtau = ctx->gtau.as<uint32_t>();
@@ -381,30 +375,11 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   m.bound_keys = a.gtau;
   if (use_shadow) {
     // the k' pre-selected rows of every query in shadow-score order -> their true scores -> the k best + the certificate
-    const size_t ck = (size_t)count * kp;
-    ZRET(ctx->sh_keys.ensure(ck * sizeof(uint64_t)));
-    ZRET(ctx->sh_scores.ensure(ck * sizeof(float)));
-    ZRET(ctx->sh_true.ensure(ck * sizeof(float)));
-    ZRET(ctx->sh_idx.ensure(ck * sizeof(uint32_t)));
-    ZRET(ctx->sh_counts.ensure((size_t)count * sizeof(uint32_t)));
-    ZRET(ctx->sh_flags.ensure(((size_t)count + 4) * sizeof(uint32_t)));
-    m.out_keys = ctx->sh_keys.as<uint64_t>(); m.out_scores = ctx->sh_scores.as<float>(); m.out_idx = ctx->sh_idx.as<uint32_t>();
-    m.out_counts = ctx->sh_counts.as<uint32_t>();
+    SearchOut pre;
+    ZRET(shadow_lists(ctx, count, kp, &pre));
+    m.out_keys = pre.keys; m.out_scores = pre.scores; m.out_idx = pre.idx; m.out_counts = pre.counts;
     hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)kp * 12 + 16, stream, m);
-    hipLaunchKernelGGL(shadow_rescore_kernel<false>, dim3((unsigned)((ck + 3) / 4)), dim3(256), 0, stream, h->lists.base,
-                       ctx->qpad.as<float>(), h->lists.dpad, h->metric, m.out_idx, m.out_counts, count, kp, ctx->sh_true.as<float>());
-    ZCHK(hipMemsetAsync(ctx->sh_flags.as<uint32_t>() + count, 0, sizeof(uint32_t), stream));
-    ShadowSelectArgs sa{};
-    sa.c_keys = m.out_keys; sa.c_shadow = m.out_scores; sa.c_true = ctx->sh_true.as<float>(); sa.c_idx = m.out_idx;
-    sa.c_counts = m.out_counts; sa.qinfo = ctx->sh_qinfo.as<f32x2>(); sa.facts = static_cast<const ShadowFacts *>(h->d_shadow_facts);
-    sa.kp = kp; sa.k = topk; sa.dscan = h->lists.dscan; sa.metric = h->metric;
-    sa.out_keys = out.keys; sa.out_scores = out.scores; sa.out_idx = out.idx; sa.out_counts = out.counts;
-    sa.flags = ctx->sh_flags.as<uint32_t>(); sa.nflag = sa.flags + count;
-    hipLaunchKernelGGL(shadow_select_kernel, dim3(count), dim3(64), 0, stream, sa);
-    ZCHK(hipGetLastError());
-    ctx->sh_count = count;
-    ctx->sh_kp = kp;
-    return 0;
+    return shadow_rescore_select(ctx, h->lists, tw, count, kp, topk, out, stream);
   }
   uint32_t *ridx = out.idx;
   if (h->metric == ZVEC_HIP_METRIC_L2 && ridx == nullptr) {

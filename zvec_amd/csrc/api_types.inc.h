@@ -221,6 +221,85 @@ struct Store {
   }
 };
 
+// fp16 twin of an fp32 store at the same positions (own base + bnorm; keys / geometry are the store's): the half-width
+// pre-selection of zvec_hip_flat_set_shadow / zvec_hip_ivf_set_shadow (zvk_shadow.hip.h).  Built for the rows present at that
+// moment; an index drops it when its rows change.
+struct ShadowTwin {
+  Store st;
+  bool on = false;
+  uint32_t kp = 0;                     // rows pre-selected per query (0: sized by the governor)
+  ShadowFacts *facts = nullptr;        // device
+  float max_err = 0.f, max_norm = 0.f;
+  ShadowGovernor gov;
+
+  void drop() {
+    st.keys = nullptr; st.extra = nullptr;      // (never its own)
+    st.release();
+    st.n = 0;
+    if (facts) (void)hipFree(facts);
+    facts = nullptr;
+    on = false;
+  }
+  // the twin of src's positions [0, n) (whole tiles of them).  Flat store (tile0 == nullptr): its first `rows` positions are rows;
+  // IVF lists: every list's first size[l] positions from tile0[l] on.  The other positions become zero rows and feed no fact.
+  int build(const Store &src, uint64_t n, uint64_t rows, const uint32_t *tile0, const uint32_t *size, uint32_t nlist,
+            uint32_t preselect, hipStream_t s) {
+    st = Store();
+    st.configure(src.dim_in, src.metric, ZVEC_HIP_DT_FP16);
+    const uint64_t tiles = (n + TILE_N - 1) / TILE_N;
+    if (hipMalloc(&st.base, (size_t)tiles * TILE_N * st.dpad * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); st.base = nullptr; return ZVEC_HIP_ERR_NO_MEMORY; }
+    if (hipMalloc(&st.bnorm, (size_t)tiles * TILE_N * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); drop(); return ZVEC_HIP_ERR_NO_MEMORY; }
+    if (hipMalloc(&facts, sizeof(ShadowFacts)) != hipSuccess) { (void)hipGetLastError(); drop(); return ZVEC_HIP_ERR_NO_MEMORY; }
+    st.cap_tiles = tiles;
+    st.n = n;
+    ZCHK(hipMemsetAsync(facts, 0, sizeof(ShadowFacts), s));
+    const uint64_t npos = tiles * TILE_N;
+    hipLaunchKernelGGL(shadow_rows_kernel, dim3((unsigned)((npos + 3) / 4)), dim3(256), 0, s, src.base, src.dpad, st.dscan, st.base,
+                       st.dpad, st.bnorm, npos, tile0, size, nlist, rows, facts);
+    ZCHK(hipGetLastError());
+    ShadowFacts f{};
+    ZCHK(hipMemcpyAsync(&f, facts, sizeof(f), hipMemcpyDeviceToHost, s));
+    ZCHK(hipStreamSynchronize(s));
+    if (!(__builtin_bit_cast(float, f.max_abs) < 65504.f)) { drop(); return ZVEC_HIP_ERR_UNSUPPORTED; }     // rows beyond the half range (or nan)
+    max_err = __builtin_bit_cast(float, f.max_err);
+    max_norm = __builtin_bit_cast(float, f.max_norm);
+    kp = preselect;
+    gov.reset();
+    on = true;
+    return 0;
+  }
+  void info(int *enabled, uint64_t *bytes, float *max_row_error, float *max_row_norm) const {
+    if (enabled) *enabled = on ? 1 : 0;
+    if (bytes) *bytes = on ? (uint64_t)st.cap_tiles * TILE_N * (st.dpad + 1) * sizeof(float) : 0;
+    if (max_row_error) *max_row_error = on ? max_err : 0.f;
+    if (max_row_norm) *max_row_norm = on ? max_norm : 0.f;
+  }
+  // k' of a search: the certify step's forced width, else the index's fixed one, else the governor's
+  uint32_t pick_kp(uint32_t forced, uint32_t topk) const {
+    return std::min<uint32_t>(64, forced ? forced : kp ? kp : gov.kp_auto(topk));     // (shadow_select_kernel: one candidate per lane)
+  }
+  uint32_t width(uint32_t topk) const { return on ? pick_kp(0, topk) : 0; }
+};
+
+// How a search may use its index's twin: as the index decides, at a forced width (the certify step's second pass over the
+// flagged queries), or not at all (the certify step's fp32 re-run; a sliced batch).
+struct ShadowMode {
+  enum Kind { automatic, forced, fp32_only } kind = automatic;
+  uint32_t kp = 0;                     // forced: the width
+};
+
+// A context's scratch of the half-width pre-selection: fp16 query rows + norms, per-query rounding facts, the k' pre-selected rows
+// of every query (keys | shadow scores | true scores | positions | counts), flags [count] + the flagged count [1]
+struct ShadowScratch {
+  DevBuf q16, qn16, qinfo, keys, scores, rescored, idx, counts, flags;
+  uint32_t count = 0;                  // queries of the last search that went through the twin (0: none)
+  uint32_t kp = 0;                     // width that search used
+  void release() {
+    q16.release(); qn16.release(); qinfo.release(); keys.release(); scores.release(); rescored.release(); idx.release();
+    counts.release(); flags.release();
+  }
+};
+
 }  // namespace
 
 // Contexts that share a gate take turns on their dominant scan kernel (in call order) while everything else of their
@@ -250,15 +329,7 @@ struct zvec_hip_ctx_s {
   DevView io_keys, io_scores, io_counts;               // the result arrays inside io_out: ONE copy brings them back
   DevBuf grp_ws, grp_of, grp_out, grp_tab;
   DevBuf direct_pos, direct_keys, direct_scores, direct_idx, direct_cnt;   // small-batch IVF route: positions, stage-1 lists
-  // half-width pre-selection (zvec_hip_ivf_set_shadow): fp16 query rows + norms, per-query rounding facts, the k' pre-selected rows
-  // of every query (keys | shadow scores | true scores | positions | counts), flags [count] + the flagged count [1]
-  DevBuf sh_q16, sh_qn16, sh_qinfo, sh_keys, sh_scores, sh_true, sh_idx, sh_counts, sh_flags;
-  uint32_t sh_count = 0;                               // queries of the last search that went through the shadow lists (0: none)
-  bool shadow_skip = false;                            // the certify step's re-run: this search must read the fp32 lists
-  uint32_t shadow_force_kp = 0;                        // the certify step's SECOND half-width pass over the flagged queries: this width
-  uint32_t sh_kp = 0;                                  // width the last shadow search on this context used
-  int sh_tier = 0;                                     // 1: inside the second pass (its own flagged queries go to the fp32 rows)
-  bool shadow_scan = false;                            // flat_scan_prepared is running over a shadow store: profiled / gated like a user-facing scan
+  ShadowScratch sh;                                    // half-width pre-selection (zvec_hip_*_set_shadow)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)
   const void *io_qp = nullptr;                         // where device code finds the uploaded queries: io_q or the mapped pin_in slot
@@ -285,14 +356,9 @@ struct zvec_hip_flat_s {
   int device = 0;
   int dtype = 0;
   Store st;
-  // fp16 twin of `st` at the same positions (own base + bnorm): zvec_hip_flat_set_shadow.  Built for the rows present at that moment;
-  // any mutation of the store drops it (the store then searches its own rows until it is set again)
-  Store shadow;
-  bool shadow_on = false;
-  uint32_t shadow_kp = 0;
-  void *d_shadow_facts = nullptr;      // zvk::ShadowFacts
-  float shadow_max_err = 0.f, shadow_max_norm = 0.f;
-  ShadowGovernor shadow_gov;
+  // fp16 twin of `st` (zvec_hip_flat_set_shadow): any mutation of the store drops it (the store then searches its own rows until it
+  // is set again)
+  ShadowTwin shadow;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)
   // The streamer is searched while it grows (flat_streamer_test.cc TestConcurrentAddAndSearch): searches hold `rw`
@@ -343,13 +409,7 @@ struct zvec_hip_ivf_s {
   Store cent;     // centroids as a flat store
   bool coarse_sep = false;             // the centroid store lives in a space of its own (dimension / metric): zvec_hip_ivf_set_coarse_space
   Store lists;    // inverted lists, each padded to whole tiles
-  // fp16 twin of `lists` at the same positions (own base + bnorm; keys / geometry are the lists'): zvec_hip_ivf_set_shadow
-  Store shadow;
-  bool shadow_on = false;
-  uint32_t shadow_kp = 0;              // rows pre-selected per query (0: from k)
-  void *d_shadow_facts = nullptr;      // zvk::ShadowFacts
-  float shadow_max_err = 0.f, shadow_max_norm = 0.f;
-  ShadowGovernor shadow_gov;
+  ShadowTwin shadow;                   // fp16 twin of `lists` (zvec_hip_ivf_set_shadow)
   uint64_t count_local = 0, count_global = 0;
   std::vector<uint32_t> h_size, h_size_global, h_tile0;
   std::vector<uint64_t> h_rows_of_largest;   // [i] = rows of the i largest local lists (bound of what i probes can scan)
