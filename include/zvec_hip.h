@@ -251,7 +251,10 @@ int zvec_hip_ivf_search_probes_dev(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const v
  * fp16 rows at twice the width, and what fails that too is re-run on the fp32
  * lists: by zvec_hip_ivf_search itself (host pointers), or — device pointers, where the search call only enqueues — by
  * zvec_hip_ivf_shadow_certify, which the caller runs on the same context with the same arguments before it reads the results
- * (*rerun = queries that ended on the fp32 lists; a call with no shadow search pending returns 0 at once).  Unsupported: fp16 / cosine indexes, rows
+ * (*rerun = queries that ended on the fp32 lists; a call with no shadow search pending returns 0 at once).  What is pending is the
+ * LAST search of the context: a certify call whose count, topk or index differs from that search's is refused (InvalidArgument), and
+ * a call on the context that does not go through a twin (a search without one, zvec_hip_flat_search_by_ids, the grouped flat searches,
+ * zvec_hip_flat_batch_distance) leaves nothing pending.  Unsupported: fp16 / cosine indexes, rows
  * beyond the half range.  enable = 0 frees the copy.  zvec_hip_ivf_shadow_info: state, bytes held, max |b - b16|, max |b16|.
  * Like zvec_hip_ivf_load, zvec_hip_ivf_set_shadow is an index-level operation: not while searches of the index are in flight.
  * Data the twin cannot serve (rows within the fp16 rounding of each other, a few rows of huge norm under inner product) would pay the

@@ -78,3 +78,80 @@ def lpt_owner(sizes, nshards, tile=128):
         owner[l] = g
         load[g] += (int(sizes[l]) + tile - 1) // tile
     return owner
+
+
+# ---- search helpers of the half-width pre-selection tests (test_gpu_shadow.py, test_gpu_shadow_parity.py) -------------------------
+def ivf_index(rng, base, nlist, metric="SquaredEuclidean", ratio=0.25, round_centroids=False):
+    """an fp32 IVF searcher over `base` (kmeans_lists structure); returns it with what the oracle needs to search the same index"""
+    import zvec_amd
+    cent, offs, order = kmeans_lists(rng, base, nlist)
+    if round_centroids:
+        cent = np.round(cent)
+    vecs, keys = base[order], order.astype(np.uint64)
+    se = zvec_amd.HipIVFSearcher(base.shape[1], metric, scan_ratio=ratio, brute_force_threshold=10)
+    assert se.load(cent, offs, vecs, keys) == 0
+    return se, cent, offs, vecs, keys
+
+
+def ivf_search(se, q, k, ctx=None, exclude=None, exclude_words=None):
+    """host pointers: a search through the twin is certified inside the call"""
+    ctx = ctx or se.create_context()
+    ctx.set_topk(k)
+    if exclude is not None:
+        ctx.set_filter(exclude)
+    if exclude_words is not None:
+        ctx.set_exclude_bitset(exclude_words)
+    assert se.search_impl(q, len(q), ctx) == 0
+    return ctx.keys.copy(), ctx.scores.copy(), ctx.counts.copy()
+
+
+def flat_search(se, q, k, exclude=None, exclude_words=None):
+    return ivf_search(se, q, k, exclude=exclude, exclude_words=exclude_words)
+
+
+def dev_lists(q, k, exclude_words):
+    import torch
+    dq = torch.from_numpy(np.ascontiguousarray(q)).cuda()
+    nq = len(q)
+    keys = torch.zeros((nq, k), dtype=torch.int64, device="cuda")
+    scores = torch.zeros((nq, k), dtype=torch.float32, device="cuda")
+    counts = torch.zeros(nq, dtype=torch.int32, device="cuda")
+    dex = None if exclude_words is None else torch.from_numpy(np.ascontiguousarray(exclude_words).view(np.int64)).cuda()
+    return dq, keys, scores, counts, dex
+
+
+def _host_lists(keys, scores, counts):
+    return keys.cpu().numpy().astype(np.uint64), scores.cpu().numpy(), counts.cpu().numpy().astype(np.uint32)
+
+
+def ivf_search_dev(se, q, k, ctx=None, exclude_words=None):
+    """device pointers: the search only enqueues, zvec_hip_ivf_shadow_certify finishes it; returns results + queries re-run"""
+    import torch
+    dq, keys, scores, counts, dex = dev_lists(q, k, exclude_words)
+    nq = len(q)
+    ctx = ctx or se.create_context()
+    nprobe, max_scan = se.probe_params()
+    ex = None if dex is None else dex.data_ptr()
+    torch.cuda.synchronize()
+    rc = se.search_dev(dq.data_ptr(), nq, k, nprobe, max_scan, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx, d_exclude=ex)
+    assert rc == 0
+    args = (dq.data_ptr(), nq, k, nprobe, max_scan, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx)
+    rerun = se.shadow_certify(*args, d_exclude=ex)
+    assert se.shadow_certify(*args, d_exclude=ex) == 0            # nothing pending any more
+    torch.cuda.synchronize()
+    return _host_lists(keys, scores, counts) + (rerun,)
+
+
+def flat_search_dev(se, q, k, ctx=None, exclude_words=None):
+    import torch
+    dq, keys, scores, counts, dex = dev_lists(q, k, exclude_words)
+    nq = len(q)
+    ctx = ctx or se.create_context()
+    ex = None if dex is None else dex.data_ptr()
+    torch.cuda.synchronize()
+    assert se.search_dev(dq.data_ptr(), nq, k, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx, d_exclude=ex) == 0
+    args = (dq.data_ptr(), nq, k, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx)
+    rerun = se.shadow_certify(*args, d_exclude=ex)
+    assert se.shadow_certify(*args, d_exclude=ex) == 0
+    torch.cuda.synchronize()
+    return _host_lists(keys, scores, counts) + (rerun,)

@@ -674,6 +674,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
+  c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
   const Store &st = h->st;
@@ -730,6 +731,7 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
+  c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
   const Store &st = h->st;

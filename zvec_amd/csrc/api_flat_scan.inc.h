@@ -683,6 +683,8 @@ int shadow_rescore_select(zvec_hip_ctx_s *ctx, const Store &rows, const ShadowTw
   ZCHK(hipGetLastError());
   sh.count = count;
   sh.kp = kp;
+  sh.topk = topk;
+  sh.owner = &twin;
   return 0;
 }
 
@@ -697,7 +699,7 @@ int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, s
                    uint32_t *rerun_out, int tier, const Search &search) {
   if (rerun_out) *rerun_out = 0;
   if (c->sh.count == 0) return 0;                      // the last search on this context did not use the twin
-  if (c->sh.count != count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (c->sh.count != count || c->sh.owner != &twin || c->sh.topk != topk) return ZVEC_HIP_ERR_INVALID_ARGUMENT;   // not this search's step
   c->sh.count = 0;
   uint32_t nflag = 0;
   ZCHK(hipMemcpyAsync(&nflag, c->sh.flags.as<uint32_t>() + count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));

@@ -294,6 +294,8 @@ struct ShadowScratch {
   DevBuf q16, qn16, qinfo, keys, scores, rescored, idx, counts, flags;
   uint32_t count = 0;                  // queries of the last search that went through the twin (0: none)
   uint32_t kp = 0;                     // width that search used
+  uint32_t topk = 0;                   // its k
+  const ShadowTwin *owner = nullptr;   // the twin it went through: a certify step of another index (or another k) is refused
   void release() {
     q16.release(); qn16.release(); qinfo.release(); keys.release(); scores.release(); rescored.release(); idx.release();
     counts.release(); flags.release();
