@@ -130,14 +130,6 @@ int zvec_hip_flat_destroy(zvec_hip_flat_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  h->shadow.drop();
-  h->st.release();
-  h->d_holes.release();
-  h->ring.release();
-  for (uint32_t i = 0; i < zvec_hip_flat_s::RING / zvec_hip_flat_s::RING_GROUP; ++i)
-    if (h->ring_used[i]) (void)hipEventDestroy(h->ring_ev[i]);
-  if (h->append_ev) (void)hipEventDestroy(h->append_ev);
-  ctx_free(h->defctx);
   delete h;
   return 0;
 }
@@ -364,17 +356,14 @@ int zvec_hip_flat_append(zvec_hip_flat_t h, const void *vecs, uint64_t n, const 
   DevBuf tmp, tk;
   for (uint64_t o = 0; o < n; o += rows_per) {
     uint64_t m = std::min(rows_per, n - o);
-    int rc = tmp.ensure((size_t)m * rb);
-    if (rc == 0 && keys) rc = tk.ensure((size_t)m * 8);
-    if (rc != 0) { tmp.release(); tk.release(); return rc; }
+    ZRET(tmp.ensure((size_t)m * rb));
+    if (keys) ZRET(tk.ensure((size_t)m * 8));
     ZCHK(hipMemcpyAsync(tmp.p, reinterpret_cast<const char *>(vecs) + (size_t)o * rb, (size_t)m * rb, hipMemcpyHostToDevice, s));
     if (keys) ZCHK(hipMemcpyAsync(tk.p, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    rc = store_append_dev(h->st, tmp.p, m, keys ? tk.as<uint64_t>() : nullptr, s);
-    if (rc == 0) rc = flat_holes_cover(h, s);
-    if (rc != 0) { tmp.release(); tk.release(); return rc; }
+    ZRET(store_append_dev(h->st, tmp.p, m, keys ? tk.as<uint64_t>() : nullptr, s));
+    ZRET(flat_holes_cover(h, s));
     ZCHK(hipStreamSynchronize(s));
   }
-  tmp.release(); tk.release();
   return 0;
 }
 
@@ -554,7 +543,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
       ZRET(shadow_prep_queries(c, tw.st, d_queries, count, s));
       SearchOut pre;
       ZRET(shadow_lists(c, count, kp, &pre));
-      Store view = tw.st;                        // the shadow rows under the store's keys (a view: owns nothing)
+      StoreView view = tw.st;                    // the shadow rows under the store's keys
       view.keys = h->st.keys;
       std::swap(c->qpad, c->sh.q16);             // the scan reads the context's prepared queries: the fp16 ones for this call
       std::swap(c->qnorm, c->sh.qn16);
@@ -677,7 +666,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
-  const Store &st = h->st;
+  const StoreView &st = h->st;
   ZRET(flat_wait_appends(h, s));
   // host-side sanitising: positions out of range or excluded by the filter bitset become holes
   const uint32_t total = offsets[count];
@@ -734,7 +723,7 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
-  const Store &st = h->st;
+  const StoreView &st = h->st;
   ZRET(flat_wait_appends(h, s));
   std::vector<uint32_t> clean(positions, positions + n);
   for (auto &p : clean) if (p >= st.n) p = IDX_NONE;

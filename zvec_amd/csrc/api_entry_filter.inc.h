@@ -239,6 +239,6 @@ extern "C" int zvec_hip_ivf_build_filter(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, c
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
-  return build_filter(c, h->device, h->lists.keys, h->count_local, h->d_dense0, h->d_tile0, h->nlist,
+  return build_filter(c, h->device, h->lists.keys, h->count_local, h->tab.d_dense0.p, h->tab.d_tile0.p, h->nlist,
                       filter, out_words, out_on_device, stream);
 }

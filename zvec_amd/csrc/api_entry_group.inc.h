@@ -13,7 +13,7 @@ namespace {
 struct GroupOut { uint32_t *groups, *ngroups; uint64_t *keys; float *scores; uint32_t *counts; };   // device arrays of the whole batch
 
 // selection over a candidate matrix of `cnt` queries (rows q0.. of the prepared batch); outputs at row offset q0
-int group_select(zvec_hip_ctx_s *c, const Store &st, const float *cs, const uint32_t *ci, uint32_t stride, uint32_t len,
+int group_select(zvec_hip_ctx_s *c, const StoreView &st, const float *cs, const uint32_t *ci, uint32_t stride, uint32_t len,
                  uint32_t q0, uint32_t cnt, const uint32_t *d_group_of, uint32_t ngroups, uint32_t gnum, uint32_t gk,
                  float threshold, bool refine, const GroupOut &out, hipStream_t s) {
   const size_t rows = (size_t)cnt * gnum;
@@ -130,7 +130,7 @@ int zvec_hip_flat_search_grouped(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
-  const Store &st = h->st;
+  const StoreView &st = h->st;
   ZRET(flat_wait_appends(h, s));
   GroupOut o{};
   ZRET(group_outputs(c, count, group_num, group_topk, &o));
@@ -177,7 +177,7 @@ int zvec_hip_flat_search_grouped_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, c
   c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
-  const Store &st = h->st;
+  const StoreView &st = h->st;
   ZRET(flat_wait_appends(h, s));
   const uint32_t total = offsets[count];
   uint32_t maxlen = 1;

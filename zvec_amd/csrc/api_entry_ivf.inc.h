@@ -34,13 +34,7 @@ static void ivf_release(zvec_hip_ivf_s *h) {
   h->cent.release(); h->lists.release();
   h->cent.n = 0; h->lists.n = 0;
   ivf_leave_coarse_space(h);
-  if (h->d_size) (void)hipFree(h->d_size);
-  if (h->d_size_global) (void)hipFree(h->d_size_global);
-  if (h->d_tile0) (void)hipFree(h->d_tile0);
-  if (h->d_order) (void)hipFree(h->d_order);
-  if (h->d_tail) (void)hipFree(h->d_tail);
-  if (h->d_dense0) (void)hipFree(h->d_dense0);
-  h->d_size = h->d_size_global = h->d_tile0 = h->d_order = h->d_tail = nullptr; h->d_dense0 = nullptr;
+  h->tab = zvec_hip_ivf_s::Tables();
   h->loaded = false; h->trained = false; h->filling = false;
 }
 
@@ -48,8 +42,6 @@ int zvec_hip_ivf_destroy(zvec_hip_ivf_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  ivf_release(h);
-  ctx_free(h->defctx);
   delete h;
   return 0;
 }
@@ -197,7 +189,6 @@ static int ivf_end_lists(zvec_hip_ivf_s *h) {
   for (uint32_t l = 0; l < nlist; ++l)
     if (h->h_cursor[l] != h->h_dense0[l + 1]) return ZVEC_HIP_ERR_NO_READY;   // fewer rows than announced
   const uint64_t tiles = h->local_tiles;
-  if (h->d_size) { (void)hipFree(h->d_size); (void)hipFree(h->d_size_global); (void)hipFree(h->d_tile0); (void)hipFree(h->d_dense0); (void)hipFree(h->d_order); (void)hipFree(h->d_tail); h->d_size = nullptr; }
   // largest lists are dealt first by the scan's work queue; chunk length adapts to the index size so
   // that a search has a few items per resident work-group yet long runs per top-k warm-up
   std::vector<uint32_t> order(nlist);
@@ -231,18 +222,14 @@ static int ivf_end_lists(zvec_hip_ivf_s *h) {
       acc += (h->h_size[l] + TILE_N - 1) / TILE_N;
     }
   }
-  ZCHK(hipMalloc(&h->d_tail, std::max<uint32_t>(nlist, 1) * 4));
-  ZCHK(hipMemcpy(h->d_tail, h->h_tail.data(), nlist * 4, hipMemcpyHostToDevice));
-  ZCHK(hipMalloc(&h->d_order, nlist * 4));
-  ZCHK(hipMemcpy(h->d_order, order.data(), nlist * 4, hipMemcpyHostToDevice));
-  ZCHK(hipMalloc(&h->d_size, nlist * 4));
-  ZCHK(hipMalloc(&h->d_size_global, nlist * 4));
-  ZCHK(hipMalloc(&h->d_tile0, nlist * 4));
-  ZCHK(hipMalloc(&h->d_dense0, (nlist + 1) * 8));
-  ZCHK(hipMemcpy(h->d_size, h->h_size.data(), nlist * 4, hipMemcpyHostToDevice));
-  ZCHK(hipMemcpy(h->d_size_global, h->h_size_global.data(), nlist * 4, hipMemcpyHostToDevice));
-  ZCHK(hipMemcpy(h->d_tile0, h->h_tile0.data(), nlist * 4, hipMemcpyHostToDevice));
-  ZCHK(hipMemcpy(h->d_dense0, h->h_dense0.data(), (nlist + 1) * 8, hipMemcpyHostToDevice));
+  zvec_hip_ivf_s::Tables t;              // the new tables first, all of them: a failure leaves the old ones in place
+  ZRET(upload(t.d_tail, h->h_tail.data(), nlist));
+  ZRET(upload(t.d_order, order.data(), nlist));
+  ZRET(upload(t.d_size, h->h_size.data(), nlist));
+  ZRET(upload(t.d_size_global, h->h_size_global.data(), nlist));
+  ZRET(upload(t.d_tile0, h->h_tile0.data(), nlist));
+  ZRET(upload(t.d_dense0, h->h_dense0.data(), (size_t)nlist + 1));
+  h->tab = std::move(t);
   h->filling = false;
   // rows of the i largest local lists: the bound of what i probes can scan (small-batch route); computed here, once,
   // because searches on different contexts read it concurrently
@@ -399,7 +386,7 @@ int zvec_hip_ivf_load_segments(zvec_hip_ivf_t h, const void *inverted_header, ui
 // nearest centroid of every row (IVFBuilder::label, ivf_builder.h:253-274: top-1 of the centroid index): device rows ->
 // device labels, in batches through assign_kernel (zvk_assign.hip.h): 128 rows x every centroid per work item, arg-min kept
 // in registers — no partial lists, no merge pass
-static int ivf_label_rows(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const Store &cs, const char *d_rows, uint64_t n,
+static int ivf_label_rows(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const StoreView &cs, const char *d_rows, uint64_t n,
                           uint32_t *d_labels, hipStream_t s) {
   const size_t rb = cs.row_bytes();
   const uint64_t BATCH = 1u << 18;
@@ -449,8 +436,7 @@ static int ivf_train(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const char *d_sample,
     ZCHK(hipStreamSynchronize(s));
   }
   // ---- Lloyd iterations on the sample ----
-  Store cs;
-  struct StoreGuard { Store &s; ~StoreGuard() { s.release(); } } cs_guard{cs};   // the k-means codebook store
+  Store cs;                              // the k-means codebook store
   cs.configure(dim, h->metric, h->dtype);
   Scoped<uint32_t> d_lab;
   ZRET(d_lab.alloc(S));
@@ -801,7 +787,7 @@ int zvec_hip_ivf_set_shadow(zvec_hip_ivf_t h, int enable, uint32_t preselect) {
   if (h->shadow.on) { h->shadow.kp = preselect; h->shadow.gov.reset(); return 0; }
   const uint64_t tiles = (h->lists.n + TILE_N - 1) / TILE_N;
   if (tiles == 0) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-  return h->shadow.build(h->lists, tiles * TILE_N, 0, h->d_tile0, h->d_size, h->nlist, preselect, h->defctx->own);
+  return h->shadow.build(h->lists, tiles * TILE_N, 0, h->tab.d_tile0.p, h->tab.d_size.p, h->nlist, preselect, h->defctx->own);
 }
 
 int zvec_hip_ivf_shadow_info(zvec_hip_ivf_t h, int *enabled, uint64_t *bytes, float *max_row_error, float *max_row_norm) {

@@ -36,8 +36,9 @@ struct zvec_hip_shards_s {
   std::vector<zvec_hip_flat_s *> flat;
   std::vector<zvec_hip_ivf_s *> ivf;
   std::vector<zvec_hip_ctx_s *> ctx;              // one context (stream + workspace) per shard
-  std::vector<DevBuf> d_q, d_ex, d_packed;        // per shard: staged queries, exclude words, packed candidate lists
-  std::vector<DevBuf> d_probe;                    // per shard: the probe lists of the whole batch (dealt coarse pass)
+  // per shard, on its device: staged queries, exclude words, packed candidate lists, the probe lists of the whole batch (dealt coarse pass)
+  struct ShardBufs { DevBuf q, ex, packed, probe; };
+  std::vector<ShardBufs> buf;
   bool deal_coarse = false;                       // IVF: the coarse pass dealt over the shards (zvec_hip_shards_deal_coarse)
   DevBuf d_gather, d_ok, d_os, d_oc;              // on devices[0]
   std::vector<std::vector<ShardRange>> ranges;    // flat: global position runs of every shard
@@ -125,7 +126,7 @@ int zvec_hip_shards_create(uint32_t dim, int dtype, int metric, int kind, const 
   h->dim = dim; h->dtype = dtype; h->metric = metric; h->kind = kind; h->G = ndev;
   h->devices.assign(devices, devices + ndev);
   h->row_bytes = (size_t)dim * (dtype == ZVEC_HIP_DT_FP16 ? 2 : 4);
-  h->d_q.resize(ndev); h->d_ex.resize(ndev); h->d_packed.resize(ndev); h->d_probe.resize(ndev); h->ranges.resize(ndev);
+  h->buf.resize(ndev); h->ranges.resize(ndev);
   int rc = 0;
   for (uint32_t g = 0; g < ndev && rc == 0; ++g) {
     zvec_hip_ctx_s *c = nullptr;
@@ -172,17 +173,14 @@ int zvec_hip_shards_destroy(zvec_hip_shards_t h) {
     { std::lock_guard<std::mutex> lk(wp->mu); wp->quit = true; wp->cv.notify_all(); }
     if (wp->th.joinable()) wp->th.join();
   }
-  for (uint32_t g = 0; g < h->G; ++g) {
-    if (g < h->devices.size()) (void)hipSetDevice(h->devices[g]);
-    if (g < h->d_q.size()) { h->d_q[g].release(); h->d_ex[g].release(); h->d_packed[g].release(); }
-  }
-  if (!h->devices.empty()) {
-    (void)hipSetDevice(h->devices[0]);
-    h->d_gather.release(); h->d_ok.release(); h->d_os.release(); h->d_oc.release();
+  for (uint32_t g = 0; g < h->buf.size(); ++g) {      // each shard's buffers with that shard's device current
+    (void)hipSetDevice(h->devices[g]);
+    h->buf[g] = zvec_hip_shards_s::ShardBufs();
   }
   for (auto f : h->flat) zvec_hip_flat_destroy(f);
   for (auto v : h->ivf) zvec_hip_ivf_destroy(v);
   for (auto c : h->ctx) ctx_free(c);
+  (void)hipSetDevice(h->devices[0]);                  // (the gather buffers live there)
   delete h;
   return 0;
 }
@@ -387,21 +385,21 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
   if (dealt) {
     for (uint32_t g = 0; g < h->G; ++g) {          // every table exists before the first peer copy into it
       ZCHK(hipSetDevice(h->devices[g]));
-      ZRET(h->d_probe[g].ensure(((size_t)count * np + count) * 4));
-      ZRET(h->d_q[g].ensure((size_t)count * h->row_bytes));
+      ZRET(h->buf[g].probe.ensure(((size_t)count * np + count) * 4));
+      ZRET(h->buf[g].q.ensure((size_t)count * h->row_bytes));
     }
     ZRET(shards_parallel(h, [&](uint32_t g) -> int {
       ZCHK(hipSetDevice(h->devices[g]));
       zvec_hip_ctx_s *c = h->ctx[g];
       hipStream_t s = c->own;
-      ZCHK(hipMemcpyAsync(h->d_q[g].p, queries, (size_t)count * h->row_bytes, hipMemcpyHostToDevice, s));
+      ZCHK(hipMemcpyAsync(h->buf[g].q.p, queries, (size_t)count * h->row_bytes, hipMemcpyHostToDevice, s));
       const uint32_t lo = std::min(count, g * per), hi = std::min(count, (g + 1) * per);
       if (hi > lo) {
-        uint32_t *idx = h->d_probe[g].as<uint32_t>() + (size_t)lo * np, *cnt = h->d_probe[g].as<uint32_t>() + (size_t)count * np + lo;
-        ZRET(zvec_hip_ivf_coarse_dev(h->ivf[g], c, h->d_q[g].as<char>() + (size_t)lo * h->row_bytes, hi - lo, nprobe, idx, cnt, s));
+        uint32_t *idx = h->buf[g].probe.as<uint32_t>() + (size_t)lo * np, *cnt = h->buf[g].probe.as<uint32_t>() + (size_t)count * np + lo;
+        ZRET(zvec_hip_ivf_coarse_dev(h->ivf[g], c, h->buf[g].q.as<char>() + (size_t)lo * h->row_bytes, hi - lo, nprobe, idx, cnt, s));
         for (uint32_t o = 0; o < h->G; ++o) {
           if (o == g) continue;
-          uint32_t *oidx = h->d_probe[o].as<uint32_t>() + (size_t)lo * np, *ocnt = h->d_probe[o].as<uint32_t>() + (size_t)count * np + lo;
+          uint32_t *oidx = h->buf[o].probe.as<uint32_t>() + (size_t)lo * np, *ocnt = h->buf[o].probe.as<uint32_t>() + (size_t)count * np + lo;
           if (h->devices[o] == h->devices[g]) {
             ZCHK(hipMemcpyAsync(oidx, idx, (size_t)(hi - lo) * np * 4, hipMemcpyDeviceToDevice, s));
             ZCHK(hipMemcpyAsync(ocnt, cnt, (size_t)(hi - lo) * 4, hipMemcpyDeviceToDevice, s));
@@ -419,9 +417,9 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
     ZCHK(hipSetDevice(h->devices[g]));
     zvec_hip_ctx_s *c = h->ctx[g];
     hipStream_t s = c->own;
-    ZRET(h->d_q[g].ensure((size_t)count * h->row_bytes));
-    ZRET(h->d_packed[g].ensure(pb));
-    if (!dealt) ZCHK(hipMemcpyAsync(h->d_q[g].p, queries, (size_t)count * h->row_bytes, hipMemcpyHostToDevice, s));
+    ZRET(h->buf[g].q.ensure((size_t)count * h->row_bytes));
+    ZRET(h->buf[g].packed.ensure(pb));
+    if (!dealt) ZCHK(hipMemcpyAsync(h->buf[g].q.p, queries, (size_t)count * h->row_bytes, hipMemcpyHostToDevice, s));
     // this shard's slice of the global exclude set
     const uint64_t *d_ex = nullptr;
     if (exclude_bitset) {
@@ -442,21 +440,21 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
       }
       std::vector<uint64_t> words((size_t)((local_n + 63) / 64) + 1, 0);
       for (const auto &r : *rs) copy_bits(exclude_bitset, r.global0, words.data(), r.local0, r.len);
-      ZRET(h->d_ex[g].ensure(words.size() * 8));
-      ZCHK(hipMemcpyAsync(h->d_ex[g].p, words.data(), words.size() * 8, hipMemcpyHostToDevice, s));
+      ZRET(h->buf[g].ex.ensure(words.size() * 8));
+      ZCHK(hipMemcpyAsync(h->buf[g].ex.p, words.data(), words.size() * 8, hipMemcpyHostToDevice, s));
       ZCHK(hipStreamSynchronize(s));     // `words` goes away
-      d_ex = h->d_ex[g].as<uint64_t>();
+      d_ex = h->buf[g].ex.as<uint64_t>();
     }
-    char *p = h->d_packed[g].as<char>();
+    char *p = h->buf[g].packed.as<char>();
     uint64_t *dk = reinterpret_cast<uint64_t *>(p);
     float *ds = reinterpret_cast<float *>(p + kb);
     uint32_t *dc = reinterpret_cast<uint32_t *>(p + kb + sb);
-    int rc = dealt ? zvec_hip_ivf_search_probes_dev(h->ivf[g], c, h->d_q[g].p, count, topk, threshold, nprobe, max_scan_count,
-                                                    h->d_probe[g].as<uint32_t>(), h->d_probe[g].as<uint32_t>() + (size_t)count * np, d_ex,
+    int rc = dealt ? zvec_hip_ivf_search_probes_dev(h->ivf[g], c, h->buf[g].q.p, count, topk, threshold, nprobe, max_scan_count,
+                                                    h->buf[g].probe.as<uint32_t>(), h->buf[g].probe.as<uint32_t>() + (size_t)count * np, d_ex,
                                                     dk, ds, dc, s)
-           : is_ivf ? zvec_hip_ivf_search_dev(h->ivf[g], c, h->d_q[g].p, count, topk, threshold, nprobe, max_scan_count, d_ex, dk, ds,
+           : is_ivf ? zvec_hip_ivf_search_dev(h->ivf[g], c, h->buf[g].q.p, count, topk, threshold, nprobe, max_scan_count, d_ex, dk, ds,
                                               dc, s)
-                    : zvec_hip_flat_search_dev(h->flat[g], c, h->d_q[g].p, count, topk, threshold, d_ex, dk, ds, dc, s);
+                    : zvec_hip_flat_search_dev(h->flat[g], c, h->buf[g].q.p, count, topk, threshold, d_ex, dk, ds, dc, s);
     if (rc != 0) return rc;
     // candidate lists -> the gather buffer on the first device (xGMI peer copy; plain D2D when the devices are equal)
     if (h->devices[g] == h->devices[0]) ZCHK(hipMemcpyAsync(gather + (size_t)g * pb, p, pb, hipMemcpyDeviceToDevice, s));
@@ -467,7 +465,7 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
   ZCHK(hipSetDevice(h->devices[0]));
   zvec_hip_ctx_s *c0 = h->ctx[0];
   if (h->G == 1) {
-    char *p = h->d_packed[0].as<char>();
+    char *p = h->buf[0].packed.as<char>();
     ZCHK(hipMemcpyAsync(out_keys, p, kb, hipMemcpyDeviceToHost, c0->own));
     ZCHK(hipMemcpyAsync(out_scores, p + kb, sb, hipMemcpyDeviceToHost, c0->own));
     ZCHK(hipMemcpyAsync(out_counts, p + kb + sb, (size_t)count * 4, hipMemcpyDeviceToHost, c0->own));

@@ -267,7 +267,7 @@ struct SearchOut {
 };
 
 // flat scan of `st` for `count` prepared queries (ctx->qpad / qnorm already filled)
-int refine_l2(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uint32_t topk, float threshold, uint64_t *keys,
+int refine_l2(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold, uint64_t *keys,
               float *scores, uint32_t *idx, uint32_t *counts, hipStream_t stream);
 
 // partial-list merges of small batches: four waves per query gather the survivors (see merge_kernel)
@@ -276,7 +276,7 @@ inline uint32_t merge_threads(uint32_t count) { return count <= 256 ? 256u : 64u
 // Sparse keep-set scan WITHOUT copying the kept rows: the wide kernel fetches the rows of a logical tile straight from
 // their stored positions (LDS-DMA with per-lane source addresses: every 128-byte row segment is still one full line).
 // `d_pos`: ascending kept positions, padded to whole tiles (+1 tile) with position 0; `kept` logical rows.
-int flat_scan_gather(zvec_hip_ctx_s *ctx, const Store &st, const uint32_t *d_pos, uint32_t kept, uint32_t count,
+int flat_scan_gather(zvec_hip_ctx_s *ctx, const StoreView &st, const uint32_t *d_pos, uint32_t kept, uint32_t count,
                      uint32_t topk, float threshold, const SearchOut &out, hipStream_t stream, bool profile_it) {
   const int cus = device_cus(ctx);
   ScanArgs a{};
@@ -340,7 +340,7 @@ int flat_scan_gather(zvec_hip_ctx_s *ctx, const Store &st, const uint32_t *d_pos
 // mode writes score[query][padded position] once into ctx->part_s (excluded and padding positions hold +inf); the
 // caller selects from the rows (merge_kernel: large k, coarse step; the group-by kernels).  The caller has sized
 // ctx->part_s for cnt rows of ceil(n / 128) * 128 floats.
-int flat_dense_scores(zvec_hip_ctx_s *ctx, const Store &st, uint32_t q0, uint32_t cnt, float threshold, const uint64_t *d_exclude,
+int flat_dense_scores(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t q0, uint32_t cnt, float threshold, const uint64_t *d_exclude,
                       hipStream_t stream, float **dump, uint32_t *dump_stride) {
   const uint64_t ntiles_d = (st.n + TILE_N - 1) / TILE_N;
   const int cus_d = device_cus(ctx);
@@ -375,7 +375,7 @@ int flat_dense_scores(zvec_hip_ctx_s *ctx, const Store &st, uint32_t q0, uint32_
 // `internal` the IVF coarse pass, the k-means labelling and the seeding pre-pass, which only need the ranking
 enum class ScanRole { internal, shadow, user };
 
-int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uint32_t topk, float threshold,
+int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold,
                        const uint64_t *d_exclude, const SearchOut &out_in, hipStream_t stream, ScanRole role) {
   const bool user_facing = role == ScanRole::user, profile_it = role != ScanRole::internal;
   SearchOut out = out_in;
@@ -434,13 +434,11 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
                          ctx->cmp_pos.as<uint32_t>(), kept, st.dpad, ctx->cmp_base.as<float>(), ctx->cmp_norm.as<float>(),
                          st.extra ? ctx->cmp_extra.as<float>() : nullptr, ctx->cmp_keys.as<uint64_t>());
       ZCHK(hipGetLastError());
-      Store tmp = st;                       // a view: same shape parameters, compacted arrays
+      StoreView tmp = st;                   // same shape parameters, compacted arrays
       tmp.base = ctx->cmp_base.as<float>(); tmp.bnorm = ctx->cmp_norm.as<float>();
       tmp.extra = st.extra ? ctx->cmp_extra.as<float>() : nullptr; tmp.keys = ctx->cmp_keys.as<uint64_t>();
-      tmp.n = kept; tmp.cap_tiles = ktiles;
-      int rc = flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, role);
-      tmp.base = nullptr; tmp.bnorm = nullptr; tmp.extra = nullptr; tmp.keys = nullptr;   // the view owns nothing
-      return rc;
+      tmp.n = kept;
+      return flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, role);
     }
   }
   // Dense-score path: the scores of a sub-batch of queries are written once to a [queries][positions] matrix by
@@ -501,9 +499,8 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
     ZRET(ctx->seed_scores.ensure((size_t)count * topk * sizeof(float)));
     ZRET(ctx->seed_counts.ensure((size_t)count * sizeof(uint32_t)));
     ZRET(ctx->seed_idx.ensure((size_t)count * topk * sizeof(uint32_t)));
-    Store view = st;                      // a view of the first SEED_ROWS rows (whole tiles of the same arrays)
-    view.n = SEED_ROWS; view.cap_tiles = SEED_ROWS / TILE_N;
-    int rc;
+    StoreView view = st;                  // the first SEED_ROWS rows (whole tiles of the same arrays)
+    view.n = SEED_ROWS;
     if (d_exclude == nullptr && (double)SEED_ROWS * 4.0 * count <= 256.0 * 1024 * 1024) {
       // no selection: the prefix's scores once (dense), then the k-th smallest of 256 disjoint minima per query (seed_bound_kernel) —
       // a bound within a rank or two of the prefix's exact k-th for a sixth of the selection's time (16 384 rows x 256 queries:
@@ -511,17 +508,13 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
       ZRET(ctx->part_s.ensure((size_t)SEED_ROWS * 4 * count));
       float *dump = nullptr;
       uint32_t dump_stride = 0;
-      rc = flat_dense_scores(ctx, view, 0, count, threshold, nullptr, stream, &dump, &dump_stride);
-      view.base = nullptr; view.bnorm = nullptr; view.extra = nullptr; view.keys = nullptr;   // the view owns nothing
-      ZRET(rc);
+      ZRET(flat_dense_scores(ctx, view, 0, count, threshold, nullptr, stream, &dump, &dump_stride));
       hipLaunchKernelGGL(seed_bound_kernel, dim3(count), dim3(256), 0, stream, dump, dump_stride, (uint32_t)SEED_ROWS, ctx->gtau.as<uint32_t>(),
                          ctx->qnorm.as<float>(), st.bnorm, st.metric, topk);
       ZCHK(hipGetLastError());
     } else {
       SearchOut so{ctx->seed_keys.as<uint64_t>(), ctx->seed_scores.as<float>(), ctx->seed_idx.as<uint32_t>(), ctx->seed_counts.as<uint32_t>()};
-      rc = flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal);
-      view.base = nullptr; view.bnorm = nullptr; view.extra = nullptr; view.keys = nullptr;   // the view owns nothing
-      ZRET(rc);
+      ZRET(flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal));
       hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
                          so.scores, so.idx, (const uint32_t *)nullptr, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
       ZCHK(hipGetLastError());
@@ -602,7 +595,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uin
 }
 
 // L2 only: direct re-scoring + re-sort of the final lists (see rescore_l2_kernel)
-int refine_l2(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uint32_t topk, float threshold, uint64_t *keys,
+int refine_l2(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold, uint64_t *keys,
               float *scores, uint32_t *idx, uint32_t *counts, hipStream_t stream) {
   if (st.metric != ZVEC_HIP_METRIC_L2) return 0;
   if ((size_t)topk * 16 + 16 > 60 * 1024) return 0;   // huge k: keep the expansion scores
@@ -619,7 +612,7 @@ int refine_l2(zvec_hip_ctx_s *ctx, const Store &st, uint32_t count, uint32_t top
   return 0;
 }
 
-int prep_queries(zvec_hip_ctx_s *ctx, const Store &st, const void *d_queries, uint32_t count, float threshold,
+int prep_queries(zvec_hip_ctx_s *ctx, const StoreView &st, const void *d_queries, uint32_t count, float threshold,
                  hipStream_t stream) {
   ZRET(ctx->qpad.ensure((size_t)count * st.dpad * sizeof(float)));
   ZRET(ctx->qnorm.ensure((size_t)count * sizeof(float)));
@@ -639,7 +632,7 @@ int prep_queries(zvec_hip_ctx_s *ctx, const Store &st, const void *d_queries, ui
 // ---- half-width pre-selection (zvk_shadow.hip.h): the steps the flat and the IVF search share ----------------------------------
 
 // the fp16 query rows of a search through `twin` and their rounding facts (ctx->sh.q16 / qn16 / qinfo)
-int shadow_prep_queries(zvec_hip_ctx_s *ctx, const Store &twin, const void *d_queries, uint32_t count, hipStream_t stream) {
+int shadow_prep_queries(zvec_hip_ctx_s *ctx, const StoreView &twin, const void *d_queries, uint32_t count, hipStream_t stream) {
   ShadowScratch &sh = ctx->sh;
   ZRET(sh.q16.ensure((size_t)count * twin.dpad * sizeof(float)));
   ZRET(sh.qn16.ensure((size_t)count * sizeof(float)));
@@ -666,7 +659,7 @@ int shadow_lists(zvec_hip_ctx_s *ctx, uint32_t count, uint32_t kp, SearchOut *pr
 
 // the k' pre-selected rows of every query (shadow_lists, in shadow-score order) -> their true scores on the fp32 rows `rows` (ctx->qpad
 // holds the prepared fp32 queries) -> the k best into `out` + the certificate, which the certify step reads back
-int shadow_rescore_select(zvec_hip_ctx_s *ctx, const Store &rows, const ShadowTwin &twin, uint32_t count, uint32_t kp, uint32_t topk,
+int shadow_rescore_select(zvec_hip_ctx_s *ctx, const StoreView &rows, const ShadowTwin &twin, uint32_t count, uint32_t kp, uint32_t topk,
                           const SearchOut &out, hipStream_t stream) {
   ShadowScratch &sh = ctx->sh;
   const size_t ck = (size_t)count * kp;
@@ -756,7 +749,7 @@ int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, s
   return 0;
 }
 
-int launch_pack(const Store &st, const void *d_rows, uint64_t n, const uint64_t *d_src, uint64_t pos0,
+int launch_pack(const StoreView &st, const void *d_rows, uint64_t n, const uint64_t *d_src, uint64_t pos0,
                 const uint64_t *d_dst, hipStream_t stream, uint64_t *keys_out = nullptr, const uint64_t *key_src = nullptr) {
   if (st.f16)
     hipLaunchKernelGGL(pack_rows_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, d_rows, n, st.dim_in,
@@ -768,7 +761,7 @@ int launch_pack(const Store &st, const void *d_rows, uint64_t n, const uint64_t 
   return 0;
 }
 
-int launch_unpack(const Store &st, uint64_t pos, void *d_out, hipStream_t stream) {
+int launch_unpack(const StoreView &st, uint64_t pos, void *d_out, hipStream_t stream) {
   if (st.f16)
     hipLaunchKernelGGL(unpack_row_kernel<true>, dim3(1), dim3(256), 0, stream, st.base, st.extra, pos, st.dscan, st.dim_in, st.dpad, d_out);
   else
@@ -778,7 +771,7 @@ int launch_unpack(const Store &st, uint64_t pos, void *d_out, hipStream_t stream
 }
 
 // rows at `n` padded positions (host array) -> host buffer, one gather launch + one copy back
-int store_get_rows(zvec_hip_ctx_s *c, const Store &st, const std::vector<uint64_t> &pos, void *out) {
+int store_get_rows(zvec_hip_ctx_s *c, const StoreView &st, const std::vector<uint64_t> &pos, void *out) {
   const size_t n = pos.size();
   if (n == 0) return 0;
   const size_t rb = st.row_bytes();
@@ -826,19 +819,6 @@ int ctx_new(int device, zvec_hip_ctx_s **out) {
   return 0;
 }
 
-void ctx_free(zvec_hip_ctx_s *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->own) (void)hipStreamSynchronize(c->own);
-  c->gtau.release(); c->ridx.release(); c->seed_keys.release(); c->seed_scores.release(); c->seed_counts.release(); c->seed_idx.release(); c->cmp_base.release(); c->cmp_norm.release(); c->cmp_extra.release(); c->cmp_keys.release(); c->cmp_pos.release(); c->cmp_cnt.release(); c->qpad.release(); c->qnorm.release(); c->part_s.release(); c->part_i.release();
-  c->coarse_keys.release(); c->coarse_scores.release(); c->coarse_idx.release(); c->coarse_cnt.release();
-  c->plan.release(); c->io_q.release(); c->io_ex.release(); c->io_out.release(); c->io_cq.release();
-  c->grp_ws.release(); c->grp_of.release(); c->grp_out.release(); c->grp_tab.release(); c->holes_ex.release(); c->direct_pos.release(); c->direct_keys.release(); c->direct_scores.release(); c->direct_idx.release(); c->direct_cnt.release(); c->stats.release(); c->sh.release(); c->pin_in.release(); c->pin_out.release(); c->done_word.release();
-  if (c->block_ev) (void)hipEventDestroy(c->block_ev);
-  for (auto e : c->ev0) (void)hipEventDestroy(e);
-  for (auto e : c->ev1) (void)hipEventDestroy(e);
-  if (c->own) (void)hipStreamDestroy(c->own);
-  delete c;
-}
+void ctx_free(zvec_hip_ctx_s *c) { delete c; }
 
 }  // namespace

@@ -69,7 +69,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     uint32_t *pb = ctx->plan.as<uint32_t>();
     dp.coarse_idx = ctx->coarse_idx.as<uint32_t>(); dp.coarse_cnt = ctx->coarse_cnt.as<uint32_t>();
     dp.nq = count; dp.nprobe = nprobe; dp.nlist = nlist; dp.max_scan_count = max_scan_count; dp.brute_force = 0;
-    dp.list_size = h->d_size; dp.list_size_global = h->d_size_global;
+    dp.list_size = h->tab.d_size.p; dp.list_size_global = h->tab.d_size_global.p;
     dp.q_nprobe = pb; dp.q_scanned = pb + count;
     d_off = pb + 2 * (size_t)count;
     if (ctx->profile && ctx->nprof < PROFILE_MAX && ctx->stats.p) {       // the slot prof_begin will take for this launch
@@ -119,7 +119,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     // 1024 candidates -> top-k lists -> the result (no refinement needed: the scores already are sum((q - b)^2))
     const uint64_t pairs = (uint64_t)count * stride;
     ZRET(ctx->direct_pos.ensure(pairs * 4));
-    hipLaunchKernelGGL(ivf_expand_direct_kernel, dim3(nprobe, count), dim3(256), 0, stream, dp, h->d_tile0, h->d_dense0,
+    hipLaunchKernelGGL(ivf_expand_direct_kernel, dim3(nprobe, count), dim3(256), 0, stream, dp, h->tab.d_tile0.p, h->tab.d_dense0.p,
                        reinterpret_cast<const uint32_t *>(d_exclude), stride, d_off, ctx->direct_pos.as<uint32_t>());
     if (!block_topk) {
       ZRET(ctx->part_s.ensure(pairs * 4));
@@ -204,7 +204,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     PlanArgs p{};
     p.coarse_idx = probe_idx; p.coarse_cnt = probe_cnt;
     p.nq = count; p.nprobe = nprobe; p.nlist = nlist; p.max_scan_count = max_scan_count; p.brute_force = brute_force;
-    p.list_size = h->d_size; p.list_size_global = h->d_size_global;
+    p.list_size = h->tab.d_size.p; p.list_size_global = h->tab.d_size_global.p;
     ZRET(ctx->plan.ensure(((size_t)2 * count + 8) * sizeof(uint32_t)));
     uint32_t *d_rows = ctx->plan.as<uint32_t>(), *d_off = d_rows + count;
     // upper bound of the rows one query scans here: the np largest local lists
@@ -217,7 +217,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     }
     if (maxlen == 0) maxlen = 1;
     if ((uint64_t)count * maxlen >= 0xffffffffull) return ZVEC_HIP_ERR_OUT_OF_RANGE;   // (slice the batch)
-    hipLaunchKernelGGL(ivf_expand_kernel<false>, dim3((count + 3) / 4), dim3(256), 0, stream, p, h->d_tile0, h->d_dense0,
+    hipLaunchKernelGGL(ivf_expand_kernel<false>, dim3((count + 3) / 4), dim3(256), 0, stream, p, h->tab.d_tile0.p, h->tab.d_dense0.p,
                        nullptr, d_rows, nullptr, nullptr);
     hipLaunchKernelGGL(u32_exclusive_scan_kernel, dim3(1), dim3(1024), 0, stream, d_rows, d_off, count, d_off + count);
     ZCHK(hipGetLastError());
@@ -226,7 +226,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     ZCHK(hipStreamSynchronize(stream));
     Scoped<uint32_t> d_pos;
     ZRET(d_pos.alloc(std::max<uint32_t>(total_rows, 1)));
-    hipLaunchKernelGGL(ivf_expand_kernel<true>, dim3((count + 3) / 4), dim3(256), 0, stream, p, h->d_tile0, h->d_dense0,
+    hipLaunchKernelGGL(ivf_expand_kernel<true>, dim3((count + 3) / 4), dim3(256), 0, stream, p, h->tab.d_tile0.p, h->tab.d_dense0.p,
                        reinterpret_cast<const uint32_t *>(d_exclude), nullptr, d_off, d_pos);
     ZCHK(hipGetLastError());
     const uint64_t pairs = (uint64_t)count * maxlen;
@@ -298,13 +298,13 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     const uint32_t nzero = (uint32_t)(o_lqoff - o_lcount);
     const uint32_t nthr = std::max<uint32_t>(std::max<uint32_t>(nzero, count), std::max<uint32_t>(nlist, 4));
     hipLaunchKernelGGL(ivf_reset_kernel, dim3((nthr + 255) / 256), dim3(256), 0, stream, pb + o_lcount, nzero, pb + o_queue,
-                       ctx->gtau.as<uint32_t>(), count, threshold, pb + o_ltpc, h->d_tail, nlist, tpc);
+                       ctx->gtau.as<uint32_t>(), count, threshold, pb + o_ltpc, h->tab.d_tail.p, nlist, tpc);
     ZCHK(hipGetLastError());
   }
   PlanArgs p{};
   p.coarse_idx = probe_idx; p.coarse_cnt = probe_cnt;
   p.nq = count; p.nprobe = nprobe; p.nlist = nlist; p.max_scan_count = max_scan_count; p.brute_force = brute_force;
-  p.list_size = h->d_size; p.list_size_global = h->d_size_global; p.list_order = h->d_order;
+  p.list_size = h->tab.d_size.p; p.list_size_global = h->tab.d_size_global.p; p.list_order = h->tab.d_order.p;
   p.list_tpc = pb + o_ltpc;
   p.rows_per_group = rows_per_group;
   p.q_nprobe = pb + o_qnprobe; p.q_scanned = pb + o_qscanned; p.q_nslots = pb + o_qnslots; p.slot_begin = pb + o_slotbegin;
@@ -344,7 +344,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   ZRET(ctx->part_s.ensure(slots_bound * ks * sizeof(float)));
   ZRET(ctx->part_i.ensure(slots_bound * ks * sizeof(uint32_t)));
 
-  const Store &sst = use_shadow ? tw.st : h->lists;                      // the store the list scan streams
+  const StoreView &sst = use_shadow ? tw.st : h->lists;                      // the store the list scan streams
   ScanArgs a{};
   a.base = sst.base; a.bnorm = sst.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
   a.queries = ctx->qpad.as<float>(); a.qnorm = ctx->qnorm.as<float>();
@@ -355,8 +355,8 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   a.dpad = sst.dpad; a.nks = sst.dpad / TILE_K; a.metric = h->metric; a.k = ks; a.threshold = threshold;
   a.gtau = ctx->gtau.as<uint32_t>();
   a.mode = 1; a.nq = count; a.n = h->lists.n; a.ndense = h->count_local; a.tiles_per_chunk = tpc; a.list_tpc = pb + o_ltpc;
-  a.total_items = p.total_items; a.queue = pb + o_queue; a.list_order = h->d_order; a.item_off = p.item_off; a.list_tile0 = h->d_tile0; a.list_size = h->d_size;
-  a.list_dense0 = h->d_dense0; a.list_qoff = p.list_qoff; a.csr_q = p.csr_q; a.csr_slot = p.csr_slot; a.nlist = nlist;
+  a.total_items = p.total_items; a.queue = pb + o_queue; a.list_order = h->tab.d_order.p; a.item_off = p.item_off; a.list_tile0 = h->tab.d_tile0.p; a.list_size = h->tab.d_size.p;
+  a.list_dense0 = h->tab.d_dense0.p; a.list_qoff = p.list_qoff; a.csr_q = p.csr_q; a.csr_slot = p.csr_slot; a.nlist = nlist;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
   // algorithmic bytes of the list scan = rows of the DISTINCT probed lists (counted on device from
   // the plan: plan_scan_kernel's work_stats) + the query rows + the result lists

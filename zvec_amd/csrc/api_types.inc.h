@@ -22,18 +22,39 @@ namespace {
 constexpr size_t LDS_LIMIT = 160 * 1024;
 constexpr int PROFILE_MAX = 8192;
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = bytes + bytes / 4 + 256;
-    ZCHK(hipMalloc(&p, want));
-    cap = want;
+// The one place device memory is allocated and freed: a typed hipMalloc block that its destructor gives back.  Move-only (a move
+// assignment hands the old block to the source, which frees it when it goes); as a local it is the device temporary of a function,
+// freed on every exit path.
+template <typename T>
+struct Scoped {
+  T *p = nullptr;
+  size_t cap = 0;        // bytes
+  Scoped() {}
+  Scoped(Scoped &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  Scoped &operator=(Scoped &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~Scoped() { release(); }
+  int alloc_bytes(size_t bytes) {
+    release();
+    ZCHK(hipMalloc(reinterpret_cast<void **>(&p), bytes));
+    cap = bytes;
     return 0;
   }
+  int alloc(size_t count) { return alloc_bytes(count * sizeof(T)); }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  operator T *() const { return p; }
+};
+
+// a host table as a device array of its own (a blocking copy)
+template <typename T>
+int upload(Scoped<T> &d, const T *src, size_t n) {
+  ZRET(d.alloc(std::max<size_t>(n, 1)));
+  ZCHK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// workspace that grows on demand and keeps what it has grown to
+struct DevBuf : Scoped<void> {
+  int ensure(size_t bytes) { return bytes <= cap ? 0 : alloc_bytes(bytes + bytes / 4 + 256); }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -49,9 +70,13 @@ struct PinnedBuf {
   void *p = nullptr;
   void *dev = nullptr;   // the same bytes as the device addresses them (host-mapped: kernels read / write the slot in place)
   size_t cap = 0;
+  PinnedBuf() {}
+  PinnedBuf(PinnedBuf &&o) noexcept { *this = std::move(o); }
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept { std::swap(p, o.p); std::swap(dev, o.dev); std::swap(cap, o.cap); return *this; }
+  ~PinnedBuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) { (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
+    release();
     size_t want = bytes + bytes / 4 + 256;
     ZCHK(hipHostMalloc(&p, want, hipHostMallocMapped));
     if (hipHostGetDevicePointer(&dev, p, 0) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; }
@@ -86,21 +111,6 @@ inline RuntimeOpts &ropts() {
   static RuntimeOpts o;
   return o;
 }
-
-// scope-owned device temporary: freed on every exit path of the enclosing function
-template <typename T>
-struct Scoped {
-  T *p = nullptr;
-  Scoped() {}
-  Scoped(const Scoped &) = delete;
-  Scoped &operator=(const Scoped &) = delete;
-  ~Scoped() { if (p) (void)hipFree(p); }
-  int alloc(size_t count) {
-    ZCHK(hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T)));
-    return 0;
-  }
-  operator T *() const { return p; }
-};
 
 // reader/writer lock that cannot starve the writer (std::shared_mutex on glibc prefers readers: searches that overlap
 // continuously would keep an append waiting): everybody passes a gate, a writer keeps it while the readers drain
@@ -165,8 +175,10 @@ struct ShadowGovernor {
   }
 };
 
-// a blocked, HBM-resident set of rows (flat store, IVF centroids, IVF inverted lists)
-struct Store {
+// What a scan reads of a blocked, HBM-resident set of rows (flat store, IVF centroids, IVF inverted lists, the fp16 twin): its shape
+// and where its arrays are.  Owns nothing and copies freely: the compacted keep-set, the seeding prefix and the twin's rows under the
+// store's keys are plain values of it with the fields they override.
+struct StoreView {
   uint32_t dim_in = 0;   // element dimension at the ABI (cosine: d+1)
   uint32_t dscan = 0;    // scanned dims
   uint32_t dpad = 0;     // 4-byte WORDS per stored row, multiple of 32 (fp32: dscan up to 32; fp16: dscan up to 64, halved)
@@ -174,7 +186,6 @@ struct Store {
   bool f16 = false;
   int metric = 0;
   uint64_t n = 0;        // padded positions in use
-  uint64_t cap_tiles = 0;
   float *base = nullptr;
   float *bnorm = nullptr;
   float *extra = nullptr;   // cosine: stored norm column
@@ -190,79 +201,95 @@ struct Store {
     dpad = f16 ? ((dscan + 63) / 64 * 64) / 2 : (dscan + TILE_K - 1) / TILE_K * TILE_K;
   }
   size_t row_bytes() const { return (size_t)dim_in * elem; }
+};
+
+// The rows an index owns: the view every reader takes (a Store converts to its StoreView), and the four arrays behind the view's
+// pointers.  Neither copied nor moved.
+struct Store : StoreView {
+  uint64_t cap_tiles = 0;
+  Store() {}
+  Store(const Store &) = delete;
+
   int reserve(uint64_t rows, hipStream_t stream) {
     uint64_t tiles = (rows + TILE_N - 1) / TILE_N;
     if (tiles <= cap_tiles) return 0;
     uint64_t nt = std::max<uint64_t>(tiles, cap_tiles + cap_tiles / 2 + 1);
-    float *nb = nullptr, *nn = nullptr, *ne = nullptr;
-    uint64_t *nk = nullptr;
-    ZCHK(hipMalloc(&nb, (size_t)nt * TILE_N * dpad * sizeof(float)));
-    ZCHK(hipMalloc(&nn, (size_t)nt * TILE_N * sizeof(float)));
-    ZCHK(hipMalloc(&nk, (size_t)nt * TILE_N * sizeof(uint64_t)));
-    if (metric == ZVEC_HIP_METRIC_COSINE) ZCHK(hipMalloc(&ne, (size_t)nt * TILE_N * sizeof(float)));
+    Arrays grown;
+    ZRET(grown.base.alloc((size_t)nt * TILE_N * dpad));
+    ZRET(grown.bnorm.alloc((size_t)nt * TILE_N));
+    ZRET(grown.keys.alloc((size_t)nt * TILE_N));
+    if (metric == ZVEC_HIP_METRIC_COSINE) ZRET(grown.extra.alloc((size_t)nt * TILE_N));
     uint64_t used_tiles = (n + TILE_N - 1) / TILE_N;
     if (used_tiles) {
-      ZCHK(hipMemcpyAsync(nb, base, (size_t)used_tiles * TILE_N * dpad * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      ZCHK(hipMemcpyAsync(nn, bnorm, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      ZCHK(hipMemcpyAsync(nk, keys, (size_t)used_tiles * TILE_N * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-      if (ne) ZCHK(hipMemcpyAsync(ne, extra, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      ZCHK(hipMemcpyAsync(grown.base, base, (size_t)used_tiles * TILE_N * dpad * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      ZCHK(hipMemcpyAsync(grown.bnorm, bnorm, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      ZCHK(hipMemcpyAsync(grown.keys, keys, (size_t)used_tiles * TILE_N * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+      if (grown.extra) ZCHK(hipMemcpyAsync(grown.extra, extra, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
       ZCHK(hipStreamSynchronize(stream));
     }
-    release();
-    base = nb; bnorm = nn; keys = nk; extra = ne; cap_tiles = nt;
+    std::swap(own, grown);               // the old arrays go with `grown` on return: hipFree waits for the device
+    point_at_own();
+    cap_tiles = nt;
     return 0;
   }
   void release() {
-    if (base) (void)hipFree(base);
-    if (bnorm) (void)hipFree(bnorm);
-    if (extra) (void)hipFree(extra);
-    if (keys) (void)hipFree(keys);
-    base = bnorm = extra = nullptr; keys = nullptr; cap_tiles = 0;
+    own = Arrays();
+    point_at_own();
+    cap_tiles = 0;
   }
+
+ private:
+  struct Arrays {
+    Scoped<float> base, bnorm, extra;
+    Scoped<uint64_t> keys;
+  } own;
+  void point_at_own() { base = own.base; bnorm = own.bnorm; extra = own.extra; keys = own.keys; }
 };
 
 // fp16 twin of an fp32 store at the same positions (own base + bnorm; keys / geometry are the store's): the half-width
 // pre-selection of zvec_hip_flat_set_shadow / zvec_hip_ivf_set_shadow (zvk_shadow.hip.h).  Built for the rows present at that
 // moment; an index drops it when its rows change.
 struct ShadowTwin {
-  Store st;
+  StoreView st;                        // its rows as a scan reads them (keys and `extra` are never its own: null here)
   bool on = false;
   uint32_t kp = 0;                     // rows pre-selected per query (0: sized by the governor)
-  ShadowFacts *facts = nullptr;        // device
+  Scoped<ShadowFacts> facts;           // device
   float max_err = 0.f, max_norm = 0.f;
   ShadowGovernor gov;
 
   void drop() {
-    st.keys = nullptr; st.extra = nullptr;      // (never its own)
-    st.release();
-    st.n = 0;
-    if (facts) (void)hipFree(facts);
-    facts = nullptr;
+    base.release(); bnorm.release(); facts.release();
+    st = StoreView();
     on = false;
   }
   // the twin of src's positions [0, n) (whole tiles of them).  Flat store (tile0 == nullptr): its first `rows` positions are rows;
   // IVF lists: every list's first size[l] positions from tile0[l] on.  The other positions become zero rows and feed no fact.
-  int build(const Store &src, uint64_t n, uint64_t rows, const uint32_t *tile0, const uint32_t *size, uint32_t nlist,
+  // Ends with on == true, or holding nothing.
+  int build(const StoreView &src, uint64_t n, uint64_t rows, const uint32_t *tile0, const uint32_t *size, uint32_t nlist,
             uint32_t preselect, hipStream_t s) {
-    st = Store();
-    st.configure(src.dim_in, src.metric, ZVEC_HIP_DT_FP16);
-    const uint64_t tiles = (n + TILE_N - 1) / TILE_N;
-    if (hipMalloc(&st.base, (size_t)tiles * TILE_N * st.dpad * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); st.base = nullptr; return ZVEC_HIP_ERR_NO_MEMORY; }
-    if (hipMalloc(&st.bnorm, (size_t)tiles * TILE_N * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); drop(); return ZVEC_HIP_ERR_NO_MEMORY; }
-    if (hipMalloc(&facts, sizeof(ShadowFacts)) != hipSuccess) { (void)hipGetLastError(); drop(); return ZVEC_HIP_ERR_NO_MEMORY; }
-    st.cap_tiles = tiles;
-    st.n = n;
-    ZCHK(hipMemsetAsync(facts, 0, sizeof(ShadowFacts), s));
-    const uint64_t npos = tiles * TILE_N;
-    hipLaunchKernelGGL(shadow_rows_kernel, dim3((unsigned)((npos + 3) / 4)), dim3(256), 0, s, src.base, src.dpad, st.dscan, st.base,
-                       st.dpad, st.bnorm, npos, tile0, size, nlist, rows, facts);
+    drop();
+    StoreView v;
+    v.configure(src.dim_in, src.metric, ZVEC_HIP_DT_FP16);
+    const uint64_t tiles = (n + TILE_N - 1) / TILE_N, npos = tiles * TILE_N;
+    Scoped<float> nb, nn;
+    Scoped<ShadowFacts> nf;
+    if (nb.alloc((size_t)npos * v.dpad) != 0 || nn.alloc(npos) != 0 || nf.alloc(1) != 0) {
+      (void)hipGetLastError();         // (the index goes on searching its own rows)
+      return ZVEC_HIP_ERR_NO_MEMORY;
+    }
+    ZCHK(hipMemsetAsync(nf, 0, sizeof(ShadowFacts), s));
+    hipLaunchKernelGGL(shadow_rows_kernel, dim3((unsigned)((npos + 3) / 4)), dim3(256), 0, s, src.base, src.dpad, v.dscan, nb.p,
+                       v.dpad, nn.p, npos, tile0, size, nlist, rows, nf.p);
     ZCHK(hipGetLastError());
     ShadowFacts f{};
-    ZCHK(hipMemcpyAsync(&f, facts, sizeof(f), hipMemcpyDeviceToHost, s));
+    ZCHK(hipMemcpyAsync(&f, nf, sizeof(f), hipMemcpyDeviceToHost, s));
     ZCHK(hipStreamSynchronize(s));
-    if (!(__builtin_bit_cast(float, f.max_abs) < 65504.f)) { drop(); return ZVEC_HIP_ERR_UNSUPPORTED; }     // rows beyond the half range (or nan)
+    if (!(__builtin_bit_cast(float, f.max_abs) < 65504.f)) return ZVEC_HIP_ERR_UNSUPPORTED;     // rows beyond the half range (or nan)
     max_err = __builtin_bit_cast(float, f.max_err);
     max_norm = __builtin_bit_cast(float, f.max_norm);
+    base = std::move(nb); bnorm = std::move(nn); facts = std::move(nf);
+    v.n = n; v.base = base; v.bnorm = bnorm;
+    st = v;
     kp = preselect;
     gov.reset();
     on = true;
@@ -270,7 +297,7 @@ struct ShadowTwin {
   }
   void info(int *enabled, uint64_t *bytes, float *max_row_error, float *max_row_norm) const {
     if (enabled) *enabled = on ? 1 : 0;
-    if (bytes) *bytes = on ? (uint64_t)st.cap_tiles * TILE_N * (st.dpad + 1) * sizeof(float) : 0;
+    if (bytes) *bytes = on ? (st.n + TILE_N - 1) / TILE_N * TILE_N * (st.dpad + 1) * sizeof(float) : 0;
     if (max_row_error) *max_row_error = on ? max_err : 0.f;
     if (max_row_norm) *max_row_norm = on ? max_norm : 0.f;
   }
@@ -279,6 +306,9 @@ struct ShadowTwin {
     return std::min<uint32_t>(64, forced ? forced : kp ? kp : gov.kp_auto(topk));     // (shadow_select_kernel: one candidate per lane)
   }
   uint32_t width(uint32_t topk) const { return on ? pick_kp(0, topk) : 0; }
+
+ private:
+  Scoped<float> base, bnorm;           // behind st.base / st.bnorm
 };
 
 // How a search may use its index's twin: as the index decides, at a forced width (the certify step's second pass over the
@@ -296,10 +326,6 @@ struct ShadowScratch {
   uint32_t kp = 0;                     // width that search used
   uint32_t topk = 0;                   // its k
   const ShadowTwin *owner = nullptr;   // the twin it went through: a certify step of another index (or another k) is refused
-  void release() {
-    q16.release(); qn16.release(); qinfo.release(); keys.release(); scores.release(); rescored.release(); idx.release();
-    counts.release(); flags.release();
-  }
 };
 
 }  // namespace
@@ -352,6 +378,15 @@ struct zvec_hip_ctx_s {
   std::vector<uint32_t> prof_dscan;
   int nprof = 0;
   int cus = 0;
+  // (the workspace members free themselves afterwards)
+  ~zvec_hip_ctx_s() {
+    (void)hipSetDevice(device);
+    if (own) (void)hipStreamSynchronize(own);
+    if (block_ev) (void)hipEventDestroy(block_ev);
+    for (auto e : ev0) (void)hipEventDestroy(e);
+    for (auto e : ev1) (void)hipEventDestroy(e);
+    if (own) (void)hipStreamDestroy(own);
+  }
 };
 
 struct zvec_hip_flat_s {
@@ -394,6 +429,13 @@ struct zvec_hip_flat_s {
   bool ring_used[RING / RING_GROUP] = {};
   uint32_t ring_next = 0;
   bool is_hole(uint64_t pos) const { return (pos >> 6) < h_holes.size() && ((h_holes[pos >> 6] >> (pos & 63)) & 1ull); }
+  // (zvec_hip_flat_destroy has made the device current and idle)
+  ~zvec_hip_flat_s() {
+    for (uint32_t i = 0; i < RING / RING_GROUP; ++i)
+      if (ring_used[i]) (void)hipEventDestroy(ring_ev[i]);
+    if (append_ev) (void)hipEventDestroy(append_ev);
+    delete defctx;
+  }
 };
 
 struct zvec_hip_ivf_s {
@@ -418,11 +460,14 @@ struct zvec_hip_ivf_s {
   std::vector<uint64_t> h_dense0;      // local dense offsets (nlist+1)
   std::vector<uint64_t> h_row_ids;     // local dense position -> original row
   std::vector<char> h_centroids;       // [nlist][dim] in the index element type
-  uint32_t *d_size = nullptr, *d_size_global = nullptr, *d_tile0 = nullptr, *d_order = nullptr, *d_tail = nullptr;
+  struct Tables {                      // the list tables on the device: built whole by ivf_end_lists, replaced whole
+    Scoped<uint32_t> d_size, d_size_global, d_tile0, d_order, d_tail;
+    Scoped<uint64_t> d_dense0;
+  } tab;
   uint32_t tiles_per_chunk = 8;
   std::vector<uint32_t> h_tail;        // 1 = list belongs to the tail of the deal order (shorter chunks)
   uint64_t local_tiles = 0;            // tiles of the lists held by this shard
-  uint64_t *d_dense0 = nullptr;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;
+  ~zvec_hip_ivf_s() { delete defctx; }
 };
