@@ -155,3 +155,260 @@ def flat_search_dev(se, q, k, ctx=None, exclude_words=None):
     assert se.shadow_certify(*args, d_exclude=ex) == 0
     torch.cuda.synchronize()
     return _host_lists(keys, scores, counts) + (rerun,)
+
+
+# ---- labelling reference of the IVF build tests (test_gpu_label_parity.py, test_gpu_build.py, test_label_reference_cpu.py) -------
+_METRIC_IDS = {"SquaredEuclidean": 0, "InnerProduct": 1, "Cosine": 2, 0: 0, 1: 1, 2: 2}
+
+
+def label_scan_width(dim, dtype, metric="SquaredEuclidean"):
+    """(scanned dims, padded scan width) of a centroid store: cosine rows end with their norm (one float, or two half slots),
+    which is not scanned; the scan is padded to the k-step, 32 floats or 64 halves (StoreView::configure)."""
+    half = np.dtype(dtype) == np.float16
+    dscan = dim - ((2 if half else 1) if _METRIC_IDS[metric] == 2 else 0)
+    step = 64 if half else 32
+    return dscan, (dscan + step - 1) // step * step
+
+
+def label_reference(cent, rows, metric="SquaredEuclidean", ignore=(), chunk=None):
+    """Nearest-centroid labelling in plain fp64, with the error bound a correct fp32 kernel may use up.
+
+    Returns (s64 [n][nlist], arg [n], gap [n], E [n][nlist]):
+      s64   L2: sum((x - c)^2) summed directly; InnerProduct: -x.c; Cosine: 1 - x.c over the scanned dims
+      arg   fp64 arg-min, the FIRST minimum on ties (numpy's argmin)
+      gap   runner-up score minus the minimum, per row (+inf with one centroid)
+      E     per-pair bound on |kernel score - s64|
+    Centroid ids in `ignore` are left out of arg / gap (their score counts as +inf): a centroid copied to a LATER id sees the same
+    arithmetic as the original and must never be returned, so it is no competitor.
+
+    The bound is derived, not tuned.  The kernels multiply exactly (fp32 operands through v_mfma_f32_32x32x2f32; a product of two
+    halves has 22 significant bits) and accumulate in fp32 in SOME order, so with u = 2^-24 a length-d sum of terms t_i is off by
+    at most gamma_d * sum|t_i|, gamma_d ~ d u.  For gamma the project's own accumulation slack is taken, (d + 8) 2^-23 with d the
+    PADDED scan width (zvk_shadow.hip.h: twice the textbook bound, because the order inside the matrix cores is not documented).
+      InnerProduct  score = -dot: one sum of d exact products, the final fused multiply-add by -1 is exact
+                      E = gamma * sum|x_i||c_i|
+      L2            score = fma(-2, dot, |x|^2 + |c|^2): the two norms are fp32 sums of d squares (gamma |x|^2, gamma |c|^2), the
+                    dot carries 2 gamma sum|x_i c_i|, the addition of the norms and the fma one rounding each, of values no larger
+                    than (|x| + |c|)^2.  With sum|x_i c_i| <= |x||c| all of it is inside
+                      E = gamma * (|x| + |c|)^2       (the "+ 8" of gamma pays for the two roundings)
+                    The 256-tile kernel compares |c|^2 - 2 x.c, which drops |x|^2 and its error: the same E covers it.  A score
+                    clamped at 0 moved towards the true (non-negative) value.
+      Cosine        score = fma(-1, dot, 1): the inner-product bound plus one rounding of a value of at most 1 + sum|x_i c_i|
+                      E = gamma * sum|x_i||c_i| + 2^-24 (1 + sum|x_i||c_i|)
+    Acceptance (label_accept): label g of row x is right iff s64(x, g) - min_j s64(x, j) <= E(x, g) + E(x, argmin): the kernel
+    saw g no worse than the arg-min, each off by its own bound at most.  A row is AMBIGUOUS when its gap is within E(x, argmin)
+    + E(x, runner-up); only such rows may be labelled differently from arg."""
+    m = _METRIC_IDS[metric]
+    c64 = np.asarray(cent).astype(np.float64)
+    x64 = np.asarray(rows).astype(np.float64)
+    dscan, dpad = label_scan_width(c64.shape[1], np.asarray(cent).dtype, m)
+    c64, x64 = c64[:, :dscan], x64[:, :dscan]
+    n, nlist = x64.shape[0], c64.shape[0]
+    gamma = (dpad + 8) * 2.0 ** -23
+    s64 = np.empty((n, nlist))
+    E = np.empty((n, nlist))
+    cn = np.sqrt((c64 ** 2).sum(1))
+    ca = np.abs(c64)
+    step = chunk or max(1, (1 << 22) // max(1, nlist * dscan))
+    for o in range(0, n, step):
+        x = x64[o:o + step]
+        if m == 0:
+            d = x[:, None, :] - c64[None]
+            s64[o:o + step] = np.einsum("ijk,ijk->ij", d, d)
+            E[o:o + step] = gamma * (np.sqrt((x ** 2).sum(1))[:, None] + cn[None]) ** 2
+        else:
+            dot = np.einsum("ik,jk->ij", x, c64)
+            mag = np.einsum("ik,jk->ij", np.abs(x), ca)
+            s64[o:o + step] = -dot if m == 1 else 1.0 - dot
+            E[o:o + step] = gamma * mag + (2.0 ** -24 * (1.0 + mag) if m == 2 else 0.0)
+    comp = s64.copy()
+    if len(ignore):
+        comp[:, list(ignore)] = np.inf
+    arg = comp.argmin(1)
+    if nlist - len(ignore) > 1:
+        two = np.partition(comp, 1, axis=1)[:, :2]
+        gap = two[:, 1] - two[:, 0]
+    else:
+        gap = np.full(n, np.inf)
+    return s64, arg, gap, E
+
+
+def label_runner_up(s64, arg, ignore=()):
+    comp = s64.copy()
+    if len(ignore):
+        comp[:, list(ignore)] = np.inf
+    comp[np.arange(len(arg)), arg] = np.inf
+    return comp.argmin(1)
+
+
+def label_ambiguous(s64, arg, gap, E, ignore=()):
+    """rows whose fp64 runner-up gap is within the two bounds: the only rows a correct kernel may label differently from arg"""
+    if s64.shape[1] - len(ignore) < 2:
+        return np.zeros(len(arg), bool)
+    i = np.arange(len(arg))
+    return gap <= E[i, arg] + E[i, label_runner_up(s64, arg, ignore)]
+
+
+def label_accept(s64, arg, E, labels):
+    """the acceptance rule, per row; a label outside [0, nlist) is never accepted"""
+    lab = np.asarray(labels).astype(np.int64)
+    ok = (lab >= 0) & (lab < s64.shape[1])
+    g = np.where(ok, lab, 0)
+    i = np.arange(len(arg))
+    return ok & (s64[i, g] - s64[i, arg] <= E[i, g] + E[i, arg])
+
+
+def check_labels(cent, rows, metric, labels, ignore=(), cap=0.01, what="", ref=None):
+    """every label accepted, none of them an ignored (duplicate) id, no more differences from the fp64 arg-min than there are
+    ambiguous rows, and (cap not None) at most `cap` of the rows ambiguous — a condition on the inputs.  Returns the reference."""
+    ref = ref or label_reference(cent, rows, metric, ignore)
+    s64, arg, gap, E = ref
+    lab = np.asarray(labels).astype(np.int64)
+    acc = label_accept(s64, arg, E, lab)
+    bad = np.nonzero(~acc)[0]
+    assert bad.size == 0, "%s: %d labels outside the band, first rows %r got %r want %r excess %r" % (
+        what, bad.size, bad[:6], lab[bad[:6]], arg[bad[:6]],
+        [float(s64[i, lab[i]] - s64[i, arg[i]] - E[i, lab[i]] - E[i, arg[i]]) if 0 <= lab[i] < s64.shape[1] else None for i in bad[:6]])
+    for d in ignore:
+        assert (lab != d).all(), "%s: the duplicate centroid %d was returned" % (what, d)
+    amb = label_ambiguous(s64, arg, gap, E, ignore)
+    ndiff = int((lab != arg).sum())
+    assert ndiff <= int(amb.sum()), "%s: %d labels differ from the fp64 arg-min, only %d rows are ambiguous" % (what, ndiff, amb.sum())
+    if cap is not None:
+        assert amb.sum() <= cap * len(arg), "%s: %d of %d rows ambiguous: badly chosen inputs" % (what, amb.sum(), len(arg))
+    return ref
+
+
+# the inputs of the labelling cases: seeded, so that the CPU test of the helper sees what the GPU sees
+LABEL_TILE_SCALES = (1.0, 30.0, 0.5, 20.0, 2.0, 50.0, 1.0, 10.0)      # neighbouring 128-centroid tiles differ 10-100x in norm
+# (index type, kind of centroids): the large-magnitude case exists for fp16 rows only
+LABEL_KINDS = [("fp32", "means"), ("fp32", "tiles"), ("fp16", "means"), ("fp16", "tiles"), ("fp16", "big")]
+LABEL_NEAR_EVERY = 4                   # every 4th row of a case is moved next to the bisector of its two nearest centroids ...
+LABEL_NEAR_BAND = (3.0, 30.0)          # ... to a runner-up gap of this many times E(x, arg) + E(x, runner-up)
+
+
+def label_steer(cent, x, sel, metric, ignore, rng, rounds=4):
+    """Moves the rows `sel` of x (in place) along c_a - c_b, a and b their two nearest centroids, until the fp64 runner-up gap
+    is k (E(x, a) + E(x, b)) with k log-uniform in 6..15.  Clustered rows alone have gaps thousands of times the band, where an
+    error far larger than the band flips nothing; these rows are decided by the band: a kernel whose scores are off by much
+    more than 30 bands (half-precision accumulation is ~4000) labels many of them wrongly and outside the acceptance rule,
+    while none is ambiguous (3 bands away at least).  The gap is linear in x along c_a - c_b (L2: 2 x.(c_a - c_b) + const,
+    InnerProduct / Cosine: x.(c_a - c_b)), so one move lands on the target; it is repeated because the pair, the band and (for
+    unit rows, which are renormalised) the gap change a little with the move, and because x is rounded to its own type.  That
+    last rounding moves the gap by less than a band or so, which is why k stays well inside LABEL_NEAR_BAND."""
+    m = _METRIC_IDS[metric]
+    sel = np.asarray(sel)
+    c64 = np.asarray(cent).astype(np.float64)
+    dscan, dpad = label_scan_width(c64.shape[1], np.asarray(cent).dtype, m)
+    c64 = c64[:, :dscan]
+    if sel.size == 0 or c64.shape[0] - len(ignore) < 2:
+        return
+    gamma = (dpad + 8) * 2.0 ** -23
+    cn2 = (c64 ** 2).sum(1)
+    k = np.exp(rng.uniform(np.log(6.0), np.log(15.0), sel.size))
+    for _ in range(rounds):
+        xs = x[sel, :dscan].astype(np.float64)
+        sc = -(xs @ c64.T) if m else cn2[None] - 2.0 * (xs @ c64.T)          # ranks the centroids; the gap itself is direct
+        if len(ignore):
+            sc[:, list(ignore)] = np.inf
+        two = np.argpartition(sc, 1, axis=1)[:, :2]
+        i = np.arange(sel.size)
+        swap = sc[i, two[:, 0]] > sc[i, two[:, 1]]
+        a, b = np.where(swap, two[:, 1], two[:, 0]), np.where(swap, two[:, 0], two[:, 1])
+        delta = c64[a] - c64[b]
+        if m == 0:
+            g = ((xs - c64[b]) ** 2).sum(1) - ((xs - c64[a]) ** 2).sum(1)
+            xn = np.sqrt((xs ** 2).sum(1))
+            band = gamma * ((xn + np.sqrt(cn2[a])) ** 2 + (xn + np.sqrt(cn2[b])) ** 2)
+        else:
+            g = (xs * delta).sum(1)
+            mag = (np.abs(xs) * (np.abs(c64[a]) + np.abs(c64[b]))).sum(1)
+            band = gamma * mag + (2.0 ** -24 * (2.0 + mag) if m == 2 else 0.0)
+        slope = (1.0 if m else 2.0) * (delta ** 2).sum(1)
+        t = np.where(slope > 0, (k * band - g) / np.where(slope > 0, slope, 1.0), 0.0)
+        xs += t[:, None] * delta
+        if m == 2:
+            xs /= np.sqrt((xs ** 2).sum(1, keepdims=True))
+        x[sel, :dscan] = xs.astype(x.dtype)
+
+
+def label_near_share(s64, arg, gap, E, ignore=()):
+    """share of the rows whose runner-up gap is LABEL_NEAR_BAND times the band: the rows that decide"""
+    if s64.shape[1] - len(ignore) < 2:
+        return 0.0
+    i = np.arange(len(arg))
+    r = gap / (E[i, arg] + E[i, label_runner_up(s64, arg, ignore)])
+    return float(((r >= LABEL_NEAR_BAND[0]) & (r <= LABEL_NEAR_BAND[1])).mean())
+
+
+def label_case(rows, nlist, dim, dtype, kind, metric="SquaredEuclidean", seed=0, near=True):
+    """(centroids, rows, ignore) of one labelling case: clustered Gaussians, rows = a centroid's mean + noise, every
+    LABEL_NEAR_EVERY-th of them then moved next to the bisector of its two nearest centroids (label_steer; near=False: none).
+    kind "means": the centroids are the means rounded to the index type; "tiles": the means of every 128-centroid tile are
+    scaled by LABEL_TILE_SCALES first (a stale accumulator or norm at a tile boundary shows only when magnitudes differ);
+    "big": elements up to ~1e3 (norms ~1e8: the fp32 norm path, not the half range).  With three or more centroids the last one
+    is a copy of centroid 1 and is returned in `ignore`.  Cosine: unit rows followed by the norm slot(s) of the converted row."""
+    npdt = np.dtype(dtype)
+    m = _METRIC_IDS[metric]
+    dscan, _ = label_scan_width(dim, npdt, m)
+    rng = np.random.default_rng([seed, rows, nlist, dim, m, npdt.itemsize, ("means", "tiles", "big").index(kind)])
+    means = rng.standard_normal((nlist, dscan))
+    if kind == "tiles":
+        means *= np.asarray(LABEL_TILE_SCALES)[(np.arange(nlist) // 128) % len(LABEL_TILE_SCALES)][:, None]
+    if kind == "big":
+        means = np.clip(means * 300.0, -900.0, 900.0)
+    own = rng.integers(0, nlist, rows)
+    scale = np.abs(means).mean(1, keepdims=True)[own] if dscan else 1.0
+    x = means[own] + 0.3 * scale * rng.standard_normal((rows, dscan))
+
+    def finish(a):
+        if m != 2:
+            return np.ascontiguousarray(a.astype(npdt))
+        norm = np.sqrt((a ** 2).sum(1, keepdims=True))
+        unit = (a / norm).astype(npdt)
+        slot = norm.astype(np.float32)
+        tail = slot.view(np.float16) if npdt == np.float16 else slot       # fp16 rows: the fp32 norm's bits in two half slots
+        return np.ascontiguousarray(np.concatenate([unit, tail], 1))
+    cent, x = finish(means), finish(x)
+    ignore = ()
+    if nlist >= 3:
+        cent[nlist - 1] = cent[1]
+        ignore = (nlist - 1,)
+    if near:
+        label_steer(cent, x, np.arange(LABEL_NEAR_EVERY - 1, rows, LABEL_NEAR_EVERY), m, ignore, rng)
+    return cent, x, ignore
+
+
+# (rows, centroids, dim): which step count, tile and path each shape hits is tabulated in tests/test_gpu_label_parity.py
+LABEL_SHAPES = [
+    (1, 1, 1), (127, 2, 31), (128, 63, 32), (129, 64, 33), (511, 127, 64), (512, 128, 65), (513, 129, 100), (767, 191, 128),
+    (512, 192, 65), (513, 193, 128), (1025, 255, 129), (767, 256, 100), (511, 256, 128), (1025, 383, 31), (640, 383, 65),
+    (600, 385, 129), (2500, 385, 64), (4000, 1000, 33), (2049, 1000, 100), (3000, 257, 768),
+]
+
+
+def label_offset_case(offset, dtype, rows=3000, nlist=256, dim=128, seed=7):
+    """rows = a common offset + unit-variance spread (cluster means 0.8, noise 0.6), centroids = offset + the cluster means:
+    the norm expansion |x|^2 + |c|^2 - 2 x.c cancels ~offset^2 dim to reach distances of ~dim"""
+    npdt = np.dtype(dtype)
+    rng = np.random.default_rng([seed, int(offset), npdt.itemsize])
+    means = 0.8 * rng.standard_normal((nlist, dim))
+    x = means[rng.integers(0, nlist, rows)] + 0.6 * rng.standard_normal((rows, dim))
+    return np.ascontiguousarray((means + offset).astype(npdt)), np.ascontiguousarray((x + offset).astype(npdt))
+
+
+def label_batch_case(rows, nlist, dim, dtype, seed=9, block=4096):
+    """a row set longer than one labelling batch: a small seeded block of clustered rows, tiled, every row with its own small
+    perturbation (no two rows equal), every LABEL_NEAR_EVERY-th row of every block then moved next to a bisector (label_steer).
+    Block b depends on (seed, b) only: a shorter row set is a prefix of a longer one."""
+    npdt = np.dtype(dtype)
+    cent, blk, ignore = label_case(block, nlist, dim, np.float64, "means", seed=seed, near=False)
+    cent = np.ascontiguousarray(cent.astype(npdt))
+    cent[nlist - 1] = cent[1]
+    x = np.empty((rows, dim), npdt)
+    for o in range(0, rows, block):
+        m = min(block, rows - o)
+        rng = np.random.default_rng([seed, o // block])
+        x[o:o + m] = (blk[:m] + 0.05 * rng.standard_normal((block, dim), dtype=np.float32)[:m]).astype(npdt)
+        label_steer(cent, x[o:o + m], np.arange(LABEL_NEAR_EVERY - 1, m, LABEL_NEAR_EVERY), 0, ignore, rng)
+    return cent, x, ignore
