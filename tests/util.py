@@ -412,3 +412,167 @@ def label_batch_case(rows, nlist, dim, dtype, seed=9, block=4096):
         x[o:o + m] = (blk[:m] + 0.05 * rng.standard_normal((block, dim), dtype=np.float32)[:m]).astype(npdt)
         label_steer(cent, x[o:o + m], np.arange(LABEL_NEAR_EVERY - 1, m, LABEL_NEAR_EVERY), 0, ignore, rng)
     return cent, x, ignore
+
+
+# ---- group-by reference of the fill-route tests (test_gpu_group_routes.py, test_group_reference_cpu.py) ---------------------------
+IDX_NONE = 0xffffffff
+
+
+def group_reference(base, queries, group_of, ngroups, gnum, gk, metric="SquaredEuclidean", threshold=None, exclude=None,
+                    candidates=None):
+    """Group-by search in plain fp64 (numpy only; nothing of oracle.flat_group_search is used).
+
+    A position competes iff it is not excluded (`exclude`: bool per position), is not a hole and has group_of[pos] < ngroups.
+    `candidates`: per query the positions that compete, in scan order; None = every position in storage order.  An entry of
+    IDX_NONE (or any entry >= n) is a hole; a position named twice competes twice, as two candidates with their own ordinals.
+    Every group keeps its gk smallest candidates under (score, scan ordinal); the groups are ordered by their best score and the
+    first gnum are kept; documents with score > threshold are cut AFTER that ranking, so a group may be listed with no document.
+    Scores: L2 sum((q - b)^2) summed directly, InnerProduct -q.b (label_reference's s64).
+
+    Returns a dict
+      s64, E    [nq][n]: fp64 score of every (query, position) and the per-pair bound on |dense fp32 score - s64|
+      queries   per query a dict
+                  groups  [(g, positions, scores)]: the listed groups in order, documents after the radius cut
+                  order   {g: (scores, positions)} of EVERY admissible group: its full ascending (score, ordinal) order
+                  bests   (scores, group numbers) of every admissible group, ascending (best score, group number)
+
+    E is label_reference's bound, which holds for the flat dense pass as it stands: the scan epilogue (zvk_scan.hip.h) forms
+    L2 as max(fma(-2, dot, |q|^2 + |b|^2), 0) with the dot product accumulated in fp32 on the matrix cores over the PADDED scan
+    width and both norms fp32 sums of squares, InnerProduct as -dot: the very expressions E = gamma (|q| + |b|)^2 and
+    E = gamma sum|q_i b_i|, gamma = (dpad + 8) 2^-23, are derived for (the clamp at 0 moves a score towards its true value)."""
+    base = np.asarray(base)
+    queries = np.atleast_2d(queries)
+    n = base.shape[0]
+    s64, _, _, E = label_reference(base, queries, metric)
+    s64, E = s64.reshape(len(queries), n), E.reshape(len(queries), n)
+    gof = np.asarray(group_of).astype(np.int64)
+    live = gof < ngroups
+    if exclude is not None:
+        live &= ~np.asarray(exclude, bool)
+    small = gof.astype(np.uint16) if ngroups <= 0xffff else gof      # (a stable sort of 16-bit keys is a radix sort)
+    out = []
+    for qi in range(len(queries)):
+        if candidates is None:
+            pos = np.nonzero(live)[0]
+        else:
+            pos = np.asarray(candidates[qi], np.int64).reshape(-1)
+            pos = pos[pos < n]
+            pos = pos[live[pos]]
+        # pos is in scan order: two stable sorts give (group, score, ordinal)
+        o1 = np.argsort(s64[qi, pos], kind="stable")
+        o2 = np.argsort(small[pos[o1]], kind="stable")
+        pos = pos[o1][o2]
+        sc, gg = s64[qi, pos], gof[pos]
+        starts = np.nonzero(np.r_[True, gg[1:] != gg[:-1]])[0] if pos.size else np.zeros(0, np.int64)
+        ends = np.r_[starts[1:], pos.size]
+        order = {int(gg[a]): (sc[a:b], pos[a:b]) for a, b in zip(starts, ends)}
+        bg = gg[starts] if pos.size else np.zeros(0, np.int64)
+        bs = sc[starts] if pos.size else np.zeros(0)
+        rank = np.lexsort((bg, bs))
+        groups = []
+        for g in bg[rank][:gnum]:
+            s, p = order[int(g)]
+            s, p = s[:gk], p[:gk]
+            if threshold is not None:
+                keep = ~(s.astype(np.float32) > np.float32(threshold))
+                s, p = s[keep], p[keep]
+            groups.append((int(g), p, s))
+        out.append({"groups": groups, "order": order, "bests": (bs[rank], bg[rank])})
+    return {"s64": s64, "E": E, "queries": out}
+
+
+def _group_places(rq, groups, ngroups_out, what):
+    """the freedom of the reference's unstable sort of the groups: as many groups as the reference lists, none twice, every one
+    admissible, and the group at place i has the best score the reference has at place i — so a group whose best score is
+    unshared sits at its place, groups tied inside the list are all there, and the last places may hold any group with that
+    best score"""
+    want = rq["groups"]
+    assert int(ngroups_out) == len(want), "%s: %d groups listed, reference %d" % (what, ngroups_out, len(want))
+    got = [int(g) for g in groups[:len(want)]]
+    assert len(set(got)) == len(got), "%s: a group is listed twice: %r" % (what, got)
+    for i, g in enumerate(got):
+        assert g in rq["order"], "%s place %d: group %d has no admissible member" % (what, i, g)
+        assert rq["order"][g][0][0] == rq["bests"][0][i], "%s place %d: group %d (best %r), reference best %r" % (
+            what, i, g, rq["order"][g][0][0], rq["bests"][0][i])
+    return got
+
+
+def check_groups_exact(rq, groups, ngroups_out, keys, scores, counts, gk, key_of, threshold=None, what=""):
+    """one query of a group-by answer (C ABI layout: groups [gnum], keys / scores [gnum][gk], counts [gnum]) against
+    group_reference on data whose scores are exact.  Lists are held exactly: the keys are key_of[the reference's first gk
+    positions under (score, ordinal)], in that order, the score bits are equal and the count after the radius is equal.
+    Groups: see _group_places."""
+    got = _group_places(rq, groups, ngroups_out, what)
+    for i, g in enumerate(got):
+        s, p = rq["order"][g]
+        s, p = s[:gk], p[:gk]
+        if threshold is not None:
+            keep = ~(s.astype(np.float32) > np.float32(threshold))
+            s, p = s[keep], p[keep]
+        c = int(counts[i])
+        assert c == len(p), "%s group %d: %d documents, reference %d" % (what, g, c, len(p))
+        wk = np.asarray(key_of)[p].astype(np.uint64)
+        assert np.array_equal(np.asarray(keys[i][:c], np.uint64), wk), "%s group %d: documents\n got %r\nwant %r" % (
+            what, g, np.asarray(keys[i][:c]), wk)
+        gs = np.ascontiguousarray(scores[i][:c], np.float32)
+        assert np.array_equal(gs.view(np.uint32), s.astype(np.float32).view(np.uint32)), "%s group %d: score bits\n got %r\nwant %r" % (
+            what, g, gs, s)
+
+
+def group_l2_rescore_bound(dim, s64):
+    """Bound on |refined L2 score - s64|, of the form (d + c) 2^-23 s64 with c = 2.  The refinement (rescore_l2_kernel) sums the
+    d squares (q_i - b_i)^2 in fp32, in a fixed tree over the lanes; the padding adds exact zeros.  With u = 2^-24: q_i - b_i
+    is rounded once, so its square carries (1 + u)^2; fma(d_i, d_i, acc) multiplies exactly and rounds the sum; whatever the
+    order, a term passes through at most d - 1 additions of two non-zero operands.  Every term is non-negative, so the result
+    is s64 (1 + theta), |theta| <= (1 + u)^(d + 1) - 1 < (d + 2) u for d u << 1.  As for label_reference's gamma the figure is
+    doubled — (d + 2) 2^-23 — which also pays for comparing an fp32 number with the fp64 one."""
+    return (dim + 2) * 2.0 ** -23 * np.asarray(s64)
+
+
+def check_groups_band(ref, qi, groups, ngroups_out, keys, scores, counts, gnum, gk, pos_of_key, metric, dim, what=""):
+    """one query of a group-by answer on REAL-VALUED data (no radius).  With s64 / E of group_reference:
+      documents  a returned document x of group g is accepted iff s64(x) - s64(gk-th of g) <= E(x) + E(gk-th); the list holds
+                 min(gk, size of g) distinct admissible members of g, in ascending order of the returned score
+      groups     a listed group g is accepted iff best(g) - best(gnum-th group) <= E(best doc of g) + E(best doc of the gnum-th)
+      scores     L2 (re-scored directly): within group_l2_rescore_bound of s64; InnerProduct: within E
+    Returns (lists that differ from the fp64 set, ambiguous lists, cut lists, group list differs, group cut ambiguous): a list
+    is ambiguous when the gap between its ranks gk and gk + 1 is <= the two bounds, the group cut when the gap between the
+    best scores at ranks gnum and gnum + 1 is.  Only ambiguous lists may differ: the caller sums and compares."""
+    rq, s64, E = ref["queries"][qi], ref["s64"][qi], ref["E"][qi]
+    bs, bg = rq["bests"]
+    nlist = min(gnum, len(bg))
+    assert int(ngroups_out) == nlist, "%s: %d groups listed, reference %d" % (what, ngroups_out, nlist)
+    got = [int(g) for g in groups[:nlist]]
+    assert len(set(got)) == len(got), "%s: a group is listed twice" % what
+    ebest = lambda g: E[rq["order"][g][1][0]]
+    gamb = False
+    if len(bg) > gnum:
+        last, nxt = int(bg[gnum - 1]), int(bg[gnum])
+        gamb = bs[gnum] - bs[gnum - 1] <= ebest(last) + ebest(nxt)
+    ndiff = namb = ncut = 0
+    for i, g in enumerate(got):
+        assert g in rq["order"], "%s place %d: group %d has no admissible member" % (what, i, g)
+        s, p = rq["order"][g]
+        if nlist:
+            last = int(bg[nlist - 1])
+            assert s[0] - bs[nlist - 1] <= ebest(g) + ebest(last), "%s: group %d (best %r) listed, rank-gnum best %r, bounds %r %r" % (
+                what, g, s[0], bs[nlist - 1], ebest(g), ebest(last))
+        c = int(counts[i])
+        assert c == min(gk, len(p)), "%s group %d: %d documents of %d members" % (what, g, c, len(p))
+        x = np.array([pos_of_key[int(k)] for k in keys[i][:c]], np.int64)
+        assert len(set(x.tolist())) == c, "%s group %d: a document twice" % (what, g)
+        member = set(p.tolist())
+        assert all(int(v) in member for v in x), "%s group %d: a document of another group or an excluded one" % (what, g)
+        kth = p[c - 1]
+        exc = s64[x] - s64[kth] - E[x] - E[kth]
+        assert np.all(exc <= 0), "%s group %d: document %d outside the band by %r" % (what, g, x[np.argmax(exc)], exc.max())
+        gs = np.asarray(scores[i][:c], np.float64)
+        assert np.all(np.diff(gs) >= 0), "%s group %d: scores not ascending" % (what, g)
+        tol = group_l2_rescore_bound(dim, s64[x]) if _METRIC_IDS[metric] == 0 else E[x]
+        err = np.abs(gs - s64[x])
+        assert np.all(err <= tol), "%s group %d: score off by %r, bound %r" % (what, g, err.max(), tol[np.argmax(err - tol)])
+        if len(p) > gk:
+            ncut += 1
+            namb += bool(s[gk] - s[gk - 1] <= E[p[gk]] + E[p[gk - 1]])
+            ndiff += set(x.tolist()) != set(p[:gk].tolist())
+    return ndiff, namb, ncut, set(got) != set(int(g) for g in bg[:nlist]), bool(gamb)
