@@ -30,11 +30,36 @@ extern "C" {
 #define ZVEC_HIP_ABI_VERSION 1
 
 /* IndexMeta::DataType subset (src/include/zvec/core/framework/index_meta.h:27-50) */
-enum { ZVEC_HIP_DT_FP32 = 0, ZVEC_HIP_DT_FP16 = 1 };
+enum {
+  ZVEC_HIP_DT_FP32 = 0,
+  ZVEC_HIP_DT_FP16 = 1,
+  ZVEC_HIP_DT_BINARY32 = 2, /* IndexMeta::DT_BINARY32 = 7 (index_meta.h:39): a row is dim / 32 uint32_t words */
+  ZVEC_HIP_DT_BINARY64 = 3  /* IndexMeta::DT_BINARY64 = 8 (index_meta.h:40): a row is dim / 64 uint64_t words */
+};
 
 /* IndexMetric names served: "SquaredEuclidean" (src/core/metric/euclidean_metric.cc:743),
  * "InnerProduct" (inner_product_metric.cc:256), "Cosine" (cosine_metric.cc:141). */
-enum { ZVEC_HIP_METRIC_L2 = 0, ZVEC_HIP_METRIC_IP = 1, ZVEC_HIP_METRIC_COSINE = 2 };
+enum {
+  ZVEC_HIP_METRIC_L2 = 0,
+  ZVEC_HIP_METRIC_IP = 1,
+  ZVEC_HIP_METRIC_COSINE = 2,
+  ZVEC_HIP_METRIC_HAMMING = 3 /* "Hamming" (src/core/metric/hamming_metric.cc:236) */
+};
+
+/* Binary rows (flat indexes only).  HammingMetric accepts DT_BINARY32 / DT_BINARY64 and nothing else (hamming_metric.cc:146-147)
+ * and scores a pair with HammingDistanceMatrix<uint32_t / uint64_t> (src/ailego/math/hamming_distance_matrix.h:41, :339):
+ *   - `dim` counts BITS; a row is dim / 32 uint32_t (BINARY32) or dim / 64 uint64_t (BINARY64) words in the host's byte order,
+ *     dim / 8 bytes either way; dim must be a non-zero multiple of 32 resp. 64 (the reference asserts !(dim & 31) / !(dim & 63))
+ *     and at most 2^20: zvec_hip_flat_create returns ZVEC_HIP_ERR_INVALID_ARGUMENT otherwise;
+ *   - score = (float) popcount(row ^ query), smaller is better; exact for every dim within the cap;
+ *   - ZVEC_HIP_METRIC_HAMMING goes with a binary dtype only and a binary dtype with ZVEC_HIP_METRIC_HAMMING only: every other
+ *     pairing is ZVEC_HIP_ERR_MISMATCH;
+ *   - served on a binary handle: flat_create / destroy / reserve, append, append_dev, put, holes, count, get_vector(s), search,
+ *     search_dev, search_by_ids, batch_distance, build_filter (exclude_bitset and threshold mean what they mean elsewhere: a
+ *     document is dropped iff score > threshold);  ZVEC_HIP_ERR_UNSUPPORTED: search_grouped*, the shadow entries, load_features,
+ *     load_blocks, zvec_hip_shards_create and zvec_hip_ivf_create with a binary dtype;
+ *   - lists are ascending by score; which of several equal scores are returned at the k-th place, and their order, is unspecified
+ *     (the reference's heap resolves ties arbitrarily). */
 
 /* IndexError values used (index_error.cc:20-71) */
 enum {

@@ -28,6 +28,10 @@ class Segment(C.Structure):
 
 ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 
+# ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes only)
+DT_FP32, DT_FP16, DT_BINARY32, DT_BINARY64 = 0, 1, 2, 3
+METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING = 0, 1, 2, 3
+
 # every symbol include/zvec_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "zvec_hip_abi_version": (C.c_int, []),

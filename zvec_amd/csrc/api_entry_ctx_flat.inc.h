@@ -113,8 +113,11 @@ int zvec_hip_ctx_set_gate(zvec_hip_ctx_t ctx, zvec_hip_gate_t gate) {
 // ---- flat -----------------------------------------------------------------------------------
 int zvec_hip_flat_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_flat_t *out) {
   if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (metric < 0 || metric > 2) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dtype < ZVEC_HIP_DT_FP32 || dtype > ZVEC_HIP_DT_BINARY64) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (metric < 0 || metric > ZVEC_HIP_METRIC_HAMMING) return ZVEC_HIP_ERR_UNSUPPORTED;
+  // Hamming goes with binary rows and binary rows with Hamming (hamming_metric.cc:146-147); dim counts bits, whole words of them
+  if (dtype_is_binary(dtype) != (metric == ZVEC_HIP_METRIC_HAMMING)) return ZVEC_HIP_ERR_MISMATCH;
+  if (dtype_is_binary(dtype) && (dim % (dtype == ZVEC_HIP_DT_BINARY64 ? 64u : 32u) != 0 || dim > (1u << 20))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (metric == ZVEC_HIP_METRIC_COSINE && dim < (dtype == ZVEC_HIP_DT_FP16 ? 3u : 2u)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_ctx_s *c = nullptr;
   ZRET(ctx_new(device, &c));
@@ -234,6 +237,7 @@ int zvec_hip_flat_append_dev(zvec_hip_flat_t h, const void *d_vecs, uint64_t n, 
 int zvec_hip_flat_load_features(zvec_hip_flat_t h, const void *features, uint64_t bytes, uint64_t count, int column_major,
                                 uint32_t batch_size, const uint64_t *keys) {
   if (!h || (!features && count) || batch_size == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;      // (the dumped layouts are transposed in units of the fp element)
   if (count == 0) return 0;
   const uint64_t elem = h->st.row_bytes();
   if (bytes < count * elem) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -277,6 +281,7 @@ int zvec_hip_flat_load_features(zvec_hip_flat_t h, const void *features, uint64_
 int zvec_hip_flat_load_blocks(zvec_hip_flat_t h, const void *blocks, uint64_t bytes, uint64_t nblocks, uint32_t block_size,
                               uint32_t block_vector_count, const uint32_t *keep) {
   if (!h || (nblocks && (!blocks || !keep)) || block_vector_count == 0 || block_vector_count > 32) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;
   if (nblocks == 0) return 0;
   const uint64_t elem = h->st.row_bytes();
   const uint64_t rows_bytes = (uint64_t)block_vector_count * elem;
@@ -576,6 +581,7 @@ static int flat_shadow_certify_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, con
 
 int zvec_hip_flat_set_shadow(zvec_hip_flat_t h, int enable, uint32_t preselect) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;      // (there is no half-width twin of bit rows)
   std::lock_guard<std::mutex> g(h->mu);
   std::unique_lock<FairSharedMutex> w_(h->rw);
   ZCHK(hipSetDevice(h->device));
@@ -592,6 +598,7 @@ int zvec_hip_flat_set_shadow(zvec_hip_flat_t h, int enable, uint32_t preselect) 
 
 int zvec_hip_flat_shadow_info(zvec_hip_flat_t h, int *enabled, uint64_t *bytes, float *max_row_error, float *max_row_norm) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;
   std::shared_lock<FairSharedMutex> r(h->rw);
   h->shadow.info(enabled, bytes, max_row_error, max_row_norm);
   return 0;
@@ -599,6 +606,7 @@ int zvec_hip_flat_shadow_info(zvec_hip_flat_t h, int *enabled, uint64_t *bytes, 
 
 int zvec_hip_flat_shadow_width(zvec_hip_flat_t h, uint32_t topk, uint32_t *rows) {
   if (!h || !rows) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;
   *rows = h->shadow.width(topk);
   return 0;
 }
@@ -607,6 +615,7 @@ int zvec_hip_flat_shadow_certify(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
                                  const uint64_t *d_exclude_bitset, uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts,
                                  void *stream, uint32_t *rerun) {
   if (!h || !d_queries || !d_out_keys || !d_out_scores || !d_out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
@@ -692,7 +701,10 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   const uint64_t pairs = (uint64_t)count * maxlen;
   ZRET(c->part_s.ensure(pairs * 4));
   ZRET(c->part_i.ensure(pairs * 4));
-  if (st.f16)
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_pkeys_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(st.base),
+                       c->qpad.as<uint32_t>(), st.bin_chunks(), d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
+  else if (st.f16)
     hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, s, st.base, c->qpad.as<float>(),
                        st.dpad, st.metric, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
   else
@@ -737,7 +749,10 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   ZCHK(hipMemcpyAsync(d_off, offs, sizeof(offs), hipMemcpyHostToDevice, s));
   ZRET(c->part_s.ensure((size_t)n * 4));
   ZRET(c->part_i.ensure((size_t)n * 4));
-  if (st.f16)
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_pkeys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(st.base),
+                       c->qpad.as<uint32_t>(), st.bin_chunks(), d_pos, d_off, 1u, n, c->part_s.as<float>(), c->part_i.as<uint32_t>());
+  else if (st.f16)
     hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(1, n)), dim3(256), 0, s, st.base, c->qpad.as<float>(), st.dpad,
                        st.metric, d_pos, d_off, 1u, n, c->part_s.as<float>(), c->part_i.as<uint32_t>());
   else

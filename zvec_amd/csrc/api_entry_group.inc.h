@@ -122,6 +122,7 @@ int zvec_hip_flat_search_grouped(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
                                  uint64_t *out_keys, float *out_scores, uint32_t *out_counts) {
   if (!h || !queries || !group_of_position || !out_groups || !out_ngroups || !out_keys || !out_scores || !out_counts)
     return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;      // (the group-by kernels read fp rows)
   if (count == 0) return 0;
   ZRET(group_args_ok(ngroups, group_num, group_topk));
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
@@ -169,6 +170,7 @@ int zvec_hip_flat_search_grouped_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, c
                                         uint32_t *out_counts) {
   if (!h || !queries || !ids || !offsets || !group_of_position || !out_groups || !out_ngroups || !out_keys || !out_scores || !out_counts)
     return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (h->st.bin) return ZVEC_HIP_ERR_UNSUPPORTED;      // (the group-by kernels read fp rows)
   if (count == 0) return 0;
   ZRET(group_args_ok(ngroups, group_num, group_topk));
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;

@@ -120,6 +120,7 @@ extern "C" {
 int zvec_hip_shards_create(uint32_t dim, int dtype, int metric, int kind, const int *devices, uint32_t ndev,
                            zvec_hip_shards_t *out) {
   if (!out || !devices || ndev == 0 || ndev > 64 || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype_is_binary(dtype) || metric == ZVEC_HIP_METRIC_HAMMING) return ZVEC_HIP_ERR_UNSUPPORTED;     // (binary rows: one flat index on one device)
   if (kind != ZVEC_HIP_SHARDS_FLAT && kind != ZVEC_HIP_SHARDS_IVF) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_shards_s *h = new (std::nothrow) zvec_hip_shards_s();
   if (!h) return ZVEC_HIP_ERR_NO_MEMORY;

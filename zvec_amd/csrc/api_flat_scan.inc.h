@@ -375,6 +375,88 @@ int flat_dense_scores(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t q0, uin
 // `internal` the IVF coarse pass, the k-means labelling and the seeding pre-pass, which only need the ranking
 enum class ScanRole { internal, shadow, user };
 
+template <bool DUMP>
+int launch_hamming_scan(const HamScanArgs &a, uint32_t grid, hipStream_t stream) {
+  const size_t lds = DUMP ? 0 : ham_lds_bytes(a.k);
+  if (a.exclude) hipLaunchKernelGGL((hamming_scan_kernel<true, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((hamming_scan_kernel<false, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+// Binary rows under the Hamming metric (zvk_hamming.hip.h): the flat scan of `st` for `count` prepared queries.  None of the fp routing
+// applies: no norms, no refinement, no seeding pre-pass, no keep-set compaction (an excluded row costs its popcounts and fails its
+// admission).  Lists of up to HAM_FUSED_MAX_K entries are kept by the scan itself, one partial list per (query, chunk of tiles), and merged;
+// longer ones are selected by merge_kernel from the dense [query][position] score matrix, in sub-batches of at most 1 GiB.
+int flat_scan_hamming(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude,
+                      const SearchOut &out, hipStream_t stream, bool profile_it) {
+  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  const uint64_t ntiles = (st.n + TILE_N - 1) / TILE_N;
+  const int cus = device_cus(ctx);
+  HamScanArgs a{};
+  a.base = reinterpret_cast<const uint32_t *>(st.base); a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
+  a.queries = ctx->qpad.as<uint32_t>(); a.cpr = st.bin_chunks(); a.k = topk; a.threshold = threshold; a.n = st.n;
+  a.ntiles = (uint32_t)ntiles; a.gtau = ctx->gtau.as<uint32_t>();
+  int pi = -1;
+  auto begin = [&](uint32_t cnt) {
+    if (!profile_it) return;
+    gate_enter(ctx, stream);
+    // (the `flops` column counts the 2 vector-ALU instructions of every 32-bit word pair)
+    pi = prof_begin(ctx, stream, (double)ntiles * TILE_N * st.dpad * 4.0 + (double)cnt * st.dpad * 4.0 + (double)cnt * topk * 12.0,
+                    2.0 * (double)cnt * (double)st.n * st.bin_words(), 0);
+  };
+  auto end = [&]() {
+    prof_end(ctx, stream, pi);
+    if (profile_it) gate_leave(ctx, stream);
+  };
+  if (topk > HAM_FUSED_MAX_K) {
+    const double row_bytes_d = (double)ntiles * TILE_N * 4.0;
+    const uint32_t sub = (uint32_t)std::max<double>(1.0, std::min<double>((double)count, std::floor(1073741824.0 / row_bytes_d)));
+    ZRET(ctx->part_s.ensure((size_t)(row_bytes_d * sub)));
+    for (uint32_t q0 = 0; q0 < count; q0 += sub) {
+      const uint32_t cnt = std::min(sub, count - q0);
+      HamScanArgs d = a;
+      d.queries = a.queries + (size_t)q0 * st.dpad; d.nq = cnt; d.tiles_per_chunk = 1; d.nchunks = (uint32_t)ntiles;
+      d.nqblocks = (cnt + HAM_QB - 1) / HAM_QB; d.dump = ctx->part_s.as<float>(); d.dump_stride = (uint32_t)(ntiles * TILE_N);
+      begin(cnt);
+      const int lrc = launch_hamming_scan<true>(d, d.nchunks * d.nqblocks, stream);
+      end();
+      ZRET(lrc);
+      MergeArgs m{};
+      m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = d.dump_stride; m.threshold = threshold;
+      m.keymap = st.keys; m.out_keys = out.keys + (size_t)q0 * topk; m.out_scores = out.scores + (size_t)q0 * topk;
+      m.out_idx = out.idx ? out.idx + (size_t)q0 * topk : nullptr; m.out_counts = out.counts + q0;
+      hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, stream, m);
+      ZCHK(hipGetLastError());
+    }
+    return 0;
+  }
+  // one wave per work-group: 16 of them per CU keep the vector ALUs and the loads in flight; a chunk is at least 4 tiles (one list
+  // warm-up per chunk) unless the base is too small to fill the chip that way
+  const uint32_t nqblocks = (count + HAM_QB - 1) / HAM_QB;
+  const uint64_t resident = (uint64_t)cus * 16;
+  const uint64_t want_chunks = std::max<uint64_t>(1, (resident + nqblocks - 1) / nqblocks);
+  uint64_t tpc = std::max<uint64_t>(1, (ntiles + want_chunks - 1) / want_chunks);
+  tpc = std::max<uint64_t>(tpc, std::min<uint64_t>(ntiles, ntiles >= 4 * resident ? 4 : 1));
+  const uint32_t nchunks = (uint32_t)((ntiles + tpc - 1) / tpc);
+  const uint64_t slots = (uint64_t)count * nchunks;
+  ZRET(ctx->part_s.ensure(slots * topk * sizeof(float)));
+  ZRET(ctx->part_i.ensure(slots * topk * sizeof(uint32_t)));
+  a.nq = count; a.tiles_per_chunk = (uint32_t)tpc; a.nchunks = nchunks; a.nqblocks = nqblocks;
+  a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
+  begin(count);
+  const int lrc = launch_hamming_scan<false>(a, nchunks * nqblocks, stream);
+  end();
+  ZRET(lrc);
+  MergeArgs m{};
+  m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk; m.threshold = threshold;
+  m.bound_keys = a.gtau; m.keymap = st.keys;
+  m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
+  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, stream, m);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
 int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold,
                        const uint64_t *d_exclude, const SearchOut &out_in, hipStream_t stream, ScanRole role) {
   const bool user_facing = role == ScanRole::user, profile_it = role != ScanRole::internal;
@@ -389,6 +471,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     ZCHK(hipMemsetAsync(out.keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, stream));
     return 0;
   }
+  if (st.bin) return flat_scan_hamming(ctx, st, count, topk, threshold, d_exclude, out, stream, profile_it);
   // Sparse keep-set: compact the kept rows and scan those (work ~ kept rows, like the CPU's skip-before-distance)
   // (a scan over shadow rows takes the gather variant only: its positions are stored positions, which the fp32 re-scoring needs; the
   // copying variant numbers the rows of the compacted copy)
@@ -617,6 +700,14 @@ int prep_queries(zvec_hip_ctx_s *ctx, const StoreView &st, const void *d_queries
   ZRET(ctx->qpad.ensure((size_t)count * st.dpad * sizeof(float)));
   ZRET(ctx->qnorm.ensure((size_t)count * sizeof(float)));
   ZRET(ctx->gtau.ensure((size_t)count * sizeof(uint32_t)));
+  if (st.bin) {          // (the threshold is not folded into the shared bounds: zvk_hamming.hip.h)
+    const uint64_t words = (uint64_t)count * st.dpad;
+    hipLaunchKernelGGL(hamming_prep_queries_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const uint32_t *>(d_queries), count, st.bin_words(), st.bin_chunks(), ctx->qpad.as<uint32_t>(),
+                       ctx->gtau.as<uint32_t>());
+    ZCHK(hipGetLastError());
+    return 0;
+  }
   if (st.f16)
     hipLaunchKernelGGL(prep_queries_kernel<true>, dim3((count + 3) / 4), dim3(256), 0, stream, d_queries, count,
                        st.dim_in, st.dscan, st.dpad, ctx->qpad.as<float>(), ctx->qnorm.as<float>(),
@@ -751,7 +842,10 @@ int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, s
 
 int launch_pack(const StoreView &st, const void *d_rows, uint64_t n, const uint64_t *d_src, uint64_t pos0,
                 const uint64_t *d_dst, hipStream_t stream, uint64_t *keys_out = nullptr, const uint64_t *key_src = nullptr) {
-  if (st.f16)
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_pack_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, static_cast<const uint32_t *>(d_rows), n,
+                       st.bin_words(), st.bin_chunks(), d_src, pos0, d_dst, reinterpret_cast<uint32_t *>(st.base), keys_out, key_src);
+  else if (st.f16)
     hipLaunchKernelGGL(pack_rows_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, d_rows, n, st.dim_in,
                        st.dscan, st.dpad, d_src, pos0, d_dst, st.base, st.bnorm, st.extra, keys_out, key_src);
   else
@@ -762,7 +856,10 @@ int launch_pack(const StoreView &st, const void *d_rows, uint64_t n, const uint6
 }
 
 int launch_unpack(const StoreView &st, uint64_t pos, void *d_out, hipStream_t stream) {
-  if (st.f16)
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_unpack_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<const uint32_t *>(st.base),
+                       (const uint64_t *)nullptr, pos, st.bin_words(), st.bin_chunks(), static_cast<uint32_t *>(d_out));
+  else if (st.f16)
     hipLaunchKernelGGL(unpack_row_kernel<true>, dim3(1), dim3(256), 0, stream, st.base, st.extra, pos, st.dscan, st.dim_in, st.dpad, d_out);
   else
     hipLaunchKernelGGL(unpack_row_kernel<false>, dim3(1), dim3(256), 0, stream, st.base, st.extra, pos, st.dscan, st.dim_in, st.dpad, d_out);
@@ -779,7 +876,10 @@ int store_get_rows(zvec_hip_ctx_s *c, const StoreView &st, const std::vector<uin
   ZRET(d_pos.alloc(n));
   ZRET(c->io_q.ensure(n * rb));
   ZCHK(hipMemcpyAsync(d_pos, pos.data(), n * 8, hipMemcpyHostToDevice, c->own));
-  if (st.f16)
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_unpack_kernel, dim3((unsigned)n), dim3(256), 0, c->own, reinterpret_cast<const uint32_t *>(st.base),
+                       static_cast<const uint64_t *>(d_pos), (uint64_t)0, st.bin_words(), st.bin_chunks(), c->io_q.as<uint32_t>());
+  else if (st.f16)
     hipLaunchKernelGGL(unpack_rows_kernel<true>, dim3((unsigned)n), dim3(256), 0, c->own, st.base, st.extra, d_pos, st.dscan, st.dim_in, st.dpad, c->io_q.p);
   else
     hipLaunchKernelGGL(unpack_rows_kernel<false>, dim3((unsigned)n), dim3(256), 0, c->own, st.base, st.extra, d_pos, st.dscan, st.dim_in, st.dpad, c->io_q.p);

@@ -178,12 +178,15 @@ struct ShadowGovernor {
 // What a scan reads of a blocked, HBM-resident set of rows (flat store, IVF centroids, IVF inverted lists, the fp16 twin): its shape
 // and where its arrays are.  Owns nothing and copies freely: the compacted keep-set, the seeding prefix and the twin's rows under the
 // store's keys are plain values of it with the fields they override.
+inline bool dtype_is_binary(int dtype) { return dtype == ZVEC_HIP_DT_BINARY32 || dtype == ZVEC_HIP_DT_BINARY64; }
+
 struct StoreView {
   uint32_t dim_in = 0;   // element dimension at the ABI (cosine: d+1)
   uint32_t dscan = 0;    // scanned dims
   uint32_t dpad = 0;     // 4-byte WORDS per stored row, multiple of 32 (fp32: dscan up to 32; fp16: dscan up to 64, halved)
   uint32_t elem = 4;     // bytes per element: 4 (fp32) or 2 (fp16)
   bool f16 = false;
+  bool bin = false;      // binary rows (Hamming): dim_in counts BITS, dpad = 4 words per 16-byte chunk, [chunk][row] inside a tile (zvk_hamming.hip.h)
   int metric = 0;
   uint64_t n = 0;        // padded positions in use
   float *base = nullptr;
@@ -195,12 +198,21 @@ struct StoreView {
     dim_in = dim;
     metric = met;
     f16 = (dtype == ZVEC_HIP_DT_FP16);
+    bin = dtype_is_binary(dtype);
     elem = f16 ? 2 : 4;
+    if (bin) {             // a row is dim / 32 words, stored as whole 16-byte chunks: at most 12 bytes of padding per row, no norm column
+      dscan = dim;
+      dpad = (dim / 32 + 3) / 4 * 4;
+      return;
+    }
     // cosine rows end with the fp32 norm of the original vector: 1 float, or 2 half slots (cosine_converter.cc:205-212)
     dscan = (met == ZVEC_HIP_METRIC_COSINE) ? dim - (f16 ? 2 : 1) : dim;
     dpad = f16 ? ((dscan + 63) / 64 * 64) / 2 : (dscan + TILE_K - 1) / TILE_K * TILE_K;
   }
-  size_t row_bytes() const { return (size_t)dim_in * elem; }
+  // bytes of a row at the ABI: the one place they are computed
+  size_t row_bytes() const { return bin ? (size_t)dim_in / 8 : (size_t)dim_in * elem; }
+  uint32_t bin_words() const { return dim_in / 32; }      // binary rows: 32-bit words per row at the ABI ...
+  uint32_t bin_chunks() const { return dpad / 4; }        // ... and 16-byte chunks per stored row
 };
 
 // The rows an index owns: the view every reader takes (a Store converts to its StoreView), and the four arrays behind the view's
@@ -216,13 +228,13 @@ struct Store : StoreView {
     uint64_t nt = std::max<uint64_t>(tiles, cap_tiles + cap_tiles / 2 + 1);
     Arrays grown;
     ZRET(grown.base.alloc((size_t)nt * TILE_N * dpad));
-    ZRET(grown.bnorm.alloc((size_t)nt * TILE_N));
+    if (!bin) ZRET(grown.bnorm.alloc((size_t)nt * TILE_N));     // (the Hamming scan reads no norms)
     ZRET(grown.keys.alloc((size_t)nt * TILE_N));
     if (metric == ZVEC_HIP_METRIC_COSINE) ZRET(grown.extra.alloc((size_t)nt * TILE_N));
     uint64_t used_tiles = (n + TILE_N - 1) / TILE_N;
     if (used_tiles) {
       ZCHK(hipMemcpyAsync(grown.base, base, (size_t)used_tiles * TILE_N * dpad * sizeof(float), hipMemcpyDeviceToDevice, stream));
-      ZCHK(hipMemcpyAsync(grown.bnorm, bnorm, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      if (grown.bnorm) ZCHK(hipMemcpyAsync(grown.bnorm, bnorm, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
       ZCHK(hipMemcpyAsync(grown.keys, keys, (size_t)used_tiles * TILE_N * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
       if (grown.extra) ZCHK(hipMemcpyAsync(grown.extra, extra, (size_t)used_tiles * TILE_N * sizeof(float), hipMemcpyDeviceToDevice, stream));
       ZCHK(hipStreamSynchronize(stream));

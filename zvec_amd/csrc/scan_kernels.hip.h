@@ -32,3 +32,4 @@
 #include "zvk_plan.hip.h"
 #include "zvk_build.hip.h"
 #include "zvk_group.hip.h"
+#include "zvk_hamming.hip.h"

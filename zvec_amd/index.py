@@ -14,22 +14,47 @@ import numpy as np
 
 from . import _lib
 
-METRIC_L2, METRIC_IP, METRIC_COSINE = 0, 1, 2
-DT_FP32, DT_FP16 = 0, 1
+from ._lib import METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING        # noqa: E402
+from ._lib import DT_FP32, DT_FP16, DT_BINARY32, DT_BINARY64                 # noqa: E402
+
+_DTYPE_NAMES = {"fp32": DT_FP32, "float32": DT_FP32, "fp16": DT_FP16, "float16": DT_FP16,   # (fp16: what HalfFloatConverter writes)
+                "binary32": DT_BINARY32,      # IndexMeta::DT_BINARY32: dim bits as dim // 32 uint32 words
+                "binary64": DT_BINARY64}      # IndexMeta::DT_BINARY64: dim bits as dim // 64 uint64 words
+_NP_OF = {DT_FP32: np.float32, DT_FP16: np.float16, DT_BINARY32: np.uint32, DT_BINARY64: np.uint64}
 
 
 def _dtype_of(dtype):
-    """IndexMeta::DataType of the rows: "fp32" (DT_FP32) or "fp16" (DT_FP16: what HalfFloatConverter writes and
-    HalfFloatReformer turns queries into, src/core/quantizer/half_float_converter.cc / half_float_reformer.cc)."""
-    if dtype in ("fp16", "float16", np.float16, DT_FP16) and dtype is not False and dtype != 0:
-        return DT_FP16, np.float16
-    return DT_FP32, np.float32
+    """IndexMeta::DataType of the rows -> (ABI value, numpy type of a row word): a name, a numpy type or the ABI value.
+    Anything else raises."""
+    if isinstance(dtype, str):
+        if dtype in _DTYPE_NAMES:
+            return _DTYPE_NAMES[dtype], _NP_OF[_DTYPE_NAMES[dtype]]
+    elif isinstance(dtype, (int, np.integer)) and not isinstance(dtype, bool):
+        if int(dtype) in _NP_OF:
+            return int(dtype), _NP_OF[int(dtype)]
+    else:
+        try:
+            t = np.dtype(dtype).type
+        except TypeError:
+            t = None
+        for k, v in _NP_OF.items():
+            if t is v:
+                return k, v
+    raise ValueError("zvec_amd: unknown row data type %r" % (dtype,))
+
+
+def _row_words(dim, dt):
+    """row length in words of its numpy type: elements for fp rows, dim // 32 resp. dim // 64 words for bit rows"""
+    return int(dim) // 32 if dt == DT_BINARY32 else int(dim) // 64 if dt == DT_BINARY64 else int(dim)
+
+
 FLT_MAX = float(np.finfo(np.float32).max)
 
 _METRIC_NAMES = {
     "SquaredEuclidean": METRIC_L2,   # src/core/metric/euclidean_metric.cc:743
     "InnerProduct": METRIC_IP,       # src/core/metric/inner_product_metric.cc:256
     "Cosine": METRIC_COSINE,         # src/core/metric/cosine_metric.cc:141
+    "Hamming": METRIC_HAMMING,       # src/core/metric/hamming_metric.cc:236 (binary rows only)
 }
 
 
@@ -336,6 +361,7 @@ class _FlatBase:
         self.metric = metric
         self.device = device
         self.dtype, self.np_dtype = _dtype_of(dtype)
+        self.row_words = _row_words(self.dim, self.dtype)     # words of np_dtype per row (== dim for fp rows)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().zvec_hip_flat_create(self.dim, self.dtype, metric, device, C.byref(self._h)),
                    "zvec_hip_flat_create")
@@ -362,7 +388,7 @@ class _FlatBase:
 
     def add_batch(self, vecs, keys=None):
         vecs = np.ascontiguousarray(vecs, self.np_dtype)
-        if vecs.ndim != 2 or vecs.shape[1] != self.dim:
+        if vecs.ndim != 2 or vecs.shape[1] != self.row_words:
             return IndexError_.InvalidArgument
         n0 = self.count()
         k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
@@ -391,13 +417,13 @@ class _FlatBase:
         return np.concatenate(parts) if parts else np.zeros(0, np.uint64)
 
     def get_vector_by_id(self, pos):
-        out = np.zeros(self.dim, self.np_dtype)
+        out = np.zeros(self.row_words, self.np_dtype)
         rc = _lib.lib().zvec_hip_flat_get_vector(self._h, int(pos), _np_ptr(out))
         return out if rc == 0 else None
 
     def get_vectors_by_ids(self, positions):
         pos = np.ascontiguousarray(positions, np.uint64)
-        out = np.zeros((pos.size, self.dim), self.np_dtype)
+        out = np.zeros((pos.size, self.row_words), self.np_dtype)
         _lib.check(_lib.lib().zvec_hip_flat_get_vectors(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_flat_get_vectors")
         return out
 
@@ -425,7 +451,7 @@ class _FlatBase:
         if ctx is None or (ctx.topk() == 0 and not ctx.group_by_search()):
             return IndexError_.InvalidArgument      # flat_searcher.cc:194-198
         q = np.ascontiguousarray(query, self.np_dtype).reshape(-1)
-        if q.size != int(count) * self.dim:
+        if q.size != int(count) * self.row_words:
             return IndexError_.InvalidArgument
         if ctx.group_by_search():
             return self._group_search(q, count, ctx, None)      # flat_streamer.cc:323-324
@@ -497,7 +523,7 @@ class _FlatBase:
         if ctx is None or (ctx.topk() == 0 and not ctx.group_by_search()):
             return IndexError_.InvalidArgument
         q = np.ascontiguousarray(query, self.np_dtype).reshape(-1)
-        if q.size != int(count) * self.dim or len(p_keys) != count:
+        if q.size != int(count) * self.row_words or len(p_keys) != count:
             return IndexError_.InvalidArgument
         if ctx.group_by_search():
             return self._group_search(q, count, ctx, p_keys)    # flat_streamer.cc:365-366
@@ -577,7 +603,7 @@ class HipFlatStreamer(_FlatBase):
         overwrites in place."""
         vecs = np.ascontiguousarray(vecs, self.np_dtype)
         ids = np.ascontiguousarray(ids, np.uint32)
-        if vecs.ndim != 2 or vecs.shape[1] != self.dim or ids.size != vecs.shape[0]:
+        if vecs.ndim != 2 or vecs.shape[1] != self.row_words or ids.size != vecs.shape[0]:
             return IndexError_.InvalidArgument
         rc = _lib.lib().zvec_hip_flat_put(self._h, _np_ptr(ids), ids.size, _np_ptr(vecs), None)
         if rc == 0:
