@@ -81,6 +81,7 @@ typedef struct zvec_hip_ivf_s *zvec_hip_ivf_t;
 typedef struct zvec_hip_ctx_s *zvec_hip_ctx_t;
 typedef struct zvec_hip_shards_s *zvec_hip_shards_t;
 typedef struct zvec_hip_gate_s *zvec_hip_gate_t;
+typedef struct zvec_hip_sparse_s *zvec_hip_sparse_t;
 
 /* library / device ------------------------------------------------------------------------- */
 int zvec_hip_abi_version(void);
@@ -544,6 +545,60 @@ int zvec_hip_ivf_build_filter(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const zvec_h
                               uint64_t *out_words, int out_on_device, void *stream);
 /* ailego::Crc32c::Hash (src/ailego/hash/crc32c.cc:626-634): raw CRC-32C update, no pre/post inversion */
 uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
+
+/* ---- flat index of sparse rows ---------------------------------------------------------------
+ * stands behind FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_streamer.cc:186-300,
+ * flat_sparse_search.h:58-148) for fp32 values under the "InnerProductSparse" metric (inner_product_metric.cc:329,491:
+ * MinusInnerProductSparseMatrix<float>::Compute).  Rules, as the reference has them:
+ *   - Row format.  A row, and a query, is `count` pairs (uint32_t index, float value), count <= 4096
+ *     (PARAM_FLAT_SPARSE_MAX_DIM_SIZE, flat_sparse_utility.h:22).  The reference discards a longer row
+ *     (flat_sparse_streamer.cc:197-201); here zvec_hip_sparse_append returns ZVEC_HIP_ERR_INVALID_ARGUMENT for it and stores
+ *     NOTHING of the call; a longer query is refused the same way.  count == 0 is a legal row and a legal query.
+ *     A batch is CSR-like: counts[n], then the runs back to back in indices[] / values[].
+ *   - Index order.  The indices of a run must be STRICTLY ascending.  The reference neither sorts nor checks:
+ *     transform_sparse_format (src/ailego/math/inner_product_matrix.h:2891-2968; SparseUtility::TransSparseFormat,
+ *     src/core/utility/sparse_utility.h:272-350) cuts a run into 16-bit segments as it comes (a segment id that goes backwards
+ *     falls into the "// std::abort()" branch, :2926-2928, and is counted into the wrong segment) and the scoring routines
+ *     (Compute, :2838-2859, and ComputeInnerProductSparseInSegment, :2866-2888) are merge joins that advance both sides on a
+ *     match: an unsorted or repeated index gives the reference an unspecified score.  Such a run is refused here:
+ *     ZVEC_HIP_ERR_INVALID_ARGUMENT from append and from the host-pointer search.  zvec_hip_sparse_search_dev cannot see its
+ *     queries' indices: runs that break the rule give unspecified scores there (never an out-of-range access).
+ *   - Score.  MINUS the inner product over the indices present in both row and query (Compute ends with *out = -sum, :2861),
+ *     smaller is better, lists ascending: the convention of ZVEC_HIP_METRIC_IP on a dense flat handle.  A pair without a
+ *     shared index (an empty row or query included, :2795-2799) scores exactly 0 and is an ordinary candidate, as in the
+ *     reference's heap.  Products are summed in fp32, in an order of the library's choosing.
+ *   - threshold and exclude_bitset mean what they mean for zvec_hip_flat_search (a document is dropped iff score > threshold;
+ *     bit i of word i / 64 = storage position i, the row's number in append order).
+ *   - Ties.  Which of several equal scores are returned at the k-th place, and their order, is unspecified (the reference's
+ *     heap resolves ties arbitrarily); zero scores tie massively.
+ *   - topk * 12 + 16 <= 60 KiB as elsewhere, else ZVEC_HIP_ERR_UNSUPPORTED.
+ * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), search by primary keys
+ * (search_bf_by_p_keys_impl), group-by, fp16 values, the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean
+ * sparse), loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
+int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
+int zvec_hip_sparse_destroy(zvec_hip_sparse_t h);
+/* room for `rows` rows and `elements` (index, value) pairs in all; the store also grows on demand, geometrically */
+int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t elements);
+/* FlatSparseStreamer::add_impl / add_with_id_impl (flat_sparse_streamer.cc:186-300) in bulk: n rows in storage order, row i
+ * being counts[i] pairs; keys == NULL -> key = storage position.  All or nothing (see Row format, Index order). */
+int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const float *values,
+                           uint64_t n, const uint64_t *keys);
+/* either output nullable */
+int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *elements);
+/* get_sparse_vector_by_id: row `pos` as stored, bit for bit.  *count always; indices / values (room for *count entries, at
+ * most 4096) may each be NULL: a size query.  ZVEC_HIP_ERR_NO_EXIST beyond the last row. */
+int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, float *values);
+/* search_impl / search_bf_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, ctx) (flat_sparse_search.h:58-148):
+ * `count` queries, query q being q_counts[q] pairs, runs back to back.  Outputs as zvec_hip_flat_search. */
+int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
+                           const float *q_values, uint32_t count, uint32_t topk, float threshold,
+                           const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+/* The same with the queries' pairs, the bitset and the outputs in device memory; enqueues on `stream` and returns.  q_counts
+ * stays a HOST array: the host cuts the batch into query blocks by length before it launches anything. */
+int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts,
+                               const uint32_t *d_q_indices, const float *d_q_values, uint32_t count, uint32_t topk,
+                               float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
+                               float *d_out_scores, uint32_t *d_out_counts, void *stream);
 
 #ifdef __cplusplus
 }

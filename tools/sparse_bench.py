@@ -1,0 +1,131 @@
+"""Flat sparse inner-product search, 1M rows of 64-192 elements over a 30 522-word vocabulary with Zipf-distributed indices, queries
+of 16-64 elements, k = 10, batches 1 / 64 / 1024: QPS and ms per step against two bounds of the box it runs on (reported, not
+gated; bench.py is the project's benchmark and does not cover sparse rows).
+
+  streaming bound  stored bytes of the index (8 per element + 16 per row) / the box's streaming figure (zvec_hip_calibrate, same
+                   process): batch 1
+  LDS-issue bound  every stored element costs every query block ceil(log2(longest run of the block)) + 1 probes of the block's
+                   LDS image; a probe is one ds_read_b32 wave instruction = 2 LDS cycles when conflict-free, one LDS per CU:
+                   elements x blocks x probes x 2 / (CUs x calibrated clock).  Lanes probe unrelated addresses, so bank
+                   conflicts come on top: the bound is not reachable, the fraction says how far the scan is from it.
+
+    python tools/sparse_bench.py [--out profiles/sparse_flat1m.json] [--steps 10] [--warmup 3]
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def zipf_runs(torch, dev, g, n, lo, hi, vocab, draws):
+    """n runs of lo..hi distinct Zipf(1)-distributed indices, ascending: counts (int64 cpu), indices (int32 cpu)"""
+    cdf = torch.cumsum(1.0 / torch.arange(1, vocab + 1, device=dev, dtype=torch.float64), 0)
+    cdf = (cdf / cdf[-1]).to(torch.float32)
+    counts, parts = [], []
+    for a in range(0, n, 50000):
+        m = min(50000, n - a)
+        w = torch.searchsorted(cdf, torch.rand((m, draws), generator=g, device=dev)).clamp_(max=vocab - 1)
+        w, _ = torch.sort(w, dim=1)
+        dup = torch.zeros_like(w, dtype=torch.bool)
+        dup[:, 1:] = w[:, 1:] == w[:, :-1]
+        # a random subset of the distinct words of the run: the `want` smallest random priorities among them
+        pri = torch.rand((m, draws), generator=g, device=dev)
+        pri[dup] = 2.0
+        want = torch.randint(lo, hi + 1, (m,), generator=g, device=dev)
+        want = torch.minimum(want, (~dup).sum(1))
+        rank = torch.argsort(torch.argsort(pri, dim=1), dim=1)
+        keep = rank < want[:, None]
+        counts.append(want.cpu())
+        parts.append(w[keep].to(torch.int32).cpu())          # (row-major: ascending inside a run)
+    return torch.cat(counts), torch.cat(parts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--vocab", type=int, default=30522)
+    ap.add_argument("--topk", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
+    se = zvec_amd.HipFlatSparseStreamer()
+    assert se.reserve(args.n, ri.numel()) == 0
+    assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy()) == 0
+    elements = se.element_count()
+    stored = elements * 8 + (args.n + 1) * 8 + args.n * 8
+    ctx = se.create_context()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    legs = []
+    for batch in (1, 64, 1024):
+        qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
+        qv = torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1
+        d_qi = qi.to(dev)
+        qc_np = qc.numpy().astype(np.uint32)
+        keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        ts = torch.cuda.Stream(device=dev)          # (a stream of its own: the null stream would mean "the context's stream")
+        ts.wait_stream(torch.cuda.current_stream(dev))
+        stream = ts.cuda_stream
+
+        def step():
+            rc = se.search_dev(qc_np, d_qi.data_ptr(), qv.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(),
+                               counts.data_ptr(), ctx, stream=stream)
+            assert rc == 0
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(ts)
+        for _ in range(args.steps):
+            step()
+        e1.record(ts)
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.steps
+        assert int(counts.min()) == args.topk and bool((scores[:, 1:] >= scores[:, :-1]).all())
+        # the host's greedy query blocks (<= 64 queries, <= 4096 elements): probes per stored element, summed over the blocks
+        probes, in_blk, elems, longest = 0, 0, 0, 0
+        for c in list(qc_np) + [None]:
+            if c is None or in_blk == 64 or elems + int(c) > 4096:
+                probes += (math.ceil(math.log2(longest)) if longest > 1 else 0) + 1
+                in_blk, elems, longest = 0, 0, 0
+            if c is not None:
+                in_blk, elems, longest = in_blk + 1, elems + int(c), max(longest, int(c))
+        legs.append({"batch": batch, "ms_per_step": ms, "qps": batch / ms * 1e3, "probes_per_element": probes})
+    del se
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for leg in legs:
+        stream_ms = stored / (gbs.value * 1e9) * 1e3
+        lds_ms = float(elements) * leg["probes_per_element"] * 2.0 / (cus * mhz.value * 1e6) * 1e3
+        leg.update(stream_bound_ms=stream_ms, stream_fraction=stream_ms / leg["ms_per_step"], lds_bound_ms=lds_ms,
+                   lds_fraction=lds_ms / leg["ms_per_step"])
+    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d" % (args.n, args.vocab, args.topk),
+           "elements": elements, "stored_bytes": stored, "cus": cus, "clock_mhz": mhz.value, "stream_gbs": gbs.value,
+           "steps": args.steps, "warmup": args.warmup, "cpu_comparison": "not compared", "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

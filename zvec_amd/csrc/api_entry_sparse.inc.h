@@ -1,0 +1,289 @@
+// api_entry_sparse.inc.h — C ABI entry points: flat index of sparse fp32 rows under InnerProductSparse (zvk_sparse.hip.h)
+// Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
+
+extern "C++" {
+namespace {
+
+template <bool DUMP>
+int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  static bool attr_set[16][2] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (!attr_set[dev & 15][0]) {
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<false, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)LDS_LIMIT));
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<true, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)LDS_LIMIT));
+    attr_set[dev & 15][0] = true;
+  }
+  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<true, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((sparse_scan_kernel<false, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+// Runs of a batch as the reference requires them: at most PARAM_FLAT_SPARSE_MAX_DIM_SIZE pairs each, indices STRICTLY ascending
+// (the merge join of ComputeInnerProductSparseInSegment, inner_product_matrix.h:2866-2888, advances both sides on a match and
+// transform_sparse_format, :2913-2930, counts a segment that goes backwards into the wrong one: unsorted or repeated indices give
+// the reference an undefined score, so they are refused here).
+int sparse_check_runs(const uint32_t *counts, const uint32_t *indices, uint64_t n, uint64_t *total) {
+  uint64_t o = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint32_t c = counts[i];
+    if (c > SPARSE_MAX_COUNT) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    if (indices)
+      for (uint32_t e = 1; e < c; ++e)
+        if (indices[o + e] <= indices[o + e - 1]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    o += c;
+  }
+  *total = o;
+  return 0;
+}
+
+// Query blocks, greedily: consecutive queries while there are at most SPARSE_QB of them and their runs fit the LDS image; a block
+// never crosses a multiple of `sub` (the dump route's sub-batches; 0 = none).  plan = q_off[count + 1] | blk[blocks + 1].
+void sparse_make_plan(const uint32_t *counts, uint32_t count, uint32_t sub, std::vector<uint32_t> &plan, uint32_t *nblocks, uint32_t *max_img) {
+  plan.assign((size_t)count + 1, 0u);
+  for (uint32_t q = 0; q < count; ++q) plan[q + 1] = plan[q] + counts[q];
+  std::vector<uint32_t> blk(1, 0u);
+  uint32_t in_blk = 0, elems = 0, mx = 0;
+  for (uint32_t q = 0; q < count; ++q) {
+    if (in_blk && (in_blk == SPARSE_QB || elems + counts[q] > SPARSE_IMG_ELEMS || (sub && q % sub == 0))) {
+      blk.push_back(q);
+      in_blk = 0;
+      elems = 0;
+    }
+    ++in_blk;
+    elems += counts[q];
+    mx = std::max(mx, elems);
+  }
+  blk.push_back(count);
+  *nblocks = (uint32_t)blk.size() - 1;
+  *max_img = mx;
+  plan.insert(plan.end(), blk.begin(), blk.end());
+}
+
+// The search proper.  The caller holds c->mu and h->rw (shared); q_counts (HOST) has passed sparse_check_runs; the query arrays
+// and every output are device pointers.  Enqueues only, except for a wait on the previous plan upload of the same context.
+int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const float *d_qval,
+                         uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude, uint64_t *d_keys, float *d_scores,
+                         uint32_t *d_counts, hipStream_t s) {
+  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  const SparseStore &st = h->st;
+  if (st.n == 0) {
+    ZCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * count, s));
+    ZCHK(hipMemsetAsync(d_keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, s));
+    return 0;
+  }
+  const bool dump = topk > SPARSE_FUSED_MAX_K;
+  // dense scores: sub-batches of at most 1 GiB
+  const uint32_t sub = dump ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, (1ull << 30) / (st.n * 4))) : 0u;
+  std::vector<uint32_t> plan;
+  uint32_t nblocks = 0, max_img = 0;
+  sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);
+  // the plan goes through the context's pinned slot: the previous search's upload has to have left it
+  if (c->sp_ev == nullptr) ZCHK(hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
+  else ZCHK(hipEventSynchronize(c->sp_ev));
+  ZRET(c->sp_pin.ensure(plan.size() * 4));
+  ZRET(c->sp_plan.ensure(plan.size() * 4));
+  memcpy(c->sp_pin.p, plan.data(), plan.size() * 4);
+  ZCHK(hipMemcpyAsync(c->sp_plan.p, c->sp_pin.p, plan.size() * 4, hipMemcpyHostToDevice, s));
+  ZCHK(hipEventRecord(c->sp_ev, s));
+  ZRET(c->gtau.ensure((size_t)count * 4));
+  hipLaunchKernelGGL(sparse_prep_queries_kernel, dim3((count + 255) / 256), dim3(256), 0, s, count, c->gtau.as<uint32_t>());
+  ZCHK(hipGetLastError());
+
+  const int cus = device_cus(c);
+  SparseScanArgs a{};
+  a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
+  a.q_off = c->sp_plan.as<uint32_t>(); a.q_idx = d_qidx; a.q_val = d_qval; a.blk = a.q_off + count + 1;
+  a.k = topk; a.threshold = threshold; a.n = st.n; a.gtau = c->gtau.as<uint32_t>();
+  const std::vector<uint32_t> blk(plan.begin() + count + 1, plan.end());
+  // one wave per work-group, 8 of them per CU: a chunk of rows per work-group and query block
+  auto chunking = [&](uint32_t nqb, uint32_t *rpc, uint32_t *nchunks) {
+    const uint64_t want = std::max<uint64_t>(1, ((uint64_t)cus * 8 + nqb - 1) / nqb);
+    uint64_t r = std::max<uint64_t>(1, (st.n + want - 1) / want);
+    // (the partial lists of a wide batch with long lists: at most 64 MiB of them)
+    while (!dump && (uint64_t)count * ((st.n + r - 1) / r) * topk * 8 > (64ull << 20) && r < st.n) r *= 2;
+    *rpc = (uint32_t)std::min<uint64_t>(r, 0x7fffffffu);
+    *nchunks = (uint32_t)((st.n + *rpc - 1) / *rpc);
+  };
+  if (dump) {
+    ZRET(c->part_s.ensure((size_t)sub * st.n * 4));
+    uint32_t b0 = 0;
+    for (uint32_t q0 = 0; q0 < count; q0 += sub) {
+      const uint32_t cnt = std::min(sub, count - q0);
+      uint32_t b1 = b0;
+      while (blk[b1] < q0 + cnt) ++b1;                // blocks [b0, b1) are the sub-batch's
+      SparseScanArgs d = a;
+      d.blk0 = b0; d.qsub0 = q0; d.nqblocks = b1 - b0; d.dump = c->part_s.as<float>();
+      chunking(d.nqblocks, &d.rows_per_chunk, &d.nchunks);
+      ZRET(launch_sparse_scan<true>(d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0), s));
+      MergeArgs m{};
+      m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
+      m.keymap = st.keys; m.out_keys = d_keys + (size_t)q0 * topk; m.out_scores = d_scores + (size_t)q0 * topk;
+      m.out_counts = d_counts + q0;
+      hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, s, m);
+      ZCHK(hipGetLastError());
+      b0 = b1;
+    }
+    return 0;
+  }
+  a.nqblocks = nblocks;
+  chunking(nblocks, &a.rows_per_chunk, &a.nchunks);
+  const uint64_t slots = (uint64_t)count * a.nchunks;
+  ZRET(c->part_s.ensure(slots * topk * sizeof(float)));
+  ZRET(c->part_i.ensure(slots * topk * sizeof(uint32_t)));
+  a.part_s = c->part_s.as<float>(); a.part_i = c->part_i.as<uint32_t>();
+  ZRET(launch_sparse_scan<false>(a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk), s));
+  MergeArgs m{};
+  m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = a.nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
+  m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
+  m.out_keys = d_keys; m.out_scores = d_scores; m.out_counts = d_counts;
+  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, s, m);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out) {
+  if (!out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = nullptr;
+  ZRET(ctx_new(device, &c));
+  zvec_hip_sparse_s *h = new (std::nothrow) zvec_hip_sparse_s();
+  if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
+  h->device = device; h->defctx = c;
+  *out = h;
+  return 0;
+}
+
+int zvec_hip_sparse_destroy(zvec_hip_sparse_t h) {
+  if (!h) return 0;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  delete h;
+  return 0;
+}
+
+int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t elements) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  std::unique_lock<FairSharedMutex> w(h->rw);
+  ZCHK(hipSetDevice(h->device));
+  return h->st.reserve(rows, elements, h->defctx->own);
+}
+
+int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const float *values, uint64_t n,
+                           const uint64_t *keys) {
+  if (!h || (n && !counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (n == 0) return 0;
+  uint64_t total = 0;
+  ZRET(sparse_check_runs(counts, indices, n, &total));       // (before anything is stored: a refused call stores nothing)
+  if (total && (!indices || !values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  std::unique_lock<FairSharedMutex> w(h->rw);
+  SparseStore &st = h->st;
+  if (st.n + n > 0xfffffffeull) return ZVEC_HIP_ERR_OUT_OF_RANGE;      // (positions are 32-bit in the partial lists)
+  ZCHK(hipSetDevice(h->device));
+  hipStream_t s = h->defctx->own;
+  ZRET(st.reserve(st.n + n, st.elems + total, s));
+  // one copy per array: offsets (the first one is the old end, already there), keys, indices, values
+  std::vector<uint64_t> off((size_t)n), ks;
+  uint64_t o = st.elems;
+  for (uint64_t i = 0; i < n; ++i) off[i] = (o += counts[i]);
+  if (!keys) {
+    ks.resize((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) ks[i] = st.n + i;
+  }
+  ZCHK(hipMemcpyAsync(st.row_off + st.n + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+  ZCHK(hipMemcpyAsync(st.keys + st.n, keys ? keys : ks.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+  if (total) {
+    ZCHK(hipMemcpyAsync(st.idx + st.elems, indices, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    ZCHK(hipMemcpyAsync(st.val + st.elems, values, (size_t)total * 4, hipMemcpyHostToDevice, s));
+  }
+  ZCHK(hipStreamSynchronize(s));
+  st.n += n;
+  st.elems += total;
+  return 0;
+}
+
+int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *elements) {
+  if (!h || (!rows && !elements)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (rows) *rows = h->st.n;
+  if (elements) *elements = h->st.elems;
+  return 0;
+}
+
+int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, float *values) {
+  if (!h || !count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  zvec_hip_ctx_s *c = h->defctx;
+  std::lock_guard<std::mutex> gc(c->mu);             // io_q is the built-in context's staging buffer
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (pos >= h->st.n) return ZVEC_HIP_ERR_NO_EXIST;
+  ZCHK(hipSetDevice(h->device));
+  const size_t words = 4 + 2 * (size_t)SPARSE_MAX_COUNT;
+  ZRET(c->io_q.ensure(words * 4));
+  hipLaunchKernelGGL(sparse_unpack_kernel, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx, h->st.val, pos, c->io_q.as<uint32_t>());
+  ZCHK(hipGetLastError());
+  std::vector<uint32_t> host(words);
+  ZCHK(hipMemcpyAsync(host.data(), c->io_q.p, words * 4, hipMemcpyDeviceToHost, c->own));
+  ZCHK(hipStreamSynchronize(c->own));
+  *count = host[0];
+  if (indices) memcpy(indices, host.data() + 4, (size_t)host[0] * 4);
+  if (values) memcpy(values, host.data() + 4 + SPARSE_MAX_COUNT, (size_t)host[0] * 4);
+  return 0;
+}
+
+int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *d_q_indices,
+                               const float *d_q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude_bitset,
+                               uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream) {
+  if (!h || !d_out_keys || !d_out_scores || !d_out_counts || (count && !q_counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;          // (query offsets are 32-bit: 2^19 x 4096 elements)
+  uint64_t total = 0;
+  ZRET(sparse_check_runs(q_counts, nullptr, count, &total));
+  if (total && (!d_q_indices || !d_q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  ZCHK(hipSetDevice(h->device));
+  return sparse_search_locked(h, c, q_counts, d_q_indices, d_q_values, count, topk, threshold, d_exclude_bitset, d_out_keys, d_out_scores,
+                              d_out_counts, pick_stream(c, stream));
+}
+
+int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
+                           const float *q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
+                           uint64_t *out_keys, float *out_scores, uint32_t *out_counts) {
+  if (!h || !out_keys || !out_scores || !out_counts || (count && !q_counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  uint64_t total = 0;
+  ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
+  if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  // indices | values in one block (never empty: an all-empty batch still uploads one unused pair)
+  const size_t te = std::max<size_t>((size_t)total, 1);
+  std::vector<uint32_t> blob(2 * te, 0u);
+  if (total) {
+    memcpy(blob.data(), q_indices, (size_t)total * 4);
+    memcpy(blob.data() + te, q_values, (size_t)total * 4);
+  }
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  ZCHK(hipSetDevice(h->device));
+  {
+    std::shared_lock<FairSharedMutex> r(h->rw);      // the row count the bitset is sized for == the rows scanned
+    ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, h->st.n, count, topk, c->cur));
+    const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
+    ZRET(sparse_search_locked(h, c, q_counts, dq, reinterpret_cast<const float *>(dq + te), count, topk, threshold,
+                              exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, c->io_keys.as<uint64_t>(), c->io_scores.as<float>(),
+                              c->io_counts.as<uint32_t>(), c->cur));
+  }
+  return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
+}

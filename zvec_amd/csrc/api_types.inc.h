@@ -370,6 +370,9 @@ struct zvec_hip_ctx_s {
   DevBuf grp_ws, grp_of, grp_out, grp_tab;
   DevBuf direct_pos, direct_keys, direct_scores, direct_idx, direct_cnt;   // small-batch IVF route: positions, stage-1 lists
   ShadowScratch sh;                                    // half-width pre-selection (zvec_hip_*_set_shadow)
+  DevBuf sp_plan;                                      // sparse search: query offsets | query-block table (api_entry_sparse.inc.h)
+  PinnedBuf sp_pin;                                    // ... its pinned source, and the event behind its last upload
+  hipEvent_t sp_ev = nullptr;
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)
   const void *io_qp = nullptr;                         // where device code finds the uploaded queries: io_q or the mapped pin_in slot
@@ -395,6 +398,7 @@ struct zvec_hip_ctx_s {
     (void)hipSetDevice(device);
     if (own) (void)hipStreamSynchronize(own);
     if (block_ev) (void)hipEventDestroy(block_ev);
+    if (sp_ev) (void)hipEventDestroy(sp_ev);
     for (auto e : ev0) (void)hipEventDestroy(e);
     for (auto e : ev1) (void)hipEventDestroy(e);
     if (own) (void)hipStreamDestroy(own);
@@ -448,6 +452,74 @@ struct zvec_hip_flat_s {
     if (append_ev) (void)hipEventDestroy(append_ev);
     delete defctx;
   }
+};
+
+// Sparse fp32 rows in CSR form (zvk_sparse.hip.h): what the scan reads, and the four arrays behind it.  A position is a row number;
+// keys and exclude bits index positions as in the flat store.  Neither copied nor moved.
+struct SparseStore {
+  uint64_t n = 0;             // rows
+  uint64_t elems = 0;         // stored (index, value) pairs
+  uint64_t cap_rows = 0, cap_elems = 0;
+  uint64_t *row_off = nullptr;   // [n + 1]
+  uint32_t *idx = nullptr;
+  float *val = nullptr;
+  uint64_t *keys = nullptr;
+  SparseStore() {}
+  SparseStore(const SparseStore &) = delete;
+
+  // room for `rows` rows and `elements` pairs; grows geometrically like Store::reserve
+  int reserve(uint64_t rows, uint64_t elements, hipStream_t stream) {
+    if (rows > cap_rows || row_off == nullptr) {
+      const uint64_t nr = std::max<uint64_t>(std::max<uint64_t>(rows, 1), cap_rows + cap_rows / 2 + 1);
+      Scoped<uint64_t> off, ks;
+      ZRET(off.alloc((size_t)nr + 1));
+      ZRET(ks.alloc((size_t)nr));
+      if (row_off) {
+        ZCHK(hipMemcpyAsync(off, row_off, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+        if (n) ZCHK(hipMemcpyAsync(ks, keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+      } else {
+        ZCHK(hipMemsetAsync(off, 0, sizeof(uint64_t), stream));       // row_off[0] = 0
+      }
+      ZCHK(hipStreamSynchronize(stream));
+      std::swap(own.row_off, off);         // the old arrays go with the locals on return: hipFree waits for the device
+      std::swap(own.keys, ks);
+      row_off = own.row_off; keys = own.keys;
+      cap_rows = nr;
+    }
+    if (elements > cap_elems) {
+      const uint64_t ne = std::max<uint64_t>(elements, cap_elems + cap_elems / 2 + 1);
+      Scoped<uint32_t> ni;
+      Scoped<float> nv;
+      ZRET(ni.alloc((size_t)ne));
+      ZRET(nv.alloc((size_t)ne));
+      if (elems) {
+        ZCHK(hipMemcpyAsync(ni, idx, (size_t)elems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        ZCHK(hipMemcpyAsync(nv, val, (size_t)elems * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        ZCHK(hipStreamSynchronize(stream));
+      }
+      std::swap(own.idx, ni);
+      std::swap(own.val, nv);
+      idx = own.idx; val = own.val;
+      cap_elems = ne;
+    }
+    return 0;
+  }
+
+ private:
+  struct Arrays {
+    Scoped<uint64_t> row_off, keys;
+    Scoped<uint32_t> idx;
+    Scoped<float> val;
+  } own;
+};
+
+struct zvec_hip_sparse_s {
+  int device = 0;
+  SparseStore st;
+  zvec_hip_ctx_s *defctx = nullptr;
+  std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)
+  FairSharedMutex rw;       // searches hold it shared, anything that may move or extend the store exclusive (as zvec_hip_flat_s)
+  ~zvec_hip_sparse_s() { delete defctx; }
 };
 
 struct zvec_hip_ivf_s {

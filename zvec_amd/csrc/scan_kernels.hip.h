@@ -33,3 +33,4 @@
 #include "zvk_build.hip.h"
 #include "zvk_group.hip.h"
 #include "zvk_hamming.hip.h"
+#include "zvk_sparse.hip.h"

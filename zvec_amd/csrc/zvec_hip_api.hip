@@ -42,5 +42,6 @@ extern "C" {
 #include "api_entry_group.inc.h"
 #include "api_entry_shards.inc.h"
 #include "api_entry_container.inc.h"
+#include "api_entry_sparse.inc.h"
 
 }  // extern "C"

@@ -1,0 +1,198 @@
+// zvk_sparse.hip.h — sparse fp32 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, staging and unpack.
+// Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
+//
+// Reference: FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_search.h:119-144) score one query
+// at a time against every stored row with MinusInnerProductSparseMatrix<float>::Compute (src/ailego/math/inner_product_matrix.h:
+// 2781-2862): a merge join of two index runs that are ascending, score = -(sum of value products over shared indices).
+//
+// Layout.  Rows are CSR: row_off[n + 1] (u64 element offsets), idx[elements] (u32, strictly ascending inside a row), val[elements]
+// (fp32), keys[n].  A position is a row number; exclude bits index positions as in the flat store.
+//
+// Scan.  ONE wave per work-group, lane = query.  A query block is up to 64 consecutive queries whose runs (at most
+// SPARSE_IMG_ELEMS elements together, chosen greedily on the host) are copied to LDS as they stand in the CSR query arrays.  The
+// wave walks the rows of its chunk; 64 stored elements are fetched by one coalesced load, then each element's (index, value) is
+// broadcast (v_readlane) and every lane binary-searches ITS OWN query's run in LDS and accumulates value * q_value: no cross-lane
+// reduction, and after a row every lane holds that row's score for its own query.  Four elements are searched at a time (four
+// independent chains of dependent LDS reads).  A run of length 0 makes no LDS read at all.  Lists are lane-owned, kept sorted by
+// insertion in LDS as [entry][lane] (lane-major: lanes that work on different entries still hit different banks); admission is
+// STRICT against min(own k-th score once the list is full, the bound the work-groups of the same query share) — zero scores tie
+// massively and a tie at the k-th place is never needed — and the threshold is a separate non-strict test.
+#pragma once
+#include "zvk_common.hip.h"
+
+namespace zvk {
+
+constexpr uint32_t SPARSE_MAX_COUNT = 4096;    // PARAM_FLAT_SPARSE_MAX_DIM_SIZE (flat_sparse_utility.h:22)
+constexpr uint32_t SPARSE_QB = 64;             // queries per query block at most (one lane each)
+constexpr uint32_t SPARSE_IMG_ELEMS = 4096;    // elements of a query block's LDS image at most (32 KiB: one longest query fits)
+constexpr uint32_t SPARSE_FUSED_MAX_K = 128;   // lane-owned lists: 64 x k x 8 bytes next to the image; longer lists take the dump route
+
+struct SparseScanArgs {
+  const uint64_t *row_off;    // [n + 1]
+  const uint32_t *idx;        // [elements]
+  const float *val;           // [elements]
+  const uint32_t *exclude;    // nullable bitset over positions, set = skip
+  const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
+  const uint32_t *q_idx;
+  const float *q_val;
+  const uint32_t *blk;        // [blocks + 1] first query of every query block
+  uint32_t blk0;              // first query block of this launch
+  uint32_t qsub0;             // DUMP: the query whose scores are row 0 of `dump`
+  uint32_t k;
+  float threshold;
+  uint64_t n;                 // rows
+  uint32_t rows_per_chunk;
+  uint32_t nchunks;
+  uint32_t nqblocks;          // query blocks of this launch
+  uint32_t *gtau;             // [nq] shared bounds (fkey of a full list's k-th score; +inf at the start)
+  float *dump;                // DUMP: [queries of the sub-batch][n] scores, +inf for excluded positions
+  float *part_s;              // [nq][nchunks][k]
+  uint32_t *part_i;
+};
+
+__host__ __device__ inline size_t sparse_lds_bytes(uint32_t img_elems, uint32_t k_lists) {
+  return ((size_t)2 * SPARSE_QB * k_lists + (size_t)2 * img_elems) * 4 + 16;
+}
+
+// One wave per work-group; item = (chunk of rows, query block).  DUMP: every score goes to the [query][position] matrix and nothing
+// is selected (large k, selected by merge_kernel).
+template <bool EXCL, bool DUMP>
+__global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a) {
+  extern __shared__ f32x4 zvk_smem4[];
+  const int lane = threadIdx.x;
+  const uint32_t k = a.k, kl = DUMP ? 0u : k;
+  float *Ls = reinterpret_cast<float *>(zvk_smem4);                   // [k][64] lane-owned lists, ascending
+  uint32_t *Li = reinterpret_cast<uint32_t *>(Ls + (size_t)SPARSE_QB * kl);
+  uint32_t *qi = Li + (size_t)SPARSE_QB * kl;                         // [tot] the block's query indices, run after run
+  const uint32_t chunk = blockIdx.x / a.nqblocks, qb = a.blk0 + (blockIdx.x - chunk * a.nqblocks);
+  const uint32_t q0 = a.blk[qb], nqb = a.blk[qb + 1] - q0;
+  const uint32_t e0 = a.q_off[q0], tot = a.q_off[q0 + nqb] - e0;
+  float *qv = reinterpret_cast<float *>(qi + tot);                    // [tot] their values
+  for (uint32_t i = lane; i < tot; i += 64) {
+    qi[i] = a.q_idx[e0 + i];
+    qv[i] = a.q_val[e0 + i];
+  }
+  const bool mine = (uint32_t)lane < nqb;
+  uint32_t qstart = 0, qlen = 0;
+  if (mine) {
+    const uint32_t b = a.q_off[q0 + lane];
+    qstart = b - e0;
+    qlen = a.q_off[q0 + lane + 1] - b;
+  }
+  // halvings that take the longest run of the block down to one element (wave-uniform)
+  uint32_t steps = 0;
+  while (__ballot(qlen > (1u << steps)) != 0) ++steps;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+
+  uint32_t cnt = 0;                   // entries of this lane's list
+  float tl = __builtin_inff();        // its k-th score once it is full
+  const uint64_t r0 = (uint64_t)chunk * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
+  for (uint64_t r = r0; r < r1; ++r) {
+    if (EXCL) {
+      if ((a.exclude[r >> 5] >> (r & 31)) & 1u) {       // (uniform)
+        if (DUMP && mine) a.dump[(size_t)(q0 + lane - a.qsub0) * a.n + r] = __builtin_inff();
+        continue;
+      }
+    }
+    uint32_t tgk = 0;
+    if (!DUMP && mine) tgk = __hip_atomic_load(&a.gtau[q0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t rb = a.row_off[r], re = a.row_off[r + 1];
+    float acc = 0.f;
+    for (uint64_t p = rb; p < re; p += 64) {
+      const uint32_t m = (uint32_t)min((uint64_t)64, re - p);
+      uint32_t ri = 0;
+      float rv = 0.f;
+      if ((uint32_t)lane < m) {
+        ri = a.idx[p + lane];
+        rv = a.val[p + lane];
+      }
+      for (uint32_t u0 = 0; u0 < m; u0 += 4) {
+        uint32_t t[4], base[4], n[4];
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const uint32_t e = u0 + u;                    // (uniform; the lane read is kept inside the wave for e >= m)
+          t[u] = bcast_u(ri, (int)(e & 63));
+          v[u] = bcast_f(rv, (int)(e & 63));
+          n[u] = e < m ? qlen : 0u;
+          base[u] = qstart;
+        }
+        // lower bound of t in the lane's run [qstart, qstart + qlen): the answer stays inside [base, base + n]
+        for (uint32_t s = 0; s < steps; ++s) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (n[u] > 1) {
+              const uint32_t half = n[u] >> 1;
+              if (qi[base[u] + half - 1] < t[u]) base[u] += half;
+              n[u] -= half;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (n[u] != 0) {
+            if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], qv[base[u]], acc);
+          }
+        }
+      }
+    }
+    const float s = 0.f - acc;        // MINUS inner product, smaller is better; no shared index: exactly +0
+    if (DUMP) {
+      if (mine) a.dump[(size_t)(q0 + lane - a.qsub0) * a.n + r] = s;
+      continue;
+    }
+    const float tg = fkey_inv(tgk);
+    if (mine && s <= a.threshold && s < fminf(tl, tg)) {
+      // the lane's own sorted insertion: entries above s move up by one, the last one of a full list drops out
+      uint32_t p = cnt < k ? cnt : k - 1;
+      while (p > 0) {
+        const float es = Ls[(size_t)(p - 1) * SPARSE_QB + lane];
+        if (!(es > s)) break;
+        Ls[(size_t)p * SPARSE_QB + lane] = es;
+        Li[(size_t)p * SPARSE_QB + lane] = Li[(size_t)(p - 1) * SPARSE_QB + lane];
+        --p;
+      }
+      Ls[(size_t)p * SPARSE_QB + lane] = s;
+      Li[(size_t)p * SPARSE_QB + lane] = (uint32_t)r;
+      if (cnt < k) ++cnt;
+      if (cnt == k) {
+        tl = Ls[(size_t)(k - 1) * SPARSE_QB + lane];
+        if (tl < tg) atomicMin(&a.gtau[q0 + lane], fkey(tl));
+      }
+    }
+  }
+  if (DUMP) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t j = 0; j < nqb; ++j) {
+    const size_t slot = (size_t)(q0 + j) * a.nchunks + chunk;
+    const uint32_t c = bcast_u(cnt, (int)j);
+    for (uint32_t e = lane; e < k; e += 64) {
+      a.part_s[slot * k + e] = e < c ? Ls[(size_t)e * SPARSE_QB + j] : __builtin_inff();
+      a.part_i[slot * k + e] = e < c ? Li[(size_t)e * SPARSE_QB + j] : IDX_NONE;
+    }
+  }
+}
+
+// Query staging.  A block's runs are contiguous in the CSR query arrays, so those arrays ARE the LDS images, block after block (the
+// scan copies [q_off[first], q_off[last + 1]) verbatim); the offsets and the block table are one small host-made plan.  What is left
+// to stage per search are the shared bounds: they start at +inf (the threshold is a separate, non-strict test).
+__global__ void __launch_bounds__(256) sparse_prep_queries_kernel(uint32_t nq, uint32_t *gtau) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nq) gtau[i] = fkey(__builtin_inff());
+}
+
+// get_vector: row `pos` -> out[0] = count, out[4 .. 4 + count) indices, out[4 + SPARSE_MAX_COUNT ..) values (as bits)
+__global__ void __launch_bounds__(256) sparse_unpack_kernel(const uint64_t *row_off, const uint32_t *idx, const float *val, uint64_t pos,
+                                                            uint32_t *out) {
+  const uint64_t b = row_off[pos];
+  const uint32_t c = (uint32_t)min((uint64_t)SPARSE_MAX_COUNT, row_off[pos + 1] - b);
+  if (threadIdx.x == 0) out[0] = c;
+  for (uint32_t i = threadIdx.x; i < c; i += 256) {
+    out[4 + i] = idx[b + i];
+    out[4 + SPARSE_MAX_COUNT + i] = __builtin_bit_cast(uint32_t, val[b + i]);
+  }
+}
+
+}  // namespace zvk

@@ -641,6 +641,112 @@ class HipFlatSearcher(_FlatBase, _FlatFeatures):
         return self.add_batch(vecs, keys)
 
 
+class HipFlatSparseStreamer:
+    """stands where "FlatSparseStreamer" / "FlatSparseSearcher" are registered (flat_sparse_streamer.cc, flat_sparse_searcher.cc):
+    a flat index of sparse fp32 rows under InnerProductSparse (zvec_hip_sparse_*).  A batch of rows or queries is CSR-like:
+    counts[n], then the runs back to back in indices (uint32, strictly ascending inside a run) and values (fp32)."""
+
+    MAX_COUNT = 4096            # PARAM_FLAT_SPARSE_MAX_DIM_SIZE (flat_sparse_utility.h:22)
+
+    def __init__(self, device=0):
+        self.device = device
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().zvec_hip_sparse_create(device, C.byref(self._h)), "zvec_hip_sparse_create")
+        self._keys_host = []      # for IndexFilter sweeps
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().zvec_hip_sparse_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def create_context(self):
+        return IndexContext(self.device)
+
+    def count(self):
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().zvec_hip_sparse_count(self._h, C.byref(n), None), "zvec_hip_sparse_count")
+        return int(n.value)
+
+    def element_count(self):
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().zvec_hip_sparse_count(self._h, None, C.byref(n)), "zvec_hip_sparse_count")
+        return int(n.value)
+
+    def reserve(self, rows, elements):
+        return _lib.lib().zvec_hip_sparse_reserve(self._h, int(rows), int(elements))
+
+    @staticmethod
+    def _runs(counts, indices, values):
+        c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        total = int(c.astype(np.uint64).sum())
+        return (c, i, v) if i.size == total and v.size == total else None
+
+    def add_batch(self, counts, indices, values, keys=None):
+        runs = self._runs(counts, indices, values)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        if runs is None or (k is not None and k.size != runs[0].size):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        n0 = self.count()
+        rc = _lib.lib().zvec_hip_sparse_append(self._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), c.size, _np_ptr(k))
+        if rc == 0 and c.size:
+            self._keys_host.append(np.arange(n0, n0 + c.size, dtype=np.uint64) if k is None else k.copy())
+        return rc
+
+    def _all_keys(self):
+        return np.concatenate(self._keys_host) if self._keys_host else np.zeros(0, np.uint64)
+
+    def get_vector_by_id(self, pos):
+        """(indices, values) of the row at storage position `pos` as stored, or None beyond the last row"""
+        n = C.c_uint32(0)
+        idx = np.zeros(self.MAX_COUNT, np.uint32)
+        val = np.zeros(self.MAX_COUNT, np.float32)
+        rc = _lib.lib().zvec_hip_sparse_get_vector(self._h, int(pos), C.byref(n), _np_ptr(idx), _np_ptr(val))
+        return (idx[:n.value].copy(), val[:n.value].copy()) if rc == 0 else None
+
+    def search_impl(self, counts, indices, values, count, ctx):
+        """search_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, context) (flat_sparse_search.h:58-148)"""
+        if ctx is None:
+            return IndexError_.InvalidArgument
+        if ctx.group_by_search():
+            return IndexError_.Unsupported              # (group-by stays with the reference's flat_sparse search)
+        if ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        runs = self._runs(counts, indices, values)
+        if runs is None or runs[0].size != int(count):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        k = ctx.topk()
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        cnts = np.zeros(count, np.uint32)
+        ex = ctx._exclude_for(self._all_keys()) if (ctx._filter_fn or ctx._exclude is not None) else None
+        rc = _lib.lib().zvec_hip_sparse_search(self._h, ctx._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), count, k, ctx.threshold(),
+                                               _np_ptr(ex), _np_ptr(keys), _np_ptr(scores), _np_ptr(cnts))
+        if rc == 0:
+            ctx._set_results(keys, scores, cnts)
+        return rc
+
+    search_bf_impl = search_impl
+
+    def search_dev(self, counts, d_indices, d_values, count, topk, d_out_keys, d_out_scores, d_out_counts, ctx,
+                   threshold=FLT_MAX, d_exclude=None, stream=None):
+        """device-pointer form (async): `counts` is a HOST array (the host cuts the batch into query blocks), everything else raw
+        device pointers (ints)."""
+        c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if c.size != int(count):
+            return IndexError_.InvalidArgument
+        return _lib.lib().zvec_hip_sparse_search_dev(
+            self._h, ctx._h, _np_ptr(c), C.c_void_p(d_indices), C.c_void_p(d_values), count, topk, threshold,
+            C.c_void_p(d_exclude) if d_exclude else None, C.c_void_p(d_out_keys), C.c_void_p(d_out_scores),
+            C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
+
+
 class HipIVFSearcher:
     """stands where "IVFSearcher"/"IVFStreamer" are registered (ivf_searcher.cc:183-250)."""
 
