@@ -572,9 +572,17 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *   - Ties.  Which of several equal scores are returned at the k-th place, and their order, is unspecified (the reference's
  *     heap resolves ties arbitrarily); zero scores tie massively.
  *   - topk * 12 + 16 <= 60 KiB as elsewhere, else ZVEC_HIP_ERR_UNSUPPORTED.
- * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), search by primary keys
- * (search_bf_by_p_keys_impl), group-by, fp16 values, the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean
- * sparse), loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
+ *   - Listed rows (zvec_hip_sparse_search_by_ids, zvec_hip_sparse_batch_distance).  `ids` / `positions` are STORAGE POSITIONS:
+ *     the caller maps primary keys to positions and drops unknown keys, as get_id(p_key) == kInvalidNodeId does in the reference
+ *     (flat_sparse_entity.h:67-70).  A position >= the row count is never dereferenced; search_by_ids never returns it and
+ *     batch_distance scores it +inf.  A position listed twice for a query is scored twice and may be returned twice (the
+ *     reference's heap takes both emplace calls).  exclude_bitset, threshold, ties and the topk cap mean what they mean for
+ *     zvec_hip_sparse_search; equal scores come in the order of the list.  out_counts[q] can be below topk simply because the
+ *     list was short; an empty list gives 0.  Host queries are validated as in zvec_hip_sparse_search.  offsets that descend,
+ *     offsets[0] != 0, a NULL where none is allowed and topk == 0 return ZVEC_HIP_ERR_INVALID_ARGUMENT and touch no output.
+ * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), group-by (search_group_p_keys
+ * included), fp16 values, the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the
+ * reference's dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
 int zvec_hip_sparse_destroy(zvec_hip_sparse_t h);
 /* room for `rows` rows and `elements` (index, value) pairs in all; the store also grows on demand, geometrically */
@@ -599,6 +607,19 @@ int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const ui
                                const uint32_t *d_q_indices, const float *d_q_values, uint32_t count, uint32_t topk,
                                float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                                float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* FlatSparseStreamer::search_bf_by_p_keys_impl (flat_sparse_streamer.cc:324-349; FlatSparseSearcher, flat_sparse_searcher.cc:
+ * 98-103; FlatSparseEntity::search_p_keys, flat_sparse_entity.h:63-77): query q against rows ids[offsets[q] .. offsets[q+1])
+ * only (offsets[count + 1], offsets[0] == 0; ids may be NULL when every list is empty).  Queries and outputs as
+ * zvec_hip_sparse_search; see Listed rows above. */
+int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts,
+                                  const uint32_t *q_indices, const float *q_values, uint32_t count, const uint32_t *ids,
+                                  const uint32_t *offsets, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
+                                  uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+/* IndexMetric::batch_distance (index_metric.h:85-87) over sparse rows, scored as search_p_keys scores its keys
+ * (flat_sparse_entity.h:63-77): one query of q_count pairs against n listed positions, scores only, in the listed order; a
+ * position beyond the rows scores +inf.  n == 0 returns 0 and writes nothing. */
+int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
+                                   const float *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,16 @@ gated; bench.py is the project's benchmark and does not cover sparse rows).
                    conflicts come on top: the bound is not reachable, the fraction says how far the scan is from it.
 
     python tools/sparse_bench.py [--out profiles/sparse_flat1m.json] [--steps 10] [--warmup 3]
+
+--by-keys: the same corpus searched by primary keys (zvec_hip_sparse_search_by_ids): 100 / 10 000 / 100 000 random distinct rows
+listed per query, batches 1 / 64, host-pointer call to host-pointer call (wall clock, median of the steps, the upload of the lists
+included).  Next to it the only other route to the same answer: zvec_hip_sparse_search with an exclude bitset set on every row
+that is not listed, which takes ONE bitset per call, so a batch whose queries have lists of their own is one call per query
+(bitsets made before the clock starts).  Both in one process, answers compared.
+
+  gather bound  8 bytes per listed element + 16 per listed row / the box's streaming figure (zvec_hip_calibrate, same process)
+
+    python tools/sparse_bench.py --by-keys [--out profiles/sparse_by_keys.json] [--steps 10] [--warmup 3]
 """
 import argparse
 import ctypes as C
@@ -44,6 +54,107 @@ def zipf_runs(torch, dev, g, n, lo, hi, vocab, draws):
     return torch.cat(counts), torch.cat(parts)
 
 
+def by_keys(args):
+    import time
+    import numpy as np
+    import torch
+    import zvec_amd
+    from zvec_amd.index import _np_ptr
+    L = zvec_amd._lib.lib()
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
+    row_len = rc_.numpy().astype(np.int64)
+    se = zvec_amd.HipFlatSparseStreamer()
+    assert se.reserve(args.n, ri.numel()) == 0
+    assert se.add_batch(row_len.astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy()) == 0
+    del ri, rv
+    ctx = se.create_context()
+    rng = np.random.default_rng(1)
+    k = args.topk
+    fmax = float(np.finfo(np.float32).max)
+
+    def median_ms(fn):
+        for _ in range(args.warmup):
+            fn()
+        t = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(t)), float(min(t))
+
+    points = []
+    for batch in (1, 64):
+        qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
+        qv = (torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1).cpu().numpy()
+        qc = qc.numpy().astype(np.uint32)
+        qi = qi.numpy().view(np.uint32).copy()
+        qo = np.zeros(batch + 1, np.int64)
+        np.cumsum(qc, out=qo[1:])
+        for length in (100, 10_000, 100_000):
+            if length > args.n:
+                continue
+            lists = [rng.choice(args.n, length, replace=False).astype(np.uint32) for _ in range(batch)]
+            ids = np.concatenate(lists)
+            offs = (np.arange(batch + 1, dtype=np.uint64) * length).astype(np.uint32)
+            keys = np.zeros((batch, k), np.uint64)
+            scores = np.zeros((batch, k), np.float32)
+            counts = np.zeros(batch, np.uint32)
+
+            def new_entry():
+                rc = L.zvec_hip_sparse_search_by_ids(se._h, ctx._h, _np_ptr(qc), _np_ptr(qi), _np_ptr(qv), batch, _np_ptr(ids), _np_ptr(offs),
+                                                     k, fmax, None, _np_ptr(keys), _np_ptr(scores), _np_ptr(counts))
+                assert rc == 0, rc
+            new_ms, new_min = median_ms(new_entry)
+            # the other route: every bit set except the listed rows', one call per query
+            words = (args.n + 63) // 64
+            bitsets = np.full((batch, words), 0xffffffffffffffff, np.uint64)
+            for q in range(batch):
+                np.bitwise_and.at(bitsets[q], lists[q] // 64, ~(np.uint64(1) << (lists[q] % 64).astype(np.uint64)))
+            keys2 = np.zeros((batch, k), np.uint64)
+            scores2 = np.zeros((batch, k), np.float32)
+            counts2 = np.zeros(batch, np.uint32)
+
+            def bitset_route():
+                for q in range(batch):
+                    rc = L.zvec_hip_sparse_search(se._h, ctx._h, _np_ptr(qc[q:q + 1]), _np_ptr(qi[qo[q]:qo[q + 1]]), _np_ptr(qv[qo[q]:qo[q + 1]]),
+                                                  1, k, fmax, _np_ptr(bitsets[q]), _np_ptr(keys2[q:q + 1]), _np_ptr(scores2[q:q + 1]),
+                                                  _np_ptr(counts2[q:q + 1]))
+                    assert rc == 0, rc
+            old_ms, old_min = median_ms(bitset_route)
+            # the same answer up to the order of the sums: a score is an fp32 sum of m <= 64 products (the longest query) of values
+            # below 1, so either route is within (m + 1) * 2^-23 * sum |products| <= 65 * 2^-23 * 64 of the exact score, and two
+            # routes within twice that of each other (the k-th candidates may swap inside that band, their scores stay within it)
+            assert counts.tolist() == counts2.tolist() == [k] * batch
+            assert bool(np.all(scores[:, 1:] >= scores[:, :-1])) and float(np.abs(scores - scores2).max()) <= 2 * 65 * 2.0 ** -23 * 64
+            elements = int(sum(int(row_len[a].sum()) for a in lists))
+            points.append({"batch": batch, "keys_per_query": length, "by_ids_ms": new_ms, "by_ids_min_ms": new_min, "bitset_route_ms": old_ms,
+                           "bitset_route_min_ms": old_min, "speedup": old_ms / new_ms, "listed_elements": elements,
+                           "gathered_bytes": elements * 8 + batch * length * 16})
+            print(json.dumps(points[-1]), flush=True)
+    del se
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = L.zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for p in points:
+        p["gather_bound_ms"] = p["gathered_bytes"] / (gbs.value * 1e9) * 1e3
+        p["bound_fraction"] = p["gather_bound_ms"] / p["by_ids_ms"]
+    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d, searched by listed rows" % (args.n, args.vocab, k),
+           "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)", "clock_mhz": mhz.value,
+           "stream_gbs": gbs.value, "steps": args.steps, "warmup": args.warmup, "points": points}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -52,7 +163,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--by-keys", action="store_true")
     args = ap.parse_args()
+    if args.by_keys:
+        return by_keys(args)
     import numpy as np
     import torch
     import zvec_amd

@@ -155,6 +155,9 @@ SYMBOLS = {
     "zvec_hip_sparse_search": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p]),
     "zvec_hip_sparse_search_dev": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p,
                                              C.c_void_p]),
+    "zvec_hip_sparse_search_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_float, _u64p, _u64p,
+                                                _f32p, _u32p]),
+    "zvec_hip_sparse_batch_distance": (C.c_int, [_h, _h, C.c_uint32, _u32p, _f32p, _u32p, C.c_uint32, _f32p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

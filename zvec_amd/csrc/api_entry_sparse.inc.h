@@ -145,6 +145,59 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   return 0;
 }
 
+// Scores of listed rows (sparse_rows_kernel): query q against the positions ids[offsets[q] .. offsets[q + 1]).  The caller holds
+// c->mu and h->rw (shared); q_counts, ids and offsets are HOST arrays, q_counts has passed sparse_check_runs and offsets starts at 0
+// and never descends; the query arrays and the bitset are device pointers.  Leaves the scores in c->part_s [entries] (+inf: position
+// beyond the rows, or excluded), the positions in c->plan [entries] and tells where the list offsets went (*d_list_off).  Enqueues
+// only, except for a wait on the previous plan upload of the same context.  A work item is (query, slice of its list): the slice is
+// as long as it takes to put 16 items on every CU, SPARSE_ROWS_SLICE at most, so that a short batch still fills the device.
+int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const float *d_qval,
+                       uint32_t count, const uint32_t *ids, const uint32_t *offsets, const uint64_t *d_exclude,
+                       const uint32_t **d_list_off, hipStream_t s) {
+  const SparseStore &st = h->st;
+  const uint32_t total = offsets[count];
+  const uint64_t want = (uint64_t)device_cus(c) * 16;
+  const uint32_t slice = (uint32_t)std::min<uint64_t>(SPARSE_ROWS_SLICE, std::max<uint64_t>(1, (total + want - 1) / want));
+  // plan = q_off[count + 1] | list_off[count + 1] | item_q[items] | item_e0[items]
+  std::vector<uint32_t> plan((size_t)2 * (count + 1), 0u), item_e0;
+  uint32_t max_run = 0;
+  for (uint32_t q = 0; q < count; ++q) {
+    plan[q + 1] = plan[q] + q_counts[q];
+    max_run = std::max(max_run, q_counts[q]);
+  }
+  memcpy(plan.data() + count + 1, offsets, ((size_t)count + 1) * 4);
+  for (uint32_t q = 0; q < count; ++q)
+    for (uint64_t e = offsets[q]; e < offsets[q + 1]; e += slice) {
+      plan.push_back(q);
+      item_e0.push_back((uint32_t)e);
+    }
+  const uint32_t items = (uint32_t)item_e0.size();
+  plan.insert(plan.end(), item_e0.begin(), item_e0.end());
+  // the plan goes through the context's pinned slot: the previous search's upload has to have left it
+  if (c->sp_ev == nullptr) ZCHK(hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
+  else ZCHK(hipEventSynchronize(c->sp_ev));
+  ZRET(c->sp_pin.ensure(plan.size() * 4));
+  ZRET(c->sp_plan.ensure(plan.size() * 4));
+  memcpy(c->sp_pin.p, plan.data(), plan.size() * 4);
+  ZCHK(hipMemcpyAsync(c->sp_plan.p, c->sp_pin.p, plan.size() * 4, hipMemcpyHostToDevice, s));
+  ZCHK(hipEventRecord(c->sp_ev, s));
+  ZRET(c->plan.ensure(std::max<size_t>(total, 1) * 4));
+  ZRET(c->part_s.ensure(std::max<size_t>(total, 1) * 4));
+  if (total) ZCHK(hipMemcpyAsync(c->plan.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
+  SparseRowsArgs a{};
+  a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
+  a.q_off = c->sp_plan.as<uint32_t>(); a.q_idx = d_qidx; a.q_val = d_qval;
+  a.ids = c->plan.as<uint32_t>(); a.list_off = a.q_off + count + 1; a.item_q = a.list_off + count + 1; a.item_e0 = a.item_q + items;
+  a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>();
+  *d_list_off = a.list_off;
+  if (items == 0) return 0;
+  const size_t lds = (size_t)2 * max_run * 4;         // (at most 32 KiB: no launch attribute needed)
+  if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<true>), dim3(items), dim3(64), lds, s, a);
+  else hipLaunchKernelGGL((sparse_rows_kernel<false>), dim3(items), dim3(64), lds, s, a);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -286,4 +339,85 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
                               c->io_counts.as<uint32_t>(), c->cur));
   }
   return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
+}
+
+// FlatSparseStreamer::search_bf_by_p_keys_impl (flat_sparse_streamer.cc:324-349; FlatSparseSearcher's, flat_sparse_searcher.cc:
+// 98-103; FlatSparseEntity::search_p_keys, flat_sparse_entity.h:63-77): query q is scored against the rows at positions
+// ids[offsets[q] .. offsets[q + 1]) only.  The caller has mapped primary keys to positions and dropped unknown keys (get_id(p_key)
+// == kInvalidNodeId); a position beyond the rows is skipped here, a position listed twice is scored twice (the reference's heap
+// takes both emplace calls).
+int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
+                                  const float *q_values, uint32_t count, const uint32_t *ids, const uint32_t *offsets, uint32_t topk,
+                                  float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
+                                  uint32_t *out_counts) {
+  if (!h || !out_keys || !out_scores || !out_counts || (count && (!q_counts || !offsets))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count == 0) return 0;
+  if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (offsets[0] != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  for (uint32_t q = 0; q < count; ++q)
+    if (offsets[q + 1] < offsets[q]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (offsets[count] && !ids) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  uint64_t total = 0;
+  ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
+  if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  // indices | values in one block (never empty: an all-empty batch still uploads one unused pair)
+  const size_t te = std::max<size_t>((size_t)total, 1);
+  std::vector<uint32_t> blob(2 * te, 0u);
+  if (total) {
+    memcpy(blob.data(), q_indices, (size_t)total * 4);
+    memcpy(blob.data() + te, q_values, (size_t)total * 4);
+  }
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  ZCHK(hipSetDevice(h->device));
+  {
+    std::shared_lock<FairSharedMutex> r(h->rw);      // the row count the bitset is sized for == the rows the positions are checked against
+    ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, h->st.n, count, topk, c->cur));
+    const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
+    const uint32_t *d_off = nullptr;
+    ZRET(sparse_rows_locked(h, c, q_counts, dq, reinterpret_cast<const float *>(dq + te), count, ids, offsets,
+                            exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, &d_off, c->cur));
+    // selection, the threshold test and position -> key: every listed entry is a slot of one candidate, a query's slots are its list
+    // (a skipped entry holds +inf, which no finite bound admits)
+    MergeArgs m{};
+    m.part_s = c->part_s.as<float>(); m.part_i = c->plan.as<uint32_t>(); m.slot_begin = d_off; m.slot_stride = 1; m.k = topk;
+    m.slot_len = 1; m.threshold = std::min(threshold, FLT_MAX); m.keymap = h->st.keys;
+    m.out_keys = c->io_keys.as<uint64_t>(); m.out_scores = c->io_scores.as<float>(); m.out_counts = c->io_counts.as<uint32_t>();
+    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, c->cur, m);
+    ZCHK(hipGetLastError());
+  }
+  return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
+}
+
+// IndexMetric::batch_distance (index_metric.h:85-87) for sparse rows: ONE query against n listed positions, scores only, in the
+// listed order (sparse_rows_kernel without the selection; FlatSparseEntity::search_p_keys, flat_sparse_entity.h:63-77, scores its
+// keys one by one the same way).  A position beyond the rows scores +inf.
+int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
+                                   const float *q_values, const uint32_t *positions, uint32_t n, float *out_scores) {
+  if (!h || (q_count && (!q_indices || !q_values)) || (n && (!positions || !out_scores))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  uint64_t total = 0;
+  ZRET(sparse_check_runs(&q_count, q_indices, 1, &total));
+  if (n == 0) return 0;
+  const size_t te = std::max<size_t>((size_t)total, 1);
+  std::vector<uint32_t> blob(2 * te, 0u);
+  if (total) {
+    memcpy(blob.data(), q_indices, (size_t)total * 4);
+    memcpy(blob.data() + te, q_values, (size_t)total * 4);
+  }
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  ZCHK(hipSetDevice(h->device));
+  hipStream_t s = c->cur;
+  ZRET(c->io_q.ensure(blob.size() * 4));
+  ZCHK(hipMemcpyAsync(c->io_q.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, s));
+  const uint32_t *dq = c->io_q.as<uint32_t>();
+  const uint32_t offs[2] = {0, n};
+  const uint32_t *d_off = nullptr;
+  ZRET(sparse_rows_locked(h, c, &q_count, dq, reinterpret_cast<const float *>(dq + te), 1, positions, offs, nullptr, &d_off, s));
+  ZCHK(hipMemcpyAsync(out_scores, c->part_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  ZCHK(hipStreamSynchronize(s));
+  return 0;
 }

@@ -1,4 +1,4 @@
-// zvk_sparse.hip.h — sparse fp32 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, staging and unpack.
+// zvk_sparse.hip.h — sparse fp32 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, staging and unpack.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Reference: FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_search.h:119-144) score one query
@@ -173,6 +173,135 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
       a.part_i[slot * k + e] = e < c ? Li[(size_t)e * SPARSE_QB + j] : IDX_NONE;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Listed rows (FlatSparseStreamer::search_bf_by_p_keys_impl, flat_sparse_streamer.cc:324-349; FlatSparseEntity::search_p_keys,
+// flat_sparse_entity.h:63-77; batch_distance): every query meets a short list of positions, so the parallelism comes from inside a
+// row: lane = STORED ELEMENT.  One wave per work-group; a work item is one query and a slice of at most SPARSE_ROWS_SLICE of its
+// listed entries.  The query's run is copied to LDS once per item.  The entries of the slice are classified lane = entry (position
+// >= n or excluded: skipped before anything of the row is fetched; else the row's two offsets), then the wave takes the live
+// entries one after the other (wave-uniform): 64 stored elements per coalesced load, every lane lower-bounds ITS OWN stored index
+// in the query's run (ceil(log2(run length)) halvings, wave-uniform trip count, one equality probe, on a hit one fmaf into a
+// lane-private sum), and after the row one butterfly adds the 64 sums up.  Rows longer than 64 elements take four loads at a time:
+// four independent chains of dependent LDS reads.  Scores leave as one coalesced store per slice into a ragged [entries] array,
+// +inf for a skipped entry; merge_kernel selects over each query's slice of it (slot_begin = the list offsets, one candidate per
+// slot), so ties are ordered by the place in the list.
+constexpr uint32_t SPARSE_ROWS_SLICE = 64;     // listed entries per work item at most (one lane each while they are classified)
+
+struct SparseRowsArgs {
+  const uint64_t *row_off;    // [n + 1]
+  const uint32_t *idx;        // [elements]
+  const float *val;           // [elements]
+  const uint32_t *exclude;    // nullable bitset over positions, set = skip
+  const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
+  const uint32_t *q_idx;
+  const float *q_val;
+  const uint32_t *ids;        // [entries] listed positions, query after query; any value (>= n: skipped)
+  const uint32_t *list_off;   // [nq + 1] entries of every query
+  const uint32_t *item_q;     // [items] the query of a work item
+  const uint32_t *item_e0;    // [items] its first entry
+  uint32_t slice;             // entries per item at most, <= SPARSE_ROWS_SLICE
+  uint64_t n;                 // rows
+  float *scores;              // [entries]
+};
+
+// halvings that take a run of qlen elements down to one: ceil(log2(qlen))
+__device__ __forceinline__ uint32_t sparse_halvings(uint32_t qlen) { return qlen > 1 ? 32u - (uint32_t)__builtin_clz(qlen - 1) : 0u; }
+
+// Stored elements [p, min(re, p + 64 U)) against the run qi / qv [qlen] in LDS (qlen > 0), lane = element: acc plus this lane's
+// products.  If the lane's index t is in the run at j, j stays inside [base, base + n) through every halving.
+template <int U>
+__device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const float *val, uint64_t p, uint64_t re, const uint32_t *qi,
+                                                 const float *qv, uint32_t qlen, uint32_t steps, int lane, float acc) {
+  uint32_t t[U], base[U], n[U];
+  float v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t e = p + (uint64_t)u * 64 + (uint32_t)lane;
+    const bool in = e < re;
+    t[u] = in ? idx[e] : 0u;
+    v[u] = in ? val[e] : 0.f;
+    n[u] = in ? qlen : 0u;
+    base[u] = 0;
+  }
+  for (uint32_t s = 0; s < steps; ++s) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (n[u] > 1) {
+        const uint32_t half = n[u] >> 1;
+        if (qi[base[u] + half - 1] < t[u]) base[u] += half;
+        n[u] -= half;
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (n[u] != 0) {
+      if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], qv[base[u]], acc);
+    }
+  }
+  return acc;
+}
+
+// The whole wave scores ONE stored row [rb, re) (wave-uniform) against the run in LDS: the sum of value products over shared
+// indices, the same bits in every lane (the butterfly's order is fixed).  A run of length 0 makes no LDS read and no load.
+// (sparse_rows_kernel's inner step; a narrow zvec_hip_sparse_search batch can walk its chunk of rows with it as well.)
+__device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const float *val, uint64_t rb, uint64_t re, const uint32_t *qi,
+                                                     const float *qv, uint32_t qlen, uint32_t steps, int lane) {
+  if (qlen == 0) return 0.f;
+  float acc = 0.f;
+  uint64_t p = rb;
+  for (; p < re && re - p > 64; p += 256) acc = sparse_lane_dot<4>(idx, val, p, re, qi, qv, qlen, steps, lane, acc);
+  if (p < re) acc = sparse_lane_dot<1>(idx, val, p, re, qi, qv, qlen, steps, lane, acc);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  return acc;
+}
+
+template <bool EXCL>
+__global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a) {
+  extern __shared__ f32x4 zvk_smem4[];
+  const int lane = threadIdx.x;
+  const uint32_t q = a.item_q[blockIdx.x], e0 = a.item_e0[blockIdx.x];
+  const uint32_t e1 = min(e0 + min(a.slice, SPARSE_ROWS_SLICE), a.list_off[q + 1]);
+  const uint32_t qb = a.q_off[q], qlen = min(a.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
+  uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);             // [qlen] the query's indices
+  float *qv = reinterpret_cast<float *>(qi + qlen);                   // [qlen] its values
+  for (uint32_t i = lane; i < qlen; i += 64) {
+    qi[i] = a.q_idx[qb + i];
+    qv[i] = a.q_val[qb + i];
+  }
+  const uint32_t steps = sparse_halvings(qlen);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+
+  // lane = listed entry: which entries are scored at all, and where their rows lie
+  const uint32_t e = e0 + (uint32_t)lane;
+  bool live = false;
+  uint64_t rb = 0, re = 0;
+  if (e < e1) {
+    const uint32_t p = a.ids[e];
+    live = p < a.n;
+    if (EXCL) {
+      if (live) live = ((a.exclude[p >> 5] >> (p & 31)) & 1u) == 0;
+    }
+    if (live) {
+      rb = a.row_off[p];
+      re = a.row_off[(uint64_t)p + 1];
+    }
+  }
+  float out = __builtin_inff();
+  uint64_t todo = __ballot(live);
+  while (todo) {                      // (uniform)
+    const int j = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
+    const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
+    const float sum = sparse_wave_row_dot(a.idx, a.val, b, en, qi, qv, qlen, steps, lane);
+    if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+  }
+  if (e < e1) a.scores[e] = out;
 }
 
 // Query staging.  A block's runs are contiguous in the CSR query arrays, so those arrays ARE the LDS images, block after block (the

@@ -734,6 +734,49 @@ class HipFlatSparseStreamer:
 
     search_bf_impl = search_impl
 
+    # primary keys -> storage positions, as FlatSparseEntity::search_p_keys does key by key (flat_sparse_entity.h:63-77): the dense
+    # streamer's helper, which needs nothing of its owner but _all_keys()
+    _p_keys_positions = _FlatBase._p_keys_positions
+
+    def search_bf_by_p_keys_impl(self, counts, indices, values, p_keys, count, ctx):
+        """FlatSparseStreamer::search_bf_by_p_keys_impl (flat_sparse_streamer.cc:324-349): p_keys[q] = the primary keys query q is
+        compared with; unknown keys are skipped, the context's filter applies per key, its exclude bitset per position; a key
+        listed twice is scored twice."""
+        if ctx is None:
+            return IndexError_.InvalidArgument
+        if ctx.group_by_search():
+            return IndexError_.Unsupported              # (search_group_p_keys stays with the reference)
+        if ctx.topk() == 0 or len(p_keys) != int(count):
+            return IndexError_.InvalidArgument
+        runs = self._runs(counts, indices, values)
+        if runs is None or runs[0].size != int(count):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        ids, offs = self._p_keys_positions(p_keys, ctx)
+        k = ctx.topk()
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        cnts = np.zeros(count, np.uint32)
+        rc = _lib.lib().zvec_hip_sparse_search_by_ids(self._h, ctx._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), count, _np_ptr(ids),
+                                                      _np_ptr(offs), k, ctx.threshold(), _np_ptr(ctx._exclude), _np_ptr(keys),
+                                                      _np_ptr(scores), _np_ptr(cnts))
+        if rc == 0:
+            ctx._set_results(keys, scores, cnts)
+        return rc
+
+    def batch_distance(self, indices, values, positions, ctx=None):
+        """IndexMetric::batch_distance: one sparse query against the listed storage positions, fp32 scores in that order (+inf for a
+        position beyond the rows)"""
+        i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        if i.size != v.size:
+            raise ValueError("zvec_amd: a sparse query needs as many values as indices")
+        pos = np.ascontiguousarray(positions, np.uint32).reshape(-1)
+        out = np.zeros(pos.size, np.float32)
+        _lib.check(_lib.lib().zvec_hip_sparse_batch_distance(self._h, ctx._h if ctx else None, i.size, _np_ptr(i), _np_ptr(v),
+                                                             _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_sparse_batch_distance")
+        return out
+
     def search_dev(self, counts, d_indices, d_values, count, topk, d_out_keys, d_out_scores, d_out_counts, ctx,
                    threshold=FLT_MAX, d_exclude=None, stream=None):
         """device-pointer form (async): `counts` is a HOST array (the host cuts the batch into query blocks), everything else raw
