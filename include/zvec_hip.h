@@ -548,9 +548,18 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
 
 /* ---- flat index of sparse rows ---------------------------------------------------------------
  * stands behind FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_streamer.cc:186-300,
- * flat_sparse_search.h:58-148) for fp32 values under the "InnerProductSparse" metric (inner_product_metric.cc:329,491:
- * MinusInnerProductSparseMatrix<float>::Compute).  Rules, as the reference has them:
- *   - Row format.  A row, and a query, is `count` pairs (uint32_t index, float value), count <= 4096
+ * flat_sparse_search.h:58-148) for fp32 and fp16 values under the "InnerProductSparse" metric (inner_product_metric.cc:329,
+ * 484-495: MinusInnerProductSparseMatrix<float>::Compute for DT_FP32, <ailego::Float16> for DT_FP16).  Rules, as the reference has
+ * them:
+ *   - Value type.  A handle serves ONE value type, chosen at zvec_hip_sparse_create_typed: ZVEC_HIP_DT_FP32 (float) or
+ *     ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes).  Every `values` pointer below (rows, queries, get_vector, host or device) is a
+ *     `const void *` / `void *` read as elements of the handle's type, the way zvec_hip_flat_* treats `vecs`.  fp16 values are
+ *     stored as halves (never widened in memory); each is widened to fp32 where it is read, which is exact (subnormals included),
+ *     and the products are formed and summed in fp32, as the reference does on an AVX host (InnerProductSparseInSegmentAVX,
+ *     src/ailego/math/inner_product_matrix_fp16.cc:1066-1226: the matched halves go through _mm256_cvtph_ps into an fp32
+ *     accumulator, :1208-1223).  No half-precision arithmetic.  Scores are fp32 for either type.  Values must be finite: inf and
+ *     NaN give unspecified scores.
+ *   - Row format.  A row, and a query, is `count` pairs (uint32_t index, value), count <= 4096
  *     (PARAM_FLAT_SPARSE_MAX_DIM_SIZE, flat_sparse_utility.h:22).  The reference discards a longer row
  *     (flat_sparse_streamer.cc:197-201); here zvec_hip_sparse_append returns ZVEC_HIP_ERR_INVALID_ARGUMENT for it and stores
  *     NOTHING of the call; a longer query is refused the same way.  count == 0 is a legal row and a legal query.
@@ -581,30 +590,34 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     list was short; an empty list gives 0.  Host queries are validated as in zvec_hip_sparse_search.  offsets that descend,
  *     offsets[0] != 0, a NULL where none is allowed and topk == 0 return ZVEC_HIP_ERR_INVALID_ARGUMENT and touch no output.
  * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), group-by (search_group_p_keys
- * included), fp16 values, the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the
- * reference's dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
+ * included), the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the reference's
+ * dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
+/* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched */
+int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out);
+/* the value type the handle was created with */
+int zvec_hip_sparse_dtype(zvec_hip_sparse_t h, int *dtype);
 int zvec_hip_sparse_destroy(zvec_hip_sparse_t h);
 /* room for `rows` rows and `elements` (index, value) pairs in all; the store also grows on demand, geometrically */
 int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t elements);
 /* FlatSparseStreamer::add_impl / add_with_id_impl (flat_sparse_streamer.cc:186-300) in bulk: n rows in storage order, row i
  * being counts[i] pairs; keys == NULL -> key = storage position.  All or nothing (see Row format, Index order). */
-int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const float *values,
+int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const void *values,
                            uint64_t n, const uint64_t *keys);
 /* either output nullable */
 int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *elements);
-/* get_sparse_vector_by_id: row `pos` as stored, bit for bit.  *count always; indices / values (room for *count entries, at
- * most 4096) may each be NULL: a size query.  ZVEC_HIP_ERR_NO_EXIST beyond the last row. */
-int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, float *values);
+/* get_sparse_vector_by_id: row `pos` as stored, bit for bit (halves come back as halves).  *count always; indices / values
+ * (room for *count entries, at most 4096) may each be NULL: a size query.  ZVEC_HIP_ERR_NO_EXIST beyond the last row. */
+int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, void *values);
 /* search_impl / search_bf_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, ctx) (flat_sparse_search.h:58-148):
  * `count` queries, query q being q_counts[q] pairs, runs back to back.  Outputs as zvec_hip_flat_search. */
 int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
-                           const float *q_values, uint32_t count, uint32_t topk, float threshold,
+                           const void *q_values, uint32_t count, uint32_t topk, float threshold,
                            const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
 /* The same with the queries' pairs, the bitset and the outputs in device memory; enqueues on `stream` and returns.  q_counts
  * stays a HOST array: the host cuts the batch into query blocks by length before it launches anything. */
 int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts,
-                               const uint32_t *d_q_indices, const float *d_q_values, uint32_t count, uint32_t topk,
+                               const uint32_t *d_q_indices, const void *d_q_values, uint32_t count, uint32_t topk,
                                float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                                float *d_out_scores, uint32_t *d_out_counts, void *stream);
 /* FlatSparseStreamer::search_bf_by_p_keys_impl (flat_sparse_streamer.cc:324-349; FlatSparseSearcher, flat_sparse_searcher.cc:
@@ -612,14 +625,14 @@ int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const ui
  * only (offsets[count + 1], offsets[0] == 0; ids may be NULL when every list is empty).  Queries and outputs as
  * zvec_hip_sparse_search; see Listed rows above. */
 int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts,
-                                  const uint32_t *q_indices, const float *q_values, uint32_t count, const uint32_t *ids,
+                                  const uint32_t *q_indices, const void *q_values, uint32_t count, const uint32_t *ids,
                                   const uint32_t *offsets, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
                                   uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
 /* IndexMetric::batch_distance (index_metric.h:85-87) over sparse rows, scored as search_p_keys scores its keys
  * (flat_sparse_entity.h:63-77): one query of q_count pairs against n listed positions, scores only, in the listed order; a
  * position beyond the rows scores +inf.  n == 0 returns 0 and writes nothing. */
 int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
-                                   const float *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
+                                   const void *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
 
 #ifdef __cplusplus
 }

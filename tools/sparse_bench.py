@@ -2,14 +2,17 @@
 of 16-64 elements, k = 10, batches 1 / 64 / 1024: QPS and ms per step against two bounds of the box it runs on (reported, not
 gated; bench.py is the project's benchmark and does not cover sparse rows).
 
-  streaming bound  stored bytes of the index (8 per element + 16 per row) / the box's streaming figure (zvec_hip_calibrate, same
-                   process): batch 1
+  streaming bound  stored bytes of the index (8 per element + 16 per row; 6 per element with --dtype fp16) / the box's streaming
+                   figure (zvec_hip_calibrate, same process): batch 1
   LDS-issue bound  every stored element costs every query block ceil(log2(longest run of the block)) + 1 probes of the block's
                    LDS image; a probe is one ds_read_b32 wave instruction = 2 LDS cycles when conflict-free, one LDS per CU:
                    elements x blocks x probes x 2 / (CUs x calibrated clock).  Lanes probe unrelated addresses, so bank
                    conflicts come on top: the bound is not reachable, the fraction says how far the scan is from it.
 
-    python tools/sparse_bench.py [--out profiles/sparse_flat1m.json] [--steps 10] [--warmup 3]
+    python tools/sparse_bench.py [--dtype fp32|fp16] [--out profiles/sparse_flat1m.json] [--steps 10] [--warmup 3]
+
+--dtype fp16: the same corpus and the same queries with every value rounded to half, in an index of fp16 values
+(zvec_hip_sparse_create_typed(ZVEC_HIP_DT_FP16, ...)); the LDS-issue bound is unchanged (a half is still one probe).
 
 --by-keys: the same corpus searched by primary keys (zvec_hip_sparse_search_by_ids): 100 / 10 000 / 100 000 random distinct rows
 listed per query, batches 1 / 64, host-pointer call to host-pointer call (wall clock, median of the steps, the upload of the lists
@@ -17,7 +20,8 @@ included).  Next to it the only other route to the same answer: zvec_hip_sparse_
 that is not listed, which takes ONE bitset per call, so a batch whose queries have lists of their own is one call per query
 (bitsets made before the clock starts).  Both in one process, answers compared.
 
-  gather bound  8 bytes per listed element + 16 per listed row / the box's streaming figure (zvec_hip_calibrate, same process)
+  gather bound  8 bytes (fp16: 6) per listed element + 16 per listed row / the box's streaming figure (zvec_hip_calibrate, same
+                process)
 
     python tools/sparse_bench.py --by-keys [--out profiles/sparse_by_keys.json] [--steps 10] [--warmup 3]
 """
@@ -67,9 +71,11 @@ def by_keys(args):
     rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
     rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
     row_len = rc_.numpy().astype(np.int64)
-    se = zvec_amd.HipFlatSparseStreamer()
+    np_val = np.float16 if args.dtype == "fp16" else np.float32
+    elem_bytes = 4 + np.dtype(np_val).itemsize
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
     assert se.reserve(args.n, ri.numel()) == 0
-    assert se.add_batch(row_len.astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy()) == 0
+    assert se.add_batch(row_len.astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
     del ri, rv
     ctx = se.create_context()
     rng = np.random.default_rng(1)
@@ -89,7 +95,7 @@ def by_keys(args):
     points = []
     for batch in (1, 64):
         qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
-        qv = (torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1).cpu().numpy()
+        qv = (torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1).cpu().numpy().astype(np_val)
         qc = qc.numpy().astype(np.uint32)
         qi = qi.numpy().view(np.uint32).copy()
         qo = np.zeros(batch + 1, np.int64)
@@ -133,7 +139,7 @@ def by_keys(args):
             elements = int(sum(int(row_len[a].sum()) for a in lists))
             points.append({"batch": batch, "keys_per_query": length, "by_ids_ms": new_ms, "by_ids_min_ms": new_min, "bitset_route_ms": old_ms,
                            "bitset_route_min_ms": old_min, "speedup": old_ms / new_ms, "listed_elements": elements,
-                           "gathered_bytes": elements * 8 + batch * length * 16})
+                           "gathered_bytes": elements * elem_bytes + batch * length * 16})
             print(json.dumps(points[-1]), flush=True)
     del se
     torch.cuda.synchronize()
@@ -146,6 +152,7 @@ def by_keys(args):
         p["gather_bound_ms"] = p["gathered_bytes"] / (gbs.value * 1e9) * 1e3
         p["bound_fraction"] = p["gather_bound_ms"] / p["by_ids_ms"]
     res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d, searched by listed rows" % (args.n, args.vocab, k),
+           "dtype": args.dtype,
            "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)", "clock_mhz": mhz.value,
            "stream_gbs": gbs.value, "steps": args.steps, "warmup": args.warmup, "points": points}
     print(json.dumps(res))
@@ -164,6 +171,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--by-keys", action="store_true")
+    ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
     args = ap.parse_args()
     if args.by_keys:
         return by_keys(args)
@@ -175,17 +183,20 @@ def main():
     g.manual_seed(1)
     rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
     rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
-    se = zvec_amd.HipFlatSparseStreamer()
+    np_val = np.float16 if args.dtype == "fp16" else np.float32
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
     assert se.reserve(args.n, ri.numel()) == 0
-    assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy()) == 0
+    assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
     elements = se.element_count()
-    stored = elements * 8 + (args.n + 1) * 8 + args.n * 8
+    stored = elements * (4 + np.dtype(np_val).itemsize) + (args.n + 1) * 8 + args.n * 8
     ctx = se.create_context()
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
     legs = []
     for batch in (1, 64, 1024):
         qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
         qv = torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1
+        if args.dtype == "fp16":
+            qv = qv.to(torch.float16)              # (the device array search_dev reads: halves for an fp16 index)
         d_qi = qi.to(dev)
         qc_np = qc.numpy().astype(np.uint32)
         keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
@@ -232,6 +243,7 @@ def main():
         leg.update(stream_bound_ms=stream_ms, stream_fraction=stream_ms / leg["ms_per_step"], lds_bound_ms=lds_ms,
                    lds_fraction=lds_ms / leg["ms_per_step"])
     res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d" % (args.n, args.vocab, args.topk),
+           "dtype": args.dtype,
            "elements": elements, "stored_bytes": stored, "cus": cus, "clock_mhz": mhz.value, "stream_gbs": gbs.value,
            "steps": args.steps, "warmup": args.warmup, "cpu_comparison": "not compared", "legs": legs}
     print(json.dumps(res))

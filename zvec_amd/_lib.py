@@ -9,6 +9,7 @@ import os
 from . import build as _build
 
 _f32p = C.c_void_p
+_valp = C.c_void_p    # sparse values: elements of the handle's type (float or IEEE binary16), `void *` in the header
 _u64p = C.c_void_p
 _u32p = C.c_void_p
 _h = C.c_void_p
@@ -147,17 +148,19 @@ SYMBOLS = {
     "zvec_hip_container_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(Segment), C.c_uint32, C.POINTER(C.c_uint32)]),
     "zvec_hip_crc32c": (C.c_uint32, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "zvec_hip_sparse_create": (C.c_int, [C.c_int, C.POINTER(_h)]),
+    "zvec_hip_sparse_create_typed": (C.c_int, [C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_sparse_dtype": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "zvec_hip_sparse_destroy": (C.c_int, [_h]),
     "zvec_hip_sparse_reserve": (C.c_int, [_h, C.c_uint64, C.c_uint64]),
-    "zvec_hip_sparse_append": (C.c_int, [_h, _u32p, _u32p, _f32p, C.c_uint64, _u64p]),
+    "zvec_hip_sparse_append": (C.c_int, [_h, _u32p, _u32p, _valp, C.c_uint64, _u64p]),
     "zvec_hip_sparse_count": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    "zvec_hip_sparse_get_vector": (C.c_int, [_h, C.c_uint64, C.POINTER(C.c_uint32), _u32p, _f32p]),
-    "zvec_hip_sparse_search": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p]),
-    "zvec_hip_sparse_search_dev": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p,
+    "zvec_hip_sparse_get_vector": (C.c_int, [_h, C.c_uint64, C.POINTER(C.c_uint32), _u32p, _valp]),
+    "zvec_hip_sparse_search": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p]),
+    "zvec_hip_sparse_search_dev": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p, _u32p,
                                              C.c_void_p]),
-    "zvec_hip_sparse_search_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_float, _u64p, _u64p,
+    "zvec_hip_sparse_search_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_float, _u64p, _u64p,
                                                 _f32p, _u32p]),
-    "zvec_hip_sparse_batch_distance": (C.c_int, [_h, _h, C.c_uint32, _u32p, _f32p, _u32p, C.c_uint32, _f32p]),
+    "zvec_hip_sparse_batch_distance": (C.c_int, [_h, _h, C.c_uint32, _u32p, _valp, _u32p, C.c_uint32, _f32p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

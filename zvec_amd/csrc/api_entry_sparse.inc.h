@@ -1,25 +1,43 @@
-// api_entry_sparse.inc.h — C ABI entry points: flat index of sparse fp32 rows under InnerProductSparse (zvk_sparse.hip.h)
+// api_entry_sparse.inc.h — C ABI entry points: flat index of sparse fp32 / fp16 rows under InnerProductSparse (zvk_sparse.hip.h)
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 extern "C++" {
 namespace {
 
-template <bool DUMP>
+template <typename VT, bool DUMP>
 int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
-  static bool attr_set[16][2] = {};
+  static bool attr_set[16] = {};        // (one per instantiation)
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15][0]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<false, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (!attr_set[dev & 15]) {
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, false, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)LDS_LIMIT));
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<true, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, true, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)LDS_LIMIT));
-    attr_set[dev & 15][0] = true;
+    attr_set[dev & 15] = true;
   }
-  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<true, DUMP>), dim3(grid), dim3(64), lds, stream, a);
-  else hipLaunchKernelGGL((sparse_scan_kernel<false, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((sparse_scan_kernel<VT, false, DUMP>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
+}
+
+// the same by the handle's value width (4 = fp32, 2 = fp16)
+template <bool DUMP>
+int launch_sparse_scan(uint32_t width, const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  return width == 2 ? launch_sparse_scan<_Float16, DUMP>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP>(a, grid, lds, stream);
+}
+
+// Host queries of a host-pointer entry: indices | values in one block, the values `width` bytes each and starting at byte te * 4
+// (te = the element count, never 0: an all-empty batch still uploads one unused pair).
+void sparse_stage_blob(uint32_t width, uint64_t total, const uint32_t *q_indices, const void *q_values, std::vector<uint32_t> &blob,
+                       size_t *te) {
+  *te = std::max<size_t>((size_t)total, 1);
+  blob.assign(*te + (*te * width + 3) / 4, 0u);
+  if (total) {
+    memcpy(blob.data(), q_indices, (size_t)total * 4);
+    memcpy(blob.data() + *te, q_values, (size_t)total * width);
+  }
 }
 
 // Runs of a batch as the reference requires them: at most PARAM_FLAT_SPARSE_MAX_DIM_SIZE pairs each, indices STRICTLY ascending
@@ -65,7 +83,7 @@ void sparse_make_plan(const uint32_t *counts, uint32_t count, uint32_t sub, std:
 
 // The search proper.  The caller holds c->mu and h->rw (shared); q_counts (HOST) has passed sparse_check_runs; the query arrays
 // and every output are device pointers.  Enqueues only, except for a wait on the previous plan upload of the same context.
-int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const float *d_qval,
+int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
                          uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude, uint64_t *d_keys, float *d_scores,
                          uint32_t *d_counts, hipStream_t s) {
   if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
@@ -118,7 +136,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
       SparseScanArgs d = a;
       d.blk0 = b0; d.qsub0 = q0; d.nqblocks = b1 - b0; d.dump = c->part_s.as<float>();
       chunking(d.nqblocks, &d.rows_per_chunk, &d.nchunks);
-      ZRET(launch_sparse_scan<true>(d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0), s));
+      ZRET(launch_sparse_scan<true>(st.width, d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
       MergeArgs m{};
       m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
       m.keymap = st.keys; m.out_keys = d_keys + (size_t)q0 * topk; m.out_scores = d_scores + (size_t)q0 * topk;
@@ -135,7 +153,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   ZRET(c->part_s.ensure(slots * topk * sizeof(float)));
   ZRET(c->part_i.ensure(slots * topk * sizeof(uint32_t)));
   a.part_s = c->part_s.as<float>(); a.part_i = c->part_i.as<uint32_t>();
-  ZRET(launch_sparse_scan<false>(a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk), s));
+  ZRET(launch_sparse_scan<false>(st.width, a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
   MergeArgs m{};
   m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = a.nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
   m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
@@ -151,7 +169,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
 // beyond the rows, or excluded), the positions in c->plan [entries] and tells where the list offsets went (*d_list_off).  Enqueues
 // only, except for a wait on the previous plan upload of the same context.  A work item is (query, slice of its list): the slice is
 // as long as it takes to put 16 items on every CU, SPARSE_ROWS_SLICE at most, so that a short batch still fills the device.
-int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const float *d_qval,
+int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
                        uint32_t count, const uint32_t *ids, const uint32_t *offsets, const uint64_t *d_exclude,
                        const uint32_t **d_list_off, hipStream_t s) {
   const SparseStore &st = h->st;
@@ -191,9 +209,15 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>();
   *d_list_off = a.list_off;
   if (items == 0) return 0;
-  const size_t lds = (size_t)2 * max_run * 4;         // (at most 32 KiB: no launch attribute needed)
-  if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<true>), dim3(items), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL((sparse_rows_kernel<false>), dim3(items), dim3(64), lds, s, a);
+  // indices | values of the longest run (at most 32 KiB: no launch attribute needed)
+  const size_t lds = (size_t)max_run * 4 + (((size_t)max_run * st.width + 3) & ~(size_t)3);
+  if (st.width == 2) {
+    if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<_Float16, true>), dim3(items), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL((sparse_rows_kernel<_Float16, false>), dim3(items), dim3(64), lds, s, a);
+  } else {
+    if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<float, true>), dim3(items), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL((sparse_rows_kernel<float, false>), dim3(items), dim3(64), lds, s, a);
+  }
   ZCHK(hipGetLastError());
   return 0;
 }
@@ -201,14 +225,24 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
 }  // namespace
 }  // extern "C++"
 
-int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out) {
+int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out) {
   if (!out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
   zvec_hip_ctx_s *c = nullptr;
   ZRET(ctx_new(device, &c));
   zvec_hip_sparse_s *h = new (std::nothrow) zvec_hip_sparse_s();
   if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
-  h->device = device; h->defctx = c;
+  h->device = device; h->dtype = dtype; h->defctx = c;
+  h->st.width = dtype == ZVEC_HIP_DT_FP16 ? 2u : 4u;
   *out = h;
+  return 0;
+}
+
+int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out) { return zvec_hip_sparse_create_typed(ZVEC_HIP_DT_FP32, device, out); }
+
+int zvec_hip_sparse_dtype(zvec_hip_sparse_t h, int *dtype) {
+  if (!h || !dtype) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  *dtype = h->dtype;
   return 0;
 }
 
@@ -228,7 +262,7 @@ int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t element
   return h->st.reserve(rows, elements, h->defctx->own);
 }
 
-int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const float *values, uint64_t n,
+int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const void *values, uint64_t n,
                            const uint64_t *keys) {
   if (!h || (n && !counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
@@ -254,7 +288,7 @@ int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const ui
   ZCHK(hipMemcpyAsync(st.keys + st.n, keys ? keys : ks.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
   if (total) {
     ZCHK(hipMemcpyAsync(st.idx + st.elems, indices, (size_t)total * 4, hipMemcpyHostToDevice, s));
-    ZCHK(hipMemcpyAsync(st.val + st.elems, values, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    ZCHK(hipMemcpyAsync(static_cast<char *>(st.val) + st.elems * st.width, values, (size_t)total * st.width, hipMemcpyHostToDevice, s));
   }
   ZCHK(hipStreamSynchronize(s));
   st.n += n;
@@ -270,7 +304,7 @@ int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *element
   return 0;
 }
 
-int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, float *values) {
+int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *count, uint32_t *indices, void *values) {
   if (!h || !count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> g(h->mu);
   zvec_hip_ctx_s *c = h->defctx;
@@ -280,19 +314,24 @@ int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *coun
   ZCHK(hipSetDevice(h->device));
   const size_t words = 4 + 2 * (size_t)SPARSE_MAX_COUNT;
   ZRET(c->io_q.ensure(words * 4));
-  hipLaunchKernelGGL(sparse_unpack_kernel, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx, h->st.val, pos, c->io_q.as<uint32_t>());
+  if (h->st.width == 2)
+    hipLaunchKernelGGL(sparse_unpack_kernel<_Float16>, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx,
+                       static_cast<const _Float16 *>(h->st.val), pos, c->io_q.as<uint32_t>());
+  else
+    hipLaunchKernelGGL(sparse_unpack_kernel<float>, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx,
+                       static_cast<const float *>(h->st.val), pos, c->io_q.as<uint32_t>());
   ZCHK(hipGetLastError());
   std::vector<uint32_t> host(words);
   ZCHK(hipMemcpyAsync(host.data(), c->io_q.p, words * 4, hipMemcpyDeviceToHost, c->own));
   ZCHK(hipStreamSynchronize(c->own));
   *count = host[0];
   if (indices) memcpy(indices, host.data() + 4, (size_t)host[0] * 4);
-  if (values) memcpy(values, host.data() + 4 + SPARSE_MAX_COUNT, (size_t)host[0] * 4);
+  if (values) memcpy(values, host.data() + 4 + SPARSE_MAX_COUNT, (size_t)host[0] * h->st.width);
   return 0;
 }
 
 int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *d_q_indices,
-                               const float *d_q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude_bitset,
+                               const void *d_q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude_bitset,
                                uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream) {
   if (!h || !d_out_keys || !d_out_scores || !d_out_counts || (count && !q_counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
@@ -310,7 +349,7 @@ int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const ui
 }
 
 int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
-                           const float *q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
+                           const void *q_values, uint32_t count, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
                            uint64_t *out_keys, float *out_scores, uint32_t *out_counts) {
   if (!h || !out_keys || !out_scores || !out_counts || (count && !q_counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
@@ -320,13 +359,9 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
   uint64_t total = 0;
   ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
   if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  // indices | values in one block (never empty: an all-empty batch still uploads one unused pair)
-  const size_t te = std::max<size_t>((size_t)total, 1);
-  std::vector<uint32_t> blob(2 * te, 0u);
-  if (total) {
-    memcpy(blob.data(), q_indices, (size_t)total * 4);
-    memcpy(blob.data() + te, q_values, (size_t)total * 4);
-  }
+  size_t te = 0;
+  std::vector<uint32_t> blob;
+  sparse_stage_blob(h->st.width, total, q_indices, q_values, blob, &te);      // (the width never changes after create)
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
@@ -334,7 +369,7 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
     std::shared_lock<FairSharedMutex> r(h->rw);      // the row count the bitset is sized for == the rows scanned
     ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, h->st.n, count, topk, c->cur));
     const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
-    ZRET(sparse_search_locked(h, c, q_counts, dq, reinterpret_cast<const float *>(dq + te), count, topk, threshold,
+    ZRET(sparse_search_locked(h, c, q_counts, dq, dq + te, count, topk, threshold,
                               exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, c->io_keys.as<uint64_t>(), c->io_scores.as<float>(),
                               c->io_counts.as<uint32_t>(), c->cur));
   }
@@ -347,7 +382,7 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
 // == kInvalidNodeId); a position beyond the rows is skipped here, a position listed twice is scored twice (the reference's heap
 // takes both emplace calls).
 int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
-                                  const float *q_values, uint32_t count, const uint32_t *ids, const uint32_t *offsets, uint32_t topk,
+                                  const void *q_values, uint32_t count, const uint32_t *ids, const uint32_t *offsets, uint32_t topk,
                                   float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
                                   uint32_t *out_counts) {
   if (!h || !out_keys || !out_scores || !out_counts || (count && (!q_counts || !offsets))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -362,13 +397,9 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
   uint64_t total = 0;
   ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
   if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  // indices | values in one block (never empty: an all-empty batch still uploads one unused pair)
-  const size_t te = std::max<size_t>((size_t)total, 1);
-  std::vector<uint32_t> blob(2 * te, 0u);
-  if (total) {
-    memcpy(blob.data(), q_indices, (size_t)total * 4);
-    memcpy(blob.data() + te, q_values, (size_t)total * 4);
-  }
+  size_t te = 0;
+  std::vector<uint32_t> blob;
+  sparse_stage_blob(h->st.width, total, q_indices, q_values, blob, &te);      // (the width never changes after create)
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
@@ -377,7 +408,7 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
     ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, h->st.n, count, topk, c->cur));
     const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
     const uint32_t *d_off = nullptr;
-    ZRET(sparse_rows_locked(h, c, q_counts, dq, reinterpret_cast<const float *>(dq + te), count, ids, offsets,
+    ZRET(sparse_rows_locked(h, c, q_counts, dq, dq + te, count, ids, offsets,
                             exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, &d_off, c->cur));
     // selection, the threshold test and position -> key: every listed entry is a slot of one candidate, a query's slots are its list
     // (a skipped entry holds +inf, which no finite bound admits)
@@ -395,17 +426,14 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
 // listed order (sparse_rows_kernel without the selection; FlatSparseEntity::search_p_keys, flat_sparse_entity.h:63-77, scores its
 // keys one by one the same way).  A position beyond the rows scores +inf.
 int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
-                                   const float *q_values, const uint32_t *positions, uint32_t n, float *out_scores) {
+                                   const void *q_values, const uint32_t *positions, uint32_t n, float *out_scores) {
   if (!h || (q_count && (!q_indices || !q_values)) || (n && (!positions || !out_scores))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   uint64_t total = 0;
   ZRET(sparse_check_runs(&q_count, q_indices, 1, &total));
   if (n == 0) return 0;
-  const size_t te = std::max<size_t>((size_t)total, 1);
-  std::vector<uint32_t> blob(2 * te, 0u);
-  if (total) {
-    memcpy(blob.data(), q_indices, (size_t)total * 4);
-    memcpy(blob.data() + te, q_values, (size_t)total * 4);
-  }
+  size_t te = 0;
+  std::vector<uint32_t> blob;
+  sparse_stage_blob(h->st.width, total, q_indices, q_values, blob, &te);
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
@@ -416,7 +444,7 @@ int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint
   const uint32_t *dq = c->io_q.as<uint32_t>();
   const uint32_t offs[2] = {0, n};
   const uint32_t *d_off = nullptr;
-  ZRET(sparse_rows_locked(h, c, &q_count, dq, reinterpret_cast<const float *>(dq + te), 1, positions, offs, nullptr, &d_off, s));
+  ZRET(sparse_rows_locked(h, c, &q_count, dq, dq + te, 1, positions, offs, nullptr, &d_off, s));
   ZCHK(hipMemcpyAsync(out_scores, c->part_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   ZCHK(hipStreamSynchronize(s));
   return 0;

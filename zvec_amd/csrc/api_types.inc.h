@@ -454,15 +454,17 @@ struct zvec_hip_flat_s {
   }
 };
 
-// Sparse fp32 rows in CSR form (zvk_sparse.hip.h): what the scan reads, and the four arrays behind it.  A position is a row number;
-// keys and exclude bits index positions as in the flat store.  Neither copied nor moved.
+// Sparse rows in CSR form (zvk_sparse.hip.h): what the scan reads, and the four arrays behind it.  A position is a row number;
+// keys and exclude bits index positions as in the flat store.  Values are `width` bytes each in HBM (4 = fp32, 2 = fp16: never
+// widened).  Neither copied nor moved.
 struct SparseStore {
+  uint32_t width = 4;         // bytes of a stored value; fixed before the first reserve
   uint64_t n = 0;             // rows
   uint64_t elems = 0;         // stored (index, value) pairs
   uint64_t cap_rows = 0, cap_elems = 0;
   uint64_t *row_off = nullptr;   // [n + 1]
   uint32_t *idx = nullptr;
-  float *val = nullptr;
+  void *val = nullptr;        // [elements] of `width` bytes
   uint64_t *keys = nullptr;
   SparseStore() {}
   SparseStore(const SparseStore &) = delete;
@@ -489,12 +491,12 @@ struct SparseStore {
     if (elements > cap_elems) {
       const uint64_t ne = std::max<uint64_t>(elements, cap_elems + cap_elems / 2 + 1);
       Scoped<uint32_t> ni;
-      Scoped<float> nv;
+      Scoped<void> nv;
       ZRET(ni.alloc((size_t)ne));
-      ZRET(nv.alloc((size_t)ne));
+      ZRET(nv.alloc_bytes((size_t)ne * width));
       if (elems) {
         ZCHK(hipMemcpyAsync(ni, idx, (size_t)elems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        ZCHK(hipMemcpyAsync(nv, val, (size_t)elems * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        ZCHK(hipMemcpyAsync(nv, val, (size_t)elems * width, hipMemcpyDeviceToDevice, stream));
         ZCHK(hipStreamSynchronize(stream));
       }
       std::swap(own.idx, ni);
@@ -509,12 +511,13 @@ struct SparseStore {
   struct Arrays {
     Scoped<uint64_t> row_off, keys;
     Scoped<uint32_t> idx;
-    Scoped<float> val;
+    Scoped<void> val;
   } own;
 };
 
 struct zvec_hip_sparse_s {
   int device = 0;
+  int dtype = 0;            // ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16: the type of every value pointer of the handle's calls
   SparseStore st;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)

@@ -1,12 +1,20 @@
-// zvk_sparse.hip.h — sparse fp32 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, staging and unpack.
+// zvk_sparse.hip.h — sparse fp32 / fp16 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, staging and unpack.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Reference: FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_search.h:119-144) score one query
 // at a time against every stored row with MinusInnerProductSparseMatrix<float>::Compute (src/ailego/math/inner_product_matrix.h:
 // 2781-2862): a merge join of two index runs that are ascending, score = -(sum of value products over shared indices).
 //
+// Value type (template parameter VT of every kernel below: float or _Float16).  InnerProductSparseMetric::sparse_distance
+// (src/core/metric/inner_product_metric.cc:484-495) picks MinusInnerProductSparseMatrix<ailego::Float16>::Compute for DT_FP16 and the
+// <float> one for DT_FP32.  The Float16 one (src/ailego/math/inner_product_matrix_fp16.cc:1924-1945) gathers the matched halves of a
+// segment (InnerProductSparseInSegmentAVX, :1066-1202), widens them with _mm256_cvtph_ps and accumulates the products in fp32
+// (:1208-1223; the scalar form, :1897-1921, sums Float16 * Float16 into a float the same way).  Here every half is widened to fp32
+// where it is read (exact, subnormals included), the product is formed and summed in fp32 with fmaf exactly as for fp32 rows: no half
+// arithmetic anywhere.  Halves stay halves in HBM and in LDS.
+//
 // Layout.  Rows are CSR: row_off[n + 1] (u64 element offsets), idx[elements] (u32, strictly ascending inside a row), val[elements]
-// (fp32), keys[n].  A position is a row number; exclude bits index positions as in the flat store.
+// (VT), keys[n].  A position is a row number; exclude bits index positions as in the flat store.
 //
 // Scan.  ONE wave per work-group, lane = query.  A query block is up to 64 consecutive queries whose runs (at most
 // SPARSE_IMG_ELEMS elements together, chosen greedily on the host) are copied to LDS as they stand in the CSR query arrays.  The
@@ -24,17 +32,17 @@ namespace zvk {
 
 constexpr uint32_t SPARSE_MAX_COUNT = 4096;    // PARAM_FLAT_SPARSE_MAX_DIM_SIZE (flat_sparse_utility.h:22)
 constexpr uint32_t SPARSE_QB = 64;             // queries per query block at most (one lane each)
-constexpr uint32_t SPARSE_IMG_ELEMS = 4096;    // elements of a query block's LDS image at most (32 KiB: one longest query fits)
+constexpr uint32_t SPARSE_IMG_ELEMS = 4096;    // elements of a query block's LDS image at most (32 KiB of fp32, 24 KiB of fp16: one longest query fits)
 constexpr uint32_t SPARSE_FUSED_MAX_K = 128;   // lane-owned lists: 64 x k x 8 bytes next to the image; longer lists take the dump route
 
 struct SparseScanArgs {
   const uint64_t *row_off;    // [n + 1]
   const uint32_t *idx;        // [elements]
-  const float *val;           // [elements]
+  const void *val;            // [elements] of the kernel's VT
   const uint32_t *exclude;    // nullable bitset over positions, set = skip
   const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
   const uint32_t *q_idx;
-  const float *q_val;
+  const void *q_val;          // VT as well
   const uint32_t *blk;        // [blocks + 1] first query of every query block
   uint32_t blk0;              // first query block of this launch
   uint32_t qsub0;             // DUMP: the query whose scores are row 0 of `dump`
@@ -50,16 +58,18 @@ struct SparseScanArgs {
   uint32_t *part_i;
 };
 
-__host__ __device__ inline size_t sparse_lds_bytes(uint32_t img_elems, uint32_t k_lists) {
-  return ((size_t)2 * SPARSE_QB * k_lists + (size_t)2 * img_elems) * 4 + 16;
+// lists | image indices (u32) | image values (`width` bytes each: 4 = fp32, 2 = fp16), the values rounded up to whole words
+__host__ __device__ inline size_t sparse_lds_bytes(uint32_t img_elems, uint32_t k_lists, uint32_t width) {
+  return ((size_t)2 * SPARSE_QB * k_lists + img_elems) * 4 + (((size_t)img_elems * width + 3) & ~(size_t)3) + 16;
 }
 
 // One wave per work-group; item = (chunk of rows, query block).  DUMP: every score goes to the [query][position] matrix and nothing
 // is selected (large k, selected by merge_kernel).
-template <bool EXCL, bool DUMP>
+template <typename VT, bool EXCL, bool DUMP>
 __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
+  const VT *val = static_cast<const VT *>(a.val), *q_val = static_cast<const VT *>(a.q_val);
   const uint32_t k = a.k, kl = DUMP ? 0u : k;
   float *Ls = reinterpret_cast<float *>(zvk_smem4);                   // [k][64] lane-owned lists, ascending
   uint32_t *Li = reinterpret_cast<uint32_t *>(Ls + (size_t)SPARSE_QB * kl);
@@ -67,10 +77,10 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
   const uint32_t chunk = blockIdx.x / a.nqblocks, qb = a.blk0 + (blockIdx.x - chunk * a.nqblocks);
   const uint32_t q0 = a.blk[qb], nqb = a.blk[qb + 1] - q0;
   const uint32_t e0 = a.q_off[q0], tot = a.q_off[q0 + nqb] - e0;
-  float *qv = reinterpret_cast<float *>(qi + tot);                    // [tot] their values
+  VT *qv = reinterpret_cast<VT *>(qi + tot);                          // [tot] their values, as stored
   for (uint32_t i = lane; i < tot; i += 64) {
     qi[i] = a.q_idx[e0 + i];
-    qv[i] = a.q_val[e0 + i];
+    qv[i] = q_val[e0 + i];
   }
   const bool mine = (uint32_t)lane < nqb;
   uint32_t qstart = 0, qlen = 0;
@@ -105,7 +115,7 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
       float rv = 0.f;
       if ((uint32_t)lane < m) {
         ri = a.idx[p + lane];
-        rv = a.val[p + lane];
+        rv = (float)val[p + lane];                        // (a half widens exactly)
       }
       for (uint32_t u0 = 0; u0 < m; u0 += 4) {
         uint32_t t[4], base[4], n[4];
@@ -132,7 +142,7 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (n[u] != 0) {
-            if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], qv[base[u]], acc);
+            if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
           }
         }
       }
@@ -192,11 +202,11 @@ constexpr uint32_t SPARSE_ROWS_SLICE = 64;     // listed entries per work item a
 struct SparseRowsArgs {
   const uint64_t *row_off;    // [n + 1]
   const uint32_t *idx;        // [elements]
-  const float *val;           // [elements]
+  const void *val;            // [elements] of the kernel's VT
   const uint32_t *exclude;    // nullable bitset over positions, set = skip
   const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
   const uint32_t *q_idx;
-  const float *q_val;
+  const void *q_val;          // VT as well
   const uint32_t *ids;        // [entries] listed positions, query after query; any value (>= n: skipped)
   const uint32_t *list_off;   // [nq + 1] entries of every query
   const uint32_t *item_q;     // [items] the query of a work item
@@ -211,9 +221,9 @@ __device__ __forceinline__ uint32_t sparse_halvings(uint32_t qlen) { return qlen
 
 // Stored elements [p, min(re, p + 64 U)) against the run qi / qv [qlen] in LDS (qlen > 0), lane = element: acc plus this lane's
 // products.  If the lane's index t is in the run at j, j stays inside [base, base + n) through every halving.
-template <int U>
-__device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const float *val, uint64_t p, uint64_t re, const uint32_t *qi,
-                                                 const float *qv, uint32_t qlen, uint32_t steps, int lane, float acc) {
+template <int U, typename VT>
+__device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const VT *val, uint64_t p, uint64_t re, const uint32_t *qi,
+                                                 const VT *qv, uint32_t qlen, uint32_t steps, int lane, float acc) {
   uint32_t t[U], base[U], n[U];
   float v[U];
 #pragma unroll
@@ -221,7 +231,7 @@ __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const floa
     const uint64_t e = p + (uint64_t)u * 64 + (uint32_t)lane;
     const bool in = e < re;
     t[u] = in ? idx[e] : 0u;
-    v[u] = in ? val[e] : 0.f;
+    v[u] = in ? (float)val[e] : 0.f;
     n[u] = in ? qlen : 0u;
     base[u] = 0;
   }
@@ -238,7 +248,7 @@ __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const floa
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (n[u] != 0) {
-      if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], qv[base[u]], acc);
+      if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
     }
   }
   return acc;
@@ -247,8 +257,9 @@ __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const floa
 // The whole wave scores ONE stored row [rb, re) (wave-uniform) against the run in LDS: the sum of value products over shared
 // indices, the same bits in every lane (the butterfly's order is fixed).  A run of length 0 makes no LDS read and no load.
 // (sparse_rows_kernel's inner step; a narrow zvec_hip_sparse_search batch can walk its chunk of rows with it as well.)
-__device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const float *val, uint64_t rb, uint64_t re, const uint32_t *qi,
-                                                     const float *qv, uint32_t qlen, uint32_t steps, int lane) {
+template <typename VT>
+__device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const VT *val, uint64_t rb, uint64_t re, const uint32_t *qi,
+                                                     const VT *qv, uint32_t qlen, uint32_t steps, int lane) {
   if (qlen == 0) return 0.f;
   float acc = 0.f;
   uint64_t p = rb;
@@ -259,7 +270,7 @@ __device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const 
   return acc;
 }
 
-template <bool EXCL>
+template <typename VT, bool EXCL>
 __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
@@ -267,10 +278,11 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
   const uint32_t e1 = min(e0 + min(a.slice, SPARSE_ROWS_SLICE), a.list_off[q + 1]);
   const uint32_t qb = a.q_off[q], qlen = min(a.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
   uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);             // [qlen] the query's indices
-  float *qv = reinterpret_cast<float *>(qi + qlen);                   // [qlen] its values
+  VT *qv = reinterpret_cast<VT *>(qi + qlen);                         // [qlen] its values, as stored
+  const VT *q_val = static_cast<const VT *>(a.q_val);
   for (uint32_t i = lane; i < qlen; i += 64) {
     qi[i] = a.q_idx[qb + i];
-    qv[i] = a.q_val[qb + i];
+    qv[i] = q_val[qb + i];
   }
   const uint32_t steps = sparse_halvings(qlen);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -298,7 +310,7 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
     todo &= todo - 1;
     const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
     const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
-    const float sum = sparse_wave_row_dot(a.idx, a.val, b, en, qi, qv, qlen, steps, lane);
+    const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
     if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
   }
   if (e < e1) a.scores[e] = out;
@@ -312,15 +324,17 @@ __global__ void __launch_bounds__(256) sparse_prep_queries_kernel(uint32_t nq, u
   if (i < nq) gtau[i] = fkey(__builtin_inff());
 }
 
-// get_vector: row `pos` -> out[0] = count, out[4 .. 4 + count) indices, out[4 + SPARSE_MAX_COUNT ..) values (as bits)
-__global__ void __launch_bounds__(256) sparse_unpack_kernel(const uint64_t *row_off, const uint32_t *idx, const float *val, uint64_t pos,
+// get_vector: row `pos` -> out[0] = count, out[4 .. 4 + count) indices, then the values as stored, back to back (VT each)
+template <typename VT>
+__global__ void __launch_bounds__(256) sparse_unpack_kernel(const uint64_t *row_off, const uint32_t *idx, const VT *val, uint64_t pos,
                                                             uint32_t *out) {
   const uint64_t b = row_off[pos];
   const uint32_t c = (uint32_t)min((uint64_t)SPARSE_MAX_COUNT, row_off[pos + 1] - b);
   if (threadIdx.x == 0) out[0] = c;
   for (uint32_t i = threadIdx.x; i < c; i += 256) {
     out[4 + i] = idx[b + i];
-    out[4 + SPARSE_MAX_COUNT + i] = __builtin_bit_cast(uint32_t, val[b + i]);
+    if constexpr (sizeof(VT) == 4) out[4 + SPARSE_MAX_COUNT + i] = __builtin_bit_cast(uint32_t, val[b + i]);
+    else reinterpret_cast<VT *>(out + 4 + SPARSE_MAX_COUNT)[i] = val[b + i];
   }
 }
 

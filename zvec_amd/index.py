@@ -643,15 +643,18 @@ class HipFlatSearcher(_FlatBase, _FlatFeatures):
 
 class HipFlatSparseStreamer:
     """stands where "FlatSparseStreamer" / "FlatSparseSearcher" are registered (flat_sparse_streamer.cc, flat_sparse_searcher.cc):
-    a flat index of sparse fp32 rows under InnerProductSparse (zvec_hip_sparse_*).  A batch of rows or queries is CSR-like:
-    counts[n], then the runs back to back in indices (uint32, strictly ascending inside a run) and values (fp32)."""
+    a flat index of sparse rows under InnerProductSparse (zvec_hip_sparse_*).  A batch of rows or queries is CSR-like: counts[n],
+    then the runs back to back in indices (uint32, strictly ascending inside a run) and values.  dtype "fp32" or "fp16"
+    (IndexMeta::DT_FP32 / DT_FP16, inner_product_metric.cc:484-495): values go in and come out as numpy.float32 / numpy.float16,
+    other float inputs are cast to that type; scores are fp32 either way."""
 
     MAX_COUNT = 4096            # PARAM_FLAT_SPARSE_MAX_DIM_SIZE (flat_sparse_utility.h:22)
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, dtype="fp32"):
         self.device = device
+        self.dtype, self.np_dtype = _dtype_of(dtype)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().zvec_hip_sparse_create(device, C.byref(self._h)), "zvec_hip_sparse_create")
+        _lib.check(_lib.lib().zvec_hip_sparse_create_typed(self.dtype, device, C.byref(self._h)), "zvec_hip_sparse_create_typed")
         self._keys_host = []      # for IndexFilter sweeps
 
     def __del__(self):
@@ -678,11 +681,10 @@ class HipFlatSparseStreamer:
     def reserve(self, rows, elements):
         return _lib.lib().zvec_hip_sparse_reserve(self._h, int(rows), int(elements))
 
-    @staticmethod
-    def _runs(counts, indices, values):
+    def _runs(self, counts, indices, values):
         c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
         i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
-        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        v = np.ascontiguousarray(values, self.np_dtype).reshape(-1)
         total = int(c.astype(np.uint64).sum())
         return (c, i, v) if i.size == total and v.size == total else None
 
@@ -705,7 +707,7 @@ class HipFlatSparseStreamer:
         """(indices, values) of the row at storage position `pos` as stored, or None beyond the last row"""
         n = C.c_uint32(0)
         idx = np.zeros(self.MAX_COUNT, np.uint32)
-        val = np.zeros(self.MAX_COUNT, np.float32)
+        val = np.zeros(self.MAX_COUNT, self.np_dtype)
         rc = _lib.lib().zvec_hip_sparse_get_vector(self._h, int(pos), C.byref(n), _np_ptr(idx), _np_ptr(val))
         return (idx[:n.value].copy(), val[:n.value].copy()) if rc == 0 else None
 
@@ -768,7 +770,7 @@ class HipFlatSparseStreamer:
         """IndexMetric::batch_distance: one sparse query against the listed storage positions, fp32 scores in that order (+inf for a
         position beyond the rows)"""
         i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
-        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        v = np.ascontiguousarray(values, self.np_dtype).reshape(-1)
         if i.size != v.size:
             raise ValueError("zvec_amd: a sparse query needs as many values as indices")
         pos = np.ascontiguousarray(positions, np.uint32).reshape(-1)
@@ -780,7 +782,7 @@ class HipFlatSparseStreamer:
     def search_dev(self, counts, d_indices, d_values, count, topk, d_out_keys, d_out_scores, d_out_counts, ctx,
                    threshold=FLT_MAX, d_exclude=None, stream=None):
         """device-pointer form (async): `counts` is a HOST array (the host cuts the batch into query blocks), everything else raw
-        device pointers (ints)."""
+        device pointers (ints).  d_values holds elements of the index's value type: halves (2 bytes each) for an fp16 index."""
         c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
         if c.size != int(count):
             return IndexError_.InvalidArgument
