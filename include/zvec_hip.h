@@ -102,6 +102,9 @@ const char *zvec_hip_error_string(int code); /* IndexError::What analogue */
  *   "scan256"   1 (default) = flat scans of fp16 rows by at least 256 queries with k <= 11 and no filter take the 256 x 256
  *               multi-phase tile when the base is streamed (past the Infinity Cache); 2 = on small bases too (tests); 0 = the
  *               128 x 128 tile always.  Same results either way (ZVEC_HIP_ASSIGN256 / ZVEC_HIP_SCAN256 in the environment).
+ *   "sparse_group_rows"  0 .. 64: zvec_hip_sparse_search_grouped dumps the scores of a sub-batch of at most this many queries
+ *               with a whole wave per stored row, of a wider one with a lane per query; 0 = never the former.  Same lists
+ *               either way on exact data.
  * Unsupported (-12) for an unknown name, invalid argument (-1) for a value outside the option's range. */
 int zvec_hip_set_option(const char *name, int value);
 int zvec_hip_get_option(const char *name, int *value);
@@ -589,9 +592,24 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     zvec_hip_sparse_search; equal scores come in the order of the list.  out_counts[q] can be below topk simply because the
  *     list was short; an empty list gives 0.  Host queries are validated as in zvec_hip_sparse_search.  offsets that descend,
  *     offsets[0] != 0, a NULL where none is allowed and topk == 0 return ZVEC_HIP_ERR_INVALID_ARGUMENT and touch no output.
- * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), group-by (search_group_p_keys
- * included), the *Sparse Euclidean metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the reference's
- * dumped sparse segments, shards, the plugin and the C++ mirror (zvec_hip_operator.hpp). */
+ *   - Group-by (zvec_hip_sparse_search_grouped, zvec_hip_sparse_search_grouped_by_ids): FlatSparseEntity::search_group and
+ *     search_group_p_keys (flat_sparse_entity.h:79-128), ranked and assembled as ConvertGroupMapToResult does
+ *     (flat_sparse_search.h:23-53; the dispatch, :77-117).  Queries are taken exactly as by zvec_hip_sparse_search /
+ *     zvec_hip_sparse_search_by_ids (CSR, values of the handle's type, runs strictly ascending and validated on the host, at
+ *     most 4096 pairs a run; count > 2^19, or for listed rows count * longest list > 2^32 - 1, returns ZVEC_HIP_ERR_OUT_OF_RANGE;
+ *     ids / offsets as for search_by_ids).  group_of_position[n], ngroups, group_num,
+ *     group_topk and the five outputs mean what they mean for zvec_hip_flat_search_grouped, same layout; a position with
+ *     group_of >= ngroups does not compete.  A group keeps its group_topk best candidates under (score, scan ordinal), the
+ *     ordinal being the storage position for the full scan and the place in the list for listed rows; groups are ranked by
+ *     their best score, equal best scores by group number, and the first group_num are kept; documents with score > threshold
+ *     are cut AFTER that ranking, so a group may be listed with no document.  A position listed twice competes twice; a
+ *     position >= the row count or excluded never competes.  A pair with no shared index scores exactly 0 and is an ordinary
+ *     candidate: the zero ties are resolved by the ordinal rule, which is stricter than the "unspecified" of Ties above.
+ *     ngroups, group_num or group_topk of 0: ZVEC_HIP_ERR_INVALID_ARGUMENT; group_num * 12 + 16 or group_topk * 16 + 16 above
+ *     60 KiB: ZVEC_HIP_ERR_UNSUPPORTED; a refused call touches no output.  An empty index gives out_ngroups[q] = 0.
+ * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), the *Sparse Euclidean
+ * metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the reference's dumped sparse segments, shards,
+ * the plugin and the C++ mirror (zvec_hip_operator.hpp). */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
 /* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched */
 int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out);
@@ -633,6 +651,20 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
  * position beyond the rows scores +inf.  n == 0 returns 0 and writes nothing. */
 int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
                                    const void *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
+/* Group-by over every row (FlatSparseEntity::search_group, flat_sparse_entity.h:79-103); see Group-by above. */
+int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
+                                   const void *q_values, uint32_t count, const uint32_t *group_of_position, uint32_t ngroups,
+                                   uint32_t group_num, uint32_t group_topk, float threshold, const uint64_t *exclude_bitset,
+                                   uint32_t *out_groups, uint32_t *out_ngroups, uint64_t *out_keys, float *out_scores,
+                                   uint32_t *out_counts);
+/* Group-by over listed rows (FlatSparseEntity::search_group_p_keys, flat_sparse_entity.h:105-128): query q against rows
+ * ids[offsets[q] .. offsets[q+1]) only, as zvec_hip_sparse_search_by_ids lists them. */
+int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts,
+                                          const uint32_t *q_indices, const void *q_values, uint32_t count, const uint32_t *ids,
+                                          const uint32_t *offsets, const uint32_t *group_of_position, uint32_t ngroups,
+                                          uint32_t group_num, uint32_t group_topk, float threshold,
+                                          const uint64_t *exclude_bitset, uint32_t *out_groups, uint32_t *out_ngroups,
+                                          uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
 
 #ifdef __cplusplus
 }

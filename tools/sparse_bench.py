@@ -24,6 +24,14 @@ that is not listed, which takes ONE bitset per call, so a batch whose queries ha
                 process)
 
     python tools/sparse_bench.py --by-keys [--out profiles/sparse_by_keys.json] [--steps 10] [--warmup 3]
+
+--grouped: the same corpus under group-by search (zvec_hip_sparse_search_grouped): 1000 groups dealt at random, group_num 10 x
+group_topk 10, batches 1 / 2 / 4 / 8 / 16 / 32 / 64, host-pointer call to return (wall clock, median of the steps).  Every batch
+is timed with "sparse_group_rows" at 0 (the lane = query score dump) and at 64 (the wave-per-row score dump), and next to them the
+plain zvec_hip_sparse_search (k = 10) of the same queries; the answers of the two dumps are compared.  The default of
+"sparse_group_rows" is read off this file: the largest batch up to which the wave-per-row dump was the faster one.
+
+    python tools/sparse_bench.py --grouped [--dtype fp32|fp16] [--out profiles/sparse_grouped.json] [--steps 10] [--warmup 3]
 """
 import argparse
 import ctypes as C
@@ -162,6 +170,101 @@ def by_keys(args):
             f.write("\n")
 
 
+def grouped(args):
+    import time
+    import numpy as np
+    import torch
+    import zvec_amd
+    from zvec_amd.index import _np_ptr
+    L = zvec_amd._lib.lib()
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
+    np_val = np.float16 if args.dtype == "fp16" else np.float32
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
+    assert se.reserve(args.n, ri.numel()) == 0
+    assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
+    del ri, rv
+    ctx = se.create_context()
+    rng = np.random.default_rng(1)
+    ngroups, gnum, gk, k = 1000, 10, 10, 10
+    group_of = rng.integers(0, ngroups, args.n).astype(np.uint32)
+    fmax = float(np.finfo(np.float32).max)
+    before = C.c_int(0)
+    assert L.zvec_hip_get_option(b"sparse_group_rows", C.byref(before)) == 0
+
+    def median_ms(fn):
+        for _ in range(args.warmup):
+            fn()
+        t = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(t)), float(min(t))
+
+    points = []
+    try:
+        for batch in (1, 2, 4, 8, 16, 32, 64):
+            qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
+            qv = (torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1).cpu().numpy().astype(np_val)
+            qc = qc.numpy().astype(np.uint32)
+            qi = qi.numpy().view(np.uint32).copy()
+            answers = {}
+            point = {"batch": batch}
+            for name, width in (("lane_per_query", 0), ("wave_per_row", 64)):
+                out = (np.zeros((batch, gnum), np.uint32), np.zeros(batch, np.uint32), np.zeros((batch, gnum, gk), np.uint64),
+                       np.zeros((batch, gnum, gk), np.float32), np.zeros((batch, gnum), np.uint32))
+                assert L.zvec_hip_set_option(b"sparse_group_rows", width) == 0
+
+                def call():
+                    rc = L.zvec_hip_sparse_search_grouped(se._h, ctx._h, _np_ptr(qc), _np_ptr(qi), _np_ptr(qv), batch, _np_ptr(group_of),
+                                                          ngroups, gnum, gk, fmax, None, *[_np_ptr(a) for a in out])
+                    assert rc == 0, rc
+                point[name + "_ms"], point[name + "_min_ms"] = median_ms(call)
+                answers[name] = out
+            keys = np.zeros((batch, k), np.uint64)
+            scores = np.zeros((batch, k), np.float32)
+            counts = np.zeros(batch, np.uint32)
+
+            def plain():
+                rc = L.zvec_hip_sparse_search(se._h, ctx._h, _np_ptr(qc), _np_ptr(qi), _np_ptr(qv), batch, k, fmax, None, _np_ptr(keys),
+                                              _np_ptr(scores), _np_ptr(counts))
+                assert rc == 0, rc
+            point["plain_search_ms"], point["plain_search_min_ms"] = median_ms(plain)
+            # the two dumps sum the same products in different orders: a score is an fp32 sum of m <= 64 products of values below 1,
+            # so either is within 65 * 2^-23 * 64 of the exact score and the two within twice that of each other, place by place
+            a, b = answers["lane_per_query"], answers["wave_per_row"]
+            assert a[1].tolist() == b[1].tolist() == [gnum] * batch and np.array_equal(a[4], b[4]) and int(a[4].min()) == gk
+            point["score_max_abs_diff"] = float(np.abs(a[3] - b[3]).max())
+            assert point["score_max_abs_diff"] <= 2 * 65 * 2.0 ** -23 * 64
+            point["same_groups"] = float(np.mean(a[0] == b[0]))
+            point["same_documents"] = float(np.mean(a[2] == b[2]))
+            # the best document overall is the best document of the best group
+            assert float(np.abs(a[3][:, 0, 0] - scores[:, 0]).max()) <= 2 * 65 * 2.0 ** -23 * 64
+            point["faster"] = "wave_per_row" if point["wave_per_row_ms"] < point["lane_per_query_ms"] else "lane_per_query"
+            points.append(point)
+            print(json.dumps(point), flush=True)
+    finally:
+        assert L.zvec_hip_set_option(b"sparse_group_rows", before.value) == 0
+    width = 0
+    for p in points:                                  # the largest batch up to which the wave-per-row dump won every time
+        if p["faster"] != "wave_per_row":
+            break
+        width = p["batch"]
+    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, group-by: %d groups, %d x %d" % (
+               args.n, args.vocab, ngroups, gnum, gk),
+           "dtype": args.dtype, "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)",
+           "steps": args.steps, "warmup": args.warmup, "wave_per_row_wins_up_to_batch": width, "points": points}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -171,10 +274,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--by-keys", action="store_true")
+    ap.add_argument("--grouped", action="store_true")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
     args = ap.parse_args()
     if args.by_keys:
         return by_keys(args)
+    if args.grouped:
+        return grouped(args)
     import numpy as np
     import torch
     import zvec_amd

@@ -46,6 +46,11 @@ int zvec_hip_set_option(const char *name, int value) {
     ropts().scan256 = value;
     return 0;
   }
+  if (strcmp(name, "sparse_group_rows") == 0) {
+    if (value < 0 || value > 64) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    ropts().sparse_group_rows = value;
+    return 0;
+  }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 int zvec_hip_get_option(const char *name, int *value) {
@@ -54,6 +59,7 @@ int zvec_hip_get_option(const char *name, int *value) {
   if (strcmp(name, "zerocopy") == 0) { *value = ropts().zerocopy; return 0; }
   if (strcmp(name, "assign256") == 0) { *value = ropts().assign256; return 0; }
   if (strcmp(name, "scan256") == 0) { *value = ropts().scan256; return 0; }
+  if (strcmp(name, "sparse_group_rows") == 0) { *value = ropts().sparse_group_rows; return 0; }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 

@@ -12,10 +12,12 @@ namespace {
 
 struct GroupOut { uint32_t *groups, *ngroups; uint64_t *keys; float *scores; uint32_t *counts; };   // device arrays of the whole batch
 
-// selection over a candidate matrix of `cnt` queries (rows q0.. of the prepared batch); outputs at row offset q0
-int group_select(zvec_hip_ctx_s *c, const StoreView &st, const float *cs, const uint32_t *ci, uint32_t stride, uint32_t len,
-                 uint32_t q0, uint32_t cnt, const uint32_t *d_group_of, uint32_t ngroups, uint32_t gnum, uint32_t gk,
-                 float threshold, bool refine, const GroupOut &out, hipStream_t s) {
+// selection over a candidate matrix of `cnt` queries (rows q0.. of the prepared batch); outputs at row offset q0.  `keys`: position
+// -> key of the store the candidates come from (dense or sparse).  `refine`: the dense store whose rows the listed documents are
+// re-scored from when its metric is L2 (the dense-score pass), nullptr when the scores are final as they stand.
+int group_select(zvec_hip_ctx_s *c, const uint64_t *keys, const StoreView *refine, const float *cs, const uint32_t *ci, uint32_t stride,
+                 uint32_t len, uint32_t q0, uint32_t cnt, const uint32_t *d_group_of, uint32_t ngroups, uint32_t gnum, uint32_t gk,
+                 float threshold, const GroupOut &out, hipStream_t s) {
   const size_t rows = (size_t)cnt * gnum;
   // workspace carve-up (8-byte items first)
   const size_t b_tmpk = rows * 8, b_rowk = rows * gk * 8, b_best = (size_t)cnt * ngroups * 4, b_tmps = rows * 4, b_sel = rows * 4,
@@ -41,7 +43,7 @@ int group_select(zvec_hip_ctx_s *c, const StoreView &st, const float *cs, const 
   m.threshold = FLT_MAX;                                 // groups are ranked before the radius applies (topk_to_group_result)
   m.out_keys = tmpk; m.out_scores = tmps; m.out_idx = sel; m.out_counts = nsel;
   hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)gnum * 12 + 16, s, m);
-  const bool l2 = refine && st.metric == ZVEC_HIP_METRIC_L2;
+  const bool l2 = refine && refine->metric == ZVEC_HIP_METRIC_L2;
   // one pass per query when the per-wave lists of all its slots fit the LDS (4 waves, else 1), otherwise a wave per slot
   const size_t lds1 = ((size_t)gnum * gk * 8 + (size_t)gnum * 8 + 16);
   const int fill_waves = lds1 * 4 <= 60 * 1024 ? 4 : (lds1 <= 60 * 1024 ? 1 : 0);
@@ -52,19 +54,20 @@ int group_select(zvec_hip_ctx_s *c, const StoreView &st, const float *cs, const 
     hipLaunchKernelGGL(group_slot_kernel, dim3(cnt), dim3(64), 0, s, sel, nsel, gnum, ngroups, tab);
 #define ZVEC_GROUP_FILL_Q(HAS, WV)                                                                                               \
     hipLaunchKernelGGL((group_fill_query_kernel<HAS, WV>), dim3(cnt), dim3(64 * WV), lds1 * WV, s, cs, ci, stride, len, d_group_of,  \
-                       ngroups, tab, nsel, gnum, gk, threshold, !l2, st.keys, rowk, rows_s, rows_i, rows_c)
+                       ngroups, tab, nsel, gnum, gk, threshold, !l2, keys, rowk, rows_s, rows_i, rows_c)
     if (ci) { if (fill_waves == 4) ZVEC_GROUP_FILL_Q(true, 4); else ZVEC_GROUP_FILL_Q(true, 1); }
     else { if (fill_waves == 4) ZVEC_GROUP_FILL_Q(false, 4); else ZVEC_GROUP_FILL_Q(false, 1); }
 #undef ZVEC_GROUP_FILL_Q
   } else if (ci)
     hipLaunchKernelGGL(group_fill_kernel<true>, dim3((unsigned)rows), dim3(64), (size_t)gk * 8 + 16, s, cs, ci, stride, len, d_group_of,
-                       sel, nsel, gnum, gk, threshold, !l2, st.keys, rowk, rows_s, rows_i, rows_c);
+                       sel, nsel, gnum, gk, threshold, !l2, keys, rowk, rows_s, rows_i, rows_c);
   else
     hipLaunchKernelGGL(group_fill_kernel<false>, dim3((unsigned)rows), dim3(64), (size_t)gk * 8 + 16, s, cs, ci, stride, len, d_group_of,
-                       sel, nsel, gnum, gk, threshold, !l2, st.keys, rowk, rows_s, rows_i, rows_c);
+                       sel, nsel, gnum, gk, threshold, !l2, keys, rowk, rows_s, rows_i, rows_c);
   ZCHK(hipGetLastError());
   if (l2) {
     // the dense scores are |q|^2 + |b|^2 - 2 q.b: the documents that made the lists are re-scored directly and re-sorted
+    const StoreView &st = *refine;
     const uint64_t pairs = (uint64_t)rows * gk;
     const float *qp = c->qpad.as<float>() + (size_t)q0 * st.dpad;
     if (st.f16)
@@ -156,8 +159,8 @@ int zvec_hip_flat_search_grouped(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
     const uint64_t *d_ex = exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr;
     ZRET(flat_effective_exclude(h, c, d_ex, s, &d_ex));
     ZRET(flat_dense_scores(c, st, q0, cnt, threshold, d_ex, s, &dump, &stride));
-    ZRET(group_select(c, st, dump, nullptr, stride, (uint32_t)st.n, q0, cnt, c->grp_of.as<uint32_t>(), ngroups, group_num, group_topk,
-                      threshold, true, o, s));
+    ZRET(group_select(c, st.keys, &st, dump, nullptr, stride, (uint32_t)st.n, q0, cnt, c->grp_of.as<uint32_t>(), ngroups, group_num,
+                      group_topk, threshold, o, s));
   }
   return group_copy_out(c, o, count, group_num, group_topk, out_groups, out_ngroups, out_keys, out_scores, out_counts, s);
 }
@@ -218,8 +221,8 @@ int zvec_hip_flat_search_grouped_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, c
   ZCHK(hipStreamSynchronize(s));                         // `clean` goes away
   // the pair scores are already direct distances: no refinement
   for (uint32_t q0 = 0; q0 < count; q0 += 32768)       // (a slice is one grid dimension of group_best_kernel)
-    ZRET(group_select(c, st, c->part_s.as<float>() + (size_t)q0 * maxlen, c->part_i.as<uint32_t>() + (size_t)q0 * maxlen, maxlen, maxlen,
-                      q0, std::min<uint32_t>(32768, count - q0), c->grp_of.as<uint32_t>(), ngroups, group_num, group_topk, threshold,
-                      false, o, s));
+    ZRET(group_select(c, st.keys, nullptr, c->part_s.as<float>() + (size_t)q0 * maxlen, c->part_i.as<uint32_t>() + (size_t)q0 * maxlen,
+                      maxlen, maxlen, q0, std::min<uint32_t>(32768, count - q0), c->grp_of.as<uint32_t>(), ngroups, group_num, group_topk,
+                      threshold, o, s));
   return group_copy_out(c, o, count, group_num, group_topk, out_groups, out_ngroups, out_keys, out_scores, out_counts, s);
 }

@@ -81,6 +81,19 @@ void sparse_make_plan(const uint32_t *counts, uint32_t count, uint32_t sub, std:
   plan.insert(plan.end(), blk.begin(), blk.end());
 }
 
+// The host-made plan of a search goes to c->sp_plan through the context's pinned slot: the previous search's upload has to have
+// left it (the only wait of the search paths below).
+int sparse_upload_plan(zvec_hip_ctx_s *c, const std::vector<uint32_t> &plan, hipStream_t s) {
+  if (c->sp_ev == nullptr) ZCHK(hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
+  else ZCHK(hipEventSynchronize(c->sp_ev));
+  ZRET(c->sp_pin.ensure(plan.size() * 4));
+  ZRET(c->sp_plan.ensure(plan.size() * 4));
+  memcpy(c->sp_pin.p, plan.data(), plan.size() * 4);
+  ZCHK(hipMemcpyAsync(c->sp_plan.p, c->sp_pin.p, plan.size() * 4, hipMemcpyHostToDevice, s));
+  ZCHK(hipEventRecord(c->sp_ev, s));
+  return 0;
+}
+
 // The search proper.  The caller holds c->mu and h->rw (shared); q_counts (HOST) has passed sparse_check_runs; the query arrays
 // and every output are device pointers.  Enqueues only, except for a wait on the previous plan upload of the same context.
 int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
@@ -99,14 +112,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   std::vector<uint32_t> plan;
   uint32_t nblocks = 0, max_img = 0;
   sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);
-  // the plan goes through the context's pinned slot: the previous search's upload has to have left it
-  if (c->sp_ev == nullptr) ZCHK(hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
-  else ZCHK(hipEventSynchronize(c->sp_ev));
-  ZRET(c->sp_pin.ensure(plan.size() * 4));
-  ZRET(c->sp_plan.ensure(plan.size() * 4));
-  memcpy(c->sp_pin.p, plan.data(), plan.size() * 4);
-  ZCHK(hipMemcpyAsync(c->sp_plan.p, c->sp_pin.p, plan.size() * 4, hipMemcpyHostToDevice, s));
-  ZCHK(hipEventRecord(c->sp_ev, s));
+  ZRET(sparse_upload_plan(c, plan, s));
   ZRET(c->gtau.ensure((size_t)count * 4));
   hipLaunchKernelGGL(sparse_prep_queries_kernel, dim3((count + 255) / 256), dim3(256), 0, s, count, c->gtau.as<uint32_t>());
   ZCHK(hipGetLastError());
@@ -169,9 +175,12 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
 // beyond the rows, or excluded), the positions in c->plan [entries] and tells where the list offsets went (*d_list_off).  Enqueues
 // only, except for a wait on the previous plan upload of the same context.  A work item is (query, slice of its list): the slice is
 // as long as it takes to put 16 items on every CU, SPARSE_ROWS_SLICE at most, so that a short batch still fills the device.
+// row_stride != 0 (the grouped search; >= the longest list): the scores go to c->part_s as a [count][row_stride] matrix instead,
+// entry j of query q's list at q * row_stride + j, and the scored positions to c->part_i in the same layout; padding and skipped
+// entries hold +inf and IDX_NONE.
 int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
                        uint32_t count, const uint32_t *ids, const uint32_t *offsets, const uint64_t *d_exclude,
-                       const uint32_t **d_list_off, hipStream_t s) {
+                       const uint32_t **d_list_off, hipStream_t s, uint32_t row_stride = 0) {
   const SparseStore &st = h->st;
   const uint32_t total = offsets[count];
   const uint64_t want = (uint64_t)device_cus(c) * 16;
@@ -191,22 +200,21 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
     }
   const uint32_t items = (uint32_t)item_e0.size();
   plan.insert(plan.end(), item_e0.begin(), item_e0.end());
-  // the plan goes through the context's pinned slot: the previous search's upload has to have left it
-  if (c->sp_ev == nullptr) ZCHK(hipEventCreateWithFlags(&c->sp_ev, hipEventDisableTiming));
-  else ZCHK(hipEventSynchronize(c->sp_ev));
-  ZRET(c->sp_pin.ensure(plan.size() * 4));
-  ZRET(c->sp_plan.ensure(plan.size() * 4));
-  memcpy(c->sp_pin.p, plan.data(), plan.size() * 4);
-  ZCHK(hipMemcpyAsync(c->sp_plan.p, c->sp_pin.p, plan.size() * 4, hipMemcpyHostToDevice, s));
-  ZCHK(hipEventRecord(c->sp_ev, s));
+  ZRET(sparse_upload_plan(c, plan, s));
   ZRET(c->plan.ensure(std::max<size_t>(total, 1) * 4));
-  ZRET(c->part_s.ensure(std::max<size_t>(total, 1) * 4));
+  const size_t cells = row_stride ? (size_t)count * row_stride : std::max<size_t>(total, 1);
+  ZRET(c->part_s.ensure(cells * 4));
+  if (row_stride) {
+    ZRET(c->part_i.ensure(cells * 4));
+    ZCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->part_s.p), 0x7f800000, cells, s));      // +inf
+    ZCHK(hipMemsetAsync(c->part_i.p, 0xff, cells * 4, s));                                             // IDX_NONE
+  }
   if (total) ZCHK(hipMemcpyAsync(c->plan.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
   SparseRowsArgs a{};
   a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
   a.q_off = c->sp_plan.as<uint32_t>(); a.q_idx = d_qidx; a.q_val = d_qval;
   a.ids = c->plan.as<uint32_t>(); a.list_off = a.q_off + count + 1; a.item_q = a.list_off + count + 1; a.item_e0 = a.item_q + items;
-  a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>();
+  a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>(); a.row_stride = row_stride; a.pos_out = c->part_i.as<uint32_t>();
   *d_list_off = a.list_off;
   if (items == 0) return 0;
   // indices | values of the longest run (at most 32 KiB: no launch attribute needed)

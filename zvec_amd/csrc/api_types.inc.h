@@ -100,6 +100,9 @@ struct RuntimeOpts {
   std::atomic<int> zerocopy{2};
   std::atomic<int> assign256{1};     // fp16 labelling on the 256 x 256 multi-phase tile (0: always the 128 x 128 one-barrier tile)
   std::atomic<int> scan256{1};       // wide fp16 flat scans (>= 256 queries, k <= 11) on the 256 x 256 multi-phase tile (0: scan8_kernel; 2: on cache-resident bases too)
+  // grouped sparse full scan: a sub-batch of at most this many queries dumps its scores with sparse_rows_dump_kernel (a wave per
+  // stored row), a wider one with sparse_scan_kernel (lane = query).  0 = never.  Default: DESIGN §3b "Group-by", from profiles/sparse_grouped*.json
+  std::atomic<int> sparse_group_rows{32};
   RuntimeOpts() {
     if (const char *e = getenv("ZVEC_HIP_SCAN256")) scan256 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("ZVEC_HIP_WAIT")) wait = std::max(0, std::min(2, atoi(e)));

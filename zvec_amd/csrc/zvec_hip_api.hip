@@ -43,5 +43,6 @@ extern "C" {
 #include "api_entry_shards.inc.h"
 #include "api_entry_container.inc.h"
 #include "api_entry_sparse.inc.h"
+#include "api_entry_sparse_group.inc.h"
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// zvk_sparse.hip.h — sparse fp32 / fp16 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, staging and unpack.
+// zvk_sparse.hip.h — sparse fp32 / fp16 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, the wave-per-row score dump, staging and unpack.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Reference: FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_search.h:119-144) score one query
@@ -213,7 +213,9 @@ struct SparseRowsArgs {
   const uint32_t *item_e0;    // [items] its first entry
   uint32_t slice;             // entries per item at most, <= SPARSE_ROWS_SLICE
   uint64_t n;                 // rows
-  float *scores;              // [entries]
+  float *scores;              // [entries]; row_stride != 0: [nq][row_stride], entry j of query q's list at q * row_stride + j
+  uint32_t row_stride;        // 0 = the ragged form
+  uint32_t *pos_out;          // row_stride != 0: the scored position of every entry in the same layout, IDX_NONE for a skipped one
 };
 
 // halvings that take a run of qlen elements down to one: ceil(log2(qlen))
@@ -313,7 +315,86 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
     const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
     if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
   }
-  if (e < e1) a.scores[e] = out;
+  if (e < e1) {
+    if (a.row_stride == 0) {
+      a.scores[e] = out;
+    } else {          // (uniform) the grouped search's candidate matrix: the caller has filled the padding
+      const size_t o = (size_t)q * a.row_stride + (e - a.list_off[q]);
+      a.scores[o] = out;
+      a.pos_out[o] = live ? a.ids[e] : IDX_NONE;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Score dump of a NARROW batch (the grouped full scan, FlatSparseEntity::search_group, flat_sparse_entity.h:79-103, which zvec calls
+// one query at a time): sparse_scan_kernel is lane = query, so a batch of one leaves 63 of its 64 lanes idle.  Here the whole wave
+// works on ONE stored row (sparse_wave_row_dot, lane = stored element).  One wave per work-group; a work item is (query, chunk of
+// rows), the chunk a multiple of 64 rows.  The query's run is copied to LDS once per item (32 KiB at most).  The wave takes 64 rows
+// at a time: lane l looks at row base + l — excluded (nothing of it is fetched) or its two offsets, one coalesced load each — then
+// the rows that hold anything are scored one after the other (wave-uniform; the offsets are broadcast), lane l keeps row base + l's
+// score, and ONE coalesced store writes the 64 scores to dump[(q - qsub0) * n + base ..]: +inf for an excluded row, exactly +0 for
+// a row or a query without elements (a run of length 0 reads no row at all).
+struct SparseRowsDumpArgs {
+  const uint64_t *row_off;    // [n + 1]
+  const uint32_t *idx;        // [elements]
+  const void *val;            // [elements] of the kernel's VT
+  const uint32_t *exclude;    // nullable bitset over positions, set = skip
+  const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
+  const uint32_t *q_idx;
+  const void *q_val;          // VT as well
+  uint32_t qsub0;             // the query whose scores are row 0 of `dump`
+  uint32_t nqsub;             // queries of this launch: qsub0 .. qsub0 + nqsub
+  uint64_t n;                 // rows
+  uint32_t rows_per_chunk;    // a multiple of 64
+  float *dump;                // [nqsub][n]
+};
+
+template <typename VT, bool EXCL>
+__global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDumpArgs a) {
+  extern __shared__ f32x4 zvk_smem4[];
+  const int lane = threadIdx.x;
+  // (the queries of one chunk are neighbours in the grid: they read the same rows)
+  const uint32_t chunk = blockIdx.x / a.nqsub, qs = blockIdx.x - chunk * a.nqsub, q = a.qsub0 + qs;
+  const uint32_t qb = a.q_off[q], qlen = min(a.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
+  uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);             // [qlen] the query's indices
+  VT *qv = reinterpret_cast<VT *>(qi + qlen);                         // [qlen] its values, as stored
+  const VT *q_val = static_cast<const VT *>(a.q_val);
+  for (uint32_t i = lane; i < qlen; i += 64) {
+    qi[i] = a.q_idx[qb + i];
+    qv[i] = q_val[qb + i];
+  }
+  const uint32_t steps = sparse_halvings(qlen);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+
+  float *out = a.dump + (size_t)qs * a.n;
+  const uint64_t r0 = (uint64_t)chunk * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
+  for (uint64_t base = r0; base < r1; base += 64) {
+    const uint64_t r = base + (uint32_t)lane;
+    bool live = r < r1;
+    if (EXCL) {
+      if (live) live = ((a.exclude[r >> 5] >> (r & 31)) & 1u) == 0;
+    }
+    float s = live ? 0.f : __builtin_inff();
+    if (qlen != 0) {                    // (uniform)
+      uint64_t rb = 0, re = 0;
+      if (live) {
+        rb = a.row_off[r];
+        re = a.row_off[r + 1];
+      }
+      uint64_t todo = __ballot(re > rb);
+      while (todo) {                    // (uniform)
+        const int j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
+        const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
+        const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
+        if (lane == j) s = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+      }
+    }
+    if (r < r1) out[r] = s;
+  }
 }
 
 // Query staging.  A block's runs are contiguous in the CSR query arrays, so those arrays ARE the LDS images, block after block (the

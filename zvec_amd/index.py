@@ -716,7 +716,7 @@ class HipFlatSparseStreamer:
         if ctx is None:
             return IndexError_.InvalidArgument
         if ctx.group_by_search():
-            return IndexError_.Unsupported              # (group-by stays with the reference's flat_sparse search)
+            return IndexError_.Unsupported              # (not routed here: group_by_search_impl serves it when called directly)
         if ctx.topk() == 0:
             return IndexError_.InvalidArgument
         runs = self._runs(counts, indices, values)
@@ -747,7 +747,7 @@ class HipFlatSparseStreamer:
         if ctx is None:
             return IndexError_.InvalidArgument
         if ctx.group_by_search():
-            return IndexError_.Unsupported              # (search_group_p_keys stays with the reference)
+            return IndexError_.Unsupported              # (not routed here: group_by_search_p_keys_impl serves it when called directly)
         if ctx.topk() == 0 or len(p_keys) != int(count):
             return IndexError_.InvalidArgument
         runs = self._runs(counts, indices, values)
@@ -765,6 +765,55 @@ class HipFlatSparseStreamer:
         if rc == 0:
             ctx._set_results(keys, scores, cnts)
         return rc
+
+    def _group_search(self, counts, indices, values, count, ctx, p_keys):
+        if ctx is None or not ctx.group_by_search() or ctx._group_topk <= 0:
+            return IndexError_.InvalidArgument
+        if ctx._group_by is None:
+            return IndexError_.InvalidArgument                  # "Invalid group-by function"
+        runs = self._runs(counts, indices, values)
+        if runs is None or runs[0].size != int(count) or (p_keys is not None and len(p_keys) != int(count)):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        allk = self._all_keys()
+        of, ids = ctx._groups_for(allk)
+        gnum, gk = ctx._group_num, ctx._group_topk
+        groups = np.zeros((count, gnum), np.uint32)
+        ngroups = np.zeros(count, np.uint32)
+        keys = np.zeros((count, gnum, gk), np.uint64)
+        scores = np.zeros((count, gnum, gk), np.float32)
+        cnts = np.zeros((count, gnum), np.uint32)
+        if len(of) == 0:
+            of = np.zeros(1, np.uint32)                         # (an empty index: nothing of it is read)
+        L = _lib.lib()
+        if p_keys is None:
+            ex = ctx._exclude_for(allk) if (ctx._filter_fn or ctx._exclude is not None) else None
+            rc = L.zvec_hip_sparse_search_grouped(self._h, ctx._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), count, _np_ptr(of),
+                                                  max(len(ids), 1), gnum, gk, ctx.threshold(), _np_ptr(ex), _np_ptr(groups),
+                                                  _np_ptr(ngroups), _np_ptr(keys), _np_ptr(scores), _np_ptr(cnts))
+        else:
+            ids_l, offs = self._p_keys_positions(p_keys, ctx)
+            rc = L.zvec_hip_sparse_search_grouped_by_ids(self._h, ctx._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), count, _np_ptr(ids_l),
+                                                         _np_ptr(offs), _np_ptr(of), max(len(ids), 1), gnum, gk, ctx.threshold(),
+                                                         _np_ptr(ctx._exclude), _np_ptr(groups), _np_ptr(ngroups), _np_ptr(keys),
+                                                         _np_ptr(scores), _np_ptr(cnts))
+        if rc == 0:
+            ctx._set_group_results(ids, groups, ngroups, keys, scores, cnts)
+        return rc
+
+    def group_by_search_impl(self, counts, indices, values, count, ctx):
+        """the group-by branch of the sparse search (flat_sparse_search.h:77-117 -> FlatSparseEntity::search_group,
+        flat_sparse_entity.h:79-103; ConvertGroupMapToResult, flat_sparse_search.h:23-53) through
+        zvec_hip_sparse_search_grouped: the context's group parameters and group_by function, its filter / exclude bitset as in
+        search_impl; results in ctx.group_result(q).  Called directly: search_impl itself still answers Unsupported under a group
+        context."""
+        return self._group_search(counts, indices, values, count, ctx, None)
+
+    def group_by_search_p_keys_impl(self, counts, indices, values, p_keys, count, ctx):
+        """the same over listed primary keys (FlatSparseEntity::search_group_p_keys, flat_sparse_entity.h:105-128) through
+        zvec_hip_sparse_search_grouped_by_ids; keys are mapped and filtered as in search_bf_by_p_keys_impl, which itself still
+        answers Unsupported under a group context."""
+        return self._group_search(counts, indices, values, count, ctx, p_keys)
 
     def batch_distance(self, indices, values, positions, ctx=None):
         """IndexMetric::batch_distance: one sparse query against the listed storage positions, fp32 scores in that order (+inf for a
