@@ -551,9 +551,18 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
 
 /* ---- flat index of sparse rows ---------------------------------------------------------------
  * stands behind FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_streamer.cc:186-300,
- * flat_sparse_search.h:58-148) for fp32 and fp16 values under the "InnerProductSparse" metric (inner_product_metric.cc:329,
- * 484-495: MinusInnerProductSparseMatrix<float>::Compute for DT_FP32, <ailego::Float16> for DT_FP16).  Rules, as the reference has
- * them:
+ * flat_sparse_search.h:58-148) for fp32 and fp16 values under one of two metrics, fixed when the handle is created
+ * (zvec_hip_sparse_create_metric):
+ *   ZVEC_HIP_METRIC_IP  "InnerProductSparse" (inner_product_metric.cc:329, 484-495: MinusInnerProductSparseMatrix<float>::Compute
+ *                       for DT_FP32, <ailego::Float16> for DT_FP16); what zvec_hip_sparse_create and _create_typed give
+ *   ZVEC_HIP_METRIC_L2  "SquaredEuclideanSparse" (SquaredEuclideanSparseMetric, src/core/metric/euclidean_metric.cc:1027-1095;
+ *                       SquaredEuclideanSparseDistanceMatrix<float>::Compute, src/ailego/math/euclidean_distance_matrix.h:
+ *                       2480-2638).  The reference's metric accepts DT_FP16 but hands out the <float> routine for it
+ *                       (euclidean_metric.cc:1070-1072), so there is no fp16 summation of its own to match: the definition
+ *                       under "Score" below is the contract for both value types.
+ * Value type, row format, index order, the 4096-pair cap, validation of host queries, exclude_bitset, threshold, the topk caps,
+ * the rules for listed rows and the group-by ranking rules are the same under both metrics; scores are smaller-is-better and
+ * lists ascend under both.  Rules, as the reference has them:
  *   - Value type.  A handle serves ONE value type, chosen at zvec_hip_sparse_create_typed: ZVEC_HIP_DT_FP32 (float) or
  *     ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes).  Every `values` pointer below (rows, queries, get_vector, host or device) is a
  *     `const void *` / `void *` read as elements of the handle's type, the way zvec_hip_flat_* treats `vecs`.  fp16 values are
@@ -575,14 +584,30 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     match: an unsorted or repeated index gives the reference an unspecified score.  Such a run is refused here:
  *     ZVEC_HIP_ERR_INVALID_ARGUMENT from append and from the host-pointer search.  zvec_hip_sparse_search_dev cannot see its
  *     queries' indices: runs that break the rule give unspecified scores there (never an out-of-range access).
- *   - Score.  MINUS the inner product over the indices present in both row and query (Compute ends with *out = -sum, :2861),
- *     smaller is better, lists ascending: the convention of ZVEC_HIP_METRIC_IP on a dense flat handle.  A pair without a
- *     shared index (an empty row or query included, :2795-2799) scores exactly 0 and is an ordinary candidate, as in the
- *     reference's heap.  Products are summed in fp32, in an order of the library's choosing.
+ *   - Score, ZVEC_HIP_METRIC_IP.  MINUS the inner product over the indices present in both row and query (Compute ends with
+ *     *out = -sum, :2861), smaller is better, lists ascending: the convention of ZVEC_HIP_METRIC_IP on a dense flat handle.  A
+ *     pair without a shared index (an empty row or query included, :2795-2799) scores exactly 0 and is an ordinary candidate,
+ *     as in the reference's heap.  Products are summed in fp32, in an order of the library's choosing.
+ *   - Score, ZVEC_HIP_METRIC_L2.  The squared distance over the UNION of the two index sets: an index present in both adds
+ *     (b - q)^2, one of the row alone b^2, one of the query alone q^2.  Scores are >= 0, never -0 and never negative.  The
+ *     score of row b against query q is s = A + R, all in fp32, halves widened exactly first:
+ *       A  summed over the stored elements of the row, in an order of the library's choosing, each step an fma, every term
+ *          non-negative: an element whose index is in the query's run adds (b - q)^2, the difference rounded once; any other
+ *          element adds b^2.
+ *       R  the query mass that matched nothing.  If every query element was matched (hits == qlen, counted while A is formed;
+ *          the empty query included) R is exactly +0.  Otherwise R = max(0, Qn - Mq), Qn the fp32 sum of q^2 over the whole
+ *          run (formed once per query per launch or work item, never per row), Mq the fp32 sum of q^2 over the matched ones.
+ *     So a row searched with itself, and any identical pair, scores exactly +0.0; a pair of empty runs scores exactly +0.0; an
+ *     empty row scores Qn and an empty query the row's sum of squares; a pair with no shared index scores |b|^2 + |q|^2 and
+ *     is an ordinary candidate, no zero tie.  (The expansion |b|^2 + |q|^2 - 2 b.q is NOT used: it cancels exactly where a
+ *     nearest-neighbour search looks and cannot return 0 for a row searched with itself.)  For fp32 values this is the
+ *     reference's quantity in another order of summation (theirs is sequential inside 16-bit index segments); it agrees with
+ *     the exact value within (rlen + 4) * 2^-23 * A + [hits < qlen] * (qlen + 4) * 2^-23 * (Qn + Mq), not bit for bit.
  *   - threshold and exclude_bitset mean what they mean for zvec_hip_flat_search (a document is dropped iff score > threshold;
  *     bit i of word i / 64 = storage position i, the row's number in append order).
  *   - Ties.  Which of several equal scores are returned at the k-th place, and their order, is unspecified (the reference's
- *     heap resolves ties arbitrarily); zero scores tie massively.
+ *     heap resolves ties arbitrarily).  Under ZVEC_HIP_METRIC_IP zero scores tie massively; under ZVEC_HIP_METRIC_L2 a zero
+ *     score means identical runs and ties are as rare as equal distances.
  *   - topk * 12 + 16 <= 60 KiB as elsewhere, else ZVEC_HIP_ERR_UNSUPPORTED.
  *   - Listed rows (zvec_hip_sparse_search_by_ids, zvec_hip_sparse_batch_distance).  `ids` / `positions` are STORAGE POSITIONS:
  *     the caller maps primary keys to positions and drops unknown keys, as get_id(p_key) == kInvalidNodeId does in the reference
@@ -603,18 +628,26 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     ordinal being the storage position for the full scan and the place in the list for listed rows; groups are ranked by
  *     their best score, equal best scores by group number, and the first group_num are kept; documents with score > threshold
  *     are cut AFTER that ranking, so a group may be listed with no document.  A position listed twice competes twice; a
- *     position >= the row count or excluded never competes.  A pair with no shared index scores exactly 0 and is an ordinary
- *     candidate: the zero ties are resolved by the ordinal rule, which is stricter than the "unspecified" of Ties above.
+ *     position >= the row count or excluded never competes.  Under ZVEC_HIP_METRIC_IP a pair with no shared index scores
+ *     exactly 0 and is an ordinary candidate: the zero ties are resolved by the ordinal rule, which is stricter than the
+ *     "unspecified" of Ties above; under ZVEC_HIP_METRIC_L2 equal scores are resolved by the same rule.
  *     ngroups, group_num or group_topk of 0: ZVEC_HIP_ERR_INVALID_ARGUMENT; group_num * 12 + 16 or group_topk * 16 + 16 above
  *     60 KiB: ZVEC_HIP_ERR_UNSUPPORTED; a refused call touches no output.  An empty index gives out_ngroups[q] = 0.
- * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), the *Sparse Euclidean
- * metrics (SquaredEuclideanSparse, MipsSquaredEuclidean sparse), loaders of the reference's dumped sparse segments, shards,
- * the plugin and the C++ mirror (zvec_hip_operator.hpp). */
+ * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), the
+ * MipsSquaredEuclideanSparse metric, loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror
+ * (zvec_hip_operator.hpp). */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
-/* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched */
+/* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
+ * InnerProductSparse. */
 int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out);
+/* dtype as above; metric: ZVEC_HIP_METRIC_IP (InnerProductSparse) or ZVEC_HIP_METRIC_L2 (SquaredEuclideanSparse).  Any other
+ * metric, or an unsupported dtype, returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.  The two creators above are
+ * calls of this one with ZVEC_HIP_METRIC_IP. */
+int zvec_hip_sparse_create_metric(int dtype, int metric, int device, zvec_hip_sparse_t *out);
 /* the value type the handle was created with */
 int zvec_hip_sparse_dtype(zvec_hip_sparse_t h, int *dtype);
+/* the metric the handle was created with */
+int zvec_hip_sparse_metric(zvec_hip_sparse_t h, int *metric);
 int zvec_hip_sparse_destroy(zvec_hip_sparse_t h);
 /* room for `rows` rows and `elements` (index, value) pairs in all; the store also grows on demand, geometrically */
 int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t elements);

@@ -32,6 +32,13 @@ plain zvec_hip_sparse_search (k = 10) of the same queries; the answers of the tw
 "sparse_group_rows" is read off this file: the largest batch up to which the wave-per-row dump was the faster one.
 
     python tools/sparse_bench.py --grouped [--dtype fp32|fp16] [--out profiles/sparse_grouped.json] [--steps 10] [--warmup 3]
+
+--metric l2: the chosen mode runs twice in one process, on an InnerProductSparse index and then on a SquaredEuclideanSparse index
+(zvec_hip_sparse_create_metric(.., ZVEC_HIP_METRIC_L2, ..)) of the same corpus with the same queries; every figure of the L2 run
+is reported beside the IP figure of the same point under an "l2_" name (reported, not gated).  The L2 scan does strictly more
+work per stored element (a square for every element, two more sums on a hit) and has no shortcut for an empty query.
+
+    python tools/sparse_bench.py --metric l2 [--by-keys | --grouped] [--dtype fp32|fp16] [--out profiles/sparse_flat1m_l2.json]
 """
 import argparse
 import ctypes as C
@@ -41,6 +48,29 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+METRIC_NAMES = {"ip": "InnerProductSparse", "l2": "SquaredEuclideanSparse"}
+
+
+def agreement_band(metric):
+    """how far two routes to the same score may lie apart on this corpus (values below 1, rows of at most 192 and queries of at
+    most 64 elements): twice the distance of either from the exact score.  ip: an fp32 sum of m <= 64 products,
+    (m + 1) * 2^-23 * sum |products| <= 65 * 2^-23 * 64.  l2 (include/zvec_hip.h, Score): (rlen + 4) * 2^-23 * A + (qlen + 4) *
+    2^-23 * (Qn + Mq) with A <= 192 * 4 and Qn, Mq <= 64"""
+    if metric == "l2":
+        return 2 * (196 * 2.0 ** -23 * 768 + 68 * 2.0 ** -23 * 128)
+    return 2 * 65 * 2.0 ** -23 * 64
+
+
+def beside(ip, l2, rows):
+    """the L2 run's figures into the IP run's result: every entry of l2[rows] that differs goes beside its IP figure as "l2_" + name"""
+    assert len(ip[rows]) == len(l2[rows])
+    for a, b in zip(ip[rows], l2[rows]):
+        a.update({"l2_" + key: value for key, value in b.items() if a.get(key) != value})
+    ip.update({"l2_" + key: value for key, value in l2.items() if key != rows and ip.get(key) != value})
+    ip["metric"] = "ip, l2 beside it"
+    return ip
 
 
 def zipf_runs(torch, dev, g, n, lo, hi, vocab, draws):
@@ -66,7 +96,7 @@ def zipf_runs(torch, dev, g, n, lo, hi, vocab, draws):
     return torch.cat(counts), torch.cat(parts)
 
 
-def by_keys(args):
+def by_keys(args, metric):
     import time
     import numpy as np
     import torch
@@ -81,7 +111,7 @@ def by_keys(args):
     row_len = rc_.numpy().astype(np.int64)
     np_val = np.float16 if args.dtype == "fp16" else np.float32
     elem_bytes = 4 + np.dtype(np_val).itemsize
-    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
     assert se.reserve(args.n, ri.numel()) == 0
     assert se.add_batch(row_len.astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
     del ri, rv
@@ -139,11 +169,10 @@ def by_keys(args):
                                                   _np_ptr(counts2[q:q + 1]))
                     assert rc == 0, rc
             old_ms, old_min = median_ms(bitset_route)
-            # the same answer up to the order of the sums: a score is an fp32 sum of m <= 64 products (the longest query) of values
-            # below 1, so either route is within (m + 1) * 2^-23 * sum |products| <= 65 * 2^-23 * 64 of the exact score, and two
-            # routes within twice that of each other (the k-th candidates may swap inside that band, their scores stay within it)
+            # the same answer up to the order of the sums (agreement_band: the k-th candidates may swap inside that band, their
+            # scores stay within it)
             assert counts.tolist() == counts2.tolist() == [k] * batch
-            assert bool(np.all(scores[:, 1:] >= scores[:, :-1])) and float(np.abs(scores - scores2).max()) <= 2 * 65 * 2.0 ** -23 * 64
+            assert bool(np.all(scores[:, 1:] >= scores[:, :-1])) and float(np.abs(scores - scores2).max()) <= agreement_band(metric)
             elements = int(sum(int(row_len[a].sum()) for a in lists))
             points.append({"batch": batch, "keys_per_query": length, "by_ids_ms": new_ms, "by_ids_min_ms": new_min, "bitset_route_ms": old_ms,
                            "bitset_route_min_ms": old_min, "speedup": old_ms / new_ms, "listed_elements": elements,
@@ -159,18 +188,15 @@ def by_keys(args):
     for p in points:
         p["gather_bound_ms"] = p["gathered_bytes"] / (gbs.value * 1e9) * 1e3
         p["bound_fraction"] = p["gather_bound_ms"] / p["by_ids_ms"]
-    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d, searched by listed rows" % (args.n, args.vocab, k),
-           "dtype": args.dtype,
+    res = {"workload": "flat sparse %s %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d, searched by listed rows" % (
+               metric.upper(), args.n, args.vocab, k),
+           "dtype": args.dtype, "metric": metric,
            "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)", "clock_mhz": mhz.value,
            "stream_gbs": gbs.value, "steps": args.steps, "warmup": args.warmup, "points": points}
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    return res
 
 
-def grouped(args):
+def grouped(args, metric):
     import time
     import numpy as np
     import torch
@@ -183,7 +209,7 @@ def grouped(args):
     rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
     rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
     np_val = np.float16 if args.dtype == "fp16" else np.float32
-    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
     assert se.reserve(args.n, ri.numel()) == 0
     assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
     del ri, rv
@@ -234,16 +260,15 @@ def grouped(args):
                                               _np_ptr(scores), _np_ptr(counts))
                 assert rc == 0, rc
             point["plain_search_ms"], point["plain_search_min_ms"] = median_ms(plain)
-            # the two dumps sum the same products in different orders: a score is an fp32 sum of m <= 64 products of values below 1,
-            # so either is within 65 * 2^-23 * 64 of the exact score and the two within twice that of each other, place by place
+            # the two dumps sum the same terms in different orders (agreement_band), place by place
             a, b = answers["lane_per_query"], answers["wave_per_row"]
             assert a[1].tolist() == b[1].tolist() == [gnum] * batch and np.array_equal(a[4], b[4]) and int(a[4].min()) == gk
             point["score_max_abs_diff"] = float(np.abs(a[3] - b[3]).max())
-            assert point["score_max_abs_diff"] <= 2 * 65 * 2.0 ** -23 * 64
+            assert point["score_max_abs_diff"] <= agreement_band(metric)
             point["same_groups"] = float(np.mean(a[0] == b[0]))
             point["same_documents"] = float(np.mean(a[2] == b[2]))
             # the best document overall is the best document of the best group
-            assert float(np.abs(a[3][:, 0, 0] - scores[:, 0]).max()) <= 2 * 65 * 2.0 ** -23 * 64
+            assert float(np.abs(a[3][:, 0, 0] - scores[:, 0]).max()) <= agreement_band(metric)
             point["faster"] = "wave_per_row" if point["wave_per_row_ms"] < point["lane_per_query_ms"] else "lane_per_query"
             points.append(point)
             print(json.dumps(point), flush=True)
@@ -254,15 +279,11 @@ def grouped(args):
         if p["faster"] != "wave_per_row":
             break
         width = p["batch"]
-    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, group-by: %d groups, %d x %d" % (
-               args.n, args.vocab, ngroups, gnum, gk),
-           "dtype": args.dtype, "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)",
+    res = {"workload": "flat sparse %s %d rows x 64-192 of %d (Zipf), queries 16-64, group-by: %d groups, %d x %d" % (
+               metric.upper(), args.n, args.vocab, ngroups, gnum, gk),
+           "dtype": args.dtype, "metric": metric, "timing": "host-pointer call to return, wall clock, median of the steps (min next to it)",
            "steps": args.steps, "warmup": args.warmup, "wave_per_row_wins_up_to_batch": width, "points": points}
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    return res
 
 
 def main():
@@ -276,11 +297,20 @@ def main():
     ap.add_argument("--by-keys", action="store_true")
     ap.add_argument("--grouped", action="store_true")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
+    ap.add_argument("--metric", choices=("ip", "l2"), default="ip")
     args = ap.parse_args()
-    if args.by_keys:
-        return by_keys(args)
-    if args.grouped:
-        return grouped(args)
+    mode, rows = (by_keys, "points") if args.by_keys else (grouped, "points") if args.grouped else (flat, "legs")
+    res = mode(args, "ip")
+    if args.metric == "l2":
+        res = beside(res, mode(args, "l2"), rows)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def flat(args, metric):
     import numpy as np
     import torch
     import zvec_amd
@@ -290,7 +320,7 @@ def main():
     rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
     rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
     np_val = np.float16 if args.dtype == "fp16" else np.float32
-    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype)
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
     assert se.reserve(args.n, ri.numel()) == 0
     assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
     elements = se.element_count()
@@ -348,15 +378,11 @@ def main():
         lds_ms = float(elements) * leg["probes_per_element"] * 2.0 / (cus * mhz.value * 1e6) * 1e3
         leg.update(stream_bound_ms=stream_ms, stream_fraction=stream_ms / leg["ms_per_step"], lds_bound_ms=lds_ms,
                    lds_fraction=lds_ms / leg["ms_per_step"])
-    res = {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d" % (args.n, args.vocab, args.topk),
-           "dtype": args.dtype,
+    res = {"workload": "flat sparse %s %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d" % (metric.upper(), args.n, args.vocab, args.topk),
+           "dtype": args.dtype, "metric": metric,
            "elements": elements, "stored_bytes": stored, "cus": cus, "clock_mhz": mhz.value, "stream_gbs": gbs.value,
            "steps": args.steps, "warmup": args.warmup, "cpu_comparison": "not compared", "legs": legs}
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    return res
 
 
 if __name__ == "__main__":

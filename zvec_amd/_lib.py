@@ -149,7 +149,9 @@ SYMBOLS = {
     "zvec_hip_crc32c": (C.c_uint32, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "zvec_hip_sparse_create": (C.c_int, [C.c_int, C.POINTER(_h)]),
     "zvec_hip_sparse_create_typed": (C.c_int, [C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_sparse_create_metric": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
     "zvec_hip_sparse_dtype": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "zvec_hip_sparse_metric": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "zvec_hip_sparse_destroy": (C.c_int, [_h]),
     "zvec_hip_sparse_reserve": (C.c_int, [_h, C.c_uint64, C.c_uint64]),
     "zvec_hip_sparse_append": (C.c_int, [_h, _u32p, _u32p, _valp, C.c_uint64, _u64p]),

@@ -1,31 +1,42 @@
-// api_entry_sparse.inc.h — C ABI entry points: flat index of sparse fp32 / fp16 rows under InnerProductSparse (zvk_sparse.hip.h)
+// api_entry_sparse.inc.h — C ABI entry points: flat index of sparse fp32 / fp16 rows under InnerProductSparse or SquaredEuclideanSparse (zvk_sparse.hip.h)
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 extern "C++" {
 namespace {
 
-template <typename VT, bool DUMP>
+template <typename VT, bool DUMP, bool L2>
 int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
   static bool attr_set[16] = {};        // (one per instantiation)
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, false, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, false, DUMP, L2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)LDS_LIMIT));
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, true, DUMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, true, DUMP, L2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)LDS_LIMIT));
     attr_set[dev & 15] = true;
   }
-  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP>), dim3(grid), dim3(64), lds, stream, a);
-  else hipLaunchKernelGGL((sparse_scan_kernel<VT, false, DUMP>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((sparse_scan_kernel<VT, false, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
 }
 
-// the same by the handle's value width (4 = fp32, 2 = fp16)
+// the same by the handle's value width (4 = fp32, 2 = fp16) and metric (l2: SquaredEuclideanSparse, else InnerProductSparse)
 template <bool DUMP>
-int launch_sparse_scan(uint32_t width, const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
-  return width == 2 ? launch_sparse_scan<_Float16, DUMP>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP>(a, grid, lds, stream);
+int launch_sparse_scan(uint32_t width, bool l2, const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  if (l2)
+    return width == 2 ? launch_sparse_scan<_Float16, DUMP, true>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP, true>(a, grid, lds, stream);
+  return width == 2 ? launch_sparse_scan<_Float16, DUMP, false>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP, false>(a, grid, lds, stream);
+}
+
+template <typename VT, bool L2>
+int launch_sparse_rows(const SparseRowsArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  // (indices | values of the longest run, at most 32 KiB: no launch attribute needed)
+  if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((sparse_rows_kernel<VT, false, L2>), dim3(grid), dim3(64), lds, stream, a);
+  ZCHK(hipGetLastError());
+  return 0;
 }
 
 // Host queries of a host-pointer entry: indices | values in one block, the values `width` bytes each and starting at byte te * 4
@@ -142,7 +153,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
       SparseScanArgs d = a;
       d.blk0 = b0; d.qsub0 = q0; d.nqblocks = b1 - b0; d.dump = c->part_s.as<float>();
       chunking(d.nqblocks, &d.rows_per_chunk, &d.nchunks);
-      ZRET(launch_sparse_scan<true>(st.width, d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
+      ZRET(launch_sparse_scan<true>(st.width, h->l2(), d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
       MergeArgs m{};
       m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
       m.keymap = st.keys; m.out_keys = d_keys + (size_t)q0 * topk; m.out_scores = d_scores + (size_t)q0 * topk;
@@ -159,7 +170,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   ZRET(c->part_s.ensure(slots * topk * sizeof(float)));
   ZRET(c->part_i.ensure(slots * topk * sizeof(uint32_t)));
   a.part_s = c->part_s.as<float>(); a.part_i = c->part_i.as<uint32_t>();
-  ZRET(launch_sparse_scan<false>(st.width, a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
+  ZRET(launch_sparse_scan<false>(st.width, h->l2(), a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
   MergeArgs m{};
   m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = a.nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
   m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
@@ -217,36 +228,41 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>(); a.row_stride = row_stride; a.pos_out = c->part_i.as<uint32_t>();
   *d_list_off = a.list_off;
   if (items == 0) return 0;
-  // indices | values of the longest run (at most 32 KiB: no launch attribute needed)
   const size_t lds = (size_t)max_run * 4 + (((size_t)max_run * st.width + 3) & ~(size_t)3);
-  if (st.width == 2) {
-    if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<_Float16, true>), dim3(items), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL((sparse_rows_kernel<_Float16, false>), dim3(items), dim3(64), lds, s, a);
-  } else {
-    if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<float, true>), dim3(items), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL((sparse_rows_kernel<float, false>), dim3(items), dim3(64), lds, s, a);
-  }
-  ZCHK(hipGetLastError());
-  return 0;
+  if (h->l2()) return st.width == 2 ? launch_sparse_rows<_Float16, true>(a, items, lds, s) : launch_sparse_rows<float, true>(a, items, lds, s);
+  return st.width == 2 ? launch_sparse_rows<_Float16, false>(a, items, lds, s) : launch_sparse_rows<float, false>(a, items, lds, s);
 }
 
 }  // namespace
 }  // extern "C++"
 
-int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out) {
+int zvec_hip_sparse_create_metric(int dtype, int metric, int device, zvec_hip_sparse_t *out) {
   if (!out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (metric != ZVEC_HIP_METRIC_IP && metric != ZVEC_HIP_METRIC_L2) return ZVEC_HIP_ERR_UNSUPPORTED;
   zvec_hip_ctx_s *c = nullptr;
   ZRET(ctx_new(device, &c));
   zvec_hip_sparse_s *h = new (std::nothrow) zvec_hip_sparse_s();
   if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
-  h->device = device; h->dtype = dtype; h->defctx = c;
+  h->device = device; h->dtype = dtype; h->metric = metric; h->defctx = c;
   h->st.width = dtype == ZVEC_HIP_DT_FP16 ? 2u : 4u;
   *out = h;
   return 0;
 }
 
-int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out) { return zvec_hip_sparse_create_typed(ZVEC_HIP_DT_FP32, device, out); }
+int zvec_hip_sparse_create_typed(int dtype, int device, zvec_hip_sparse_t *out) {
+  return zvec_hip_sparse_create_metric(dtype, ZVEC_HIP_METRIC_IP, device, out);
+}
+
+int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out) {
+  return zvec_hip_sparse_create_metric(ZVEC_HIP_DT_FP32, ZVEC_HIP_METRIC_IP, device, out);
+}
+
+int zvec_hip_sparse_metric(zvec_hip_sparse_t h, int *metric) {
+  if (!h || !metric) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  *metric = h->metric;
+  return 0;
+}
 
 int zvec_hip_sparse_dtype(zvec_hip_sparse_t h, int *dtype) {
   if (!h || !dtype) return ZVEC_HIP_ERR_INVALID_ARGUMENT;

@@ -11,17 +11,17 @@
 //                sparse_scan_kernel<.., DUMP = true> (lane = query)
 //   listed rows  sparse_rows_kernel with a row stride: [queries][longest list] scores and positions, +inf / IDX_NONE for padding
 //                and for skipped entries
-// The scores are final as they stand (minus the inner product): nothing is refined.
+// The scores are final as they stand (minus the inner product, or the squared distance A + R of an L2 handle): nothing is refined.
 
 }  // extern "C"
 
 namespace {
 
-template <typename VT>
+template <typename VT, bool L2>
 int launch_sparse_rows_dump(const SparseRowsDumpArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
   // (indices | values of one run: at most 32 KiB, no launch attribute needed)
-  if (a.exclude) hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, true>), dim3(grid), dim3(64), lds, stream, a);
-  else hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, false>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.exclude) hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
+  else hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, false, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
 }
@@ -111,8 +111,13 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
       a.rows_per_chunk = (uint32_t)std::min<uint64_t>((((st.n + want - 1) / want + 63) / 64) * 64, 0x7fffffc0u);
       const uint32_t nchunks = (uint32_t)((st.n + a.rows_per_chunk - 1) / a.rows_per_chunk);
       const size_t lds = (size_t)max_run * 4 + (((size_t)max_run * st.width + 3) & ~(size_t)3);
-      if (st.width == 2) ZRET(launch_sparse_rows_dump<_Float16>(a, nchunks * cnt, lds, s));
-      else ZRET(launch_sparse_rows_dump<float>(a, nchunks * cnt, lds, s));
+      if (h->l2()) {
+        if (st.width == 2) ZRET((launch_sparse_rows_dump<_Float16, true>(a, nchunks * cnt, lds, s)));
+        else ZRET((launch_sparse_rows_dump<float, true>(a, nchunks * cnt, lds, s)));
+      } else {
+        if (st.width == 2) ZRET((launch_sparse_rows_dump<_Float16, false>(a, nchunks * cnt, lds, s)));
+        else ZRET((launch_sparse_rows_dump<float, false>(a, nchunks * cnt, lds, s)));
+      }
     } else {
       SparseScanArgs a{};
       a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = d_ex; a.q_off = d_qoff; a.q_idx = dq; a.q_val = dqv;
@@ -121,7 +126,7 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
       const uint64_t want = std::max<uint64_t>(1, (cus * 8 + a.nqblocks - 1) / a.nqblocks);
       a.rows_per_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (st.n + want - 1) / want), 0x7fffffffu);
       a.nchunks = (uint32_t)((st.n + a.rows_per_chunk - 1) / a.rows_per_chunk);
-      ZRET(launch_sparse_scan<true>(st.width, a, a.nchunks * a.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
+      ZRET(launch_sparse_scan<true>(st.width, h->l2(), a, a.nchunks * a.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
     }
     ZRET(group_select(c, st.keys, nullptr, dump, nullptr, (uint32_t)st.n, (uint32_t)st.n, q0, cnt, c->grp_of.as<uint32_t>(), ngroups,
                       group_num, group_topk, threshold, o, s));

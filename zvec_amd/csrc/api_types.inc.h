@@ -521,6 +521,8 @@ struct SparseStore {
 struct zvec_hip_sparse_s {
   int device = 0;
   int dtype = 0;            // ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16: the type of every value pointer of the handle's calls
+  int metric = ZVEC_HIP_METRIC_IP;      // ZVEC_HIP_METRIC_IP (InnerProductSparse) or ZVEC_HIP_METRIC_L2 (SquaredEuclideanSparse); fixed at creation
+  bool l2() const { return metric == ZVEC_HIP_METRIC_L2; }
   SparseStore st;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)

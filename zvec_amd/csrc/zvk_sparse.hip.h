@@ -1,4 +1,4 @@
-// zvk_sparse.hip.h — sparse fp32 / fp16 rows under InnerProductSparse: CSR rows in HBM, the query-block scan, listed rows, the wave-per-row score dump, staging and unpack.
+// zvk_sparse.hip.h — sparse fp32 / fp16 rows under InnerProductSparse and SquaredEuclideanSparse: CSR rows in HBM, the query-block scan, listed rows, the wave-per-row score dump, staging and unpack.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Reference: FlatSparseStreamer / FlatSparseSearcher (src/core/algorithm/flat_sparse/flat_sparse_search.h:119-144) score one query
@@ -25,6 +25,20 @@
 // insertion in LDS as [entry][lane] (lane-major: lanes that work on different entries still hit different banks); admission is
 // STRICT against min(own k-th score once the list is full, the bound the work-groups of the same query share) — zero scores tie
 // massively and a tie at the k-th place is never needed — and the threshold is a separate non-strict test.
+//
+// Metric (template parameter L2 of the three scoring kernels and the two helpers; false = InnerProductSparse, the code above, with
+// no run-time branch on the metric anywhere).  SquaredEuclideanSparse (SquaredEuclideanSparseMetric, src/core/metric/
+// euclidean_metric.cc:1027-1095, which hands out SquaredEuclideanSparseDistanceMatrix<float>::Compute, src/ailego/math/
+// euclidean_distance_matrix.h:2480-2638, for DT_FP16 as well as DT_FP32, :1070-1072) runs over the UNION of the two index sets: a
+// shared index adds (b - q)^2, an index of the row alone b^2, an index of the query alone q^2.  Here the score is s = A + R, all
+// fp32, halves widened first:
+//   A   over the stored elements of the row, each one fmaf(x, x, A) with x = b - q (rounded once) where the index is in the query's
+//       run and x = b where it is not; the same walk counts the hits and sums Mq = the q^2 of the matched query elements
+//   R   the query mass that met nothing: exactly +0 if hits == qlen (the empty query included), else max(0, Qn - Mq), Qn = the
+//       sum of q^2 over the whole run, formed ONCE per work item from the LDS image (never per row)
+// so identical runs, a pair of empty runs included, score exactly +0.0 (the norm expansion |b|^2 + |q|^2 - 2 b.q cancels exactly
+// there and cannot), every term is >= 0 and a score is never -0.  Nothing is skipped for an empty query or a pair without a shared
+// index: both are ordinary, non-zero candidates.
 #pragma once
 #include "zvk_common.hip.h"
 
@@ -65,7 +79,7 @@ __host__ __device__ inline size_t sparse_lds_bytes(uint32_t img_elems, uint32_t 
 
 // One wave per work-group; item = (chunk of rows, query block).  DUMP: every score goes to the [query][position] matrix and nothing
 // is selected (large k, selected by merge_kernel).
-template <typename VT, bool EXCL, bool DUMP>
+template <typename VT, bool EXCL, bool DUMP, bool L2 = false>
 __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
@@ -94,6 +108,14 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
   while (__ballot(qlen > (1u << steps)) != 0) ++steps;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
+  // L2: Qn, the squares of the lane's own run, once per work item (a lane-owned walk of the image)
+  [[maybe_unused]] float qn = 0.f;
+  if constexpr (L2) {
+    for (uint32_t i = 0; i < qlen; ++i) {
+      const float x = (float)qv[qstart + i];
+      qn = __builtin_fmaf(x, x, qn);
+    }
+  }
 
   uint32_t cnt = 0;                   // entries of this lane's list
   float tl = __builtin_inff();        // its k-th score once it is full
@@ -109,6 +131,8 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
     if (!DUMP && mine) tgk = __hip_atomic_load(&a.gtau[q0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t rb = a.row_off[r], re = a.row_off[r + 1];
     float acc = 0.f;
+    [[maybe_unused]] float mq = 0.f;        // L2: the squares of the query elements this row matched, and how many
+    [[maybe_unused]] uint32_t hits = 0;
     for (uint64_t p = rb; p < re; p += 64) {
       const uint32_t m = (uint32_t)min((uint64_t)64, re - p);
       uint32_t ri = 0;
@@ -139,15 +163,34 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
             }
           }
         }
+        if constexpr (L2) {
+          // every real element adds a square, a run of length 0 included; e >= m broadcast v = 0 from a lane >= m and add +0
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (n[u] != 0) {
-            if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
+          for (int u = 0; u < 4; ++u) {
+            float x = v[u];
+            if (n[u] != 0) {
+              if (qi[base[u]] == t[u]) {
+                const float qx = (float)qv[base[u]];
+                x = v[u] - qx;
+                mq = __builtin_fmaf(qx, qx, mq);
+                ++hits;
+              }
+            }
+            acc = __builtin_fmaf(x, x, acc);
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (n[u] != 0) {
+              if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
+            }
           }
         }
       }
     }
-    const float s = 0.f - acc;        // MINUS inner product, smaller is better; no shared index: exactly +0
+    float s;
+    if constexpr (L2) s = acc + (hits == qlen ? 0.f : fmaxf(0.f, qn - mq));      // A + R: >= +0, never -0
+    else s = 0.f - acc;               // MINUS inner product, smaller is better; no shared index: exactly +0
     if (DUMP) {
       if (mine) a.dump[(size_t)(q0 + lane - a.qsub0) * a.n + r] = s;
       continue;
@@ -223,9 +266,12 @@ __device__ __forceinline__ uint32_t sparse_halvings(uint32_t qlen) { return qlen
 
 // Stored elements [p, min(re, p + 64 U)) against the run qi / qv [qlen] in LDS (qlen > 0), lane = element: acc plus this lane's
 // products.  If the lane's index t is in the run at j, j stays inside [base, base + n) through every halving.
-template <int U, typename VT>
+// L2: acc plus this lane's squares ((b - q)^2 on a hit, b^2 otherwise; qlen == 0 is served: no LDS read, every element adds b^2),
+// mq plus the q^2 of its hits, hits plus their number.  Not L2: mq and hits are left alone.
+template <int U, typename VT, bool L2 = false>
 __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const VT *val, uint64_t p, uint64_t re, const uint32_t *qi,
-                                                 const VT *qv, uint32_t qlen, uint32_t steps, int lane, float acc) {
+                                                 const VT *qv, uint32_t qlen, uint32_t steps, int lane, float acc, float &mq,
+                                                 uint32_t &hits) {
   uint32_t t[U], base[U], n[U];
   float v[U];
 #pragma unroll
@@ -247,32 +293,74 @@ __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const VT *
       }
     }
   }
+  if constexpr (L2) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if (n[u] != 0) {
-      if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
+    for (int u = 0; u < U; ++u) {
+      float x = v[u];                 // (a lane beyond the row holds 0 and adds +0)
+      if (n[u] != 0) {
+        if (qi[base[u]] == t[u]) {
+          const float qx = (float)qv[base[u]];
+          x = v[u] - qx;
+          mq = __builtin_fmaf(qx, qx, mq);
+          ++hits;
+        }
+      }
+      acc = __builtin_fmaf(x, x, acc);
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (n[u] != 0) {
+        if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
+      }
     }
   }
   return acc;
 }
 
+// L2: Qn of the run in LDS, the sum of its squares, the same bits in every lane (lane-strided fmaf, then the butterfly)
+template <typename VT>
+__device__ __forceinline__ float sparse_wave_run_norm(const VT *qv, uint32_t qlen, int lane) {
+  float qn = 0.f;
+  for (uint32_t i = lane; i < qlen; i += 64) {
+    const float x = (float)qv[i];
+    qn = __builtin_fmaf(x, x, qn);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) qn += __shfl_xor(qn, o);
+  return qn;
+}
+
 // The whole wave scores ONE stored row [rb, re) (wave-uniform) against the run in LDS: the sum of value products over shared
 // indices, the same bits in every lane (the butterfly's order is fixed).  A run of length 0 makes no LDS read and no load.
 // (sparse_rows_kernel's inner step; a narrow zvec_hip_sparse_search batch can walk its chunk of rows with it as well.)
-template <typename VT>
+// L2: the row's SCORE A + R instead, the same bits in every lane: the butterfly adds up A, Mq and the hits, qn is the run's
+// sparse_wave_run_norm.  No shortcut for a run of length 0 (the row's squares are summed) nor for an empty row (it scores R).
+template <typename VT, bool L2 = false>
 __device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const VT *val, uint64_t rb, uint64_t re, const uint32_t *qi,
-                                                     const VT *qv, uint32_t qlen, uint32_t steps, int lane) {
-  if (qlen == 0) return 0.f;
-  float acc = 0.f;
+                                                     const VT *qv, uint32_t qlen, uint32_t steps, int lane, float qn = 0.f) {
+  if constexpr (!L2) {
+    if (qlen == 0) return 0.f;
+  }
+  float acc = 0.f, mq = 0.f;
+  uint32_t hits = 0;
   uint64_t p = rb;
-  for (; p < re && re - p > 64; p += 256) acc = sparse_lane_dot<4>(idx, val, p, re, qi, qv, qlen, steps, lane, acc);
-  if (p < re) acc = sparse_lane_dot<1>(idx, val, p, re, qi, qv, qlen, steps, lane, acc);
+  for (; p < re && re - p > 64; p += 256) acc = sparse_lane_dot<4, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
+  if (p < re) acc = sparse_lane_dot<1, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if constexpr (L2) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mq += __shfl_xor(mq, o);
+      hits += __shfl_xor(hits, o);
+    }
+    return acc + (hits == qlen ? 0.f : fmaxf(0.f, qn - mq));      // A + R: >= +0, never -0
+  }
   return acc;
 }
 
-template <typename VT, bool EXCL>
+template <typename VT, bool EXCL, bool L2 = false>
 __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
@@ -289,6 +377,8 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
   const uint32_t steps = sparse_halvings(qlen);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
+  [[maybe_unused]] float qn = 0.f;
+  if constexpr (L2) qn = sparse_wave_run_norm(qv, qlen, lane);
 
   // lane = listed entry: which entries are scored at all, and where their rows lie
   const uint32_t e = e0 + (uint32_t)lane;
@@ -312,8 +402,13 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
     todo &= todo - 1;
     const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
     const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
-    const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
-    if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+    if constexpr (L2) {
+      const float s = sparse_wave_row_dot<VT, true>(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane, qn);
+      if (lane == j) out = s;
+    } else {
+      const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
+      if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+    }
   }
   if (e < e1) {
     if (a.row_stride == 0) {
@@ -334,7 +429,8 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
 // at a time: lane l looks at row base + l — excluded (nothing of it is fetched) or its two offsets, one coalesced load each — then
 // the rows that hold anything are scored one after the other (wave-uniform; the offsets are broadcast), lane l keeps row base + l's
 // score, and ONE coalesced store writes the 64 scores to dump[(q - qsub0) * n + base ..]: +inf for an excluded row, exactly +0 for
-// a row or a query without elements (a run of length 0 reads no row at all).
+// a row or a query without elements (a run of length 0 reads no row at all).  L2: an empty row scores Qn, and a run of length 0
+// skips nothing (every row that holds anything is read and scores the sum of its squares).
 struct SparseRowsDumpArgs {
   const uint64_t *row_off;    // [n + 1]
   const uint32_t *idx;        // [elements]
@@ -350,7 +446,7 @@ struct SparseRowsDumpArgs {
   float *dump;                // [nqsub][n]
 };
 
-template <typename VT, bool EXCL>
+template <typename VT, bool EXCL, bool L2 = false>
 __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDumpArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
@@ -367,6 +463,8 @@ __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDu
   const uint32_t steps = sparse_halvings(qlen);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
+  [[maybe_unused]] float qn = 0.f;
+  if constexpr (L2) qn = sparse_wave_run_norm(qv, qlen, lane);
 
   float *out = a.dump + (size_t)qs * a.n;
   const uint64_t r0 = (uint64_t)chunk * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
@@ -376,8 +474,8 @@ __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDu
     if (EXCL) {
       if (live) live = ((a.exclude[r >> 5] >> (r & 31)) & 1u) == 0;
     }
-    float s = live ? 0.f : __builtin_inff();
-    if (qlen != 0) {                    // (uniform)
+    float s = live ? (L2 ? qn : 0.f) : __builtin_inff();      // (L2: an empty row scores R = Qn, +0 for a run of length 0)
+    if (L2 || qlen != 0) {              // (uniform)
       uint64_t rb = 0, re = 0;
       if (live) {
         rb = a.row_off[r];
@@ -389,8 +487,13 @@ __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDu
         todo &= todo - 1;
         const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
         const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
-        const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
-        if (lane == j) s = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+        if constexpr (L2) {
+          const float sc = sparse_wave_row_dot<VT, true>(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane, qn);
+          if (lane == j) s = sc;
+        } else {
+          const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
+          if (lane == j) s = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
+        }
       }
     }
     if (r < r1) out[r] = s;

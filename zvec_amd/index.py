@@ -62,6 +62,13 @@ def metric_from_name(name):
     return _METRIC_NAMES[name]
 
 
+# the metrics of a sparse index (HipFlatSparseStreamer)
+_SPARSE_METRIC_NAMES = {
+    "InnerProductSparse": METRIC_IP,         # src/core/metric/inner_product_metric.cc:329
+    "SquaredEuclideanSparse": METRIC_L2,     # src/core/metric/euclidean_metric.cc:1027-1095
+}
+
+
 class IndexError_:
     """Negative IndexError values used on this path (index_error.cc:20-71)."""
     Success = 0
@@ -643,18 +650,24 @@ class HipFlatSearcher(_FlatBase, _FlatFeatures):
 
 class HipFlatSparseStreamer:
     """stands where "FlatSparseStreamer" / "FlatSparseSearcher" are registered (flat_sparse_streamer.cc, flat_sparse_searcher.cc):
-    a flat index of sparse rows under InnerProductSparse (zvec_hip_sparse_*).  A batch of rows or queries is CSR-like: counts[n],
+    a flat index of sparse rows (zvec_hip_sparse_*) under metric "InnerProductSparse" (scores are minus the inner product) or
+    "SquaredEuclideanSparse" (scores are squared distances over the union of the two index sets; include/zvec_hip.h, "Score"),
+    readable as .metric.  A batch of rows or queries is CSR-like: counts[n],
     then the runs back to back in indices (uint32, strictly ascending inside a run) and values.  dtype "fp32" or "fp16"
     (IndexMeta::DT_FP32 / DT_FP16, inner_product_metric.cc:484-495): values go in and come out as numpy.float32 / numpy.float16,
     other float inputs are cast to that type; scores are fp32 either way."""
 
     MAX_COUNT = 4096            # PARAM_FLAT_SPARSE_MAX_DIM_SIZE (flat_sparse_utility.h:22)
 
-    def __init__(self, device=0, dtype="fp32"):
+    def __init__(self, device=0, dtype="fp32", metric="InnerProductSparse"):
+        if metric not in _SPARSE_METRIC_NAMES:
+            raise ValueError("zvec_amd: a sparse index serves %s, not %r" % (" and ".join(sorted(_SPARSE_METRIC_NAMES)), metric))
         self.device = device
+        self.metric = metric
         self.dtype, self.np_dtype = _dtype_of(dtype)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().zvec_hip_sparse_create_typed(self.dtype, device, C.byref(self._h)), "zvec_hip_sparse_create_typed")
+        _lib.check(_lib.lib().zvec_hip_sparse_create_metric(self.dtype, _SPARSE_METRIC_NAMES[metric], device, C.byref(self._h)),
+                   "zvec_hip_sparse_create_metric")
         self._keys_host = []      # for IndexFilter sweeps
 
     def __del__(self):
