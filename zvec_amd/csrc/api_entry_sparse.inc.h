@@ -4,6 +4,23 @@
 extern "C++" {
 namespace {
 
+// A handle's value width (4 = fp32, 2 = fp16) as a type: f(VT()).  With its metric (l2: SquaredEuclideanSparse, else
+// InnerProductSparse) as well: f(VT(), std::bool_constant<L2>()).
+template <typename F>
+int sparse_dispatch(uint32_t width, F &&f) {
+  return width == 2 ? f(_Float16()) : f(float());
+}
+template <typename F>
+int sparse_dispatch(uint32_t width, bool l2, F &&f) {
+  return sparse_dispatch(width, [&](auto vt) { return l2 ? f(vt, std::true_type()) : f(vt, std::false_type()); });
+}
+
+// what every scoring kernel reads (the exclude bitset and the query arrays are device pointers)
+SparseOperands sparse_operands(const SparseStore &st, const void *d_exclude, const uint32_t *d_qoff, const uint32_t *d_qidx,
+                               const void *d_qval) {
+  return {st.row_off, st.idx, st.val, static_cast<const uint32_t *>(d_exclude), d_qoff, d_qidx, d_qval};
+}
+
 template <typename VT, bool DUMP, bool L2>
 int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
   static bool attr_set[16] = {};        // (one per instantiation)
@@ -16,24 +33,24 @@ int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipSt
                              (int)LDS_LIMIT));
     attr_set[dev & 15] = true;
   }
-  if (a.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.op.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
   else hipLaunchKernelGGL((sparse_scan_kernel<VT, false, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
 }
 
-// the same by the handle's value width (4 = fp32, 2 = fp16) and metric (l2: SquaredEuclideanSparse, else InnerProductSparse)
+// the same for the handle's value type and metric
 template <bool DUMP>
-int launch_sparse_scan(uint32_t width, bool l2, const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
-  if (l2)
-    return width == 2 ? launch_sparse_scan<_Float16, DUMP, true>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP, true>(a, grid, lds, stream);
-  return width == 2 ? launch_sparse_scan<_Float16, DUMP, false>(a, grid, lds, stream) : launch_sparse_scan<float, DUMP, false>(a, grid, lds, stream);
+int launch_sparse_scan(const zvec_hip_sparse_s *h, const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
+  return sparse_dispatch(h->st.width, h->l2(), [&](auto vt, auto l2) {
+    return launch_sparse_scan<decltype(vt), DUMP, decltype(l2)::value>(a, grid, lds, stream);
+  });
 }
 
 template <typename VT, bool L2>
 int launch_sparse_rows(const SparseRowsArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
   // (indices | values of the longest run, at most 32 KiB: no launch attribute needed)
-  if (a.exclude) hipLaunchKernelGGL((sparse_rows_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.op.exclude) hipLaunchKernelGGL((sparse_rows_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
   else hipLaunchKernelGGL((sparse_rows_kernel<VT, false, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
@@ -66,6 +83,31 @@ int sparse_check_runs(const uint32_t *counts, const uint32_t *indices, uint64_t 
     o += c;
   }
   *total = o;
+  return 0;
+}
+
+// The queries of a host-pointer entry, after the entry's own pointers and (the plain entries) after count == 0 and topk == 0:
+// the batch size, the merge list of merge_k entries (0: none, the grouped entries' lists are group_args_ok's), the runs, and arrays
+// where there are pairs.  *total = the queries' pairs.  Allocates and copies nothing.
+int sparse_queries_ok(const uint32_t *q_counts, const uint32_t *q_indices, const void *q_values, uint32_t count, uint32_t merge_k,
+                      uint64_t *total) {
+  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;          // (query offsets are 32-bit: 2^19 x 4096 elements)
+  if (merge_k && (size_t)merge_k * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  ZRET(sparse_check_runs(q_counts, q_indices, count, total));
+  if (*total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  return 0;
+}
+
+// The listed positions of a by-ids entry (count > 0): the list offsets start at 0 and never descend, and there is an array where
+// there are entries.  *maxlen = the longest list, at least 1.
+int sparse_lists_ok(const uint32_t *ids, const uint32_t *offsets, uint32_t count, uint32_t *maxlen) {
+  if (!offsets || offsets[0] != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  *maxlen = 1;
+  for (uint32_t q = 0; q < count; ++q) {
+    if (offsets[q + 1] < offsets[q]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    *maxlen = std::max(*maxlen, offsets[q + 1] - offsets[q]);
+  }
+  if (offsets[count] && !ids) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   return 0;
 }
 
@@ -105,6 +147,35 @@ int sparse_upload_plan(zvec_hip_ctx_s *c, const std::vector<uint32_t> &plan, hip
   return 0;
 }
 
+// Dense scores of a batch are dumped in sub-batches of at most 1 GiB: the queries of one (`cap` at most, never 0).
+uint32_t sparse_sub_batch(uint64_t cap, uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (1ull << 30) / (n * 4))); }
+
+// sparse_scan_kernel's grid: one wave per work-group, 8 of them per CU, a chunk of rows per work-group and query block.
+// part_k != 0 (the fused route): the partial lists of `count` queries, part_k entries each, take at most 64 MiB (a wide batch with
+// long lists gets longer chunks).
+void sparse_chunking(zvec_hip_ctx_s *c, uint64_t n, uint32_t nqb, uint32_t count, uint32_t part_k, uint32_t *rpc, uint32_t *nchunks) {
+  const uint64_t want = std::max<uint64_t>(1, ((uint64_t)device_cus(c) * 8 + nqb - 1) / nqb);
+  uint64_t r = std::max<uint64_t>(1, (n + want - 1) / want);
+  while (part_k && (uint64_t)count * ((n + r - 1) / r) * part_k * 8 > (64ull << 20) && r < n) r *= 2;
+  *rpc = (uint32_t)std::min<uint64_t>(r, 0x7fffffffu);
+  *nchunks = (uint32_t)((n + *rpc - 1) / *rpc);
+}
+
+// Every score of the queries [q0, q0 + cnt) of a planned batch: dump[(q - q0) * n + position], +inf for an excluded position,
+// through sparse_scan_kernel<.., DUMP> (lane = query; it reads no k, threshold or shared bound).  plan = sparse_make_plan's for
+// `count` queries, uploaded behind op.q_off; its blocks cross neither q0 nor q0 + cnt (the plan's `sub`), so the sub-batch is the
+// blocks [b0, b1).
+int sparse_dump_scores(const zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const SparseOperands &op, const std::vector<uint32_t> &plan,
+                       uint32_t count, uint32_t max_img, uint32_t q0, uint32_t cnt, float *dump, hipStream_t s) {
+  const auto blk = plan.begin() + count + 1;
+  const uint32_t b0 = (uint32_t)(std::lower_bound(blk, plan.end(), q0) - blk);
+  const uint32_t b1 = (uint32_t)(std::lower_bound(blk, plan.end(), q0 + cnt) - blk);
+  SparseScanArgs a{};
+  a.op = op; a.blk = op.q_off + count + 1; a.blk0 = b0; a.qsub0 = q0; a.nqblocks = b1 - b0; a.n = h->st.n; a.dump = dump;
+  sparse_chunking(c, a.n, a.nqblocks, count, 0, &a.rows_per_chunk, &a.nchunks);
+  return launch_sparse_scan<true>(h, a, a.nchunks * a.nqblocks, sparse_lds_bytes(max_img, 0, h->st.width), s);
+}
+
 // The search proper.  The caller holds c->mu and h->rw (shared); q_counts (HOST) has passed sparse_check_runs; the query arrays
 // and every output are device pointers.  Enqueues only, except for a wait on the previous plan upload of the same context.
 int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
@@ -118,8 +189,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
     return 0;
   }
   const bool dump = topk > SPARSE_FUSED_MAX_K;
-  // dense scores: sub-batches of at most 1 GiB
-  const uint32_t sub = dump ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, (1ull << 30) / (st.n * 4))) : 0u;
+  const uint32_t sub = dump ? sparse_sub_batch(count, st.n) : 0u;
   std::vector<uint32_t> plan;
   uint32_t nblocks = 0, max_img = 0;
   sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);
@@ -128,49 +198,30 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   hipLaunchKernelGGL(sparse_prep_queries_kernel, dim3((count + 255) / 256), dim3(256), 0, s, count, c->gtau.as<uint32_t>());
   ZCHK(hipGetLastError());
 
-  const int cus = device_cus(c);
-  SparseScanArgs a{};
-  a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
-  a.q_off = c->sp_plan.as<uint32_t>(); a.q_idx = d_qidx; a.q_val = d_qval; a.blk = a.q_off + count + 1;
-  a.k = topk; a.threshold = threshold; a.n = st.n; a.gtau = c->gtau.as<uint32_t>();
-  const std::vector<uint32_t> blk(plan.begin() + count + 1, plan.end());
-  // one wave per work-group, 8 of them per CU: a chunk of rows per work-group and query block
-  auto chunking = [&](uint32_t nqb, uint32_t *rpc, uint32_t *nchunks) {
-    const uint64_t want = std::max<uint64_t>(1, ((uint64_t)cus * 8 + nqb - 1) / nqb);
-    uint64_t r = std::max<uint64_t>(1, (st.n + want - 1) / want);
-    // (the partial lists of a wide batch with long lists: at most 64 MiB of them)
-    while (!dump && (uint64_t)count * ((st.n + r - 1) / r) * topk * 8 > (64ull << 20) && r < st.n) r *= 2;
-    *rpc = (uint32_t)std::min<uint64_t>(r, 0x7fffffffu);
-    *nchunks = (uint32_t)((st.n + *rpc - 1) / *rpc);
-  };
+  const SparseOperands op = sparse_operands(st, d_exclude, c->sp_plan.as<uint32_t>(), d_qidx, d_qval);
   if (dump) {
     ZRET(c->part_s.ensure((size_t)sub * st.n * 4));
-    uint32_t b0 = 0;
     for (uint32_t q0 = 0; q0 < count; q0 += sub) {
       const uint32_t cnt = std::min(sub, count - q0);
-      uint32_t b1 = b0;
-      while (blk[b1] < q0 + cnt) ++b1;                // blocks [b0, b1) are the sub-batch's
-      SparseScanArgs d = a;
-      d.blk0 = b0; d.qsub0 = q0; d.nqblocks = b1 - b0; d.dump = c->part_s.as<float>();
-      chunking(d.nqblocks, &d.rows_per_chunk, &d.nchunks);
-      ZRET(launch_sparse_scan<true>(st.width, h->l2(), d, d.nchunks * d.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
+      ZRET(sparse_dump_scores(h, c, op, plan, count, max_img, q0, cnt, c->part_s.as<float>(), s));
       MergeArgs m{};
-      m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
+      m.part_s = c->part_s.as<float>(); m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
       m.keymap = st.keys; m.out_keys = d_keys + (size_t)q0 * topk; m.out_scores = d_scores + (size_t)q0 * topk;
       m.out_counts = d_counts + q0;
       hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, s, m);
       ZCHK(hipGetLastError());
-      b0 = b1;
     }
     return 0;
   }
+  SparseScanArgs a{};
+  a.op = op; a.blk = op.q_off + count + 1; a.k = topk; a.threshold = threshold; a.n = st.n; a.gtau = c->gtau.as<uint32_t>();
   a.nqblocks = nblocks;
-  chunking(nblocks, &a.rows_per_chunk, &a.nchunks);
+  sparse_chunking(c, st.n, nblocks, count, topk, &a.rows_per_chunk, &a.nchunks);
   const uint64_t slots = (uint64_t)count * a.nchunks;
   ZRET(c->part_s.ensure(slots * topk * sizeof(float)));
   ZRET(c->part_i.ensure(slots * topk * sizeof(uint32_t)));
   a.part_s = c->part_s.as<float>(); a.part_i = c->part_i.as<uint32_t>();
-  ZRET(launch_sparse_scan<false>(st.width, h->l2(), a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
+  ZRET(launch_sparse_scan<false>(h, a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
   MergeArgs m{};
   m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = a.nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
   m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
@@ -222,15 +273,14 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   }
   if (total) ZCHK(hipMemcpyAsync(c->plan.p, ids, (size_t)total * 4, hipMemcpyHostToDevice, s));
   SparseRowsArgs a{};
-  a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
-  a.q_off = c->sp_plan.as<uint32_t>(); a.q_idx = d_qidx; a.q_val = d_qval;
-  a.ids = c->plan.as<uint32_t>(); a.list_off = a.q_off + count + 1; a.item_q = a.list_off + count + 1; a.item_e0 = a.item_q + items;
+  a.op = sparse_operands(st, d_exclude, c->sp_plan.as<uint32_t>(), d_qidx, d_qval);
+  a.ids = c->plan.as<uint32_t>(); a.list_off = a.op.q_off + count + 1; a.item_q = a.list_off + count + 1; a.item_e0 = a.item_q + items;
   a.slice = slice; a.n = st.n; a.scores = c->part_s.as<float>(); a.row_stride = row_stride; a.pos_out = c->part_i.as<uint32_t>();
   *d_list_off = a.list_off;
   if (items == 0) return 0;
-  const size_t lds = (size_t)max_run * 4 + (((size_t)max_run * st.width + 3) & ~(size_t)3);
-  if (h->l2()) return st.width == 2 ? launch_sparse_rows<_Float16, true>(a, items, lds, s) : launch_sparse_rows<float, true>(a, items, lds, s);
-  return st.width == 2 ? launch_sparse_rows<_Float16, false>(a, items, lds, s) : launch_sparse_rows<float, false>(a, items, lds, s);
+  return sparse_dispatch(st.width, h->l2(), [&](auto vt, auto l2) {
+    return launch_sparse_rows<decltype(vt), decltype(l2)::value>(a, items, sparse_run_lds_bytes(max_run, st.width), s);
+  });
 }
 
 }  // namespace
@@ -338,13 +388,13 @@ int zvec_hip_sparse_get_vector(zvec_hip_sparse_t h, uint64_t pos, uint32_t *coun
   ZCHK(hipSetDevice(h->device));
   const size_t words = 4 + 2 * (size_t)SPARSE_MAX_COUNT;
   ZRET(c->io_q.ensure(words * 4));
-  if (h->st.width == 2)
-    hipLaunchKernelGGL(sparse_unpack_kernel<_Float16>, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx,
-                       static_cast<const _Float16 *>(h->st.val), pos, c->io_q.as<uint32_t>());
-  else
-    hipLaunchKernelGGL(sparse_unpack_kernel<float>, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx,
-                       static_cast<const float *>(h->st.val), pos, c->io_q.as<uint32_t>());
-  ZCHK(hipGetLastError());
+  ZRET(sparse_dispatch(h->st.width, [&](auto vt) -> int {
+    using VT = decltype(vt);
+    hipLaunchKernelGGL(sparse_unpack_kernel<VT>, dim3(1), dim3(256), 0, c->own, h->st.row_off, h->st.idx, static_cast<const VT *>(h->st.val),
+                       pos, c->io_q.as<uint32_t>());
+    ZCHK(hipGetLastError());
+    return 0;
+  }));
   std::vector<uint32_t> host(words);
   ZCHK(hipMemcpyAsync(host.data(), c->io_q.p, words * 4, hipMemcpyDeviceToHost, c->own));
   ZCHK(hipStreamSynchronize(c->own));
@@ -378,11 +428,8 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
   if (!h || !out_keys || !out_scores || !out_counts || (count && !q_counts)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
   uint64_t total = 0;
-  ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
-  if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  ZRET(sparse_queries_ok(q_counts, q_indices, q_values, count, topk, &total));
   size_t te = 0;
   std::vector<uint32_t> blob;
   sparse_stage_blob(h->st.width, total, q_indices, q_values, blob, &te);      // (the width never changes after create)
@@ -412,15 +459,10 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
   if (!h || !out_keys || !out_scores || !out_counts || (count && (!q_counts || !offsets))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (offsets[0] != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t q = 0; q < count; ++q)
-    if (offsets[q + 1] < offsets[q]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (offsets[count] && !ids) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   uint64_t total = 0;
-  ZRET(sparse_check_runs(q_counts, q_indices, count, &total));
-  if (total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  uint32_t maxlen = 0;
+  ZRET(sparse_queries_ok(q_counts, q_indices, q_values, count, topk, &total));
+  ZRET(sparse_lists_ok(ids, offsets, count, &maxlen));       // (the longest list is of no use here)
   size_t te = 0;
   std::vector<uint32_t> blob;
   sparse_stage_blob(h->st.width, total, q_indices, q_values, blob, &te);      // (the width never changes after create)

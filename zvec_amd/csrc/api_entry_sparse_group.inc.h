@@ -20,13 +20,13 @@ namespace {
 template <typename VT, bool L2>
 int launch_sparse_rows_dump(const SparseRowsDumpArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
   // (indices | values of one run: at most 32 KiB, no launch attribute needed)
-  if (a.exclude) hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
+  if (a.op.exclude) hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, true, L2>), dim3(grid), dim3(64), lds, stream, a);
   else hipLaunchKernelGGL((sparse_rows_dump_kernel<VT, false, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
   return 0;
 }
 
-// what the two entry points check alike, in the order of zvec_hip_sparse_search; *total = the queries' pairs
+// what the two entry points check alike before count == 0 returns 0; *total = the queries' pairs
 int sparse_group_args_ok(zvec_hip_sparse_t h, const uint32_t *q_counts, const uint32_t *q_indices, const void *q_values, uint32_t count,
                          const uint32_t *group_of_position, uint32_t ngroups, uint32_t gnum, uint32_t gk, const uint32_t *out_groups,
                          const uint32_t *out_ngroups, const uint64_t *out_keys, const float *out_scores, const uint32_t *out_counts,
@@ -34,10 +34,7 @@ int sparse_group_args_ok(zvec_hip_sparse_t h, const uint32_t *q_counts, const ui
   if (!h || !group_of_position || !out_groups || !out_ngroups || !out_keys || !out_scores || !out_counts || (count && !q_counts))
     return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   ZRET(group_args_ok(ngroups, gnum, gk));
-  if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;          // (query offsets are 32-bit: 2^19 x 4096 elements)
-  ZRET(sparse_check_runs(q_counts, q_indices, count, total));
-  if (*total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  return 0;
+  return sparse_queries_ok(q_counts, q_indices, q_values, count, 0, total);
 }
 
 // an empty index: no groups (and nothing stale in the caller's arrays)
@@ -83,10 +80,8 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
   ZCHK(hipMemcpyAsync(c->grp_of.p, group_of_position, (size_t)st.n * 4, hipMemcpyHostToDevice, s));
   ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, st.n, count, 1, s));
   const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
-  const void *dqv = dq + te;
-  const uint32_t *d_ex = exclude_bitset ? c->io_ex.as<uint32_t>() : nullptr;
   // query slices: the score matrix stays <= 1 GiB, and a slice is one grid dimension of group_best_kernel (<= 65535)
-  const uint32_t sub = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(count, 32768), (1ull << 30) / (st.n * 4)));
+  const uint32_t sub = sparse_sub_batch(std::min<uint64_t>(count, 32768), st.n);
   std::vector<uint32_t> plan;
   uint32_t nblocks = 0, max_img = 0, max_run = 0;
   sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);          // q_off[count + 1] | blk[blocks + 1]
@@ -94,43 +89,25 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
   ZRET(sparse_upload_plan(c, plan, s));
   ZRET(c->part_s.ensure((size_t)sub * st.n * 4));
   float *dump = c->part_s.as<float>();
-  const uint32_t *d_qoff = c->sp_plan.as<uint32_t>();
+  const SparseOperands op = sparse_operands(st, exclude_bitset ? c->io_ex.p : nullptr, c->sp_plan.as<uint32_t>(), dq, dq + te);
   const uint32_t wave_rows = (uint32_t)ropts().sparse_group_rows.load(std::memory_order_relaxed);
-  const uint64_t cus = (uint64_t)device_cus(c);
-  uint32_t b0 = 0;
   for (uint32_t q0 = 0; q0 < count; q0 += sub) {
     const uint32_t cnt = std::min(sub, count - q0);
-    uint32_t b1 = b0;
-    while (plan[(size_t)count + 1 + b1] < q0 + cnt) ++b1;                    // query blocks [b0, b1) are the sub-batch's
     if (cnt <= wave_rows) {
       // a wave per stored row: 16 one-wave work-groups per CU, a chunk is whole 64-row stores
       SparseRowsDumpArgs a{};
-      a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = d_ex; a.q_off = d_qoff; a.q_idx = dq; a.q_val = dqv;
-      a.qsub0 = q0; a.nqsub = cnt; a.n = st.n; a.dump = dump;
-      const uint64_t want = std::max<uint64_t>(1, (cus * 16 + cnt - 1) / cnt);
+      a.op = op; a.qsub0 = q0; a.nqsub = cnt; a.n = st.n; a.dump = dump;
+      const uint64_t want = std::max<uint64_t>(1, ((uint64_t)device_cus(c) * 16 + cnt - 1) / cnt);
       a.rows_per_chunk = (uint32_t)std::min<uint64_t>((((st.n + want - 1) / want + 63) / 64) * 64, 0x7fffffc0u);
       const uint32_t nchunks = (uint32_t)((st.n + a.rows_per_chunk - 1) / a.rows_per_chunk);
-      const size_t lds = (size_t)max_run * 4 + (((size_t)max_run * st.width + 3) & ~(size_t)3);
-      if (h->l2()) {
-        if (st.width == 2) ZRET((launch_sparse_rows_dump<_Float16, true>(a, nchunks * cnt, lds, s)));
-        else ZRET((launch_sparse_rows_dump<float, true>(a, nchunks * cnt, lds, s)));
-      } else {
-        if (st.width == 2) ZRET((launch_sparse_rows_dump<_Float16, false>(a, nchunks * cnt, lds, s)));
-        else ZRET((launch_sparse_rows_dump<float, false>(a, nchunks * cnt, lds, s)));
-      }
+      ZRET(sparse_dispatch(st.width, h->l2(), [&](auto vt, auto l2) {
+        return launch_sparse_rows_dump<decltype(vt), decltype(l2)::value>(a, nchunks * cnt, sparse_run_lds_bytes(max_run, st.width), s);
+      }));
     } else {
-      SparseScanArgs a{};
-      a.row_off = st.row_off; a.idx = st.idx; a.val = st.val; a.exclude = d_ex; a.q_off = d_qoff; a.q_idx = dq; a.q_val = dqv;
-      a.blk = d_qoff + count + 1; a.blk0 = b0; a.qsub0 = q0; a.nqblocks = b1 - b0; a.n = st.n; a.dump = dump;
-      // one wave per work-group, 8 of them per CU: a chunk of rows per work-group and query block (as sparse_search_locked)
-      const uint64_t want = std::max<uint64_t>(1, (cus * 8 + a.nqblocks - 1) / a.nqblocks);
-      a.rows_per_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (st.n + want - 1) / want), 0x7fffffffu);
-      a.nchunks = (uint32_t)((st.n + a.rows_per_chunk - 1) / a.rows_per_chunk);
-      ZRET(launch_sparse_scan<true>(st.width, h->l2(), a, a.nchunks * a.nqblocks, sparse_lds_bytes(max_img, 0, st.width), s));
+      ZRET(sparse_dump_scores(h, c, op, plan, count, max_img, q0, cnt, dump, s));
     }
     ZRET(group_select(c, st.keys, nullptr, dump, nullptr, (uint32_t)st.n, (uint32_t)st.n, q0, cnt, c->grp_of.as<uint32_t>(), ngroups,
                       group_num, group_topk, threshold, o, s));
-    b0 = b1;
   }
   return group_copy_out(c, o, count, group_num, group_topk, out_groups, out_ngroups, out_keys, out_scores, out_counts, s);
 }
@@ -144,13 +121,8 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
   ZRET(sparse_group_args_ok(h, q_counts, q_indices, q_values, count, group_of_position, ngroups, group_num, group_topk, out_groups,
                             out_ngroups, out_keys, out_scores, out_counts, &total));
   if (count == 0) return 0;
-  if (!offsets || offsets[0] != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  uint32_t maxlen = 1;
-  for (uint32_t q = 0; q < count; ++q) {
-    if (offsets[q + 1] < offsets[q]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-    maxlen = std::max(maxlen, offsets[q + 1] - offsets[q]);
-  }
-  if (offsets[count] && !ids) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  uint32_t maxlen = 0;
+  ZRET(sparse_lists_ok(ids, offsets, count, &maxlen));
   if ((uint64_t)count * maxlen > 0xffffffffull) return ZVEC_HIP_ERR_OUT_OF_RANGE;      // (cells of the candidate matrix)
   size_t te = 0;
   std::vector<uint32_t> blob;

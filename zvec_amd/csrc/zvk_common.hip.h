@@ -89,6 +89,9 @@ __device__ __forceinline__ float bcast_f(float v, int l) {
 __device__ __forceinline__ uint32_t bcast_u(uint32_t v, int l) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
+__device__ __forceinline__ uint64_t bcast_u64(uint64_t v, int l) {
+  return ((uint64_t)bcast_u((uint32_t)(v >> 32), l) << 32) | bcast_u((uint32_t)v, l);
+}
 
 // order-preserving float <-> uint32 map (so that atomicMin on the key is a float min, negative IP scores included)
 __device__ __forceinline__ uint32_t fkey(float f) {

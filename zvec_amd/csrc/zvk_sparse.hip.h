@@ -26,16 +26,18 @@
 // STRICT against min(own k-th score once the list is full, the bound the work-groups of the same query share) — zero scores tie
 // massively and a tie at the k-th place is never needed — and the threshold is a separate non-strict test.
 //
-// Metric (template parameter L2 of the three scoring kernels and the two helpers; false = InnerProductSparse, the code above, with
-// no run-time branch on the metric anywhere).  SquaredEuclideanSparse (SquaredEuclideanSparseMetric, src/core/metric/
+// Metric (template parameter L2 of the three scoring kernels and of the helpers they share: sparse_match_step, sparse_score,
+// sparse_lane_dot, sparse_wave_row_score, sparse_stage_run, sparse_wave_score_rows; false = InnerProductSparse, the code above,
+// with no run-time branch on the metric anywhere).  SquaredEuclideanSparse (SquaredEuclideanSparseMetric, src/core/metric/
 // euclidean_metric.cc:1027-1095, which hands out SquaredEuclideanSparseDistanceMatrix<float>::Compute, src/ailego/math/
 // euclidean_distance_matrix.h:2480-2638, for DT_FP16 as well as DT_FP32, :1070-1072) runs over the UNION of the two index sets: a
 // shared index adds (b - q)^2, an index of the row alone b^2, an index of the query alone q^2.  Here the score is s = A + R, all
 // fp32, halves widened first:
 //   A   over the stored elements of the row, each one fmaf(x, x, A) with x = b - q (rounded once) where the index is in the query's
 //       run and x = b where it is not; the same walk counts the hits and sums Mq = the q^2 of the matched query elements
-//   R   the query mass that met nothing: exactly +0 if hits == qlen (the empty query included), else max(0, Qn - Mq), Qn = the
-//       sum of q^2 over the whole run, formed ONCE per work item from the LDS image (never per row)
+//       (sparse_match_step)
+//   R   the query mass that met nothing: exactly +0 if hits == qlen (the empty query included), else max(0, Qn - Mq)
+//       (sparse_score), Qn = the sum of q^2 over the whole run, formed ONCE per work item from the LDS image (never per row)
 // so identical runs, a pair of empty runs included, score exactly +0.0 (the norm expansion |b|^2 + |q|^2 - 2 b.q cancels exactly
 // there and cannot), every term is >= 0 and a score is never -0.  Nothing is skipped for an empty query or a pair without a shared
 // index: both are ordinary, non-zero candidates.
@@ -49,7 +51,8 @@ constexpr uint32_t SPARSE_QB = 64;             // queries per query block at mos
 constexpr uint32_t SPARSE_IMG_ELEMS = 4096;    // elements of a query block's LDS image at most (32 KiB of fp32, 24 KiB of fp16: one longest query fits)
 constexpr uint32_t SPARSE_FUSED_MAX_K = 128;   // lane-owned lists: 64 x k x 8 bytes next to the image; longer lists take the dump route
 
-struct SparseScanArgs {
+// What every scoring kernel reads: the stored rows, the exclude bits and the queries.  The first member of each argument struct.
+struct SparseOperands {
   const uint64_t *row_off;    // [n + 1]
   const uint32_t *idx;        // [elements]
   const void *val;            // [elements] of the kernel's VT
@@ -57,6 +60,10 @@ struct SparseScanArgs {
   const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
   const uint32_t *q_idx;
   const void *q_val;          // VT as well
+};
+
+struct SparseScanArgs {
+  SparseOperands op;
   const uint32_t *blk;        // [blocks + 1] first query of every query block
   uint32_t blk0;              // first query block of this launch
   uint32_t qsub0;             // DUMP: the query whose scores are row 0 of `dump`
@@ -76,6 +83,59 @@ struct SparseScanArgs {
 __host__ __device__ inline size_t sparse_lds_bytes(uint32_t img_elems, uint32_t k_lists, uint32_t width) {
   return ((size_t)2 * SPARSE_QB * k_lists + img_elems) * 4 + (((size_t)img_elems * width + 3) & ~(size_t)3) + 16;
 }
+// the same for ONE run and no lists (sparse_stage_run): indices | values
+__host__ __device__ inline size_t sparse_run_lds_bytes(uint32_t run_elems, uint32_t width) {
+  return (size_t)run_elems * 4 + (((size_t)run_elems * width + 3) & ~(size_t)3);
+}
+
+// One halving of the lower bound of t[u] in a run of the LDS image qi, U independent chains of dependent LDS reads.  n[u] comes in
+// as the run's length (0: no read at all) and base[u] as its start; the answer stays inside [base[u], base[u] + n[u]], and after
+// as many halvings as take the longest run down to one element (wave-uniform) n[u] is 1 or 0.
+template <int U>
+__device__ __forceinline__ void sparse_halve(const uint32_t *qi, const uint32_t (&t)[U], uint32_t (&base)[U], uint32_t (&n)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (n[u] > 1) {
+      const uint32_t half = n[u] >> 1;
+      if (qi[base[u] + half - 1] < t[u]) base[u] += half;
+      n[u] -= half;
+    }
+  }
+}
+
+// One stored element (index t, value v) once the halvings have left its lower bound in the run at base (n = 1) or the run is
+// empty (n = 0): one equality probe, and
+//   not L2  on a hit one fmaf of the value product into acc; mq and hits are left alone
+//   L2      every element adds a square to acc, (b - q)^2 on a hit and b^2 otherwise, a run of length 0 included (v = 0 from a
+//           lane or an element beyond the row adds +0); a hit adds its q^2 to mq and 1 to hits
+template <typename VT, bool L2>
+__device__ __forceinline__ void sparse_match_step(const uint32_t *qi, const VT *qv, uint32_t base, uint32_t n, uint32_t t, float v,
+                                                  float &acc, float &mq, uint32_t &hits) {
+  if constexpr (L2) {
+    float x = v;
+    if (n != 0) {
+      if (qi[base] == t) {
+        const float qx = (float)qv[base];
+        x = v - qx;
+        mq = __builtin_fmaf(qx, qx, mq);
+        ++hits;
+      }
+    }
+    acc = __builtin_fmaf(x, x, acc);
+  } else {
+    if (n != 0) {
+      if (qi[base] == t) acc = __builtin_fmaf(v, (float)qv[base], acc);
+    }
+  }
+}
+
+// A row's sums -> its score, smaller is better.  Not L2: MINUS the inner product; no shared index: exactly +0.  L2: A + R, >= +0
+// and never -0.
+template <bool L2>
+__device__ __forceinline__ float sparse_score(float acc, float mq, uint32_t hits, uint32_t qlen, float qn) {
+  if constexpr (L2) return acc + (hits == qlen ? 0.f : fmaxf(0.f, qn - mq));
+  else return 0.f - acc;
+}
 
 // One wave per work-group; item = (chunk of rows, query block).  DUMP: every score goes to the [query][position] matrix and nothing
 // is selected (large k, selected by merge_kernel).
@@ -83,25 +143,26 @@ template <typename VT, bool EXCL, bool DUMP, bool L2 = false>
 __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a) {
   extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
-  const VT *val = static_cast<const VT *>(a.val), *q_val = static_cast<const VT *>(a.q_val);
+  const SparseOperands &o = a.op;
+  const VT *val = static_cast<const VT *>(o.val), *q_val = static_cast<const VT *>(o.q_val);
   const uint32_t k = a.k, kl = DUMP ? 0u : k;
   float *Ls = reinterpret_cast<float *>(zvk_smem4);                   // [k][64] lane-owned lists, ascending
   uint32_t *Li = reinterpret_cast<uint32_t *>(Ls + (size_t)SPARSE_QB * kl);
   uint32_t *qi = Li + (size_t)SPARSE_QB * kl;                         // [tot] the block's query indices, run after run
   const uint32_t chunk = blockIdx.x / a.nqblocks, qb = a.blk0 + (blockIdx.x - chunk * a.nqblocks);
   const uint32_t q0 = a.blk[qb], nqb = a.blk[qb + 1] - q0;
-  const uint32_t e0 = a.q_off[q0], tot = a.q_off[q0 + nqb] - e0;
+  const uint32_t e0 = o.q_off[q0], tot = o.q_off[q0 + nqb] - e0;
   VT *qv = reinterpret_cast<VT *>(qi + tot);                          // [tot] their values, as stored
   for (uint32_t i = lane; i < tot; i += 64) {
-    qi[i] = a.q_idx[e0 + i];
+    qi[i] = o.q_idx[e0 + i];
     qv[i] = q_val[e0 + i];
   }
   const bool mine = (uint32_t)lane < nqb;
   uint32_t qstart = 0, qlen = 0;
   if (mine) {
-    const uint32_t b = a.q_off[q0 + lane];
+    const uint32_t b = o.q_off[q0 + lane];
     qstart = b - e0;
-    qlen = a.q_off[q0 + lane + 1] - b;
+    qlen = o.q_off[q0 + lane + 1] - b;
   }
   // halvings that take the longest run of the block down to one element (wave-uniform)
   uint32_t steps = 0;
@@ -109,7 +170,7 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   // L2: Qn, the squares of the lane's own run, once per work item (a lane-owned walk of the image)
-  [[maybe_unused]] float qn = 0.f;
+  float qn = 0.f;
   if constexpr (L2) {
     for (uint32_t i = 0; i < qlen; ++i) {
       const float x = (float)qv[qstart + i];
@@ -122,23 +183,23 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
   const uint64_t r0 = (uint64_t)chunk * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
   for (uint64_t r = r0; r < r1; ++r) {
     if (EXCL) {
-      if ((a.exclude[r >> 5] >> (r & 31)) & 1u) {       // (uniform)
+      if ((o.exclude[r >> 5] >> (r & 31)) & 1u) {       // (uniform)
         if (DUMP && mine) a.dump[(size_t)(q0 + lane - a.qsub0) * a.n + r] = __builtin_inff();
         continue;
       }
     }
     uint32_t tgk = 0;
     if (!DUMP && mine) tgk = __hip_atomic_load(&a.gtau[q0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint64_t rb = a.row_off[r], re = a.row_off[r + 1];
+    const uint64_t rb = o.row_off[r], re = o.row_off[r + 1];
     float acc = 0.f;
-    [[maybe_unused]] float mq = 0.f;        // L2: the squares of the query elements this row matched, and how many
-    [[maybe_unused]] uint32_t hits = 0;
+    float mq = 0.f;                   // L2: the squares of the query elements this row matched, and how many
+    uint32_t hits = 0;
     for (uint64_t p = rb; p < re; p += 64) {
       const uint32_t m = (uint32_t)min((uint64_t)64, re - p);
       uint32_t ri = 0;
       float rv = 0.f;
       if ((uint32_t)lane < m) {
-        ri = a.idx[p + lane];
+        ri = o.idx[p + lane];
         rv = (float)val[p + lane];                        // (a half widens exactly)
       }
       for (uint32_t u0 = 0; u0 < m; u0 += 4) {
@@ -153,44 +214,12 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
           base[u] = qstart;
         }
         // lower bound of t in the lane's run [qstart, qstart + qlen): the answer stays inside [base, base + n]
-        for (uint32_t s = 0; s < steps; ++s) {
+        for (uint32_t s = 0; s < steps; ++s) sparse_halve<4>(qi, t, base, n);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (n[u] > 1) {
-              const uint32_t half = n[u] >> 1;
-              if (qi[base[u] + half - 1] < t[u]) base[u] += half;
-              n[u] -= half;
-            }
-          }
-        }
-        if constexpr (L2) {
-          // every real element adds a square, a run of length 0 included; e >= m broadcast v = 0 from a lane >= m and add +0
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            float x = v[u];
-            if (n[u] != 0) {
-              if (qi[base[u]] == t[u]) {
-                const float qx = (float)qv[base[u]];
-                x = v[u] - qx;
-                mq = __builtin_fmaf(qx, qx, mq);
-                ++hits;
-              }
-            }
-            acc = __builtin_fmaf(x, x, acc);
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (n[u] != 0) {
-              if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
-            }
-          }
-        }
+        for (int u = 0; u < 4; ++u) sparse_match_step<VT, L2>(qi, qv, base[u], n[u], t[u], v[u], acc, mq, hits);
       }
     }
-    float s;
-    if constexpr (L2) s = acc + (hits == qlen ? 0.f : fmaxf(0.f, qn - mq));      // A + R: >= +0, never -0
-    else s = 0.f - acc;               // MINUS inner product, smaller is better; no shared index: exactly +0
+    const float s = sparse_score<L2>(acc, mq, hits, qlen, qn);
     if (DUMP) {
       if (mine) a.dump[(size_t)(q0 + lane - a.qsub0) * a.n + r] = s;
       continue;
@@ -243,13 +272,7 @@ __global__ void __launch_bounds__(64) sparse_scan_kernel(const SparseScanArgs a)
 constexpr uint32_t SPARSE_ROWS_SLICE = 64;     // listed entries per work item at most (one lane each while they are classified)
 
 struct SparseRowsArgs {
-  const uint64_t *row_off;    // [n + 1]
-  const uint32_t *idx;        // [elements]
-  const void *val;            // [elements] of the kernel's VT
-  const uint32_t *exclude;    // nullable bitset over positions, set = skip
-  const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
-  const uint32_t *q_idx;
-  const void *q_val;          // VT as well
+  SparseOperands op;
   const uint32_t *ids;        // [entries] listed positions, query after query; any value (>= n: skipped)
   const uint32_t *list_off;   // [nq + 1] entries of every query
   const uint32_t *item_q;     // [items] the query of a work item
@@ -264,11 +287,11 @@ struct SparseRowsArgs {
 // halvings that take a run of qlen elements down to one: ceil(log2(qlen))
 __device__ __forceinline__ uint32_t sparse_halvings(uint32_t qlen) { return qlen > 1 ? 32u - (uint32_t)__builtin_clz(qlen - 1) : 0u; }
 
-// Stored elements [p, min(re, p + 64 U)) against the run qi / qv [qlen] in LDS (qlen > 0), lane = element: acc plus this lane's
-// products.  If the lane's index t is in the run at j, j stays inside [base, base + n) through every halving.
+// Stored elements [p, min(re, p + 64 U)) against the run in LDS, lane = element: acc plus this lane's products.  If the lane's
+// index t is in the run at j, j stays inside [base, base + n) through every halving.
 // L2: acc plus this lane's squares ((b - q)^2 on a hit, b^2 otherwise; qlen == 0 is served: no LDS read, every element adds b^2),
-// mq plus the q^2 of its hits, hits plus their number.  Not L2: mq and hits are left alone.
-template <int U, typename VT, bool L2 = false>
+// mq plus the q^2 of its hits, hits plus their number.  Not L2: qlen > 0, and mq and hits are left alone.
+template <int U, typename VT, bool L2>
 __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const VT *val, uint64_t p, uint64_t re, const uint32_t *qi,
                                                  const VT *qv, uint32_t qlen, uint32_t steps, int lane, float acc, float &mq,
                                                  uint32_t &hits) {
@@ -279,42 +302,13 @@ __device__ __forceinline__ float sparse_lane_dot(const uint32_t *idx, const VT *
     const uint64_t e = p + (uint64_t)u * 64 + (uint32_t)lane;
     const bool in = e < re;
     t[u] = in ? idx[e] : 0u;
-    v[u] = in ? (float)val[e] : 0.f;
+    v[u] = in ? (float)val[e] : 0.f;      // (a lane beyond the row holds 0)
     n[u] = in ? qlen : 0u;
     base[u] = 0;
   }
-  for (uint32_t s = 0; s < steps; ++s) {
+  for (uint32_t s = 0; s < steps; ++s) sparse_halve<U>(qi, t, base, n);
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (n[u] > 1) {
-        const uint32_t half = n[u] >> 1;
-        if (qi[base[u] + half - 1] < t[u]) base[u] += half;
-        n[u] -= half;
-      }
-    }
-  }
-  if constexpr (L2) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float x = v[u];                 // (a lane beyond the row holds 0 and adds +0)
-      if (n[u] != 0) {
-        if (qi[base[u]] == t[u]) {
-          const float qx = (float)qv[base[u]];
-          x = v[u] - qx;
-          mq = __builtin_fmaf(qx, qx, mq);
-          ++hits;
-        }
-      }
-      acc = __builtin_fmaf(x, x, acc);
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (n[u] != 0) {
-        if (qi[base[u]] == t[u]) acc = __builtin_fmaf(v[u], (float)qv[base[u]], acc);
-      }
-    }
-  }
+  for (int u = 0; u < U; ++u) sparse_match_step<VT, L2>(qi, qv, base[u], n[u], t[u], v[u], acc, mq, hits);
   return acc;
 }
 
@@ -331,54 +325,87 @@ __device__ __forceinline__ float sparse_wave_run_norm(const VT *qv, uint32_t qle
   return qn;
 }
 
-// The whole wave scores ONE stored row [rb, re) (wave-uniform) against the run in LDS: the sum of value products over shared
-// indices, the same bits in every lane (the butterfly's order is fixed).  A run of length 0 makes no LDS read and no load.
-// (sparse_rows_kernel's inner step; a narrow zvec_hip_sparse_search batch can walk its chunk of rows with it as well.)
-// L2: the row's SCORE A + R instead, the same bits in every lane: the butterfly adds up A, Mq and the hits, qn is the run's
+// The whole wave scores ONE stored row [rb, re) (wave-uniform) against the run in LDS, the same bits in every lane (lane-wise sums
+// first, then the butterfly, whose order is fixed).  Not L2: minus the sum of value products over shared indices; a run of length
+// 0 makes no LDS read and no load and scores 0.f - 0.f = +0.  L2: A + R; the butterfly adds up A, Mq and the hits, qn is the run's
 // sparse_wave_run_norm.  No shortcut for a run of length 0 (the row's squares are summed) nor for an empty row (it scores R).
-template <typename VT, bool L2 = false>
-__device__ __forceinline__ float sparse_wave_row_dot(const uint32_t *idx, const VT *val, uint64_t rb, uint64_t re, const uint32_t *qi,
-                                                     const VT *qv, uint32_t qlen, uint32_t steps, int lane, float qn = 0.f) {
-  if constexpr (!L2) {
-    if (qlen == 0) return 0.f;
-  }
+// (the inner step of sparse_rows_kernel and sparse_rows_dump_kernel; a narrow zvec_hip_sparse_search batch can walk its chunk of
+// rows with it as well.)
+template <typename VT, bool L2>
+__device__ __forceinline__ float sparse_wave_row_score(const uint32_t *idx, const VT *val, uint64_t rb, uint64_t re, const uint32_t *qi,
+                                                       const VT *qv, uint32_t qlen, uint32_t steps, int lane, float qn) {
   float acc = 0.f, mq = 0.f;
   uint32_t hits = 0;
-  uint64_t p = rb;
-  for (; p < re && re - p > 64; p += 256) acc = sparse_lane_dot<4, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
-  if (p < re) acc = sparse_lane_dot<1, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
+  if (L2 || qlen != 0) {                // (uniform)
+    uint64_t p = rb;
+    for (; p < re && re - p > 64; p += 256) acc = sparse_lane_dot<4, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
+    if (p < re) acc = sparse_lane_dot<1, VT, L2>(idx, val, p, re, qi, qv, qlen, steps, lane, acc, mq, hits);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if constexpr (L2) {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if constexpr (L2) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mq += __shfl_xor(mq, o);
-      hits += __shfl_xor(hits, o);
+      for (int o = 32; o > 0; o >>= 1) {
+        mq += __shfl_xor(mq, o);
+        hits += __shfl_xor(hits, o);
+      }
     }
-    return acc + (hits == qlen ? 0.f : fmaxf(0.f, qn - mq));      // A + R: >= +0, never -0
   }
-  return acc;
+  return sparse_score<L2>(acc, mq, hits, qlen, qn);
 }
 
-template <typename VT, bool EXCL, bool L2 = false>
-__global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a) {
+// ONE query's run in LDS (indices | values, sparse_run_lds_bytes of it), the same in every lane of the wave that staged it
+template <typename VT>
+struct SparseRun {
+  uint32_t *qi;               // [qlen] the query's indices
+  VT *qv;                     // [qlen] its values, as stored
+  uint32_t qlen;
+  uint32_t steps;             // sparse_halvings(qlen)
+  float qn;                   // L2: Qn, the sum of the run's squares (sparse_wave_run_norm); else 0
+};
+
+// The whole wave copies query q's run to LDS, once per work item.
+template <typename VT, bool L2>
+__device__ __forceinline__ SparseRun<VT> sparse_stage_run(const SparseOperands &o, uint32_t q, int lane) {
   extern __shared__ f32x4 zvk_smem4[];
-  const int lane = threadIdx.x;
-  const uint32_t q = a.item_q[blockIdx.x], e0 = a.item_e0[blockIdx.x];
-  const uint32_t e1 = min(e0 + min(a.slice, SPARSE_ROWS_SLICE), a.list_off[q + 1]);
-  const uint32_t qb = a.q_off[q], qlen = min(a.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
-  uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);             // [qlen] the query's indices
-  VT *qv = reinterpret_cast<VT *>(qi + qlen);                         // [qlen] its values, as stored
-  const VT *q_val = static_cast<const VT *>(a.q_val);
+  const uint32_t qb = o.q_off[q], qlen = min(o.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
+  uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);
+  VT *qv = reinterpret_cast<VT *>(qi + qlen);
+  const VT *q_val = static_cast<const VT *>(o.q_val);
   for (uint32_t i = lane; i < qlen; i += 64) {
-    qi[i] = a.q_idx[qb + i];
+    qi[i] = o.q_idx[qb + i];
     qv[i] = q_val[qb + i];
   }
   const uint32_t steps = sparse_halvings(qlen);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  [[maybe_unused]] float qn = 0.f;
+  float qn = 0.f;
   if constexpr (L2) qn = sparse_wave_run_norm(qv, qlen, lane);
+  return {qi, qv, qlen, steps, qn};
+}
+
+// Up to 64 rows, lane l holding the offsets [rb, re) of its own: the wave scores the rows of the lanes in `todo` one after the
+// other (wave-uniform; the offsets are broadcast).  Returns this lane's own row's score, `out` for a lane that is not in `todo`.
+template <typename VT, bool L2>
+__device__ __forceinline__ float sparse_wave_score_rows(const SparseOperands &o, uint64_t todo, uint64_t rb, uint64_t re,
+                                                        const uint32_t *qi, const VT *qv, uint32_t qlen, uint32_t steps, int lane,
+                                                        float qn, float out) {
+  while (todo) {                        // (uniform)
+    const int j = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    const float sc = sparse_wave_row_score<VT, L2>(o.idx, static_cast<const VT *>(o.val), bcast_u64(rb, j), bcast_u64(re, j), qi, qv,
+                                                   qlen, steps, lane, qn);
+    if (lane == j) out = sc;
+  }
+  return out;
+}
+
+template <typename VT, bool EXCL, bool L2 = false>
+__global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a) {
+  const int lane = threadIdx.x;
+  const SparseOperands &o = a.op;
+  const uint32_t q = a.item_q[blockIdx.x], e0 = a.item_e0[blockIdx.x];
+  const uint32_t e1 = min(e0 + min(a.slice, SPARSE_ROWS_SLICE), a.list_off[q + 1]);
+  const auto [qi, qv, qlen, steps, qn] = sparse_stage_run<VT, L2>(o, q, lane);
 
   // lane = listed entry: which entries are scored at all, and where their rows lie
   const uint32_t e = e0 + (uint32_t)lane;
@@ -388,35 +415,22 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
     const uint32_t p = a.ids[e];
     live = p < a.n;
     if (EXCL) {
-      if (live) live = ((a.exclude[p >> 5] >> (p & 31)) & 1u) == 0;
+      if (live) live = ((o.exclude[p >> 5] >> (p & 31)) & 1u) == 0;
     }
     if (live) {
-      rb = a.row_off[p];
-      re = a.row_off[(uint64_t)p + 1];
+      rb = o.row_off[p];
+      re = o.row_off[(uint64_t)p + 1];
     }
   }
   float out = __builtin_inff();
-  uint64_t todo = __ballot(live);
-  while (todo) {                      // (uniform)
-    const int j = __builtin_ctzll(todo);
-    todo &= todo - 1;
-    const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
-    const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
-    if constexpr (L2) {
-      const float s = sparse_wave_row_dot<VT, true>(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane, qn);
-      if (lane == j) out = s;
-    } else {
-      const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
-      if (lane == j) out = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
-    }
-  }
+  out = sparse_wave_score_rows<VT, L2>(o, __ballot(live), rb, re, qi, qv, qlen, steps, lane, qn, out);
   if (e < e1) {
     if (a.row_stride == 0) {
       a.scores[e] = out;
     } else {          // (uniform) the grouped search's candidate matrix: the caller has filled the padding
-      const size_t o = (size_t)q * a.row_stride + (e - a.list_off[q]);
-      a.scores[o] = out;
-      a.pos_out[o] = live ? a.ids[e] : IDX_NONE;
+      const size_t c = (size_t)q * a.row_stride + (e - a.list_off[q]);
+      a.scores[c] = out;
+      a.pos_out[c] = live ? a.ids[e] : IDX_NONE;
     }
   }
 }
@@ -424,7 +438,7 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Score dump of a NARROW batch (the grouped full scan, FlatSparseEntity::search_group, flat_sparse_entity.h:79-103, which zvec calls
 // one query at a time): sparse_scan_kernel is lane = query, so a batch of one leaves 63 of its 64 lanes idle.  Here the whole wave
-// works on ONE stored row (sparse_wave_row_dot, lane = stored element).  One wave per work-group; a work item is (query, chunk of
+// works on ONE stored row (sparse_wave_row_score, lane = stored element).  One wave per work-group; a work item is (query, chunk of
 // rows), the chunk a multiple of 64 rows.  The query's run is copied to LDS once per item (32 KiB at most).  The wave takes 64 rows
 // at a time: lane l looks at row base + l — excluded (nothing of it is fetched) or its two offsets, one coalesced load each — then
 // the rows that hold anything are scored one after the other (wave-uniform; the offsets are broadcast), lane l keeps row base + l's
@@ -432,13 +446,7 @@ __global__ void __launch_bounds__(64) sparse_rows_kernel(const SparseRowsArgs a)
 // a row or a query without elements (a run of length 0 reads no row at all).  L2: an empty row scores Qn, and a run of length 0
 // skips nothing (every row that holds anything is read and scores the sum of its squares).
 struct SparseRowsDumpArgs {
-  const uint64_t *row_off;    // [n + 1]
-  const uint32_t *idx;        // [elements]
-  const void *val;            // [elements] of the kernel's VT
-  const uint32_t *exclude;    // nullable bitset over positions, set = skip
-  const uint32_t *q_off;      // [nq + 1] element offsets of the queries in q_idx / q_val
-  const uint32_t *q_idx;
-  const void *q_val;          // VT as well
+  SparseOperands op;
   uint32_t qsub0;             // the query whose scores are row 0 of `dump`
   uint32_t nqsub;             // queries of this launch: qsub0 .. qsub0 + nqsub
   uint64_t n;                 // rows
@@ -448,23 +456,11 @@ struct SparseRowsDumpArgs {
 
 template <typename VT, bool EXCL, bool L2 = false>
 __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDumpArgs a) {
-  extern __shared__ f32x4 zvk_smem4[];
   const int lane = threadIdx.x;
+  const SparseOperands &o = a.op;
   // (the queries of one chunk are neighbours in the grid: they read the same rows)
   const uint32_t chunk = blockIdx.x / a.nqsub, qs = blockIdx.x - chunk * a.nqsub, q = a.qsub0 + qs;
-  const uint32_t qb = a.q_off[q], qlen = min(a.q_off[q + 1] - qb, SPARSE_MAX_COUNT);
-  uint32_t *qi = reinterpret_cast<uint32_t *>(zvk_smem4);             // [qlen] the query's indices
-  VT *qv = reinterpret_cast<VT *>(qi + qlen);                         // [qlen] its values, as stored
-  const VT *q_val = static_cast<const VT *>(a.q_val);
-  for (uint32_t i = lane; i < qlen; i += 64) {
-    qi[i] = a.q_idx[qb + i];
-    qv[i] = q_val[qb + i];
-  }
-  const uint32_t steps = sparse_halvings(qlen);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  [[maybe_unused]] float qn = 0.f;
-  if constexpr (L2) qn = sparse_wave_run_norm(qv, qlen, lane);
+  const auto [qi, qv, qlen, steps, qn] = sparse_stage_run<VT, L2>(o, q, lane);
 
   float *out = a.dump + (size_t)qs * a.n;
   const uint64_t r0 = (uint64_t)chunk * a.rows_per_chunk, r1 = min(a.n, r0 + a.rows_per_chunk);
@@ -472,29 +468,16 @@ __global__ void __launch_bounds__(64) sparse_rows_dump_kernel(const SparseRowsDu
     const uint64_t r = base + (uint32_t)lane;
     bool live = r < r1;
     if (EXCL) {
-      if (live) live = ((a.exclude[r >> 5] >> (r & 31)) & 1u) == 0;
+      if (live) live = ((o.exclude[r >> 5] >> (r & 31)) & 1u) == 0;
     }
     float s = live ? (L2 ? qn : 0.f) : __builtin_inff();      // (L2: an empty row scores R = Qn, +0 for a run of length 0)
     if (L2 || qlen != 0) {              // (uniform)
       uint64_t rb = 0, re = 0;
       if (live) {
-        rb = a.row_off[r];
-        re = a.row_off[r + 1];
+        rb = o.row_off[r];
+        re = o.row_off[r + 1];
       }
-      uint64_t todo = __ballot(re > rb);
-      while (todo) {                    // (uniform)
-        const int j = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const uint64_t b = ((uint64_t)bcast_u((uint32_t)(rb >> 32), j) << 32) | bcast_u((uint32_t)rb, j);
-        const uint64_t en = ((uint64_t)bcast_u((uint32_t)(re >> 32), j) << 32) | bcast_u((uint32_t)re, j);
-        if constexpr (L2) {
-          const float sc = sparse_wave_row_dot<VT, true>(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane, qn);
-          if (lane == j) s = sc;
-        } else {
-          const float sum = sparse_wave_row_dot(a.idx, static_cast<const VT *>(a.val), b, en, qi, qv, qlen, steps, lane);
-          if (lane == j) s = 0.f - sum;   // MINUS inner product, smaller is better; no shared index: exactly +0
-        }
-      }
+      s = sparse_wave_score_rows<VT, L2>(o, __ballot(re > rb), rb, re, qi, qv, qlen, steps, lane, qn, s);
     }
     if (r < r1) out[r] = s;
   }
