@@ -215,3 +215,34 @@ def test_wide_batch_filter_with_a_handful_of_kept_rows(zv, oracle, kept):
     ok, os_, _, oc = oracle.flat_search(base, q, k, O.METRIC_L2, exclude_bits=ex)
     assert np.array_equal(ctx.counts, oc) and int(oc.max(initial=0)) == min(k, kept)
     tie_tolerant_compare(ctx.keys, ctx.scores, ctx.counts, ok, os_, oc, what="gather kept=%d" % kept)
+
+
+def test_wide_batch_filter_seeds_the_gathered_scan(zv):
+    """>= 262 144 kept rows (64 x 4096) under a wide batch: flat_scan_gather scans a prefix of the kept rows first and seeds the
+    shared bounds from it, on the fp32 rows of a user-facing search.  270 000 of 300 000 rows kept (0.9: the most the gather
+    variant takes), 72 queries (> 64).  Reference: every fp64 distance (tests/util.py), the excluded positions then taken out,
+    the k best by (score, position).  Integer data: scores bit-exact, keys equal outside exact ties at the boundary."""
+    from tests.util import exact_l2
+    rng = np.random.default_rng(270)
+    n, dim, nq, k, kept = 300_000, 8, 72, 10, 270_000
+    base = rng.integers(0, 100, (n, dim)).astype(np.float32)
+    q = rng.integers(0, 100, (nq, dim)).astype(np.float32)
+    drop = np.ones(n, bool)
+    drop[rng.choice(n, kept, replace=False)] = False
+    se = zv.HipFlatSearcher(dim, "SquaredEuclidean")
+    assert se.load(base) == 0                                  # keys = positions
+    ctx = se.create_context()
+    ctx.set_topk(k)
+    ctx.set_exclude_bitset(O.pack_bits(drop))
+    assert se.search_impl(q, nq, ctx) == 0
+    ok = np.zeros((nq, k), np.uint64)
+    os_ = np.zeros((nq, k), np.float32)
+    for q0 in range(0, nq, 8):
+        d = exact_l2(base, q[q0:q0 + 8])
+        d[:, drop] = np.inf
+        top = np.argsort(d, axis=1, kind="stable")[:, :k]
+        ok[q0:q0 + 8] = top
+        os_[q0:q0 + 8] = np.take_along_axis(d, top, 1)
+    oc = np.full(nq, k, np.uint32)
+    tie_tolerant_compare(ctx.keys, ctx.scores, ctx.counts, ok, os_, oc, what="seeded gather")
+    assert not drop[ctx.keys.astype(np.int64)].any()

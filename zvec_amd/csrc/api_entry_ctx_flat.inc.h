@@ -674,7 +674,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   if (!h || !queries || !ids || !offsets || !out_keys || !out_scores || !out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
@@ -707,23 +707,9 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   const uint64_t pairs = (uint64_t)count * maxlen;
   ZRET(c->part_s.ensure(pairs * 4));
   ZRET(c->part_i.ensure(pairs * 4));
-  if (st.bin)
-    hipLaunchKernelGGL(hamming_pkeys_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(st.base),
-                       c->qpad.as<uint32_t>(), st.bin_chunks(), d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  else if (st.f16)
-    hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, s, st.base, c->qpad.as<float>(),
-                       st.dpad, st.metric, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  else
-    hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, s, st.base, c->qpad.as<float>(),
-                       st.dpad, st.metric, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  ZCHK(hipGetLastError());
-  MergeArgs m{};
-  m.part_s = c->part_s.as<float>(); m.part_i = c->part_i.as<uint32_t>(); m.part_keys = nullptr; m.slot_begin = nullptr;
-  m.slots_per_q = 1; m.slot_stride = 1; m.part_counts = nullptr; m.k = topk; m.slot_len = maxlen; m.threshold = threshold;
-  m.keymap = st.keys; m.out_keys = c->io_keys.as<uint64_t>(); m.out_scores = c->io_scores.as<float>(); m.out_idx = nullptr;
-  m.out_counts = c->io_counts.as<uint32_t>();
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, s, m);
-  ZCHK(hipGetLastError());
+  ZRET(launch_pkeys_score(st, c->qpad.p, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>(), s));
+  const SearchOut out{c->io_keys.as<uint64_t>(), c->io_scores.as<float>(), nullptr, c->io_counts.as<uint32_t>()};
+  ZRET(launch_merge(merge_stream(c->part_s.as<float>(), c->part_i.as<uint32_t>(), 1, maxlen, false, topk, threshold, st.keys, out), count, 64, s));
   return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, s);
 }
 
@@ -755,16 +741,7 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   ZCHK(hipMemcpyAsync(d_off, offs, sizeof(offs), hipMemcpyHostToDevice, s));
   ZRET(c->part_s.ensure((size_t)n * 4));
   ZRET(c->part_i.ensure((size_t)n * 4));
-  if (st.bin)
-    hipLaunchKernelGGL(hamming_pkeys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(st.base),
-                       c->qpad.as<uint32_t>(), st.bin_chunks(), d_pos, d_off, 1u, n, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  else if (st.f16)
-    hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(1, n)), dim3(256), 0, s, st.base, c->qpad.as<float>(), st.dpad,
-                       st.metric, d_pos, d_off, 1u, n, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  else
-    hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(1, n)), dim3(256), 0, s, st.base, c->qpad.as<float>(), st.dpad,
-                       st.metric, d_pos, d_off, 1u, n, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  ZCHK(hipGetLastError());
+  ZRET(launch_pkeys_score(st, c->qpad.p, d_pos, d_off, 1, n, c->part_s.as<float>(), c->part_i.as<uint32_t>(), s));
   ZCHK(hipMemcpyAsync(out_scores, c->part_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   ZCHK(hipStreamSynchronize(s));
   return 0;

@@ -38,11 +38,9 @@ int group_select(zvec_hip_ctx_s *c, const uint64_t *keys, const StoreView *refin
   hipLaunchKernelGGL(group_best_kernel, dim3(splits, cnt), dim3(256), 0, s, cs, ci, stride, len, d_group_of, ngroups, best);
   const uint64_t nb = (uint64_t)cnt * ngroups;
   hipLaunchKernelGGL(group_keys_to_scores_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, best, nb);
-  MergeArgs m{};
-  m.part_s = reinterpret_cast<const float *>(best); m.slots_per_q = 1; m.slot_stride = 1; m.k = gnum; m.slot_len = ngroups;
-  m.threshold = FLT_MAX;                                 // groups are ranked before the radius applies (topk_to_group_result)
-  m.out_keys = tmpk; m.out_scores = tmps; m.out_idx = sel; m.out_counts = nsel;
-  hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)gnum * 12 + 16, s, m);
+  // (FLT_MAX: groups are ranked before the radius applies, topk_to_group_result)
+  ZRET(launch_merge(merge_dense_rows(reinterpret_cast<const float *>(best), ngroups, gnum, FLT_MAX, nullptr, SearchOut{tmpk, tmps, sel, nsel}),
+                    cnt, 64, s));
   const bool l2 = refine && refine->metric == ZVEC_HIP_METRIC_L2;
   // one pass per query when the per-wave lists of all its slots fit the LDS (4 waves, else 1), otherwise a wave per slot
   const size_t lds1 = ((size_t)gnum * gk * 8 + (size_t)gnum * 8 + 16);
@@ -87,7 +85,7 @@ int group_select(zvec_hip_ctx_s *c, const uint64_t *keys, const StoreView *refin
 
 int group_args_ok(uint32_t ngroups, uint32_t gnum, uint32_t gk) {
   if (ngroups == 0 || gnum == 0 || gk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if ((size_t)gnum * 12 + 16 > 60 * 1024 || (size_t)gk * 16 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (!merge_fits(gnum) || (size_t)gk * 16 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
   return 0;
 }
 
@@ -148,10 +146,9 @@ int zvec_hip_flat_search_grouped(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   ZRET(host_search_wrap_begin(c, queries, (size_t)count * st.row_bytes(), exclude_bitset, st.n, count, 1, s));
   ZRET(prep_queries(c, st, c->io_qp, count, threshold, s));
   const uint64_t ntiles = (st.n + TILE_N - 1) / TILE_N;
-  const double row_bytes = (double)ntiles * TILE_N * 4.0;
   // query slices: the score matrix stays <= 1 GiB, and a slice is one grid dimension of group_best_kernel (<= 65535)
-  const uint32_t sub = (uint32_t)std::max<double>(1.0, std::min<double>(std::min<double>((double)count, 32768.0), std::floor(1073741824.0 / row_bytes)));
-  ZRET(c->part_s.ensure((size_t)(row_bytes * sub)));
+  const uint32_t sub = dense_sub_batch(std::min<uint32_t>(count, 32768), ntiles * TILE_N);
+  ZRET(c->part_s.ensure((size_t)ntiles * TILE_N * 4 * sub));
   for (uint32_t q0 = 0; q0 < count; q0 += sub) {
     const uint32_t cnt = std::min(sub, count - q0);
     float *dump = nullptr;
@@ -211,13 +208,7 @@ int zvec_hip_flat_search_grouped_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, c
   const uint64_t pairs = (uint64_t)count * maxlen;
   ZRET(c->part_s.ensure(pairs * 4));
   ZRET(c->part_i.ensure(pairs * 4));
-  if (st.f16)
-    hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, s, st.base, c->qpad.as<float>(),
-                       st.dpad, st.metric, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  else
-    hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, s, st.base, c->qpad.as<float>(),
-                       st.dpad, st.metric, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>());
-  ZCHK(hipGetLastError());
+  ZRET(launch_pkeys_score(st, c->qpad.p, d_pos, d_off, count, maxlen, c->part_s.as<float>(), c->part_i.as<uint32_t>(), s));
   ZCHK(hipStreamSynchronize(s));                         // `clean` goes away
   // the pair scores are already direct distances: no refinement
   for (uint32_t q0 = 0; q0 < count; q0 += 32768)       // (a slice is one grid dimension of group_best_kernel)

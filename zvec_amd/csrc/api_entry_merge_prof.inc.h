@@ -9,7 +9,7 @@ int zvec_hip_merge_topk_dev(zvec_hip_ctx_t ctx, const uint64_t *d_keys, const fl
     return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0 || nparts == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if ((size_t)topk * 12 + 16 > 64 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (merge_lds_bytes(topk) > SHARD_MERGE_LDS_MAX) return ZVEC_HIP_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> g(ctx->mu);
   ZCHK(hipSetDevice(ctx->device));
   hipStream_t s = pick_stream(ctx, stream);
@@ -17,9 +17,7 @@ int zvec_hip_merge_topk_dev(zvec_hip_ctx_t ctx, const uint64_t *d_keys, const fl
   m.part_s = d_scores; m.part_i = nullptr; m.part_keys = d_keys; m.slot_begin = nullptr; m.slots_per_q = nparts;
   m.slot_stride = count; m.part_counts = d_counts; m.k = topk; m.slot_len = topk; m.threshold = FLT_MAX; m.keymap = nullptr;
   m.out_keys = d_out_keys; m.out_scores = d_out_scores; m.out_idx = nullptr; m.out_counts = d_out_counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, s, m);
-  ZCHK(hipGetLastError());
-  return 0;
+  return launch_merge(m, count, 64, s);
 }
 
 uint64_t zvec_hip_packed_bytes(uint32_t count, uint32_t topk) {
@@ -33,7 +31,7 @@ int zvec_hip_merge_topk_packed_dev(zvec_hip_ctx_t ctx, const void *d_packed, uin
   if (!ctx || !d_packed || !d_out_keys || !d_out_scores || !d_out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0 || nparts == 0 || part_stride < zvec_hip_packed_bytes(count, topk) || (part_stride & 7)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if ((size_t)topk * 12 + 16 > 64 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (merge_lds_bytes(topk) > SHARD_MERGE_LDS_MAX) return ZVEC_HIP_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> g(ctx->mu);
   ZCHK(hipSetDevice(ctx->device));
   hipStream_t s = pick_stream(ctx, stream);
@@ -45,9 +43,7 @@ int zvec_hip_merge_topk_packed_dev(zvec_hip_ctx_t ctx, const void *d_packed, uin
   m.part_i = nullptr; m.slot_begin = nullptr; m.slots_per_q = nparts; m.slot_stride = count; m.packed_stride = part_stride;
   m.k = topk; m.slot_len = topk; m.threshold = FLT_MAX; m.keymap = nullptr;
   m.out_keys = d_out_keys; m.out_scores = d_out_scores; m.out_idx = nullptr; m.out_counts = d_out_counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, s, m);
-  ZCHK(hipGetLastError());
-  return 0;
+  return launch_merge(m, count, 64, s);
 }
 
 int zvec_hip_merge_topk(zvec_hip_ctx_t ctx, const uint64_t *keys, const float *scores, const uint32_t *counts,

@@ -363,7 +363,7 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
   if (!h || !queries || !out_keys || !out_scores || !out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if ((size_t)topk * 12 + 16 > 64 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (merge_lds_bytes(topk) > SHARD_MERGE_LDS_MAX) return ZVEC_HIP_ERR_UNSUPPORTED;
   const bool is_ivf = h->kind == ZVEC_HIP_SHARDS_IVF;
   std::lock_guard<std::mutex> lk(h->mu);
   if (is_ivf)

@@ -23,16 +23,8 @@ SparseOperands sparse_operands(const SparseStore &st, const void *d_exclude, con
 
 template <typename VT, bool DUMP, bool L2>
 int launch_sparse_scan(const SparseScanArgs &a, uint32_t grid, size_t lds, hipStream_t stream) {
-  static bool attr_set[16] = {};        // (one per instantiation)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, false, DUMP, L2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)LDS_LIMIT));
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_scan_kernel<VT, true, DUMP, L2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)LDS_LIMIT));
-    attr_set[dev & 15] = true;
-  }
+  ZRET((raise_dynamic_lds<&sparse_scan_kernel<VT, false, DUMP, L2>>(LDS_LIMIT)));
+  ZRET((raise_dynamic_lds<&sparse_scan_kernel<VT, true, DUMP, L2>>(LDS_LIMIT)));
   if (a.op.exclude) hipLaunchKernelGGL((sparse_scan_kernel<VT, true, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
   else hipLaunchKernelGGL((sparse_scan_kernel<VT, false, DUMP, L2>), dim3(grid), dim3(64), lds, stream, a);
   ZCHK(hipGetLastError());
@@ -92,7 +84,7 @@ int sparse_check_runs(const uint32_t *counts, const uint32_t *indices, uint64_t 
 int sparse_queries_ok(const uint32_t *q_counts, const uint32_t *q_indices, const void *q_values, uint32_t count, uint32_t merge_k,
                       uint64_t *total) {
   if (count > (1u << 19)) return ZVEC_HIP_ERR_OUT_OF_RANGE;          // (query offsets are 32-bit: 2^19 x 4096 elements)
-  if (merge_k && (size_t)merge_k * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (merge_k && !merge_fits(merge_k)) return ZVEC_HIP_ERR_UNSUPPORTED;
   ZRET(sparse_check_runs(q_counts, q_indices, count, total));
   if (*total && (!q_indices || !q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   return 0;
@@ -147,9 +139,6 @@ int sparse_upload_plan(zvec_hip_ctx_s *c, const std::vector<uint32_t> &plan, hip
   return 0;
 }
 
-// Dense scores of a batch are dumped in sub-batches of at most 1 GiB: the queries of one (`cap` at most, never 0).
-uint32_t sparse_sub_batch(uint64_t cap, uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (1ull << 30) / (n * 4))); }
-
 // sparse_scan_kernel's grid: one wave per work-group, 8 of them per CU, a chunk of rows per work-group and query block.
 // part_k != 0 (the fused route): the partial lists of `count` queries, part_k entries each, take at most 64 MiB (a wide batch with
 // long lists gets longer chunks).
@@ -181,15 +170,12 @@ int sparse_dump_scores(const zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const Spar
 int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
                          uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude, uint64_t *d_keys, float *d_scores,
                          uint32_t *d_counts, hipStream_t s) {
-  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
   const SparseStore &st = h->st;
-  if (st.n == 0) {
-    ZCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * count, s));
-    ZCHK(hipMemsetAsync(d_keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, s));
-    return 0;
-  }
+  if (st.n == 0) return empty_results(d_keys, d_counts, count, topk, s);
+  const SearchOut out{d_keys, d_scores, nullptr, d_counts};
   const bool dump = topk > SPARSE_FUSED_MAX_K;
-  const uint32_t sub = dump ? sparse_sub_batch(count, st.n) : 0u;
+  const uint32_t sub = dump ? dense_sub_batch(count, st.n) : 0u;      // (a dumped row is the st.n scores of one query)
   std::vector<uint32_t> plan;
   uint32_t nblocks = 0, max_img = 0;
   sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);
@@ -204,12 +190,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
     for (uint32_t q0 = 0; q0 < count; q0 += sub) {
       const uint32_t cnt = std::min(sub, count - q0);
       ZRET(sparse_dump_scores(h, c, op, plan, count, max_img, q0, cnt, c->part_s.as<float>(), s));
-      MergeArgs m{};
-      m.part_s = c->part_s.as<float>(); m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)st.n; m.threshold = threshold;
-      m.keymap = st.keys; m.out_keys = d_keys + (size_t)q0 * topk; m.out_scores = d_scores + (size_t)q0 * topk;
-      m.out_counts = d_counts + q0;
-      hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, s, m);
-      ZCHK(hipGetLastError());
+      ZRET(launch_merge(merge_dense_rows(c->part_s.as<float>(), (uint32_t)st.n, topk, threshold, st.keys, out_from_row(out, q0, topk)), cnt, 64, s));
     }
     return 0;
   }
@@ -222,13 +203,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   ZRET(c->part_i.ensure(slots * topk * sizeof(uint32_t)));
   a.part_s = c->part_s.as<float>(); a.part_i = c->part_i.as<uint32_t>();
   ZRET(launch_sparse_scan<false>(h, a, a.nchunks * nblocks, sparse_lds_bytes(max_img, topk, st.width), s));
-  MergeArgs m{};
-  m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = a.nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
-  m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
-  m.out_keys = d_keys; m.out_scores = d_scores; m.out_counts = d_counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, s, m);
-  ZCHK(hipGetLastError());
-  return 0;
+  return launch_merge(merge_partials(a.part_s, a.part_i, a.nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), s);
 }
 
 // Scores of listed rows (sparse_rows_kernel): query q against the positions ids[offsets[q] .. offsets[q + 1]).  The caller holds
@@ -478,12 +453,9 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
                             exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, &d_off, c->cur));
     // selection, the threshold test and position -> key: every listed entry is a slot of one candidate, a query's slots are its list
     // (a skipped entry holds +inf, which no finite bound admits)
-    MergeArgs m{};
-    m.part_s = c->part_s.as<float>(); m.part_i = c->plan.as<uint32_t>(); m.slot_begin = d_off; m.slot_stride = 1; m.k = topk;
-    m.slot_len = 1; m.threshold = std::min(threshold, FLT_MAX); m.keymap = h->st.keys;
-    m.out_keys = c->io_keys.as<uint64_t>(); m.out_scores = c->io_scores.as<float>(); m.out_counts = c->io_counts.as<uint32_t>();
-    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, c->cur, m);
-    ZCHK(hipGetLastError());
+    const SearchOut out{c->io_keys.as<uint64_t>(), c->io_scores.as<float>(), nullptr, c->io_counts.as<uint32_t>()};
+    ZRET(launch_merge(merge_slot_ranges(c->part_s.as<float>(), c->plan.as<uint32_t>(), d_off, 1, nullptr, topk, std::min(threshold, FLT_MAX),
+                                        h->st.keys, out), count, merge_threads(count), c->cur));
   }
   return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
 }

@@ -81,7 +81,7 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
   ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, st.n, count, 1, s));
   const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
   // query slices: the score matrix stays <= 1 GiB, and a slice is one grid dimension of group_best_kernel (<= 65535)
-  const uint32_t sub = sparse_sub_batch(std::min<uint64_t>(count, 32768), st.n);
+  const uint32_t sub = dense_sub_batch(std::min<uint32_t>(count, 32768), st.n);
   std::vector<uint32_t> plan;
   uint32_t nblocks = 0, max_img = 0, max_run = 0;
   sparse_make_plan(q_counts, count, sub, plan, &nblocks, &max_img);          // q_off[count + 1] | blk[blocks + 1]

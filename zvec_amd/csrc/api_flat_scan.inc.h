@@ -48,17 +48,26 @@ const Knobs &knobs() {
   return k;
 }
 
-template <int NG, bool M16, bool EXCL, bool F16>
-int launch_scan_t(const ScanArgs &a, uint32_t max_items, int cus, hipStream_t stream) {
-  static bool attr_set[16] = {false};
-  size_t lds = scan_lds_bytes(NG, a.k, M16);
+// A kernel that takes more than the default 64 KiB of dynamic LDS has its limit raised to `bytes` before its first launch on a
+// device: once per (kernel instantiation, device).  Contexts on different threads launch the same kernel (c->mu is per context),
+// hence the atomic flags; two threads that both find the flag clear set the same value twice.
+template <auto Kernel>
+int raise_dynamic_lds(size_t bytes) {
+  static std::atomic<bool> done[16];
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan_kernel<NG, M16, EXCL, F16>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-    attr_set[dev & 15] = true;
+  std::atomic<bool> &d = done[dev & 15];
+  if (!d.load(std::memory_order_acquire)) {
+    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    d.store(true, std::memory_order_release);
   }
+  return 0;
+}
+
+template <int NG, bool M16, bool EXCL, bool F16>
+int launch_scan_t(const ScanArgs &a, uint32_t max_items, int cus, hipStream_t stream) {
+  size_t lds = scan_lds_bytes(NG, a.k, M16);
+  ZRET((raise_dynamic_lds<&scan_kernel<NG, M16, EXCL, F16>>(LDS_LIMIT)));
   int occ = 0;
   ZCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_kernel<NG, M16, EXCL, F16>, 256, lds));
   if (occ < 1) occ = 1;
@@ -84,15 +93,8 @@ int launch_scan(const ScanArgs &a, bool f16, uint32_t max_items, int cus, hipStr
 // pre-filter: 118.9 / 116.1 against 124.5 TFLOP/s on one box; DESIGN.md §3.  It is not kept.)
 template <bool EXCL, bool F16, bool GATHER>
 int launch_scan8_t(const ScanArgs &a, uint32_t max_items, int cus, hipStream_t stream, int *occ_out) {
-  static bool attr_set[16] = {false};
   size_t lds = scan8_lds_bytes(a.k);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan8_kernel<EXCL, F16, GATHER>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-    attr_set[dev & 15] = true;
-  }
+  ZRET((raise_dynamic_lds<&scan8_kernel<EXCL, F16, GATHER>>(LDS_LIMIT)));
   int occ = 0;
   ZCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan8_kernel<EXCL, F16, GATHER>, 512, lds));
   if (occ < 1) occ = 1;
@@ -118,15 +120,9 @@ int launch_scan8(const ScanArgs &a, bool f16, uint32_t max_items, int cus, hipSt
 
 // wide fp16 flat scan on the 256 x 256 multi-phase tile (zvk_scan256.hip.h): ONE work-group of 8 waves per CU
 int launch_scan256_f16(const ScanArgs &a, uint32_t max_items, int cus, hipStream_t stream) {
-  static bool attr_set[16] = {false};
   const size_t lds = scan256_lds_bytes(a.k);
   if (lds > LDS_LIMIT || a.nq < (uint32_t)S256_ROWS || a.nks < 2) return ZVEC_HIP_ERR_UNSUPPORTED;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&scan256_f16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-    attr_set[dev & 15] = true;
-  }
+  ZRET(raise_dynamic_lds<&scan256_f16_kernel>(LDS_LIMIT));
   const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)max_items, (uint64_t)cus);
   if (grid == 0) return 0;
   hipLaunchKernelGGL(scan256_f16_kernel, dim3(grid), dim3(512), lds, stream, a);
@@ -137,13 +133,7 @@ int launch_scan256_f16(const ScanArgs &a, uint32_t max_items, int cus, hipStream
 // nearest-centroid assignment (zvk_assign.hip.h): one work item = 128 rows x every centroid, two work-groups per CU
 template <bool F16>
 int launch_assign(const AssignArgs &a, int cus, hipStream_t s) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<F16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ASSIGN_LDS));
-    attr_set[dev & 15] = true;
-  }
+  ZRET(raise_dynamic_lds<&assign_kernel<F16>>(ASSIGN_LDS));
   const uint32_t items = (a.nq + ASSIGN_ROWS - 1) / ASSIGN_ROWS;
   const uint32_t grid = std::min<uint32_t>(items, (uint32_t)cus * 2u);
   if (grid == 0) return 0;
@@ -156,13 +146,7 @@ int launch_assign(const AssignArgs &a, int cus, hipStream_t s) {
 // of 8 waves per CU (129 KiB of LDS)
 template <bool L2>
 int launch_assign256_f16_t(const AssignArgs &a, int cus, hipStream_t s) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 15]) {
-    ZCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&assign256_f16_kernel<L2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)A256_LDS));
-    attr_set[dev & 15] = true;
-  }
+  ZRET(raise_dynamic_lds<&assign256_f16_kernel<L2>>(A256_LDS));
   const uint32_t items = (a.nq + A256_ROWS - 1) / A256_ROWS;
   const uint32_t grid = std::min<uint32_t>(items, (uint32_t)cus);
   if (grid == 0) return 0;
@@ -203,7 +187,8 @@ FlatSplit flat_split(uint64_t ntiles, uint32_t nqtiles, uint64_t resident) {
   FlatSplit f;
   const uint64_t slots_q = std::max<uint64_t>(1, (resident + nqtiles - 1) / nqtiles);    // chunks in flight per query tile
   uint64_t tpc = std::max<uint64_t>(1, (ntiles + slots_q - 1) / slots_q);
-  // >= 4 tiles per top-k warm-up — unless the base is too small to fill the chip that way
+  // >= 4 tiles per top-k warm-up — unless the base is too small to fill the chip that way (a single query over the
+  // 4096 IVF centroids: 32 one-tile items instead of 8 four-tile ones, 141 -> 40 us)
   tpc = std::max<uint64_t>(tpc, std::min<uint64_t>(ntiles, ntiles >= 4 * resident ? 4 : 1));
   f.tpc = (uint32_t)tpc;
   f.nchunks = (uint32_t)((ntiles + tpc - 1) / tpc);
@@ -273,38 +258,122 @@ int refine_l2(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t
 // partial-list merges of small batches: four waves per query gather the survivors (see merge_kernel)
 inline uint32_t merge_threads(uint32_t count) { return count <= 256 ? 256u : 64u; }
 
+// merge_kernel's dynamic LDS: the list of k (score, slot, index) entries.  (It holds 1 KiB of static LDS beside it.)  The search
+// paths admit lists up to MERGE_LDS_MAX, the shard-merge entries up to SHARD_MERGE_LDS_MAX: DESIGN.md "One place per item".
+inline size_t merge_lds_bytes(uint32_t k) { return (size_t)k * 12 + 16; }
+constexpr size_t MERGE_LDS_MAX = 60 * 1024, SHARD_MERGE_LDS_MAX = 64 * 1024;
+inline bool merge_fits(uint32_t k) { return merge_lds_bytes(k) <= MERGE_LDS_MAX; }
+
+// the one launch of merge_kernel: a work-group of `threads` (64, or 256 = merge_threads of a small batch) per list to produce
+int launch_merge(const MergeArgs &m, uint32_t blocks, uint32_t threads, hipStream_t stream) {
+  hipLaunchKernelGGL(merge_kernel, dim3(blocks), dim3(threads), merge_lds_bytes(m.k), stream, m);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+// rows [q0, ..) of a batch's outputs, k entries per row
+inline SearchOut out_from_row(const SearchOut &o, uint32_t q0, uint32_t k) {
+  return SearchOut{o.keys + (size_t)q0 * k, o.scores + (size_t)q0 * k, o.idx ? o.idx + (size_t)q0 * k : nullptr, o.counts + q0};
+}
+
+// The four shapes of a merge.  What they share: the k best under `threshold` into `out`, keys through `keymap` (nullptr: positions).
+inline MergeArgs merge_into(uint32_t k, float threshold, const uint64_t *keymap, const SearchOut &out) {
+  MergeArgs m{};
+  m.slot_stride = 1; m.k = k; m.threshold = threshold; m.keymap = keymap;
+  m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
+  return m;
+}
+// (1) select from dense rows: one row of `stride` scores per list, the candidate's index is its place in the row
+inline MergeArgs merge_dense_rows(const float *rows, uint32_t stride, uint32_t k, float threshold, const uint64_t *keymap, const SearchOut &out) {
+  MergeArgs m = merge_into(k, threshold, keymap, out);
+  m.part_s = rows; m.slots_per_q = 1; m.slot_len = stride;
+  return m;
+}
+// (2) fold a query's `nchunks` contiguous partial lists of k entries; gtau: the scan's shared bounds, valid upper bounds of every
+// query's final k-th score
+inline MergeArgs merge_partials(const float *part_s, const uint32_t *part_i, uint32_t nchunks, const uint32_t *gtau, uint32_t k,
+                                float threshold, const uint64_t *keymap, const SearchOut &out) {
+  MergeArgs m = merge_into(k, threshold, keymap, out);
+  m.part_s = part_s; m.part_i = part_i; m.slots_per_q = nchunks; m.slot_len = k; m.bound_keys = gtau;
+  return m;
+}
+// (3) select from a position stream: `slots` runs of `slot_len` (score, position) candidates per list; by_ordinal: equal scores
+// in the order of the stream instead of the order of the positions
+inline MergeArgs merge_stream(const float *part_s, const uint32_t *part_i, uint32_t slots, uint32_t slot_len, bool by_ordinal,
+                              uint32_t k, float threshold, const uint64_t *keymap, const SearchOut &out) {
+  MergeArgs m = merge_into(k, threshold, keymap, out);
+  m.part_s = part_s; m.part_i = part_i; m.slots_per_q = slots; m.slot_len = slot_len; m.order_by_ordinal = by_ordinal ? 1 : 0;
+  return m;
+}
+// (4) a query's slots are [slot_begin[q], slot_begin[q + 1]), slot_len candidates each (the IVF plan's probe order; a by-ids list)
+inline MergeArgs merge_slot_ranges(const float *part_s, const uint32_t *part_i, const uint32_t *slot_begin, uint32_t slot_len,
+                                   const uint32_t *gtau, uint32_t k, float threshold, const uint64_t *keymap, const SearchOut &out) {
+  MergeArgs m = merge_into(k, threshold, keymap, out);
+  m.part_s = part_s; m.part_i = part_i; m.slot_begin = slot_begin; m.slot_len = slot_len; m.bound_keys = gtau;
+  return m;
+}
+
+// Queries per sub-batch of a dense [query][row_floats] score matrix that stays <= 1 GiB: `cap` at most, never 0.
+inline uint32_t dense_sub_batch(uint64_t cap, uint64_t row_floats) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (1ull << 30) / (row_floats * 4)));
+}
+
+// The store-and-query part of a scan's arguments: the rows of `st` against the prepared queries [q0, ..) of the context.  The
+// caller adds what differs (k, mode, split, outputs, IVF tables).
+inline ScanArgs scan_operands(zvec_hip_ctx_s *ctx, const StoreView &st, const uint64_t *d_exclude, float threshold, uint32_t q0 = 0) {
+  ScanArgs a{};
+  a.base = st.base; a.bnorm = st.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
+  a.queries = ctx->qpad.as<float>() + (size_t)q0 * st.dpad; a.qnorm = ctx->qnorm.as<float>() + q0;
+  a.dpad = st.dpad; a.nks = st.dpad / TILE_K; a.metric = st.metric; a.threshold = threshold;
+  a.gtau = ctx->gtau.as<uint32_t>() + q0;
+  return a;
+}
+
+// the lists of the bound-seeding pre-pass (ctx->seed_*), sized for this search
+int seed_lists(zvec_hip_ctx_s *ctx, uint32_t count, uint32_t topk, SearchOut *so) {
+  ZRET(ctx->seed_keys.ensure((size_t)count * topk * sizeof(uint64_t)));
+  ZRET(ctx->seed_scores.ensure((size_t)count * topk * sizeof(float)));
+  ZRET(ctx->seed_counts.ensure((size_t)count * sizeof(uint32_t)));
+  ZRET(ctx->seed_idx.ensure((size_t)count * topk * sizeof(uint32_t)));
+  *so = SearchOut{ctx->seed_keys.as<uint64_t>(), ctx->seed_scores.as<float>(), ctx->seed_idx.as<uint32_t>(), ctx->seed_counts.as<uint32_t>()};
+  return 0;
+}
+
+// profile slot of a flat fp scan of `rows` rows: the rows and the queries read once, the lists written
+int flat_prof_begin(zvec_hip_ctx_s *ctx, const StoreView &st, uint64_t rows, uint32_t count, uint32_t topk, hipStream_t stream) {
+  const double bytes = (double)rows * st.dscan * st.elem + (double)count * st.dscan * st.elem + (double)count * topk * 12.0;
+  return prof_begin(ctx, stream, bytes, 2.0 * (double)count * (double)rows * st.dscan, 0);
+}
+
+// no rows: empty results
+int empty_results(uint64_t *keys, uint32_t *counts, uint32_t count, uint32_t topk, hipStream_t stream) {
+  ZCHK(hipMemsetAsync(counts, 0, sizeof(uint32_t) * count, stream));
+  ZCHK(hipMemsetAsync(keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, stream));
+  return 0;
+}
+
 // Sparse keep-set scan WITHOUT copying the kept rows: the wide kernel fetches the rows of a logical tile straight from
 // their stored positions (LDS-DMA with per-lane source addresses: every 128-byte row segment is still one full line).
 // `d_pos`: ascending kept positions, padded to whole tiles (+1 tile) with position 0; `kept` logical rows.
 int flat_scan_gather(zvec_hip_ctx_s *ctx, const StoreView &st, const uint32_t *d_pos, uint32_t kept, uint32_t count,
                      uint32_t topk, float threshold, const SearchOut &out, hipStream_t stream, bool profile_it) {
   const int cus = device_cus(ctx);
-  ScanArgs a{};
-  a.base = st.base; a.bnorm = st.bnorm; a.exclude = nullptr; a.gather_pos = d_pos;
-  a.queries = ctx->qpad.as<float>(); a.qnorm = ctx->qnorm.as<float>();
-  a.dpad = st.dpad; a.nks = st.dpad / TILE_K; a.metric = st.metric; a.threshold = threshold;
-  a.gtau = ctx->gtau.as<uint32_t>();
-  a.mode = 0; a.nq = count;
+  ScanArgs a = scan_operands(ctx, st, nullptr, threshold);
+  a.gather_pos = d_pos; a.mode = 0; a.nq = count;
   const uint32_t nqtiles = (count + W8_ROWS - 1) / W8_ROWS;
   // seeded bounds from the first SEED rows of the kept set (see flat_scan_prepared)
   constexpr uint32_t SEED_ROWS = 4096;
-  if (kept >= 64 * SEED_ROWS && topk <= 64 && (size_t)topk * 12 + 16 <= 60 * 1024) {
-    ZRET(ctx->seed_keys.ensure((size_t)count * topk * sizeof(uint64_t)));
-    ZRET(ctx->seed_scores.ensure((size_t)count * topk * sizeof(float)));
-    ZRET(ctx->seed_counts.ensure((size_t)count * sizeof(uint32_t)));
-    ZRET(ctx->seed_idx.ensure((size_t)count * topk * sizeof(uint32_t)));
+  if (kept >= 64 * SEED_ROWS && topk <= 64 && merge_fits(topk)) {
+    SearchOut so;                                      // (its positions are logical, gathered ones: mapped through d_pos below)
+    ZRET(seed_lists(ctx, count, topk, &so));
     ZRET(ctx->part_s.ensure((size_t)count * SEED_ROWS * sizeof(float)));
     ScanArgs d = a;
     d.k = 1; d.n = SEED_ROWS; d.ndense = SEED_ROWS; d.tiles_per_chunk = 1; d.nchunks = SEED_ROWS / TILE_N; d.nqtiles = nqtiles;
     d.dump = ctx->part_s.as<float>(); d.dump_stride = SEED_ROWS;
     ZRET(launch_scan8(d, st.f16, ((d.nchunks + 7) / 8) * 8 * nqtiles, cus, stream));
-    MergeArgs m{};
-    m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = SEED_ROWS; m.threshold = threshold;
-    m.out_keys = ctx->seed_keys.as<uint64_t>(); m.out_scores = ctx->seed_scores.as<float>(); m.out_counts = ctx->seed_counts.as<uint32_t>();
-    m.out_idx = ctx->seed_idx.as<uint32_t>();          // logical (gathered) positions: mapped through d_pos below
-    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, stream, m);
+    ZRET(launch_merge(merge_dense_rows(d.dump, SEED_ROWS, topk, threshold, nullptr, so), count, 64, stream));
     hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
-                       m.out_scores, m.out_idx, d_pos, m.out_counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
+                       so.scores, so.idx, d_pos, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
     ZCHK(hipGetLastError());
   }
   int occ8 = 1;
@@ -320,20 +389,10 @@ int flat_scan_gather(zvec_hip_ctx_s *ctx, const StoreView &st, const uint32_t *d
   ZRET(ctx->part_i.ensure(slots * topk * sizeof(uint32_t)));
   a.n = kept; a.ndense = kept; a.tiles_per_chunk = (uint32_t)tpc; a.nchunks = nchunks; a.nqtiles = nqtiles;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
-  int pi = -1;
-  if (profile_it) {
-    double bytes = (double)kept * st.dscan * st.elem + (double)count * st.dscan * st.elem + (double)count * topk * 12.0;
-    pi = prof_begin(ctx, stream, bytes, 2.0 * (double)count * (double)kept * st.dscan, 0);
-  }
+  const int pi = profile_it ? flat_prof_begin(ctx, st, kept, count, topk, stream) : -1;
   ZRET(launch_scan8(a, st.f16, ((nchunks + 7) / 8) * 8 * nqtiles, cus, stream));
   prof_end(ctx, stream, pi);
-  MergeArgs m{};
-  m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk;
-  m.threshold = threshold; m.bound_keys = a.gtau; m.keymap = st.keys;
-  m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, stream, m);
-  ZCHK(hipGetLastError());
-  return 0;
+  return launch_merge(merge_partials(a.part_s, a.part_i, nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), stream);
 }
 
 // Dense scores of queries [q0, q0 + cnt) of the prepared batch against every row of the store: the scan kernel in dump
@@ -355,12 +414,8 @@ int flat_dense_scores(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t q0, uin
   while (!wide_d && ngd > 2 && ntiles_d * ((cnt + ngd * QGROUP - 1) / (ngd * QGROUP)) < 2ull * cus_d) ngd /= 2;
   const uint32_t rows_d = wide_d ? W8_ROWS : ngd * QGROUP;
   const uint32_t nqt = (cnt + rows_d - 1) / rows_d;
-  ScanArgs a{};
-  a.base = st.base; a.bnorm = st.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
-  a.queries = ctx->qpad.as<float>() + (size_t)q0 * st.dpad; a.qnorm = ctx->qnorm.as<float>() + q0;
-  a.dpad = st.dpad; a.nks = st.dpad / TILE_K; a.metric = st.metric; a.k = 1; a.threshold = threshold;
-  a.mode = 0; a.nq = cnt; a.n = st.n; a.ndense = st.n; a.tiles_per_chunk = 1; a.nchunks = (uint32_t)ntiles_d; a.nqtiles = nqt;
-  a.gtau = ctx->gtau.as<uint32_t>() + q0;
+  ScanArgs a = scan_operands(ctx, st, d_exclude, threshold, q0);
+  a.k = 1; a.mode = 0; a.nq = cnt; a.n = st.n; a.ndense = st.n; a.tiles_per_chunk = 1; a.nchunks = (uint32_t)ntiles_d; a.nqtiles = nqt;
   a.dump = ctx->part_s.as<float>(); a.dump_stride = (uint32_t)(ntiles_d * TILE_N);
   a.part_s = nullptr; a.part_i = nullptr;
   if (wide_d) ZRET(launch_scan8(a, st.f16, (uint32_t)((ntiles_d + 7) / 8) * 8 * nqt, cus_d, stream));
@@ -390,7 +445,7 @@ int launch_hamming_scan(const HamScanArgs &a, uint32_t grid, hipStream_t stream)
 // longer ones are selected by merge_kernel from the dense [query][position] score matrix, in sub-batches of at most 1 GiB.
 int flat_scan_hamming(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude,
                       const SearchOut &out, hipStream_t stream, bool profile_it) {
-  if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
   const uint64_t ntiles = (st.n + TILE_N - 1) / TILE_N;
   const int cus = device_cus(ctx);
   HamScanArgs a{};
@@ -410,9 +465,8 @@ int flat_scan_hamming(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, 
     if (profile_it) gate_leave(ctx, stream);
   };
   if (topk > HAM_FUSED_MAX_K) {
-    const double row_bytes_d = (double)ntiles * TILE_N * 4.0;
-    const uint32_t sub = (uint32_t)std::max<double>(1.0, std::min<double>((double)count, std::floor(1073741824.0 / row_bytes_d)));
-    ZRET(ctx->part_s.ensure((size_t)(row_bytes_d * sub)));
+    const uint32_t sub = dense_sub_batch(count, ntiles * TILE_N);
+    ZRET(ctx->part_s.ensure((size_t)ntiles * TILE_N * 4 * sub));
     for (uint32_t q0 = 0; q0 < count; q0 += sub) {
       const uint32_t cnt = std::min(sub, count - q0);
       HamScanArgs d = a;
@@ -422,39 +476,25 @@ int flat_scan_hamming(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, 
       const int lrc = launch_hamming_scan<true>(d, d.nchunks * d.nqblocks, stream);
       end();
       ZRET(lrc);
-      MergeArgs m{};
-      m.part_s = d.dump; m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = d.dump_stride; m.threshold = threshold;
-      m.keymap = st.keys; m.out_keys = out.keys + (size_t)q0 * topk; m.out_scores = out.scores + (size_t)q0 * topk;
-      m.out_idx = out.idx ? out.idx + (size_t)q0 * topk : nullptr; m.out_counts = out.counts + q0;
-      hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, stream, m);
-      ZCHK(hipGetLastError());
+      ZRET(launch_merge(merge_dense_rows(d.dump, d.dump_stride, topk, threshold, st.keys, out_from_row(out, q0, topk)), cnt, 64, stream));
     }
     return 0;
   }
   // one wave per work-group: 16 of them per CU keep the vector ALUs and the loads in flight; a chunk is at least 4 tiles (one list
   // warm-up per chunk) unless the base is too small to fill the chip that way
   const uint32_t nqblocks = (count + HAM_QB - 1) / HAM_QB;
-  const uint64_t resident = (uint64_t)cus * 16;
-  const uint64_t want_chunks = std::max<uint64_t>(1, (resident + nqblocks - 1) / nqblocks);
-  uint64_t tpc = std::max<uint64_t>(1, (ntiles + want_chunks - 1) / want_chunks);
-  tpc = std::max<uint64_t>(tpc, std::min<uint64_t>(ntiles, ntiles >= 4 * resident ? 4 : 1));
-  const uint32_t nchunks = (uint32_t)((ntiles + tpc - 1) / tpc);
+  const FlatSplit fs = flat_split(ntiles, nqblocks, (uint64_t)cus * 16);
+  const uint32_t tpc = fs.tpc, nchunks = fs.nchunks;
   const uint64_t slots = (uint64_t)count * nchunks;
   ZRET(ctx->part_s.ensure(slots * topk * sizeof(float)));
   ZRET(ctx->part_i.ensure(slots * topk * sizeof(uint32_t)));
-  a.nq = count; a.tiles_per_chunk = (uint32_t)tpc; a.nchunks = nchunks; a.nqblocks = nqblocks;
+  a.nq = count; a.tiles_per_chunk = tpc; a.nchunks = nchunks; a.nqblocks = nqblocks;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
   begin(count);
   const int lrc = launch_hamming_scan<false>(a, nchunks * nqblocks, stream);
   end();
   ZRET(lrc);
-  MergeArgs m{};
-  m.part_s = a.part_s; m.part_i = a.part_i; m.slots_per_q = nchunks; m.slot_stride = 1; m.k = topk; m.slot_len = topk; m.threshold = threshold;
-  m.bound_keys = a.gtau; m.keymap = st.keys;
-  m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, stream, m);
-  ZCHK(hipGetLastError());
-  return 0;
+  return launch_merge(merge_partials(a.part_s, a.part_i, nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), stream);
 }
 
 int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t topk, float threshold,
@@ -465,12 +505,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     ZRET(ctx->ridx.ensure((size_t)count * topk * sizeof(uint32_t)));
     out.idx = ctx->ridx.as<uint32_t>();
   }
-  if (st.n == 0) {
-    // no rows: empty results
-    ZCHK(hipMemsetAsync(out.counts, 0, sizeof(uint32_t) * count, stream));
-    ZCHK(hipMemsetAsync(out.keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, stream));
-    return 0;
-  }
+  if (st.n == 0) return empty_results(out.keys, out.counts, count, topk, stream);
   if (st.bin) return flat_scan_hamming(ctx, st, count, topk, threshold, d_exclude, out, stream, profile_it);
   // Sparse keep-set: compact the kept rows and scan those (work ~ kept rows, like the CPU's skip-before-distance)
   // (a scan over shadow rows takes the gather variant only: its positions are stored positions, which the fp32 re-scoring needs; the
@@ -490,11 +525,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     // whenever a tenth of the rows can be skipped
     const bool can_gather = !knobs().no_gather && count > 2 * QGROUP && pick_ng(count, topk) == 4 && scan8_lds_bytes(topk) <= LDS_LIMIT - 1024;
     if ((double)kept <= (can_gather ? 0.9 : 0.5) * (double)st.n && (user_facing || can_gather)) {
-      if (kept == 0) {
-        ZCHK(hipMemsetAsync(out.counts, 0, sizeof(uint32_t) * count, stream));
-        ZCHK(hipMemsetAsync(out.keys, 0xff, sizeof(uint64_t) * (size_t)count * topk, stream));
-        return 0;
-      }
+      if (kept == 0) return empty_results(out.keys, out.counts, count, topk, stream);
       const uint64_t ktiles = ((uint64_t)kept + TILE_N - 1) / TILE_N;
       if (can_gather) {
         // wide batch: gather the kept rows inside the scan instead of copying them first
@@ -534,7 +565,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     const uint64_t ntiles_d = (st.n + TILE_N - 1) / TILE_N;
     const double row_bytes_d = (double)ntiles_d * TILE_N * 4.0;
     const bool small_base = (double)st.n * st.dpad * 4.0 <= 64.0 * 1024 * 1024;
-    const bool k_fits_merge = (size_t)topk * 12 + 16 <= 60 * 1024;
+    const bool k_fits_merge = merge_fits(topk);
     // (tests force the 256 x 256 tile onto small bases: option scan256 = 2)
     const bool forced256 = ropts().scan256.load(std::memory_order_relaxed) == 2 && st.f16 && count >= (uint32_t)S256_ROWS &&
                            st.dpad / TILE_K >= 2 && scan256_lds_bytes(topk) <= LDS_LIMIT;
@@ -543,20 +574,14 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     if (want_b && !k_fits_merge) return ZVEC_HIP_ERR_UNSUPPORTED;
     if ((want_a || want_b) && k_fits_merge) {
       // sub-batches so that the score matrix stays <= 1 GiB
-      const uint32_t sub = (uint32_t)std::max<double>(1.0, std::min<double>((double)count, std::floor(1073741824.0 / row_bytes_d)));
-      ZRET(ctx->part_s.ensure((size_t)(row_bytes_d * sub)));
+      const uint32_t sub = dense_sub_batch(count, ntiles_d * TILE_N);
+      ZRET(ctx->part_s.ensure((size_t)ntiles_d * TILE_N * 4 * sub));
       for (uint32_t q0 = 0; q0 < count; q0 += sub) {
         const uint32_t cnt = std::min(sub, count - q0);
         float *dump = nullptr;
         uint32_t dump_stride = 0;
         ZRET(flat_dense_scores(ctx, st, q0, cnt, threshold, d_exclude, stream, &dump, &dump_stride));
-        MergeArgs m{};
-        m.part_s = dump; m.part_i = nullptr; m.part_keys = nullptr; m.slot_begin = nullptr; m.slots_per_q = 1;
-        m.slot_stride = 1; m.part_counts = nullptr; m.k = topk; m.slot_len = dump_stride; m.threshold = threshold;
-        m.keymap = st.keys; m.out_keys = out.keys + (size_t)q0 * topk; m.out_scores = out.scores + (size_t)q0 * topk;
-        m.out_idx = out.idx ? out.idx + (size_t)q0 * topk : nullptr; m.out_counts = out.counts + q0;
-        hipLaunchKernelGGL(merge_kernel, dim3(cnt), dim3(64), (size_t)topk * 12 + 16, stream, m);
-        ZCHK(hipGetLastError());
+        ZRET(launch_merge(merge_dense_rows(dump, dump_stride, topk, threshold, st.keys, out_from_row(out, q0, topk)), cnt, 64, stream));
       }
       if (user_facing) ZRET(refine_l2(ctx, st, count, topk, threshold, out.keys, out.scores, out.idx, out.counts, stream));
       return 0;
@@ -578,10 +603,8 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
   // with a bound that only ~k * chunk_rows / sample_rows of its rows pass.
   const uint64_t SEED_ROWS = wide256 ? (uint64_t)knobs().seed_rows256 : 4096;
   if (!knobs().no_seed && st.n >= 64 * 4096 && topk <= 64 && count >= 16) {
-    ZRET(ctx->seed_keys.ensure((size_t)count * topk * sizeof(uint64_t)));
-    ZRET(ctx->seed_scores.ensure((size_t)count * topk * sizeof(float)));
-    ZRET(ctx->seed_counts.ensure((size_t)count * sizeof(uint32_t)));
-    ZRET(ctx->seed_idx.ensure((size_t)count * topk * sizeof(uint32_t)));
+    SearchOut so;
+    ZRET(seed_lists(ctx, count, topk, &so));
     StoreView view = st;                  // the first SEED_ROWS rows (whole tiles of the same arrays)
     view.n = SEED_ROWS;
     if (d_exclude == nullptr && (double)SEED_ROWS * 4.0 * count <= 256.0 * 1024 * 1024) {
@@ -596,7 +619,6 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
                          ctx->qnorm.as<float>(), st.bnorm, st.metric, topk);
       ZCHK(hipGetLastError());
     } else {
-      SearchOut so{ctx->seed_keys.as<uint64_t>(), ctx->seed_scores.as<float>(), ctx->seed_idx.as<uint32_t>(), ctx->seed_counts.as<uint32_t>()};
       ZRET(flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal));
       hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
                          so.scores, so.idx, (const uint32_t *)nullptr, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
@@ -622,21 +644,10 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
                            : (uint64_t)cus * (ng >= 4 ? 2 : (ng == 2 ? 2 : 3));   // work-groups per CU each shape reaches
   // items are equal-sized in a flat scan, so ONE wave of work-groups (items == resident slots) is the balanced
   // choice and gives the longest tile runs per top-k warm-up
-  FlatSplit fs;
-  if (wide) {
-    fs = flat_split(ntiles, nqtiles, resident);
-    if (wide256 && (fs.tpc & 1)) {          // the kernel walks the chunk in PAIRS of tiles
-      fs.tpc += 1;
-      fs.nchunks = (uint32_t)((ntiles + fs.tpc - 1) / fs.tpc);
-    }
-  } else {
-    uint64_t want_chunks = std::max<uint64_t>(1, (resident + nqtiles - 1) / nqtiles);
-    uint64_t tpc1 = std::max<uint64_t>(1, (ntiles + want_chunks - 1) / want_chunks);
-    // >= 4 tiles per top-k warm-up — unless the base is too small to fill the chip that way (a single query over the
-    // 4096 IVF centroids: 32 one-tile items instead of 8 four-tile ones, 141 -> 40 us)
-    tpc1 = std::max<uint64_t>(tpc1, std::min<uint64_t>(ntiles, ntiles >= 4 * resident ? 4 : 1));
-    fs.tpc = (uint32_t)tpc1;
-    fs.nchunks = (uint32_t)((ntiles + tpc1 - 1) / tpc1);
+  FlatSplit fs = flat_split(ntiles, nqtiles, resident);
+  if (wide256 && (fs.tpc & 1)) {          // the kernel walks the chunk in PAIRS of tiles
+    fs.tpc += 1;
+    fs.nchunks = (uint32_t)((ntiles + fs.tpc - 1) / fs.tpc);
   }
   const uint64_t tpc = fs.tpc;
   uint32_t nchunks = fs.nchunks;
@@ -644,19 +655,13 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
   ZRET(ctx->part_s.ensure(slots * topk * sizeof(float)));
   ZRET(ctx->part_i.ensure(slots * topk * sizeof(uint32_t)));
 
-  ScanArgs a{};
-  a.base = st.base; a.bnorm = st.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
-  a.queries = ctx->qpad.as<float>(); a.qnorm = ctx->qnorm.as<float>();
-  a.dpad = st.dpad; a.nks = st.dpad / TILE_K; a.metric = st.metric; a.k = topk; a.threshold = threshold;
-  a.gtau = ctx->gtau.as<uint32_t>();
-  a.mode = 0; a.nq = count; a.n = st.n; a.ndense = st.n; a.tiles_per_chunk = (uint32_t)tpc; a.nchunks = nchunks; a.nqtiles = nqtiles;
+  ScanArgs a = scan_operands(ctx, st, d_exclude, threshold);
+  a.k = topk; a.mode = 0; a.nq = count; a.n = st.n; a.ndense = st.n; a.tiles_per_chunk = (uint32_t)tpc; a.nchunks = nchunks; a.nqtiles = nqtiles;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
   int pi = -1;
   if (profile_it) {
     gate_enter(ctx, stream);            // (user-facing scans only: the seeding pre-pass and coarse passes are not gated)
-    double bytes = (double)st.n * st.dscan * st.elem + (double)count * st.dscan * st.elem + (double)count * topk * 12.0;
-    double flops = 2.0 * (double)count * (double)st.n * st.dscan;
-    pi = prof_begin(ctx, stream, bytes, flops, 0);
+    pi = flat_prof_begin(ctx, st, st.n, count, topk, stream);
   }
   int lrc;
   if (wide256) lrc = launch_scan256_f16(a, ((nchunks + 7) / 8) * 8 * nqtiles, cus, stream);
@@ -666,13 +671,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
   if (profile_it) gate_leave(ctx, stream);
   ZRET(lrc);
 
-  MergeArgs m{};
-  m.part_s = a.part_s; m.part_i = a.part_i; m.part_keys = nullptr; m.slot_begin = nullptr;
-  m.slots_per_q = nchunks; m.slot_stride = 1; m.part_counts = nullptr; m.k = topk; m.slot_len = topk; m.threshold = threshold;
-  m.bound_keys = a.gtau;   // the scan's shared bounds: valid upper bounds of every query's final k-th score
-  m.keymap = st.keys; m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, stream, m);
-  ZCHK(hipGetLastError());
+  ZRET(launch_merge(merge_partials(a.part_s, a.part_i, nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), stream));
   if (user_facing) ZRET(refine_l2(ctx, st, count, topk, threshold, out.keys, out.scores, out.idx, out.counts, stream));
   return 0;
 }
@@ -716,6 +715,25 @@ int prep_queries(zvec_hip_ctx_s *ctx, const StoreView &st, const void *d_queries
     hipLaunchKernelGGL(prep_queries_kernel<false>, dim3((count + 3) / 4), dim3(256), 0, stream, d_queries, count,
                        st.dim_in, st.dscan, st.dpad, ctx->qpad.as<float>(), ctx->qnorm.as<float>(),
                        ctx->gtau.as<uint32_t>(), threshold);
+  ZCHK(hipGetLastError());
+  return 0;
+}
+
+// Scores of listed rows: prepared query q against the positions d_pos[d_off[q] .. d_off[q + 1]) of `st` (bit rows, fp16 or fp32; the
+// metric is the view's) -> part_s / part_i [count][stride], holes and the unused tail +inf / IDX_NONE
+int launch_pkeys_score(const StoreView &st, const void *queries, const uint32_t *d_pos, const uint32_t *d_off, uint32_t count,
+                       uint32_t stride, float *part_s, uint32_t *part_i, hipStream_t stream) {
+  const float *q = static_cast<const float *>(queries);
+  if (st.bin)
+    hipLaunchKernelGGL(hamming_pkeys_kernel, dim3((unsigned)(((uint64_t)count * stride + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint32_t *>(st.base), static_cast<const uint32_t *>(queries), st.bin_chunks(), d_pos, d_off,
+                       count, stride, part_s, part_i);
+  else if (st.f16)
+    hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, stride)), dim3(256), 0, stream, st.base, q, st.dpad,
+                       st.metric, d_pos, d_off, count, stride, part_s, part_i);
+  else
+    hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(count, stride)), dim3(256), 0, stream, st.base, q, st.dpad,
+                       st.metric, d_pos, d_off, count, stride, part_s, part_i);
   ZCHK(hipGetLastError());
   return 0;
 }

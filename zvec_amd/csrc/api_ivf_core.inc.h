@@ -36,7 +36,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   // 8: 390 -> 369, 16: 586 -> 655 — the direct route costs the same for every query, the tile route shares the lists)
   const bool direct = !brute_force && !coarse_only && count <= (uint32_t)knobs().ivf_direct_q && (uint64_t)count * direct_rows <= (4u << 20) &&
                       (double)count * (double)direct_rows * (double)h->lists.row_bytes() <= 2.5e9 &&
-                      (size_t)topk * 12 + 16 <= 60 * 1024 && (size_t)nprobe * 12 + 16 <= 60 * 1024;
+                      merge_fits(topk) && merge_fits(nprobe);
 
   // The direct route scores rows straight from the prepared query rows and needs no norms: when the caller's rows already ARE
   // prepared rows (no padding: dim_in == the scanned dims == whole 128-byte k-steps; 16-byte aligned) the preparation launch is
@@ -98,12 +98,8 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       else
         hipLaunchKernelGGL(rows_score_kernel<false>, dim3((unsigned)((cpairs + 3) / 4)), dim3(256), 0, stream, h->cent.base,
                            qrows, h->cent.dpad, h->cent.metric, nlist, count, cstride, ctx->part_s.as<float>());
-      MergeArgs m{};
-      m.part_s = ctx->part_s.as<float>(); m.slots_per_q = 1; m.slot_stride = 1; m.k = nprobe; m.slot_len = cstride; m.threshold = FLT_MAX;
-      m.out_keys = co.keys; m.out_scores = co.scores; m.out_idx = co.idx; m.out_counts = co.counts;
       dp.coarse_idx = co.idx; dp.coarse_cnt = co.counts;                  // (the buffers may just have grown)
-      hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(256), (size_t)nprobe * 12 + 16, stream, m);     // four waves share the row
-      ZCHK(hipGetLastError());
+      ZRET(launch_merge(merge_dense_rows(ctx->part_s.as<float>(), cstride, nprobe, FLT_MAX, nullptr, co), count, 256, stream));   // four waves share the row
     } else {
       ZRET(flat_scan_prepared(ctx, h->cent, count, nprobe, FLT_MAX, nullptr, co, stream, ScanRole::internal));
     }
@@ -130,6 +126,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     const int pi = prof_begin(ctx, stream, (double)count * h->lists.dscan * h->lists.elem + (double)count * topk * 12.0, 0, 1);
     if (pi >= 0) ctx->prof_dscan[pi] = h->lists.dscan | (h->lists.f16 ? 0x80000000u : 0u);
     const uint32_t bpq = (stride + PKEYS_BLOCK - 1) / PKEYS_BLOCK;
+    int lrc = 0;
     if (block_topk) {
       ZRET(ctx->direct_scores.ensure((uint64_t)count * bpq * topk * 4));
       ZRET(ctx->direct_idx.ensure((uint64_t)count * bpq * topk * 4));
@@ -141,32 +138,24 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
         hipLaunchKernelGGL(pkeys_topk_kernel<false>, dim3(count * bpq), dim3(256), 0, stream, h->lists.base, qrows, h->lists.dpad,
                            h->metric, ctx->direct_pos.as<uint32_t>(), d_off, count, stride, topk, ctx->direct_scores.as<float>(),
                            ctx->direct_idx.as<uint32_t>());
-    } else if (h->lists.f16)
-      hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, stride)), dim3(256), 0, stream, h->lists.base,
-                         qrows, h->lists.dpad, h->metric, ctx->direct_pos.as<uint32_t>(), d_off, count, stride,
-                         ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(count, stride)), dim3(256), 0, stream, h->lists.base,
-                         qrows, h->lists.dpad, h->metric, ctx->direct_pos.as<uint32_t>(), d_off, count, stride,
-                         ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>());
+    } else {               // (the lists' metric is the index's: both are set once, by zvec_hip_ivf_create)
+      lrc = launch_pkeys_score(h->lists, qrows, ctx->direct_pos.as<uint32_t>(), d_off, count, stride, ctx->part_s.as<float>(),
+                               ctx->part_i.as<uint32_t>(), stream);
+    }
     prof_end(ctx, stream, pi);
+    ZRET(lrc);
     ZCHK(hipGetLastError());
     if (block_topk) {
       // (equal scores: list order, then entry order = the order of the candidate stream, as below)
-      MergeArgs f{};
-      f.part_s = ctx->direct_scores.as<float>(); f.part_i = ctx->direct_idx.as<uint32_t>(); f.slots_per_q = bpq; f.slot_stride = 1;
-      f.k = topk; f.slot_len = topk; f.threshold = threshold; f.order_by_ordinal = 1; f.keymap = h->lists.keys;
-      f.out_keys = out.keys; f.out_scores = out.scores; f.out_idx = out.idx; f.out_counts = out.counts;
-      hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(256), (size_t)topk * 12 + 16, stream, f);
-      ZCHK(hipGetLastError());
+      ZRET(launch_merge(merge_stream(ctx->direct_scores.as<float>(), ctx->direct_idx.as<uint32_t>(), bpq, topk, true, topk, threshold,
+                                     h->lists.keys, out), count, 256, stream));
       ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
       return 0;
     }
     // equal scores keep the reference's order — probe rank, then position in the list — which here is the ORDER of the
     // candidate stream, not the order of the positions
-    MergeArgs m{};
-    m.part_s = ctx->part_s.as<float>(); m.part_i = ctx->part_i.as<uint32_t>(); m.slots_per_q = 1; m.slot_stride = 1;
-    m.k = topk; m.threshold = threshold; m.order_by_ordinal = 1;
+    const float *ps = ctx->part_s.as<float>();
+    const uint32_t *ppos = ctx->part_i.as<uint32_t>();
     if (runs > 1) {
       // step 1: block (query, run) keeps the top-k of its 1024 candidates; step 2: a query's `runs` lists -> its result
       const uint64_t blocks = (uint64_t)count * runs;
@@ -174,21 +163,13 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       ZRET(ctx->direct_scores.ensure(blocks * topk * 4));
       ZRET(ctx->direct_idx.ensure(blocks * topk * 4));
       ZRET(ctx->direct_cnt.ensure(blocks * 4));
-      m.slot_len = RUN;
-      m.out_keys = ctx->direct_keys.as<uint64_t>(); m.out_scores = ctx->direct_scores.as<float>();
-      m.out_idx = ctx->direct_idx.as<uint32_t>(); m.out_counts = ctx->direct_cnt.as<uint32_t>();
-      hipLaunchKernelGGL(merge_kernel, dim3((unsigned)blocks), dim3(64), (size_t)topk * 12 + 16, stream, m);
-      MergeArgs f{};
-      f.part_s = m.out_scores; f.part_i = m.out_idx; f.slots_per_q = runs; f.slot_stride = 1; f.k = topk; f.slot_len = topk;
-      f.threshold = threshold; f.order_by_ordinal = 1; f.keymap = h->lists.keys;
-      f.out_keys = out.keys; f.out_scores = out.scores; f.out_idx = out.idx; f.out_counts = out.counts;
-      hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(256), (size_t)topk * 12 + 16, stream, f);
+      const SearchOut run{ctx->direct_keys.as<uint64_t>(), ctx->direct_scores.as<float>(), ctx->direct_idx.as<uint32_t>(),
+                          ctx->direct_cnt.as<uint32_t>()};
+      ZRET(launch_merge(merge_stream(ps, ppos, 1, RUN, true, topk, threshold, nullptr, run), (uint32_t)blocks, 64, stream));
+      ZRET(launch_merge(merge_stream(run.scores, run.idx, runs, topk, true, topk, threshold, h->lists.keys, out), count, 256, stream));
     } else {
-      m.slot_len = stride;
-      m.keymap = h->lists.keys; m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
-      hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, stream, m);
+      ZRET(launch_merge(merge_stream(ps, ppos, 1, stride, true, topk, threshold, h->lists.keys, out), count, 64, stream));
     }
-    ZCHK(hipGetLastError());
     ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
     return 0;
   }
@@ -200,7 +181,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   if (scan_lds_bytes(1, topk, true) > LDS_LIMIT - 1024) {
     // Large k (beyond ~470): the result lists no longer fit beside the staging buffers.  Rare, so served by the plain
     // route: expand every query's probed lists into positions, score each (query, row) pair directly, select.
-    if ((size_t)topk * 12 + 16 > 60 * 1024) return ZVEC_HIP_ERR_UNSUPPORTED;
+    if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
     PlanArgs p{};
     p.coarse_idx = probe_idx; p.coarse_cnt = probe_cnt;
     p.nq = count; p.nprobe = nprobe; p.nlist = nlist; p.max_scan_count = max_scan_count; p.brute_force = brute_force;
@@ -234,21 +215,10 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     ZRET(ctx->part_i.ensure(pairs * 4));
     // (re-prepare the queries with the caller's RNN radius: the coarse pass ran without one)
     ZRET(prep_queries(ctx, h->lists, d_queries, count, threshold, stream));
-    if (h->lists.f16)
-      hipLaunchKernelGGL(pkeys_score_kernel<true>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, stream, h->lists.base,
-                         ctx->qpad.as<float>(), h->lists.dpad, h->metric, d_pos, d_off, count, (uint32_t)maxlen,
-                         ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(pkeys_score_kernel<false>, dim3(pkeys_score_blocks(count, maxlen)), dim3(256), 0, stream, h->lists.base,
-                         ctx->qpad.as<float>(), h->lists.dpad, h->metric, d_pos, d_off, count, (uint32_t)maxlen,
-                         ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>());
-    ZCHK(hipGetLastError());
-    MergeArgs m{};
-    m.part_s = ctx->part_s.as<float>(); m.part_i = ctx->part_i.as<uint32_t>();
-    m.slots_per_q = 1; m.slot_stride = 1; m.k = topk; m.slot_len = (uint32_t)maxlen; m.threshold = threshold;
-    m.keymap = h->lists.keys; m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
-    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(64), (size_t)topk * 12 + 16, stream, m);
-    ZCHK(hipGetLastError());
+    ZRET(launch_pkeys_score(h->lists, ctx->qpad.as<float>(), d_pos, d_off, count, (uint32_t)maxlen, ctx->part_s.as<float>(),
+                            ctx->part_i.as<uint32_t>(), stream));
+    ZRET(launch_merge(merge_stream(ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>(), 1, (uint32_t)maxlen, false, topk, threshold,
+                                   h->lists.keys, out), count, 64, stream));
     ZCHK(hipStreamSynchronize(stream));    // d_pos is freed on return
     ctx->q_nprobe = nullptr; ctx->q_scanned = nullptr; ctx->last_count = 0;
     return 0;
@@ -345,16 +315,12 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   ZRET(ctx->part_i.ensure(slots_bound * ks * sizeof(uint32_t)));
 
   const StoreView &sst = use_shadow ? tw.st : h->lists;                      // the store the list scan streams
-  ScanArgs a{};
-  a.base = sst.base; a.bnorm = sst.bnorm; a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
-  a.queries = ctx->qpad.as<float>(); a.qnorm = ctx->qnorm.as<float>();
+  ScanArgs a = scan_operands(ctx, sst, d_exclude, threshold);     // (the twin's metric is the lists', which is the index's)
   if (use_shadow) {
     ZRET(shadow_prep_queries(ctx, sst, d_queries, count, stream));
     a.queries = ctx->sh.q16.as<float>(); a.qnorm = ctx->sh.qn16.as<float>();
   }
-  a.dpad = sst.dpad; a.nks = sst.dpad / TILE_K; a.metric = h->metric; a.k = ks; a.threshold = threshold;
-  a.gtau = ctx->gtau.as<uint32_t>();
-  a.mode = 1; a.nq = count; a.n = h->lists.n; a.ndense = h->count_local; a.tiles_per_chunk = tpc; a.list_tpc = pb + o_ltpc;
+  a.k = ks; a.mode = 1; a.nq = count; a.n = h->lists.n; a.ndense = h->count_local; a.tiles_per_chunk = tpc; a.list_tpc = pb + o_ltpc;
   a.total_items = p.total_items; a.queue = pb + o_queue; a.list_order = h->tab.d_order.p; a.item_off = p.item_off; a.list_tile0 = h->tab.d_tile0.p; a.list_size = h->tab.d_size.p;
   a.list_dense0 = h->tab.d_dense0.p; a.list_qoff = p.list_qoff; a.csr_q = p.csr_q; a.csr_slot = p.csr_slot; a.nlist = nlist;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();
@@ -369,16 +335,12 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   ZRET(lrc);
 
   // 4. merge the per-(query, probe, chunk) partial lists in probe order
-  MergeArgs m{};
-  m.part_s = a.part_s; m.part_i = a.part_i; m.part_keys = nullptr; m.slot_begin = p.slot_begin; m.slots_per_q = 0;
-  m.slot_stride = 1; m.part_counts = nullptr; m.k = ks; m.slot_len = ks; m.threshold = threshold; m.keymap = h->lists.keys;
-  m.bound_keys = a.gtau;
   if (use_shadow) {
     // the k' pre-selected rows of every query in shadow-score order -> their true scores -> the k best + the certificate
     SearchOut pre;
     ZRET(shadow_lists(ctx, count, kp, &pre));
-    m.out_keys = pre.keys; m.out_scores = pre.scores; m.out_idx = pre.idx; m.out_counts = pre.counts;
-    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)kp * 12 + 16, stream, m);
+    ZRET(launch_merge(merge_slot_ranges(a.part_s, a.part_i, p.slot_begin, kp, a.gtau, kp, threshold, h->lists.keys, pre), count,
+                      merge_threads(count), stream));
     return shadow_rescore_select(ctx, h->lists, tw, count, kp, topk, out, stream);
   }
   uint32_t *ridx = out.idx;
@@ -386,9 +348,8 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     ZRET(ctx->ridx.ensure((size_t)count * topk * sizeof(uint32_t)));
     ridx = ctx->ridx.as<uint32_t>();
   }
-  m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = ridx; m.out_counts = out.counts;
-  hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(merge_threads(count)), (size_t)topk * 12 + 16, stream, m);
-  ZCHK(hipGetLastError());
+  ZRET(launch_merge(merge_slot_ranges(a.part_s, a.part_i, p.slot_begin, topk, a.gtau, topk, threshold, h->lists.keys,
+                                      SearchOut{out.keys, out.scores, ridx, out.counts}), count, merge_threads(count), stream));
   ZRET(refine_l2(ctx, h->lists, count, topk, threshold, out.keys, out.scores, ridx, out.counts, stream));
   return 0;
 }
