@@ -633,9 +633,24 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     "unspecified" of Ties above; under ZVEC_HIP_METRIC_L2 equal scores are resolved by the same rule.
  *     ngroups, group_num or group_topk of 0: ZVEC_HIP_ERR_INVALID_ARGUMENT; group_num * 12 + 16 or group_topk * 16 + 16 above
  *     60 KiB: ZVEC_HIP_ERR_UNSUPPORTED; a refused call touches no output.  An empty index gives out_ngroups[q] = 0.
+ *   - Inverted lists (zvec_hip_sparse_set_inverted, zvec_hip_sparse_inverted_info), ZVEC_HIP_METRIC_IP only, fp32 or fp16 values,
+ *     off by default.  The reference has no such layout: it scans.  enable != 0 asks for a second, term-major layout of the same
+ *     rows: the distinct stored indices in ascending order, and per index the list of (storage position, value as stored) of the
+ *     rows that hold it, ascending by position.  While it is on, zvec_hip_sparse_search and zvec_hip_sparse_search_dev walk only
+ *     the lists of the query's own indices instead of every stored element, for every topk they accept; their contract is the one
+ *     above, unchanged: score = -(sum over shared indices), formed with fp32 fma in an order of the library's choosing (here:
+ *     the query's run order), a pair without a shared index scores the same zero as without the lists and is an ordinary candidate,
+ *     exclude_bitset, threshold, ascending lists, unspecified ties, the 4096-pair cap, validation of host queries and the topk
+ *     refusal as above.  The same call twice returns the same bits.  The lists are built on the host from the stored rows by the
+ *     first search that needs them; zvec_hip_sparse_append only marks them out of date, and the next such search rebuilds them
+ *     once (`builds` counts the builds; the info call never builds).  More than 2^32 - 1 stored pairs, or more than 2^32 - 4096
+ *     rows, make such a search return ZVEC_HIP_ERR_OUT_OF_RANGE.  enable == 0 frees the lists.  Listed rows, group-by and
+ *     zvec_hip_sparse_get_vector read the rows themselves whether the lists are on or off.  On a ZVEC_HIP_METRIC_L2 handle
+ *     zvec_hip_sparse_set_inverted returns ZVEC_HIP_ERR_UNSUPPORTED and changes nothing: the distance over the union of the index
+ *     sets would need the expansion that "Score, ZVEC_HIP_METRIC_L2" rules out.  A NULL handle: ZVEC_HIP_ERR_INVALID_ARGUMENT.
  * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), the
  * MipsSquaredEuclideanSparse metric, loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror
- * (zvec_hip_operator.hpp). */
+ * (zvec_hip_operator.hpp); by the inverted lists: ZVEC_HIP_METRIC_L2, listed rows and group-by. */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
 /* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
  * InnerProductSparse. */
@@ -684,6 +699,13 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
  * position beyond the rows scores +inf.  n == 0 returns 0 and writes nothing. */
 int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
                                    const void *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
+/* The term-major twin of the rows; see Inverted lists above. */
+int zvec_hip_sparse_set_inverted(zvec_hip_sparse_t h, int enable);
+/* enabled: asked for; bytes: device memory the lists hold now (0 before the first build); terms: distinct stored indices at the last
+ * build; tile_rows: consecutive positions one work item of the search accumulates (a constant of the library, reported whether the
+ * lists are on or off); builds: builds since the handle was created.  Every output nullable. */
+int zvec_hip_sparse_inverted_info(zvec_hip_sparse_t h, int *enabled, uint64_t *bytes, uint64_t *terms, uint32_t *tile_rows,
+                                  uint64_t *builds);
 /* Group-by over every row (FlatSparseEntity::search_group, flat_sparse_entity.h:79-103); see Group-by above. */
 int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
                                    const void *q_values, uint32_t count, const uint32_t *group_of_position, uint32_t ngroups,

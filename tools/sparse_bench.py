@@ -39,6 +39,14 @@ is reported beside the IP figure of the same point under an "l2_" name (reported
 work per stored element (a square for every element, two more sums on a hit) and has no shortcut for an empty query.
 
     python tools/sparse_bench.py --metric l2 [--by-keys | --grouped] [--dtype fp32|fp16] [--out profiles/sparse_flat1m_l2.json]
+
+--inverted: the full-scan mode's corpus and queries (batches 1 / 64 / 1024, k = 10, device-pointer call on a stream, device events)
+searched twice in one process, by the row scan and through the term-major twin (zvec_hip_sparse_set_inverted), for fp32 and for fp16
+values: ms per step of both routes, the twin's build time (the first search after it was asked for, wall clock, minus a later step),
+its bytes and term count, and whether the two answers agree (every list full and ascending, scores within agreement_band of each
+other place by place).  Reported, not gated; InnerProductSparse only.
+
+    python tools/sparse_bench.py --inverted [--out profiles/sparse_inverted.json] [--steps 10] [--warmup 3]
 """
 import argparse
 import ctypes as C
@@ -286,6 +294,87 @@ def grouped(args, metric):
     return res
 
 
+def inverted(args, metric):
+    import time
+    import numpy as np
+    import torch
+    import zvec_amd
+    assert metric == "ip", "the twin serves InnerProductSparse only"
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
+    batches = []
+    for batch in (1, 64, 1024):
+        qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
+        batches.append((batch, qc.numpy().astype(np.uint32), qi.to(dev), torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1))
+    ts = torch.cuda.Stream(device=dev)              # (a stream of its own: the null stream would mean "the context's stream")
+    ts.wait_stream(torch.cuda.current_stream(dev))
+    runs = []
+    for dtype in ("fp32", "fp16"):
+        np_val = np.float16 if dtype == "fp16" else np.float32
+        se = zvec_amd.HipFlatSparseStreamer(dtype=dtype)
+        assert se.reserve(args.n, ri.numel()) == 0
+        assert se.add_batch(rc_.numpy().astype(np.uint32), ri.numpy().view(np.uint32), rv.numpy().astype(np_val)) == 0
+        ctx = se.create_context()
+
+        def measure(batch, qc_np, d_qi, qv):
+            keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+            scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+            counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+
+            def step():
+                rc = se.search_dev(qc_np, d_qi.data_ptr(), qv.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(),
+                                   counts.data_ptr(), ctx, stream=ts.cuda_stream)
+                assert rc == 0
+            for _ in range(args.warmup):
+                step()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            for _ in range(args.steps):
+                step()
+            e1.record(ts)
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / args.steps, scores.cpu().numpy(), counts.cpu().numpy()
+
+        legs = []
+        for batch, qc_np, d_qi, qv in batches:
+            qv = qv.to(torch.float16) if dtype == "fp16" else qv
+            ms, scores, counts = measure(batch, qc_np, d_qi, qv)
+            legs.append({"batch": batch, "row_scan_ms": ms, "_scores": scores, "_counts": counts, "_q": (qc_np, d_qi, qv)})
+        se.set_inverted(True)
+        batch, qc_np, d_qi, qv = (legs[0]["batch"],) + legs[0]["_q"]
+        keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert se.search_dev(qc_np, d_qi.data_ptr(), qv.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                             ctx, stream=ts.cuda_stream) == 0
+        torch.cuda.synchronize()
+        first_ms = (time.perf_counter() - t0) * 1e3
+        for leg in legs:
+            ms, scores, counts = measure(leg["batch"], *leg.pop("_q"))
+            a, ca = leg.pop("_scores"), leg.pop("_counts")
+            full = bool(int(counts.min()) == args.topk == int(ca.min())) and bool(np.all(scores[:, 1:] >= scores[:, :-1]))
+            leg.update(inverted_ms=ms, score_max_abs_diff=float(np.abs(scores - a).max()),
+                       answers_agree=bool(full and float(np.abs(scores - a).max()) <= agreement_band(metric)))
+            print(json.dumps(dict(leg, dtype=dtype)), flush=True)
+        info = se.inverted_info()
+        assert info["builds"] == 1
+        runs.append({"dtype": dtype, "elements": se.element_count(), "twin_bytes": info["bytes"], "twin_terms": info["terms"],
+                     "tile_rows": info["tile_rows"], "build_ms": first_ms - legs[0]["inverted_ms"], "legs": legs})
+        del se, ctx
+        torch.cuda.synchronize()
+    return {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d: row scan and inverted lists, one process" % (
+                args.n, args.vocab, args.topk),
+            "metric": metric, "timing": "device events around the steps of a device-pointer call on a stream; build_ms: wall clock of the "
+            "first search after zvec_hip_sparse_set_inverted (host build included) minus a later step", "agreement_band": agreement_band(metric),
+            "steps": args.steps, "warmup": args.warmup, "runs": runs}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -296,10 +385,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--by-keys", action="store_true")
     ap.add_argument("--grouped", action="store_true")
+    ap.add_argument("--inverted", action="store_true")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
     ap.add_argument("--metric", choices=("ip", "l2"), default="ip")
     args = ap.parse_args()
     mode, rows = (by_keys, "points") if args.by_keys else (grouped, "points") if args.grouped else (flat, "legs")
+    if args.inverted:
+        if args.metric != "ip":
+            ap.error("--inverted serves InnerProductSparse only")
+        mode = inverted
     res = mode(args, "ip")
     if args.metric == "l2":
         res = beside(res, mode(args, "l2"), rows)

@@ -165,8 +165,16 @@ int sparse_dump_scores(const zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const Spar
   return launch_sparse_scan<true>(h, a, a.nchunks * a.nqblocks, sparse_lds_bytes(max_img, 0, h->st.width), s);
 }
 
-// The search proper.  The caller holds c->mu and h->rw (shared); q_counts (HOST) has passed sparse_check_runs; the query arrays
-// and every output are device pointers.  Enqueues only, except for a wait on the previous plan upload of the same context.
+// api_entry_sparse_inverted.inc.h: the term-major twin.  sparse_lock_current takes h->rw shared with the twin current if it is
+// asked for (it rebuilds a stale one under the exclusive lock first); sparse_inverted_search_locked is the search over it.
+int sparse_lock_current(zvec_hip_sparse_s *h, std::shared_lock<FairSharedMutex> &r);
+int sparse_inverted_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx,
+                                  const void *d_qval, uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude,
+                                  const SearchOut &out, hipStream_t s);
+
+// The search proper.  The caller holds c->mu and h->rw (shared, through sparse_lock_current); q_counts (HOST) has passed
+// sparse_check_runs; the query arrays and every output are device pointers.  Enqueues only, except for a wait on the previous plan
+// upload of the same context.
 int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *q_counts, const uint32_t *d_qidx, const void *d_qval,
                          uint32_t count, uint32_t topk, float threshold, const uint64_t *d_exclude, uint64_t *d_keys, float *d_scores,
                          uint32_t *d_counts, hipStream_t s) {
@@ -174,6 +182,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   const SparseStore &st = h->st;
   if (st.n == 0) return empty_results(d_keys, d_counts, count, topk, s);
   const SearchOut out{d_keys, d_scores, nullptr, d_counts};
+  if (h->inv.ready()) return sparse_inverted_search_locked(h, c, q_counts, d_qidx, d_qval, count, topk, threshold, d_exclude, out, s);
   const bool dump = topk > SPARSE_FUSED_MAX_K;
   const uint32_t sub = dump ? dense_sub_batch(count, st.n) : 0u;      // (a dumped row is the st.n scores of one query)
   std::vector<uint32_t> plan;
@@ -342,6 +351,7 @@ int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const ui
   ZCHK(hipStreamSynchronize(s));
   st.n += n;
   st.elems += total;
+  h->inv.stale = true;        // (rebuilt by the next search that needs it)
   return 0;
 }
 
@@ -391,8 +401,9 @@ int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const ui
   if (total && (!d_q_indices || !d_q_values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
-  std::shared_lock<FairSharedMutex> r(h->rw);
   ZCHK(hipSetDevice(h->device));
+  std::shared_lock<FairSharedMutex> r(h->rw, std::defer_lock);
+  ZRET(sparse_lock_current(h, r));
   return sparse_search_locked(h, c, q_counts, d_q_indices, d_q_values, count, topk, threshold, d_exclude_bitset, d_out_keys, d_out_scores,
                               d_out_counts, pick_stream(c, stream));
 }
@@ -412,7 +423,8 @@ int zvec_hip_sparse_search(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32
   std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
   {
-    std::shared_lock<FairSharedMutex> r(h->rw);      // the row count the bitset is sized for == the rows scanned
+    std::shared_lock<FairSharedMutex> r(h->rw, std::defer_lock);      // the row count the bitset is sized for == the rows scanned
+    ZRET(sparse_lock_current(h, r));
     ZRET(host_search_wrap_begin(c, blob.data(), blob.size() * 4, exclude_bitset, h->st.n, count, topk, c->cur));
     const uint32_t *dq = static_cast<const uint32_t *>(c->io_qp);
     ZRET(sparse_search_locked(h, c, q_counts, dq, dq + te, count, topk, threshold,

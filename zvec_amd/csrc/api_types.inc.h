@@ -518,12 +518,33 @@ struct SparseStore {
   } own;
 };
 
+// Term-major twin of a SparseStore (zvec_hip_sparse_set_inverted, zvk_sparse_inv.hip.h): the distinct stored indices, the posting
+// offsets, and per posting the storage position and the value as stored.  `want`, `stale` and the arrays change only under the
+// handle's exclusive lock; an append marks the twin stale and the next search that needs it rebuilds it (api_entry_sparse_inverted.inc.h).
+struct InvertedTwin {
+  bool want = false;          // asked for by zvec_hip_sparse_set_inverted
+  bool stale = true;          // the arrays do not hold the store's rows
+  uint64_t builds = 0;
+  uint32_t nterms = 0;
+  uint64_t elems = 0;         // postings
+  Scoped<uint32_t> terms, ppos;
+  Scoped<uint64_t> list_off;
+  Scoped<void> pval;
+  bool ready() const { return want && !stale; }
+  uint64_t bytes() const { return terms.cap + ppos.cap + list_off.cap + pval.cap; }
+  void drop() {
+    terms.release(); ppos.release(); list_off.release(); pval.release();
+    nterms = 0; elems = 0; stale = true;
+  }
+};
+
 struct zvec_hip_sparse_s {
   int device = 0;
   int dtype = 0;            // ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16: the type of every value pointer of the handle's calls
   int metric = ZVEC_HIP_METRIC_IP;      // ZVEC_HIP_METRIC_IP (InnerProductSparse) or ZVEC_HIP_METRIC_L2 (SquaredEuclideanSparse); fixed at creation
   bool l2() const { return metric == ZVEC_HIP_METRIC_L2; }
   SparseStore st;
+  InvertedTwin inv;         // off unless zvec_hip_sparse_set_inverted asked for it
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)
   FairSharedMutex rw;       // searches hold it shared, anything that may move or extend the store exclusive (as zvec_hip_flat_s)

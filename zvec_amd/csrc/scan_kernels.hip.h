@@ -34,3 +34,4 @@
 #include "zvk_group.hip.h"
 #include "zvk_hamming.hip.h"
 #include "zvk_sparse.hip.h"
+#include "zvk_sparse_inv.hip.h"

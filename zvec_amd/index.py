@@ -724,6 +724,19 @@ class HipFlatSparseStreamer:
         rc = _lib.lib().zvec_hip_sparse_get_vector(self._h, int(pos), C.byref(n), _np_ptr(idx), _np_ptr(val))
         return (idx[:n.value].copy(), val[:n.value].copy()) if rc == 0 else None
 
+    def set_inverted(self, enable=True):
+        """inverted lists (zvec_hip_sparse_set_inverted): a term-major twin of the rows, InnerProductSparse only; while it is on,
+        search_impl and search_dev walk the lists of the query's own indices instead of every stored row.  Built by the first search
+        that needs it, rebuilt once by the first search after an append."""
+        _lib.check(_lib.lib().zvec_hip_sparse_set_inverted(self._h, int(bool(enable))), "zvec_hip_sparse_set_inverted")
+
+    def inverted_info(self):
+        on, nbytes, terms, tile, builds = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        _lib.check(_lib.lib().zvec_hip_sparse_inverted_info(self._h, C.byref(on), C.byref(nbytes), C.byref(terms), C.byref(tile),
+                                                            C.byref(builds)), "zvec_hip_sparse_inverted_info")
+        return {"enabled": bool(on.value), "bytes": int(nbytes.value), "terms": int(terms.value), "tile_rows": int(tile.value),
+                "builds": int(builds.value)}
+
     def search_impl(self, counts, indices, values, count, ctx):
         """search_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, context) (flat_sparse_search.h:58-148)"""
         if ctx is None:
