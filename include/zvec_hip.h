@@ -56,7 +56,8 @@ enum {
  *     pairing is ZVEC_HIP_ERR_MISMATCH;
  *   - served on a binary handle: flat_create / destroy / reserve, append, append_dev, put, holes, count, get_vector(s), search,
  *     search_dev, search_by_ids, batch_distance, build_filter (exclude_bitset and threshold mean what they mean elsewhere: a
- *     document is dropped iff score > threshold);  ZVEC_HIP_ERR_UNSUPPORTED: search_grouped*, the shadow entries, load_features,
+ *     document is dropped iff score > threshold), and — DT_BINARY32 only, fed with fp32 rows / queries that are turned into sign
+ *     bits on the device ("fp32 -> sign bits" below) — append_fp32, append_fp32_dev, search_fp32, search_fp32_dev;  ZVEC_HIP_ERR_UNSUPPORTED: search_grouped*, the shadow entries, load_features,
  *     load_blocks, zvec_hip_shards_create and zvec_hip_ivf_create with a binary dtype;
  *   - lists are ascending by score; which of several equal scores are returned at the k-th place, and their order, is unspecified
  *     (the reference's heap resolves ties arbitrarily). */
@@ -513,6 +514,50 @@ int zvec_hip_container_segments(const void *image, uint64_t bytes, int checksum,
  * AVX-512 host code (norm summation order, correctly rounded sqrt / divide). */
 int zvec_hip_reform_queries_dev(zvec_hip_ctx_t ctx, const float *d_in, uint32_t count, uint32_t dim, int cosine,
                                 int out_dtype, void *d_out, void *stream);
+
+/* ---- fp32 -> sign bits (binary quantisation) ------------------------------------------------------------------
+ * BinaryConverter on the rows of an index (src/core/quantizer/binary_converter.cc:25-128, :138-167) and BinaryReformer on every
+ * query (src/core/quantizer/binary_reformer.cc:46-68), on the device.  Both run ailego::BinaryQuantizer::encode
+ * (src/ailego/algorithm/binary_quantizer.cc:40-57): bit j of word w is in[32 w + j] >= threshold, LSB first; the threshold is the
+ * quantizer's (binary_quantizer.h:48-55, 0 unless set; BinaryQuantizer::train does nothing, binary_quantizer.cc:35-37).
+ *   d_in / in: [count][dim] fp32, rows at their natural 4-byte alignment; d_out / out: [count][ceil(dim / 32)] uint32_t, row-major —
+ *   a DT_BINARY32 row of 32 * ceil(dim / 32) bits (BinaryConverterHolder::dimension, binary_converter.cc:93-102).
+ *   Bit i of a row is in[i] >= threshold for i < encode_dims and 0 for every other bit of the row's words: encode(in, encode_dims,
+ *   out) written into a zeroed row.  The comparison is the C one: -0.0f >= 0.0f holds, nan gives 0, +inf 1, -inf 0, a denormal
+ *   compares by its value.  1 <= encode_dims <= dim <= 2^20.
+ *   encode_dims exists because the reference's two sides disagree: BinaryConverterHolder::Iterator::encode_record calls
+ *   encode(vec, dim_ / 2, ...) with dim_ the PADDED bit count 32 * ceil(dim / 32) (binary_converter.cc:34-39, :69-73), so the rows
+ *   it converts carry bits for the first 32 * ceil(dim / 32) / 2 input values only, while its reformer encodes all `dim` values of a
+ *   query (binary_reformer.cc:62).  encode_dims = dim is what the names promise; encode_dims = 32 * ceil(dim / 32) / 2 reproduces
+ *   the reference's converted rows.  (BinaryReformer's batch form, binary_reformer.cc:71-92, encodes the count * dim values as ONE
+ *   run, which equals the per-query form only when dim is a multiple of 32; the per-query form is the one served here.)
+ * zvec_hip_binary_encode_dev only enqueues work on `stream` (NULL: the context's).  zvec_hip_binary_encode is the same through host
+ * pointers, staged through the device in bounded slices.  count == 0 returns 0 and writes nothing; a NULL context or pointer,
+ * dim == 0, dim > 2^20 or encode_dims outside [1, dim] is ZVEC_HIP_ERR_INVALID_ARGUMENT and touches no output. */
+int zvec_hip_binary_encode_dev(zvec_hip_ctx_t ctx, const float *d_in, uint64_t count, uint32_t dim, uint32_t encode_dims,
+                               float threshold, uint32_t *d_out, void *stream);
+int zvec_hip_binary_encode(zvec_hip_ctx_t ctx, const float *in, uint64_t count, uint32_t dim, uint32_t encode_dims,
+                           float threshold, uint32_t *out);
+/* IndexConverter::transform + IndexBuilder::build of a "BinaryConverter" index (binary_converter.cc:185-196; flat_builder.cc:188-276),
+ * IndexStreamer::add_impl behind the converter: n fp32 rows of `dim` values are encoded on the device (encode_dims, threshold as
+ * above) and stored exactly as zvec_hip_flat_append[_dev] stores the same words — positions, keys (NULL: key = position), all of
+ * the rows or none.  The handle must be ZVEC_HIP_DT_BINARY32 with 32 * ceil(dim / 32) bits; every other handle (DT_BINARY64, which
+ * the converter never emits, binary_converter.cc:100-102; the fp types; another width) is ZVEC_HIP_ERR_MISMATCH.  n == 0 returns 0. */
+int zvec_hip_flat_append_fp32(zvec_hip_flat_t h, const float *vecs, uint64_t n, uint32_t dim, uint32_t encode_dims,
+                              float threshold, const uint64_t *keys);
+int zvec_hip_flat_append_fp32_dev(zvec_hip_flat_t h, const float *d_vecs, uint64_t n, uint32_t dim, uint32_t encode_dims,
+                                  float threshold, const uint64_t *d_keys, void *stream);
+/* BinaryReformer::transform of every query (binary_reformer.cc:46-68: all `dim` values encoded, against bin_threshold) followed by
+ * zvec_hip_flat_search[_dev] (search_impl, index_runner.h:490-531): outputs, ties, threshold, exclude_bitset and the topk cap are
+ * those calls'.  queries: [count][dim] fp32.  The handle pairs with `dim` as for zvec_hip_flat_append_fp32.  The encoded queries
+ * live in the context's workspace: the device-pointer form allocates nothing once the workspace has grown to the batch. */
+int zvec_hip_flat_search_fp32(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t dim, float bin_threshold,
+                              uint32_t count, uint32_t topk, float threshold, const uint64_t *exclude_bitset,
+                              uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+int zvec_hip_flat_search_fp32_dev(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t dim,
+                                  float bin_threshold, uint32_t count, uint32_t topk, float threshold,
+                                  const uint64_t *d_exclude_bitset, uint64_t *d_out_keys, float *d_out_scores,
+                                  uint32_t *d_out_counts, void *stream);
 
 /* ---- predicate materialisation --------------------------------------------------------
  * Replaces the per-candidate IndexFilter callback (index_filter.h:48-50) whose producers are

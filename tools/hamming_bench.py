@@ -6,6 +6,12 @@ runs on (reported, not gated; bench.py is the project's benchmark and does not c
                    2 cycles on a SIMD, i.e. 32 word pairs per cycle and SIMD; 4 SIMDs x CUs; at the calibrated shader clock
 
     python tools/hamming_bench.py [--out profiles/hamming_flat1m_768b.json] [--steps 20] [--warmup 5]
+
+--from-fp32 measures the index fed with fp32 embeddings instead (n x bits fp32 values turned into sign bits on the GPU): the encoder
+alone and the fp32 append in GB/s of fp32 input against the box's streaming figure of the same run, and search_fp32 beside the
+bit-fed search at the same batches.  Reported, not gated.
+
+    python tools/hamming_bench.py --from-fp32 [--out profiles/hamming_from_fp32.json]
 """
 import argparse
 import ctypes as C
@@ -24,7 +30,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--from-fp32", action="store_true", help="feed the index with fp32 rows / queries (encoder, fp32 append, search_fp32)")
     args = ap.parse_args()
+    if args.from_fp32:
+        return from_fp32(args)
     import torch
     import zvec_amd
     dev = torch.device("cuda:0")
@@ -79,6 +88,97 @@ def main():
                    valu_fraction=valu_ms / leg["ms_per_step"])
     res = {"workload": "flat hamming %d x %d bits, k=%d" % (args.n, args.bits, args.topk), "stored_bytes": stored, "cus": cus,
            "clock_mhz": mhz.value, "stream_gbs": gbs.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def _timed(torch, stream, steps, warmup, step):
+    """ms per step, events on `stream` around `steps` calls"""
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(steps):
+        step()
+    e1.record(stream)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def from_fp32(args):
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    n, dim, words = args.n, args.bits, (args.bits + 31) // 32
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rows = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
+    in_bytes = float(n) * dim * 4
+    ts = torch.cuda.Stream(device=dev)
+    ts.wait_stream(torch.cuda.current_stream(dev))
+    stream = ts.cuda_stream
+    ectx = zvec_amd.IndexContext(0)
+    enc_out = torch.empty((n, words), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    enc_ms = _timed(torch, ts, args.steps, args.warmup,
+                    lambda: ectx.binary_encode_dev(rows.data_ptr(), n, dim, enc_out.data_ptr(), stream=stream))
+
+    # the fp32 append (encode + pack into the blocked layout), a fresh index per step; reserved, so no growth copy is timed
+    def fresh():
+        se = zvec_amd.HipFlatSearcher(words * 32, "Hamming", dtype="binary32")
+        assert se.reserve(n) == 0
+        return se
+    app = []
+    for _ in range(max(2, min(args.steps, 5))):
+        se = fresh()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(ts)
+        assert se.add_batch_fp32_dev(rows.data_ptr(), n, dim, stream=stream) == 0
+        e1.record(ts)
+        torch.cuda.synchronize()
+        app.append(e0.elapsed_time(e1))
+    app_ms = min(app[1:])
+    ctx = se.create_context()
+    legs = []
+    for batch in (1, 256, 1024):
+        q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+        qw = torch.empty((batch, words), dtype=torch.int32, device=dev)
+        keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        ectx.binary_encode_dev(q.data_ptr(), batch, dim, qw.data_ptr(), stream=stream)
+
+        def fp32_step():
+            assert se.search_fp32_dev(q.data_ptr(), dim, batch, args.topk, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx,
+                                      stream=stream) == 0
+
+        def bits_step():
+            assert se.search_dev(qw.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx, stream=stream) == 0
+        ms_fp32 = _timed(torch, ts, args.steps, args.warmup, fp32_step)
+        fp32_scores = scores.clone()
+        ms_bits = _timed(torch, ts, args.steps, args.warmup, bits_step)
+        assert int(counts.min()) == args.topk and bool((scores == fp32_scores).all())
+        legs.append({"batch": batch, "search_fp32_ms": ms_fp32, "search_fp32_qps": batch / ms_fp32 * 1e3, "search_bits_ms": ms_bits,
+                     "search_bits_qps": batch / ms_bits * 1e3})
+    del rows, enc_out, se
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    enc_gbs, app_gbs = in_bytes / enc_ms / 1e6, in_bytes / app_ms / 1e6
+    res = {"workload": "flat hamming fed with fp32: %d x %d values, k=%d" % (n, dim, args.topk), "input_bytes": in_bytes,
+           "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup,
+           "encode": {"ms": enc_ms, "input_gbs": enc_gbs, "stream_fraction": enc_gbs / gbs.value},
+           "append_fp32": {"ms": app_ms, "input_gbs": app_gbs, "stream_fraction": app_gbs / gbs.value},
+           "legs": legs}
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:

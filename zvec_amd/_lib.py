@@ -145,6 +145,14 @@ SYMBOLS = {
     "zvec_hip_flat_build_filter": (C.c_int, [_h, _h, C.POINTER(DocFilterDesc), _u64p, C.c_int, C.c_void_p]),
     "zvec_hip_ivf_build_filter": (C.c_int, [_h, _h, C.POINTER(DocFilterDesc), _u64p, C.c_int, C.c_void_p]),
     "zvec_hip_reform_queries_dev": (C.c_int, [_h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "zvec_hip_binary_encode_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+    "zvec_hip_binary_encode": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
+    "zvec_hip_flat_append_fp32": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, _u64p]),
+    "zvec_hip_flat_append_fp32_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, _u64p, C.c_void_p]),
+    "zvec_hip_flat_search_fp32": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_float, _u64p,
+                                            _u64p, _f32p, _u32p]),
+    "zvec_hip_flat_search_fp32_dev": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_float, _u64p,
+                                                _u64p, _f32p, _u32p, C.c_void_p]),
     "zvec_hip_container_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(Segment), C.c_uint32, C.POINTER(C.c_uint32)]),
     "zvec_hip_crc32c": (C.c_uint32, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "zvec_hip_sparse_create": (C.c_int, [C.c_int, C.POINTER(_h)]),

@@ -376,6 +376,7 @@ struct zvec_hip_ctx_s {
   DevBuf sp_plan;                                      // sparse search: query offsets | query-block table (api_entry_sparse.inc.h)
   PinnedBuf sp_pin;                                    // ... its pinned source, and the event behind its last upload
   hipEvent_t sp_ev = nullptr;
+  DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)
   const void *io_qp = nullptr;                         // where device code finds the uploaded queries: io_q or the mapped pin_in slot
@@ -447,6 +448,7 @@ struct zvec_hip_flat_s {
   hipEvent_t ring_ev[RING / RING_GROUP] = {};
   bool ring_used[RING / RING_GROUP] = {};
   uint32_t ring_next = 0;
+  DevBuf enc;               // zvec_hip_flat_append_fp32[_dev]: the encoded words of a slice of rows, between the encoder and the pack kernel
   bool is_hole(uint64_t pos) const { return (pos >> 6) < h_holes.size() && ((h_holes[pos >> 6] >> (pos & 63)) & 1ull); }
   // (zvec_hip_flat_destroy has made the device current and idle)
   ~zvec_hip_flat_s() {

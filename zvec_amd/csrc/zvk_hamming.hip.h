@@ -1,4 +1,5 @@
-// zvk_hamming.hip.h — binary rows under the Hamming metric: blocked layout, pack / unpack, the XOR + population-count scan.
+// zvk_hamming.hip.h — binary rows under the Hamming metric: blocked layout, pack / unpack, the XOR + population-count scan, the
+// fp32 -> sign-bit encoder.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Reference: HammingMetric (src/core/metric/hamming_metric.cc) over HammingDistanceMatrix<uint32_t / uint64_t, 1, 1>
@@ -259,6 +260,46 @@ __global__ void __launch_bounds__(256) hamming_unpack_kernel(const uint32_t *bas
                                                              uint32_t *out) {
   const uint64_t p = pos ? pos[blockIdx.x] : pos1;
   for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) out[(size_t)blockIdx.x * words + w] = base[ham_offset(p, w >> 2, cpr) + (w & 3)];
+}
+
+// fp32 rows -> sign bits: ailego::BinaryQuantizer::encode (src/ailego/algorithm/binary_quantizer.cc:40-57) into a zeroed row of
+// ceil(dim / 32) words — bit i of a row is in[i] >= threshold for i < encode_dims (LSB first), every other bit of the row's words 0.
+// What BinaryConverter does to the rows of an index (encode_dims = the converter's half, binary_converter.cc:69-73) and
+// BinaryReformer to every query (encode_dims = dim, binary_reformer.cc:46-68).
+//
+// A streaming reader, 4 bytes in per bit out.  One wave per row at a time, a wave instruction per 64 consecutive values: lane l
+// loads value 64 g + l (256 contiguous bytes per load; dword loads, so a row needs no more than its natural 4-byte alignment), the
+// wave's ballot of the comparison IS words 2 g and 2 g + 1.  BENC_GROUPS loads are issued before the first ballot; their up to
+// 2 * BENC_GROUPS words leave in one store of the first lanes.  The comparison is the plain fp32 one: -0 >= 0, nan never, denormals
+// by their value (fp32 denormals are not flushed on gfx950).
+constexpr int BENC_GROUPS = 4;
+__global__ void __launch_bounds__(256) binary_encode_kernel(const float *in, uint64_t count, uint32_t dim, uint32_t encode_dims, float threshold,
+                                                            uint32_t *out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t words = (dim + 31) / 32, groups = (words + 1) / 2;
+  for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < count; row += (uint64_t)gridDim.x * 4) {
+    const float *src = in + (size_t)row * dim;
+    uint32_t *dst = out + (size_t)row * words;
+    for (uint32_t g0 = 0; g0 < groups; g0 += BENC_GROUPS) {
+      float v[BENC_GROUPS];
+      bool in_range[BENC_GROUPS];
+#pragma unroll
+      for (int u = 0; u < BENC_GROUPS; ++u) {
+        const uint32_t i = (g0 + u) * 64 + lane;
+        in_range[u] = i < encode_dims;                 // (encode_dims <= dim: nothing beyond the row is read)
+        v[u] = in_range[u] ? src[i] : 0.f;
+      }
+      uint32_t mine = 0;
+#pragma unroll
+      for (int u = 0; u < BENC_GROUPS; ++u) {
+        const uint64_t m = __ballot(in_range[u] && v[u] >= threshold);
+        if (lane == 2u * u) mine = (uint32_t)m;
+        if (lane == 2u * u + 1) mine = (uint32_t)(m >> 32);
+      }
+      const uint32_t w = g0 * 2 + lane;
+      if (lane < 2 * BENC_GROUPS && w < words) dst[w] = mine;
+    }
+  }
 }
 
 }  // namespace zvk

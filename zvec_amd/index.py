@@ -331,6 +331,24 @@ class IndexContext:
         _lib.check(_lib.lib().zvec_hip_reform_queries_dev(self._h, C.c_void_p(d_in), int(count), int(dim), int(bool(cosine)), dt,
                                                           C.c_void_p(d_out), C.c_void_p(stream or 0)), "zvec_hip_reform_queries_dev")
 
+    def binary_encode_dev(self, d_in, count, dim, d_out, threshold=0.0, encode_dims=None, stream=None):
+        """BinaryConverter / BinaryReformer on fp32 rows already in HBM (device pointers): [count][dim] fp32 -> [count][ceil(dim / 32)]
+        uint32 words, bit i of a row = in[i] >= threshold for i < encode_dims (default: dim), every other bit 0.  Only enqueues."""
+        _lib.check(_lib.lib().zvec_hip_binary_encode_dev(self._h, C.c_void_p(d_in), int(count), int(dim),
+                                                         int(dim if encode_dims is None else encode_dims), float(threshold),
+                                                         C.c_void_p(d_out), C.c_void_p(stream or 0)), "zvec_hip_binary_encode_dev")
+
+    def binary_encode(self, rows, threshold=0.0, encode_dims=None):
+        """the same for host rows ([count][dim], anything numpy turns into fp32): returns the words, uint32 [count][ceil(dim / 32)]"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2:
+            raise ValueError("zvec_amd: binary_encode takes [count][dim] rows")
+        count, dim = rows.shape
+        out = np.zeros((count, (dim + 31) // 32), np.uint32)
+        _lib.check(_lib.lib().zvec_hip_binary_encode(self._h, _np_ptr(rows), count, dim, int(dim if encode_dims is None else encode_dims),
+                                                     float(threshold), _np_ptr(out)), "zvec_hip_binary_encode")
+        return out
+
     def synchronize(self):
         _lib.check(_lib.lib().zvec_hip_ctx_synchronize(self._h), "zvec_hip_ctx_synchronize")
 
@@ -414,6 +432,32 @@ class _FlatBase:
             self._keys_host.append(("range", n0, n0 + int(n)))
         return rc
 
+    def add_batch_fp32(self, rows, keys=None, threshold=0.0, encode_dims=None):
+        """fp32 rows into a "Hamming" index of binary32 rows (BinaryConverter in front of the builder): [n][dim] rows are turned into
+        sign bits on the GPU — bit i = rows[:, i] >= threshold for i < encode_dims (default: all dim values; the reference's converter
+        stops at 32 * ceil(dim / 32) // 2, include/zvec_hip.h) — and stored as add_batch stores the same words.  The index must hold
+        32 * ceil(dim / 32) bits."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2:
+            return IndexError_.InvalidArgument
+        n0 = self.count()
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        rc = _lib.lib().zvec_hip_flat_append_fp32(self._h, _np_ptr(rows), rows.shape[0], rows.shape[1],
+                                                  int(rows.shape[1] if encode_dims is None else encode_dims), float(threshold), _np_ptr(k))
+        if rc == 0 and rows.shape[0]:
+            self._keys_host.append(np.arange(n0, n0 + rows.shape[0], dtype=np.uint64) if k is None else k.copy())
+        return rc
+
+    def add_batch_fp32_dev(self, d_ptr, n, dim, d_keys_ptr=None, threshold=0.0, encode_dims=None, stream=None):
+        """add_batch_fp32 for rows already resident in HBM (device pointer, [n][dim] fp32 row-major); only enqueues"""
+        n0 = self.count()
+        rc = _lib.lib().zvec_hip_flat_append_fp32_dev(self._h, C.c_void_p(d_ptr), int(n), int(dim), int(dim if encode_dims is None else encode_dims),
+                                                      float(threshold), C.c_void_p(d_keys_ptr) if d_keys_ptr else None,
+                                                      C.c_void_p(stream) if stream else None)
+        if rc == 0 and d_keys_ptr is None and n:
+            self._keys_host.append(("range", n0, n0 + int(n)))
+        return rc
+
     def _all_keys(self):
         parts = []
         for p in self._keys_host:
@@ -479,6 +523,36 @@ class _FlatBase:
     # brute force == the flat scan itself (flat_streamer.cc:304-344)
     search_bf_impl = search_impl
 
+    def search_impl_fp32(self, queries, count, ctx, bin_threshold=0.0):
+        """search_impl of a "Hamming" index of binary32 rows with fp32 queries ([count][dim]): BinaryReformer::transform on the GPU
+        (every value against bin_threshold), then the search — results, filter and threshold as search_impl."""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim != 2 or q.shape[0] != int(count):
+            return IndexError_.InvalidArgument
+        k = ctx.topk()
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        counts = np.zeros(count, np.uint32)
+        if ctx._doc_filter is not None:
+            ex = self.build_filter(ctx._doc_filter, ctx)
+        else:
+            ex = ctx._exclude_for(self._all_keys()) if (ctx._filter_fn or ctx._exclude is not None) else None
+        rc = _lib.lib().zvec_hip_flat_search_fp32(self._h, ctx._h, _np_ptr(q), q.shape[1], float(bin_threshold), count, k, ctx.threshold(),
+                                                  _np_ptr(ex), _np_ptr(keys), _np_ptr(scores), _np_ptr(counts))
+        if rc == 0:
+            ctx._set_results(keys, scores, counts, self._vectors_of_keys)
+        return rc
+
+    def search_fp32_dev(self, d_queries, dim, count, topk, d_out_keys, d_out_scores, d_out_counts, ctx, bin_threshold=0.0,
+                        threshold=FLT_MAX, d_exclude=None, stream=None):
+        """device-pointer form of search_impl_fp32 (async): all arguments are raw device pointers (ints)."""
+        return _lib.lib().zvec_hip_flat_search_fp32_dev(
+            self._h, ctx._h, C.c_void_p(d_queries), int(dim), float(bin_threshold), count, topk, threshold,
+            C.c_void_p(d_exclude) if d_exclude else None, C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts),
+            C.c_void_p(stream) if stream else None)
+
     def _group_search(self, q, count, ctx, p_keys):
         """group_by_search_impl / group_by_search_p_keys_impl (flat_streamer.cc:391-483)"""
         if ctx._group_by is None:
@@ -535,6 +609,10 @@ class _FlatBase:
         if ctx.group_by_search():
             return self._group_search(q, count, ctx, p_keys)    # flat_streamer.cc:365-366
         ids, offs = self._p_keys_positions(p_keys, ctx)
+        return self._search_listed(q, ids, offs, count, ctx)
+
+    def _search_listed(self, q, ids, offs, count, ctx):
+        """query i against the storage positions ids[offs[i] .. offs[i + 1]) (zvec_hip_flat_search_by_ids)"""
         k = ctx.topk()
         keys_o = np.zeros((count, k), np.uint64)
         scores = np.zeros((count, k), np.float32)
@@ -545,6 +623,19 @@ class _FlatBase:
         if rc == 0:
             ctx._set_results(keys_o, scores, counts, self._vectors_of_keys)
         return rc
+
+    def search_by_positions_impl(self, query, positions, count, ctx):
+        """search_bf_by_p_keys_impl for a caller that already holds storage positions: positions[i] = the rows query i is compared
+        with (positions beyond the count and holes are skipped)."""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(query, self.np_dtype).reshape(-1)
+        if q.size != int(count) * self.row_words or len(positions) != count:
+            return IndexError_.InvalidArgument
+        lens = [len(p) for p in positions]
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+        ids = np.concatenate([np.asarray(p, np.uint32).reshape(-1) for p in positions] + [np.zeros(0 if offs[-1] else 1, np.uint32)])
+        return self._search_listed(q, np.ascontiguousarray(ids, np.uint32), offs, count, ctx)
 
     def batch_distance(self, query, positions, ctx=None):
         """IndexMetric::batch_distance: one query against the listed storage positions, scores in that order"""
@@ -646,6 +737,57 @@ class HipFlatSearcher(_FlatBase, _FlatFeatures):
 
     def load(self, vecs, keys=None):
         return self.add_batch(vecs, keys)
+
+
+class HipBinaryPreselectFlat:
+    """Pre-select on sign bits, re-score on the fp32 rows: the usual deployment of a binary-quantised index, composed of two flat
+    indexes that hold the same documents at the same storage positions —
+      bits   a "Hamming" index of 32 * ceil(dim / 32) bits, fed through add_batch_fp32 / search_impl_fp32 (bit i = value i >= threshold),
+      rows   an fp32 index of `dim` elements under `metric` ("SquaredEuclidean", "InnerProduct" or "Cosine"; `dim` is the index's
+             element dimension, so Cosine rows and queries are the converted ones, norm slot included).
+    search(queries, k, refine) takes min(n, k * refine) candidates per query from the bits and returns the k best of exactly those
+    by the fp32 index's listed-rows search (search_by_positions_impl): no scoring and no kernel of its own, and the contract of
+    that search for equal scores."""
+
+    def __init__(self, dim, metric, device=0, threshold=0.0):
+        if isinstance(metric, str):
+            metric = metric_from_name(metric)
+        if metric not in (METRIC_L2, METRIC_IP, METRIC_COSINE):
+            raise ValueError("zvec_amd: HipBinaryPreselectFlat re-scores under SquaredEuclidean, InnerProduct or Cosine")
+        self.dim = int(dim)
+        self.threshold = float(threshold)
+        self.bits = HipFlatSearcher((self.dim + 31) // 32 * 32, METRIC_HAMMING, device, "binary32")   # keys = storage positions
+        self.rows = HipFlatSearcher(self.dim, metric, device)                                          # keys = the caller's
+        self._bctx, self._rctx = self.bits.create_context(), self.rows.create_context()
+        self.candidates = None        # of the last search: (positions uint32 [count][k * refine], counts [count])
+
+    def count(self):
+        return self.rows.count()
+
+    def add_batch(self, rows, keys=None):
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            return IndexError_.InvalidArgument
+        if self.bits.count() != self.rows.count():
+            return IndexError_.Mismatch                     # (an earlier add_batch stored one half only)
+        rc = self.bits.add_batch_fp32(rows, None, self.threshold)
+        return rc if rc != 0 else self.rows.add_batch(rows, keys)
+
+    def search(self, queries, k, refine=4):
+        """returns (keys uint64 [count][k], scores fp32 [count][k], counts uint32 [count]), ascending by the fp32 score"""
+        q = np.ascontiguousarray(queries, np.float32)
+        n = self.count()
+        if q.ndim != 2 or q.shape[1] != self.dim or k <= 0 or refine <= 0 or n == 0:
+            raise ValueError("zvec_amd: HipBinaryPreselectFlat.search takes [count][dim] queries, k > 0, refine > 0 on a non-empty index")
+        count = q.shape[0]
+        self._bctx.set_topk(min(n, int(k) * int(refine)))
+        _lib.check(self.bits.search_impl_fp32(q, count, self._bctx, self.threshold), "HipBinaryPreselectFlat: binary stage")
+        pos, cnt = self._bctx.keys.astype(np.uint32), self._bctx.counts
+        self.candidates = (pos, cnt)
+        self._rctx.set_topk(int(k))
+        _lib.check(self.rows.search_by_positions_impl(q, [pos[i, :int(cnt[i])] for i in range(count)], count, self._rctx),
+                   "HipBinaryPreselectFlat: fp32 stage")
+        return self._rctx.keys, self._rctx.scores, self._rctx.counts
 
 
 class HipFlatSparseStreamer:
