@@ -106,6 +106,9 @@ const char *zvec_hip_error_string(int code); /* IndexError::What analogue */
  *   "sparse_group_rows"  0 .. 64: zvec_hip_sparse_search_grouped dumps the scores of a sub-batch of at most this many queries
  *               with a whole wave per stored row, of a wider one with a lane per query; 0 = never the former.  Same lists
  *               either way on exact data.
+ *   "sparse_inverted_build"  1 (default) = the inverted lists of a sparse index are built on the device; 0 = on the host, the
+ *               reference of the device build.  Read when a build starts.  The same bytes, and so the same search results,
+ *               either way.
  * Unsupported (-12) for an unknown name, invalid argument (-1) for a value outside the option's range. */
 int zvec_hip_set_option(const char *name, int value);
 int zvec_hip_get_option(const char *name, int *value);
@@ -751,6 +754,18 @@ int zvec_hip_sparse_set_inverted(zvec_hip_sparse_t h, int enable);
  * lists are on or off); builds: builds since the handle was created.  Every output nullable. */
 int zvec_hip_sparse_inverted_info(zvec_hip_sparse_t h, int *enabled, uint64_t *bytes, uint64_t *terms, uint32_t *tile_rows,
                                   uint64_t *builds);
+/* The lists as they are held, copied to host memory: terms[*nterms] ascending and distinct, list_off[*nterms + 1] (the last one is
+ * *elems), ppos[*elems] ascending inside every list, pval[*elems] in the handle's value type, bit for bit as stored.  Lists that are
+ * out of date are rebuilt first, as by a search.  *nterms and *elems are always written; the array pointers may be NULL to ask for
+ * the sizes only.  terms_cap counts the entries of `terms` (list_off has room for terms_cap + 1), elems_cap those of ppos and pval:
+ * ZVEC_HIP_ERR_OUT_OF_RANGE when a capacity of a non-NULL array is too small, ZVEC_HIP_ERR_UNSUPPORTED while the lists are off. */
+int zvec_hip_sparse_inverted_export(zvec_hip_sparse_t h, uint32_t *terms, uint64_t terms_cap, uint64_t *list_off, uint32_t *ppos,
+                                    void *pval, uint64_t elems_cap, uint64_t *nterms, uint64_t *elems);
+/* The build that made the lists held now: route 0 = host, 1 = device (option "sparse_inverted_build"), -1 while nothing is built;
+ * passes: 8-bit digit passes of the device build's sort, ceil(bits(OR of the stored indices) / 8), 0 on the host route; block_elems:
+ * elements one work-group of the device sort's scatter handles (a constant of the library, reported before any build); ms: wall-clock
+ * time of the build.  Every output nullable. */
+int zvec_hip_sparse_inverted_build_info(zvec_hip_sparse_t h, int *route, uint32_t *passes, uint32_t *block_elems, double *ms);
 /* Group-by over every row (FlatSparseEntity::search_group, flat_sparse_entity.h:79-103); see Group-by above. */
 int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
                                    const void *q_values, uint32_t count, const uint32_t *group_of_position, uint32_t ngroups,

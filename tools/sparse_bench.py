@@ -46,7 +46,18 @@ values: ms per step of both routes, the twin's build time (the first search afte
 its bytes and term count, and whether the two answers agree (every list full and ascending, scores within agreement_band of each
 other place by place).  Reported, not gated; InnerProductSparse only.
 
-    python tools/sparse_bench.py --inverted [--out profiles/sparse_inverted.json] [--steps 10] [--warmup 3]
+It then times ONE build of the twin on each route of the option "sparse_inverted_build" (0 = host, 1 = device: zvk_sparse_invb.hip.h)
+on the same handle: the lists are dropped and asked for again (set_inverted(0) / set_inverted(1)), one search forces the build, and
+zvec_hip_sparse_inverted_build_info tells its route, digit passes and wall-clock ms.  These go to --build-out with the box's
+streaming figure (zvec_hip_calibrate, same process) and the bytes the device build cannot avoid moving over that figure as its bound:
+
+  build bytes   per element: 4 read for the OR; per digit pass 4 read for the histogram, 4 (first pass: the indices) or 8 (key and
+                ordinal) read and 8 written for the scatter; 4 written for the positions; 2 x 4 read for the heads; 4 + 4 + value
+                read and 4 + value written for the postings; per row 8 read (row offsets); per term 12 written.  The count
+                tables are left out (1 / 2 byte per element and pass), and so is every miss of the scatter's and the gathers' lines.
+
+    python tools/sparse_bench.py --inverted [--out profiles/sparse_inverted.json] [--build-out profiles/sparse_inverted_build.json]
+                                 [--steps 10] [--warmup 3]
 """
 import argparse
 import ctypes as C
@@ -311,7 +322,7 @@ def inverted(args, metric):
         batches.append((batch, qc.numpy().astype(np.uint32), qi.to(dev), torch.rand(qi.numel(), generator=g, device=dev) * 2 - 1))
     ts = torch.cuda.Stream(device=dev)              # (a stream of its own: the null stream would mean "the context's stream")
     ts.wait_stream(torch.cuda.current_stream(dev))
-    runs = []
+    runs, builds = [], []
     for dtype in ("fp32", "fp16"):
         np_val = np.float16 if dtype == "fp16" else np.float32
         se = zvec_amd.HipFlatSparseStreamer(dtype=dtype)
@@ -366,12 +377,59 @@ def inverted(args, metric):
         assert info["builds"] == 1
         runs.append({"dtype": dtype, "elements": se.element_count(), "twin_bytes": info["bytes"], "twin_terms": info["terms"],
                      "tile_rows": info["tile_rows"], "build_ms": first_ms - legs[0]["inverted_ms"], "legs": legs})
+        # one build on each route, timed by the library
+        L = zvec_amd._lib.lib()
+        before = C.c_int(0)
+        assert L.zvec_hip_get_option(b"sparse_inverted_build", C.byref(before)) == 0
+        build = {"dtype": dtype, "rows": args.n, "elements": se.element_count(), "terms": info["terms"]}
+        b_keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        b_scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        b_counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        try:
+            for name, route in (("host", 0), ("device", 1)):
+                assert L.zvec_hip_set_option(b"sparse_inverted_build", route) == 0
+                se.set_inverted(False)
+                se.set_inverted(True)
+                assert se.search_dev(qc_np, d_qi.data_ptr(), qv.data_ptr(), batch, args.topk, b_keys.data_ptr(), b_scores.data_ptr(),
+                                     b_counts.data_ptr(), ctx, stream=ts.cuda_stream) == 0
+                torch.cuda.synchronize()
+                bi = se.inverted_build_info()
+                assert bi["route"] == route and se.inverted_info()["terms"] == info["terms"]
+                build[name + "_ms"] = bi["ms"]
+                if route:
+                    build.update(passes=bi["passes"], block_elems=bi["block_elems"])
+        finally:
+            assert L.zvec_hip_set_option(b"sparse_inverted_build", before.value) == 0
+        width = np.dtype(np_val).itemsize
+        per_element = 4 + sum(4 + (4 if p == 0 else 8) + 8 for p in range(build["passes"])) + 4 + 8 + (8 + width) + (4 + width)
+        build["device_bytes"] = build["elements"] * per_element + args.n * 8 + build["terms"] * 12
+        build["speedup"] = build["host_ms"] / build["device_ms"]
+        print(json.dumps(build), flush=True)
+        builds.append(build)
         del se, ctx
         torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for b in builds:
+        b["bound_ms"] = b["device_bytes"] / (gbs.value * 1e9) * 1e3
+        b["bound_fraction"] = b["bound_ms"] / b["device_ms"]
+    build_res = {"workload": "term-major twin of flat sparse IP %d rows x 64-192 of %d (Zipf): one build on each route of "
+                             "\"sparse_inverted_build\", one process" % (args.n, args.vocab),
+                 "timing": "zvec_hip_sparse_inverted_build_info's ms: wall clock of the build inside the first search after the lists were "
+                           "dropped and asked for again; one build each, not repeated", "clock_mhz": mhz.value, "stream_gbs": gbs.value,
+                 "bound": "device_bytes / stream_gbs (tools/sparse_bench.py, build bytes)", "builds": builds}
+    print(json.dumps(build_res))
+    if args.build_out:
+        with open(args.build_out, "w") as f:
+            json.dump(build_res, f, indent=1)
+            f.write("\n")
     return {"workload": "flat sparse IP %d rows x 64-192 of %d (Zipf), queries 16-64, k=%d: row scan and inverted lists, one process" % (
                 args.n, args.vocab, args.topk),
             "metric": metric, "timing": "device events around the steps of a device-pointer call on a stream; build_ms: wall clock of the "
-            "first search after zvec_hip_sparse_set_inverted (host build included) minus a later step", "agreement_band": agreement_band(metric),
+            "first search after zvec_hip_sparse_set_inverted (the build included) minus a later step", "agreement_band": agreement_band(metric),
             "steps": args.steps, "warmup": args.warmup, "runs": runs}
 
 
@@ -386,6 +444,8 @@ def main():
     ap.add_argument("--by-keys", action="store_true")
     ap.add_argument("--grouped", action="store_true")
     ap.add_argument("--inverted", action="store_true")
+    ap.add_argument("--build-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                        "sparse_inverted_build.json"), help="--inverted: where the build timings go")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
     ap.add_argument("--metric", choices=("ip", "l2"), default="ip")
     args = ap.parse_args()

@@ -174,6 +174,10 @@ SYMBOLS = {
     "zvec_hip_sparse_set_inverted": (C.c_int, [_h, C.c_int]),
     "zvec_hip_sparse_inverted_info": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                                 C.POINTER(C.c_uint64)]),
+    "zvec_hip_sparse_inverted_export": (C.c_int, [_h, _u32p, C.c_uint64, _u64p, _u32p, _valp, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]),
+    "zvec_hip_sparse_inverted_build_info": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                      C.POINTER(C.c_double)]),
     "zvec_hip_sparse_search_grouped": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
     "zvec_hip_sparse_search_grouped_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32,

@@ -103,6 +103,9 @@ struct RuntimeOpts {
   // grouped sparse full scan: a sub-batch of at most this many queries dumps its scores with sparse_rows_dump_kernel (a wave per
   // stored row), a wider one with sparse_scan_kernel (lane = query).  0 = never.  Default: DESIGN §3b "Group-by", from profiles/sparse_grouped*.json
   std::atomic<int> sparse_group_rows{32};
+  // how a stale term-major twin of a sparse index is rebuilt: 1 = on the device (zvk_sparse_invb.hip.h), 0 = on the host (the
+  // reference of the device build: the same bytes).  Read when a build starts.  DESIGN §3b "Inverted lists"
+  std::atomic<int> sparse_inverted_build{1};
   RuntimeOpts() {
     if (const char *e = getenv("ZVEC_HIP_SCAN256")) scan256 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("ZVEC_HIP_WAIT")) wait = std::max(0, std::min(2, atoi(e)));
@@ -529,6 +532,9 @@ struct InvertedTwin {
   uint64_t builds = 0;
   uint32_t nterms = 0;
   uint64_t elems = 0;         // postings
+  int route = -1;             // the build that made the arrays: 0 host, 1 device; -1 while nothing is built
+  uint32_t passes = 0;        // digit passes of that build's sort (0 on the host route)
+  double build_ms = 0.0;      // its wall-clock time
   Scoped<uint32_t> terms, ppos;
   Scoped<uint64_t> list_off;
   Scoped<void> pval;
@@ -537,6 +543,7 @@ struct InvertedTwin {
   void drop() {
     terms.release(); ppos.release(); list_off.release(); pval.release();
     nterms = 0; elems = 0; stale = true;
+    route = -1; passes = 0; build_ms = 0.0;
   }
 };
 

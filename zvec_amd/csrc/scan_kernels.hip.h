@@ -35,3 +35,4 @@
 #include "zvk_hamming.hip.h"
 #include "zvk_sparse.hip.h"
 #include "zvk_sparse_inv.hip.h"
+#include "zvk_sparse_invb.hip.h"

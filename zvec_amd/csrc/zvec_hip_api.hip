@@ -8,6 +8,7 @@
 #include <sched.h>
 #include <time.h>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

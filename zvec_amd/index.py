@@ -879,6 +879,26 @@ class HipFlatSparseStreamer:
         return {"enabled": bool(on.value), "bytes": int(nbytes.value), "terms": int(terms.value), "tile_rows": int(tile.value),
                 "builds": int(builds.value)}
 
+    def inverted_export(self):
+        """the inverted lists as they are held (zvec_hip_sparse_inverted_export; brought up to date first, as by a search):
+        (terms uint32 [nterms], list_off uint64 [nterms + 1], ppos uint32 [elements], pval [elements] in the handle's dtype)"""
+        L = _lib.lib()
+        nt, ne = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(L.zvec_hip_sparse_inverted_export(self._h, None, 0, None, None, None, 0, C.byref(nt), C.byref(ne)),
+                   "zvec_hip_sparse_inverted_export")
+        terms, list_off = np.zeros(nt.value, np.uint32), np.zeros(nt.value + 1, np.uint64)
+        ppos, pval = np.zeros(ne.value, np.uint32), np.zeros(ne.value, self.np_dtype)
+        _lib.check(L.zvec_hip_sparse_inverted_export(self._h, _np_ptr(terms), nt.value, _np_ptr(list_off), _np_ptr(ppos), _np_ptr(pval),
+                                                     ne.value, C.byref(nt), C.byref(ne)), "zvec_hip_sparse_inverted_export")
+        return terms, list_off, ppos, pval
+
+    def inverted_build_info(self):
+        """the build that made the lists held now (zvec_hip_sparse_inverted_build_info): route 0 host / 1 device / -1 none yet"""
+        route, passes, block, ms = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0.0)
+        _lib.check(_lib.lib().zvec_hip_sparse_inverted_build_info(self._h, C.byref(route), C.byref(passes), C.byref(block), C.byref(ms)),
+                   "zvec_hip_sparse_inverted_build_info")
+        return {"route": int(route.value), "passes": int(passes.value), "block_elems": int(block.value), "ms": float(ms.value)}
+
     def search_impl(self, counts, indices, values, count, ctx):
         """search_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, context) (flat_sparse_search.h:58-148)"""
         if ctx is None:
