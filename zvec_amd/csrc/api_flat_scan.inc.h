@@ -258,8 +258,11 @@ int refine_l2(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count, uint32_t
 // partial-list merges of small batches: four waves per query gather the survivors (see merge_kernel)
 inline uint32_t merge_threads(uint32_t count) { return count <= 256 ? 256u : 64u; }
 
-// merge_kernel's dynamic LDS: the list of k (score, slot, index) entries.  (It holds 1 KiB of static LDS beside it.)  The search
-// paths admit lists up to MERGE_LDS_MAX, the shard-merge entries up to SHARD_MERGE_LDS_MAX: DESIGN.md "One place per item".
+// merge_kernel's dynamic LDS: the list of k (score, slot, index) entries.  It holds 7172 bytes (7 KiB) of static LDS beside it: the
+// 512 gathered survivors (surv_hi 4 KiB, surv_lo 2 KiB), wave_min 1 KiB and the append counter.  The search paths admit lists up to
+// MERGE_LDS_MAX, the shard-merge entries up to SHARD_MERGE_LDS_MAX: DESIGN.md "One place per item".  From k = 4863 on the two
+// together pass 64 KiB; a work-group of gfx950 may take up to 160 KiB, and the launch needs no raised limit for it (the dynamic
+// part alone stays within 64 KiB): both largest lists, k = 5118 and k = 5460, launch and are pinned by tests/test_gpu_merge.py.
 inline size_t merge_lds_bytes(uint32_t k) { return (size_t)k * 12 + 16; }
 constexpr size_t MERGE_LDS_MAX = 60 * 1024, SHARD_MERGE_LDS_MAX = 64 * 1024;
 inline bool merge_fits(uint32_t k) { return merge_lds_bytes(k) <= MERGE_LDS_MAX; }
@@ -277,9 +280,12 @@ inline SearchOut out_from_row(const SearchOut &o, uint32_t q0, uint32_t k) {
 }
 
 // The four shapes of a merge.  What they share: the k best under `threshold` into `out`, keys through `keymap` (nullptr: positions).
+// The threshold is clamped to FLT_MAX here, where every route passes: holes and the unused tail of a list score +inf with the index
+// IDX_NONE, and merge_kernel keeps them out only because +inf never passes its bound (a caller's +inf for "no radius" would admit
+// them and read keymap[IDX_NONE]).  (std::min, as the sparse entries clamp: a NaN threshold stays NaN and admits nothing.)
 inline MergeArgs merge_into(uint32_t k, float threshold, const uint64_t *keymap, const SearchOut &out) {
   MergeArgs m{};
-  m.slot_stride = 1; m.k = k; m.threshold = threshold; m.keymap = keymap;
+  m.slot_stride = 1; m.k = k; m.threshold = std::min(threshold, FLT_MAX); m.keymap = keymap;
   m.out_keys = out.keys; m.out_scores = out.scores; m.out_idx = out.idx; m.out_counts = out.counts;
   return m;
 }
