@@ -440,6 +440,19 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
 int zvec_hip_ctx_profile(zvec_hip_ctx_t ctx, int enable);
 int zvec_hip_ctx_profile_read(zvec_hip_ctx_t ctx, uint64_t *launches, double *scan_ms,
                               double *algorithmic_bytes, double *algorithmic_flops, int reset);
+/* Which route the last flat search on ctx took (zvec_hip_flat_search / _search_dev over fp rows): the profile above names a
+ * launch by its duration only, this names it by what the host dispatched.  Cleared when such a search starts; a search that
+ * went in slices ORs them.  Host bookkeeping, no device call.  Defined only straight after such a search: every other
+ * search kind on the context (IVF, whose coarse pass is a flat scan; k-means labelling; group-by, by-ids, Hamming and
+ * sparse searches) leaves the word undefined — they may OR bits into it and never clear it.
+ *   bits 0..8    shape of the main scan: 0 dense-score path, 1 / 2 / 3 the 4-wave tile with 1 / 2 / 4 query groups, 4 the 16-row
+ *                shape, 5 the 8-wave 128 x 128 tile, 6 the 256 x 256 fp16 tile, 7 the gathering 8-wave tile (sparse keep-set),
+ *                8 the kept rows were copied to a compacted store first (the scan of the copy sets its own shape bit as well)
+ *   bit 9        the main scan ran its exclusion variant
+ *   bits 10..11  seeding of the shared admission bounds: 0 none, 1 the k-th of 256 minima of a dense prefix dump, 2 the k-th score
+ *                of a prefix scan with lists
+ *   bits 16..25  seeding 2 only: bits 0..9 of the prefix scan itself */
+int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route);
 
 /* Per-box calibration for the measurement line (bench.py `roofline.box_clock_mhz` / `box_stream_gbs`): what this box's HBM delivers
  * to a pure streaming reader (16-byte non-temporal loads over `bytes` of device memory: d_buf, or a scratch allocation when NULL),

@@ -179,6 +179,18 @@ def test_runtime_options_round_trip_without_a_gpu():
     assert L.zvec_hip_set_option(None, 1) != 0
 
 
+def test_route_read_back_validates_its_arguments_without_a_gpu():
+    """zvec_hip_ctx_last_route is host bookkeeping: declared, bound and exported (the symbol tests above), and it refuses a null
+    context or a null output before touching anything"""
+    import ctypes as C
+    from zvec_amd import _lib
+    L = _lib.lib()
+    assert "zvec_hip_ctx_last_route" in _declared_symbols() and "zvec_hip_ctx_last_route" in _lib.SYMBOLS
+    r = C.c_uint32(123)
+    assert L.zvec_hip_ctx_last_route(None, C.byref(r)) == -31 and r.value == 123
+    assert L.zvec_hip_ctx_last_route(None, None) == -31
+
+
 def test_shadow_entry_points_refuse_null_handles_without_a_gpu():
     """the half-width pre-selection entry points (zvec_hip_ivf_set_shadow / zvec_hip_flat_set_shadow and their _info / _certify
     companions) validate their arguments before any device call"""

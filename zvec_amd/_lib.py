@@ -185,6 +185,7 @@ SYMBOLS = {
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    "zvec_hip_ctx_last_route": (C.c_int, [_h, C.POINTER(C.c_uint32)]),
 }
 
 _LIB = None

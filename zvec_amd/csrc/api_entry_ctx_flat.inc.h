@@ -548,6 +548,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
   // the kernels address the padded query matrix with 32-bit word offsets: very large batches go in slices
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(h->st.dpad, 1u));
   c->sh.count = 0;
+  c->route = 0;                 // (zvec_hip_ctx_last_route: what this search launches)
   // Half-width pre-selection (zvk_shadow.hip.h, as for the IVF lists): the scan streams the fp16 twin of the store for k' rows per
   // query — half the bytes of a small batch's HBM-bound scan, and fp16 matrix work instead of fp32 for a wide one —, those are
   // re-scored on the fp32 rows, the k best certified; zvec_hip_flat_shadow_certify re-runs what fails.

@@ -86,6 +86,14 @@ int zvec_hip_ctx_profile(zvec_hip_ctx_t ctx, int enable) {
   return 0;
 }
 
+// which route the context's last flat search took: host bookkeeping only, no device call
+int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route) {
+  if (!ctx || !route) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *route = ctx->route;
+  return 0;
+}
+
 int zvec_hip_ctx_profile_read(zvec_hip_ctx_t ctx, uint64_t *launches, double *scan_ms, double *algorithmic_bytes,
                               double *algorithmic_flops, int reset) {
   if (!ctx) return ZVEC_HIP_ERR_INVALID_ARGUMENT;

@@ -358,6 +358,17 @@ int empty_results(uint64_t *keys, uint32_t *counts, uint32_t count, uint32_t top
   return 0;
 }
 
+// Route read-back (zvec_hip_ctx_last_route, include/zvec_hip.h): a user-facing flat search clears ctx->route, flat_scan_prepared and
+// flat_scan_gather OR in what they launch.  Written on the host only; nothing reads it to decide anything.
+//   bits 0..8   the main scan's shape, bit 9 whether its exclusion variant ran
+//   bits 10..11 how the shared bounds were seeded (ROUTE_SEED_*)
+//   bits 16..25 shape (and exclusion bit) of the seeding prefix's own scan, where that is a scan with lists: the recursive
+//               flat_scan_prepared, flat_scan_gather's gathered prefix.  (seed_bound_kernel reads a dense dump: no shape.)
+constexpr uint32_t ROUTE_DENSE = 1u << 0, ROUTE_NG1 = 1u << 1, ROUTE_NG2 = 1u << 2, ROUTE_NG4 = 1u << 3, ROUTE_M16 = 1u << 4,
+                   ROUTE_SCAN8 = 1u << 5, ROUTE_SCAN256 = 1u << 6, ROUTE_GATHER = 1u << 7, ROUTE_COMPACT = 1u << 8,
+                   ROUTE_EXCL = 1u << 9, ROUTE_SEED_SHIFT = 10, ROUTE_SEED_BOUND = 1u << ROUTE_SEED_SHIFT,
+                   ROUTE_SEED_GTAU = 2u << ROUTE_SEED_SHIFT, ROUTE_PREFIX_SHIFT = 16, ROUTE_SHAPE_MASK = 0x3ffu;
+
 // Sparse keep-set scan WITHOUT copying the kept rows: the wide kernel fetches the rows of a logical tile straight from
 // their stored positions (LDS-DMA with per-lane source addresses: every 128-byte row segment is still one full line).
 // `d_pos`: ascending kept positions, padded to whole tiles (+1 tile) with position 0; `kept` logical rows.
@@ -379,9 +390,11 @@ int flat_scan_gather(zvec_hip_ctx_s *ctx, const StoreView &st, const uint32_t *d
     ZRET(launch_scan8(d, st.f16, ((d.nchunks + 7) / 8) * 8 * nqtiles, cus, stream));
     ZRET(launch_merge(merge_dense_rows(d.dump, SEED_ROWS, topk, threshold, nullptr, so), count, 64, stream));
     hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
-                       so.scores, so.idx, d_pos, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
+                       so.scores, so.idx, d_pos, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk, threshold);
     ZCHK(hipGetLastError());
+    ctx->route |= ROUTE_SEED_GTAU | (ROUTE_GATHER << ROUTE_PREFIX_SHIFT);
   }
+  ctx->route |= ROUTE_GATHER;
   int occ8 = 1;
   a.k = topk;
   ZRET(launch_scan8(a, st.f16, 0, cus, stream, &occ8));
@@ -558,6 +571,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
       tmp.base = ctx->cmp_base.as<float>(); tmp.bnorm = ctx->cmp_norm.as<float>();
       tmp.extra = st.extra ? ctx->cmp_extra.as<float>() : nullptr; tmp.keys = ctx->cmp_keys.as<uint64_t>();
       tmp.n = kept;
+      ctx->route |= ROUTE_COMPACT;
       return flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, role);
     }
   }
@@ -579,6 +593,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     const bool want_b = pick_ng(count, topk) < 1;
     if (want_b && !k_fits_merge) return ZVEC_HIP_ERR_UNSUPPORTED;
     if ((want_a || want_b) && k_fits_merge) {
+      ctx->route |= ROUTE_DENSE | (d_exclude ? ROUTE_EXCL : 0u);
       // sub-batches so that the score matrix stays <= 1 GiB
       const uint32_t sub = dense_sub_batch(count, ntiles_d * TILE_N);
       ZRET(ctx->part_s.ensure((size_t)ntiles_d * TILE_N * 4 * sub));
@@ -624,10 +639,19 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
       hipLaunchKernelGGL(seed_bound_kernel, dim3(count), dim3(256), 0, stream, dump, dump_stride, (uint32_t)SEED_ROWS, ctx->gtau.as<uint32_t>(),
                          ctx->qnorm.as<float>(), st.bnorm, st.metric, topk);
       ZCHK(hipGetLastError());
+      ctx->route |= ROUTE_SEED_BOUND;
     } else {
+      // The prefix scan is a fused scan of its own: its work-groups publish their full lists' k-th scores into ctx->gtau as they
+      // go, WITHOUT slack, and in the summation order of ITS tile shape.  None of that may reach the main scan: seed_gtau_kernel
+      // STORES the bound (the slacked k-th score under the threshold, or the threshold alone for a short list), it does not fold
+      // it into what the prefix scan left behind.
+      const uint32_t outer = ctx->route;
+      ctx->route = 0;
       ZRET(flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal));
+      ctx->route = outer | ROUTE_SEED_GTAU | ((ctx->route & ROUTE_SHAPE_MASK) << ROUTE_PREFIX_SHIFT);
       hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
-                         so.scores, so.idx, (const uint32_t *)nullptr, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk);
+                         so.scores, so.idx, (const uint32_t *)nullptr, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk,
+                         threshold);
       ZCHK(hipGetLastError());
     }
   }
@@ -676,6 +700,8 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
   prof_end(ctx, stream, pi);
   if (profile_it) gate_leave(ctx, stream);
   ZRET(lrc);
+  ctx->route |= (wide256 ? ROUTE_SCAN256 : wide ? ROUTE_SCAN8 : m16_small ? ROUTE_M16 : ng == 4 ? ROUTE_NG4 : ng == 2 ? ROUTE_NG2 : ROUTE_NG1) |
+                (d_exclude ? ROUTE_EXCL : 0u);
 
   ZRET(launch_merge(merge_partials(a.part_s, a.part_i, nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), stream));
   if (user_facing) ZRET(refine_l2(ctx, st, count, topk, threshold, out.keys, out.scores, out.idx, out.counts, stream));

@@ -400,6 +400,7 @@ struct zvec_hip_ctx_s {
   std::vector<uint32_t> prof_dscan;
   int nprof = 0;
   int cus = 0;
+  uint32_t route = 0;                                  // which flat scan route the last user-facing flat search took (ROUTE_*, api_flat_scan.inc.h)
   // (the workspace members free themselves afterwards)
   ~zvec_hip_ctx_s() {
     (void)hipSetDevice(device);

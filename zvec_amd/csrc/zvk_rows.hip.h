@@ -153,7 +153,9 @@ __global__ void ivf_reset_kernel(uint32_t *zero0, uint32_t nzero, uint32_t *queu
   if (i < nlist) list_tpc[i] = level_tpc(list_tail[i], tpc);
 }
 
-// gtau[q] = min(gtau[q], k-th score of a sample scan + slack) — only for full sample lists.
+// gtau[q] = min(threshold, k-th score of a sample scan + slack) for a full sample list, the threshold for a short one: a STORE.
+// Whatever the sample scan itself left in gtau (a fused scan publishes its full lists' k-th scores there, without slack and in its
+// own tile shape's summation order) is overwritten, so the only seeded value the main scan ever sees carries the slack.
 // The k-th best score of ANY subset of the rows bounds the final k-th score from above, so starting every
 // work-group of the main scan at that bound drops nothing it could keep; it only spares the list warm-up.
 // Slack: the sample scan and the main scan may sum the same row's dot product in different orders (different tile
@@ -163,9 +165,11 @@ __global__ void ivf_reset_kernel(uint32_t *zero0, uint32_t nzero, uint32_t *queu
 // sample's winners (through `pos_map` when the sample was a gathered view).
 __global__ void seed_gtau_kernel(uint32_t *gtau, const float *scores, const uint32_t *idx, const uint32_t *pos_map,
                                  const uint32_t *counts, const float *qnorm, const float *bnorm, int metric, uint32_t n,
-                                 uint32_t k) {
+                                 uint32_t k, float threshold) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || counts[i] < k) return;
+  if (i >= n) return;
+  const uint32_t tkey = fkey(threshold);
+  if (counts[i] < k) { gtau[i] = tkey; return; }
   const float s = scores[(size_t)i * k + (k - 1)];
   float bmax = 0.f;
   for (uint32_t j = 0; j < k; ++j) {
@@ -175,7 +179,7 @@ __global__ void seed_gtau_kernel(uint32_t *gtau, const float *scores, const uint
   }
   const float mag = (metric == 0) ? qnorm[i] + bmax : sqrtf(qnorm[i] * bmax);
   const float b = s + 8e-6f * mag + fabsf(s) * 1e-6f + 1e-30f;
-  if (b == b) atomicMin(&gtau[i], fkey(b));
+  gtau[i] = (b == b) ? min(tkey, fkey(b)) : tkey;
 }
 
 

@@ -371,6 +371,12 @@ class IndexContext:
                                                         C.byref(f), int(reset)), "profile_read")
         return {"launches": int(n.value), "scan_ms": ms.value, "bytes": b.value, "flops": f.value}
 
+    def last_route(self):
+        """route word of the last flat search on this context (zvec_hip_ctx_last_route: main shape, exclusion, seeding, prefix shape)"""
+        r = C.c_uint32(0)
+        _lib.check(_lib.lib().zvec_hip_ctx_last_route(self._h, C.byref(r)), "zvec_hip_ctx_last_route")
+        return int(r.value)
+
 
 def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
