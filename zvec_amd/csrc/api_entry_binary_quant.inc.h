@@ -26,8 +26,8 @@ inline bool benc_handle_pairs(const zvec_hip_flat_s *h, uint32_t dim) {
   return h->dtype == ZVEC_HIP_DT_BINARY32 && h->st.dim_in == benc_words(dim) * 32u;
 }
 
-// `m` fp32 device rows -> sign bits -> the store, through h->enc in slices; the caller holds h->mu and h->rw (exclusive), has
-// reserved the store for the rows and ordered `s` behind earlier appends
+// `m` fp32 device rows -> sign bits -> the store, through h->enc in slices; the caller is inside a FlatWrite on `s` and has
+// reserved the store for the rows
 int flat_append_encoded(zvec_hip_flat_s *h, const float *d_rows, uint64_t m, uint32_t dim, uint32_t encode_dims, float threshold,
                         const uint64_t *d_keys, hipStream_t s) {
   const uint32_t words = benc_words(dim);
@@ -82,23 +82,12 @@ int zvec_hip_flat_append_fp32_dev(zvec_hip_flat_t h, const float *d_vecs, uint64
   if (!benc_handle_pairs(h, dim)) return ZVEC_HIP_ERR_MISMATCH;
   if (n == 0) return 0;
   if (!d_vecs) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = pick_stream(h->defctx, stream);
-  ZRET(flat_order_after_appends(h, s));                // (an earlier append on another stream; a growing store is copied on `s`)
+  FlatWrite w(h);
+  ZRET(w.open(stream));
   // everything that can refuse comes before the first row is stored: all of the rows or none
   if (h->st.n + n >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  ZRET(h->st.reserve(h->st.n + n, s));
-  int rc = flat_append_encoded(h, d_vecs, n, dim, encode_dims, threshold, d_keys, s);
-  if (rc == 0) rc = flat_holes_cover(h, s);
-  if (rc == 0) rc = flat_publish_async(h, ~0u, s);
-  if (rc == 0 && s != h->defctx->own) {              // (as zvec_hip_flat_append_dev: the caller's stream may not outlive this call)
-    if (!h->append_ev) ZCHK(hipEventCreateWithFlags(&h->append_ev, hipEventDisableTiming));
-    ZCHK(hipEventRecord(h->append_ev, s));
-    h->append_dirty = false;
-  }
-  return rc;
+  ZRET(h->st.reserve(h->st.n + n, w.s));
+  return w.finish_enqueued(flat_append_encoded(h, d_vecs, n, dim, encode_dims, threshold, d_keys, w.s));
 }
 
 int zvec_hip_flat_append_fp32(zvec_hip_flat_t h, const float *vecs, uint64_t n, uint32_t dim, uint32_t encode_dims, float threshold,
@@ -107,26 +96,26 @@ int zvec_hip_flat_append_fp32(zvec_hip_flat_t h, const float *vecs, uint64_t n, 
   if (!benc_handle_pairs(h, dim)) return ZVEC_HIP_ERR_MISMATCH;
   if (n == 0) return 0;
   if (!vecs) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
-  ZRET(flat_order_after_appends(h, s));
+  FlatWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = w.s;
   if (h->st.n + n >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
   ZRET(h->st.reserve(h->st.n + n, s));
   const uint64_t rows_per = std::max<uint64_t>(1, BENC_SLICE_BYTES / ((uint64_t)dim * 4));
   DevBuf tmp, tk;
   ZRET(tmp.ensure((size_t)std::min(rows_per, n) * dim * 4));
   if (keys) ZRET(tk.ensure((size_t)std::min(rows_per, n) * 8));
-  for (uint64_t o = 0; o < n; o += rows_per) {
-    const uint64_t m = std::min(rows_per, n - o);
-    ZCHK(hipMemcpyAsync(tmp.p, vecs + (size_t)o * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, s));
-    if (keys) ZCHK(hipMemcpyAsync(tk.p, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    ZRET(flat_append_encoded(h, tmp.as<float>(), m, dim, encode_dims, threshold, keys ? tk.as<uint64_t>() : nullptr, s));
-    ZRET(flat_holes_cover(h, s));
-    ZCHK(hipStreamSynchronize(s));
-  }
-  return 0;
+  auto slices = [&]() -> int {
+    for (uint64_t o = 0; o < n; o += rows_per) {
+      const uint64_t m = std::min(rows_per, n - o);
+      ZCHK(hipMemcpyAsync(tmp.p, vecs + (size_t)o * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, s));
+      if (keys) ZCHK(hipMemcpyAsync(tk.p, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
+      ZRET(flat_append_encoded(h, tmp.as<float>(), m, dim, encode_dims, threshold, keys ? tk.as<uint64_t>() : nullptr, s));
+      ZCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+  };
+  return w.finish_synced(slices());
 }
 
 int zvec_hip_flat_search_fp32_dev(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t dim, float bin_threshold,

@@ -149,25 +149,20 @@ int zvec_hip_flat_destroy(zvec_hip_flat_t h) {
   return 0;
 }
 
-int zvec_hip_flat_reserve(zvec_hip_flat_t h, uint64_t capacity) {
-  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  return h->st.reserve(capacity, h->defctx->own);
-}
-
-// the device copy of the hole bits has to span the store whenever holes exist (caller holds h->rw exclusively)
-static int flat_holes_cover(zvec_hip_flat_s *h, hipStream_t s) {
-  if (h->nholes == 0) return 0;
+// The device copy of the hole bits (caller holds h->rw exclusively): it spans the store whenever holes exist, and follows the host
+// words [lo, hi] that a put changed (lo > hi: none).  After a reallocation everything is uploaded, else the changed words only.
+static int flat_holes_cover(zvec_hip_flat_s *h, hipStream_t s, uint64_t lo = ~0ull, uint64_t hi = 0) {
+  if (h->nholes == 0 && !(h->d_holes.p && lo <= hi)) return 0;       // (no hole, and no bit to clear in a copy made earlier)
   const uint64_t words = (h->st.n + 63) / 64 + 1;
   h->h_holes.resize(words, 0);
-  if (words * 8 <= h->d_holes.cap) return 0;
-  ZRET(h->d_holes.ensure(words * 16));
-  ZCHK(hipMemsetAsync(h->d_holes.p, 0, h->d_holes.cap, s));
-  ZCHK(hipMemcpyAsync(h->d_holes.p, h->h_holes.data(), words * 8, hipMemcpyHostToDevice, s));
-  ZCHK(hipStreamSynchronize(s));
+  if (words * 8 > h->d_holes.cap) {
+    ZRET(h->d_holes.ensure(words * 16));
+    ZCHK(hipMemsetAsync(h->d_holes.p, 0, h->d_holes.cap, s));
+    lo = 0; hi = words - 1;
+  }
+  if (lo > hi) return 0;
+  ZCHK(hipMemcpyAsync(h->d_holes.as<uint64_t>() + lo, h->h_holes.data() + lo, (size_t)(std::min(hi, words - 1) - lo + 1) * 8, hipMemcpyHostToDevice, s));
+  ZCHK(hipStreamSynchronize(s));                 // (h_holes is pageable and may be resized by the next call)
   return 0;
 }
 
@@ -188,8 +183,8 @@ static int flat_ring_slot(zvec_hip_flat_s *h, char **rows, uint64_t **keys, uint
   *slot = sl;
   return 0;
 }
-// an asynchronous mutation has been enqueued on `s`: note it for the readers (flat_wait_appends); slot = the ring slot
-// its kernels read, or ~0u
+// an asynchronous mutation has been enqueued on `s`: note it for whoever enqueues on another stream next (flat_order_after_appends);
+// slot = the ring slot its kernels read, or ~0u
 static int flat_publish_async(zvec_hip_flat_s *h, uint32_t slot, hipStream_t s) {
   if (slot != ~0u && slot % zvec_hip_flat_s::RING_GROUP == zvec_hip_flat_s::RING_GROUP - 1) {
     const uint32_t grp = slot / zvec_hip_flat_s::RING_GROUP;
@@ -202,45 +197,78 @@ static int flat_publish_async(zvec_hip_flat_s *h, uint32_t slot, hipStream_t s) 
   h->append_dirty = true;
   return 0;
 }
-// a mutation is about to be enqueued on `s`: it must follow the ones enqueued on another stream (caller holds rw exclusively)
-static int flat_order_after_appends(zvec_hip_flat_s *h, hipStream_t s) {
-  if (!h->append_pending || h->append_stream == s) return 0;
-  if (!h->append_ev) ZCHK(hipEventCreateWithFlags(&h->append_ev, hipEventDisableTiming));
-  if (h->append_dirty) { ZCHK(hipEventRecord(h->append_ev, h->append_stream)); h->append_dirty = false; }
-  ZCHK(hipStreamWaitEvent(s, h->append_ev, 0));
-  return 0;
-}
-// a reader is about to enqueue work on `s` (caller holds rw shared): see zvec_hip_flat_s::append_ev
-static int flat_wait_appends(zvec_hip_flat_s *h, hipStream_t s) {
+// work is about to be enqueued on `s`: it must follow the mutations that are only enqueued on another stream (see
+// zvec_hip_flat_s::append_ev).  Readers hold rw shared, run concurrently and pass h->ev_mu; a writer holds rw exclusively and passes null.
+static int flat_order_after_appends(zvec_hip_flat_s *h, hipStream_t s, std::mutex *ev_mu) {
   if (!h->append_pending || h->append_stream == s) return 0;
   {
-    std::lock_guard<std::mutex> g(h->ev_mu);
+    std::unique_lock<std::mutex> g;
+    if (ev_mu) g = std::unique_lock<std::mutex>(*ev_mu);
     if (!h->append_ev) ZCHK(hipEventCreateWithFlags(&h->append_ev, hipEventDisableTiming));
     if (h->append_dirty) { ZCHK(hipEventRecord(h->append_ev, h->append_stream)); h->append_dirty = false; }
   }
   ZCHK(hipStreamWaitEvent(s, h->append_ev, 0));
   return 0;
 }
+// a reader is about to enqueue work on `s` (caller holds rw shared)
+static int flat_wait_appends(zvec_hip_flat_s *h, hipStream_t s) { return flat_order_after_appends(h, s, &h->ev_mu); }
 
-int zvec_hip_flat_append_dev(zvec_hip_flat_t h, const void *d_vecs, uint64_t n, const uint64_t *d_keys, void *stream) {
-  if (!h || (!d_vecs && n)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = pick_stream(h->defctx, stream);
-  ZRET(flat_order_after_appends(h, s));                                    // (an earlier append on another stream)
-  int rc = store_append_dev(h->st, d_vecs, n, d_keys, s);
-  if (rc == 0) rc = flat_holes_cover(h, s);
-  // the row count is published now, the pack kernel is only enqueued on `s`: readers on other streams wait for it
-  if (rc == 0 && n) rc = flat_publish_async(h, ~0u, s);
-  if (rc == 0 && n && s != h->defctx->own) {
-    // the caller's stream may not outlive this call: its event is recorded now, not when a reader first needs it
+// One mutation of a flat store, from the locks to what readers are told (the rules: zvec_hip_flat_s::append_ev).  It holds h->mu, then
+// h->rw exclusively, while it lives.  open() readies the stream `s`; an entry that stores rows enqueues its copies and packs there and
+// returns through one of the two endings.  An ending runs whatever `rc` is — rows stored before a failure are covered and published like any others —
+// and returns the first error.
+struct FlatWrite {
+  zvec_hip_flat_s *const h;
+  hipStream_t s = nullptr;
+  explicit FlatWrite(zvec_hip_flat_s *h_) : h(h_), g(h_->mu), w(h_->rw) {}
+  // `stream`: the caller's, or null for the store's own
+  int open(void *stream = nullptr) {
+    ZCHK(hipSetDevice(h->device));
+    s = stream ? reinterpret_cast<hipStream_t>(stream) : h->defctx->own;
+    h->shadow.drop();                                // any mutation: the fp16 twin no longer mirrors the store
+    // an earlier append may still be only enqueued on another stream: a growing store is copied on `s`, rows are overwritten on `s`
+    return flat_order_after_appends(h, s, nullptr);
+  }
+  // the call returns with work only enqueued on `s`: the row count is published now, so readers on other streams must wait for `s`.
+  // slot = the ring slot the work reads, or ~0u; [lo, hi] = the hole words it changed
+  int finish_enqueued(int rc, uint32_t slot = ~0u, uint64_t lo = ~0ull, uint64_t hi = 0) {
+    int e = flat_holes_cover(h, s, lo, hi);
+    if (e == 0) e = flat_publish_async(h, slot, s);
+    // a caller's stream may not outlive this call: its event is recorded now, not when a reader first needs it
+    if (e == 0 && s != h->defctx->own) e = record_now();
+    return rc ? rc : e;
+  }
+  // the call returns with `s` drained: whatever it copied out of the caller's memory or through its own temporaries is done
+  int finish_synced(int rc, uint64_t lo = ~0ull, uint64_t hi = 0) {
+    const int e = flat_holes_cover(h, s, lo, hi);
+    const hipError_t he = hipStreamSynchronize(s);
+    return rc ? rc : e ? e : he != hipSuccess ? ZVEC_HIP_ERR_RUNTIME : 0;
+  }
+
+ private:
+  std::lock_guard<std::mutex> g;
+  std::unique_lock<FairSharedMutex> w;
+  int record_now() {
     if (!h->append_ev) ZCHK(hipEventCreateWithFlags(&h->append_ev, hipEventDisableTiming));
     ZCHK(hipEventRecord(h->append_ev, s));
     h->append_dirty = false;
+    return 0;
   }
-  return rc;
+};
+
+int zvec_hip_flat_reserve(zvec_hip_flat_t h, uint64_t capacity) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  FlatWrite w(h);
+  ZRET(w.open());
+  return h->st.reserve(capacity, w.s);               // (no row is stored: nothing to cover or publish, and a growing reserve has synchronised)
+}
+
+int zvec_hip_flat_append_dev(zvec_hip_flat_t h, const void *d_vecs, uint64_t n, const uint64_t *d_keys, void *stream) {
+  if (!h || (!d_vecs && n)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  FlatWrite w(h);
+  ZRET(w.open(stream));
+  if (n == 0) return 0;
+  return w.finish_enqueued(store_append_dev(h->st, d_vecs, n, d_keys, w.s));     // the pack kernel is only enqueued
 }
 
 // FlatSearcher::load of a dumped "flat.features"-style segment (FlatBuilder<32>::write_row_index / write_column_index,
@@ -253,11 +281,9 @@ int zvec_hip_flat_load_features(zvec_hip_flat_t h, const void *features, uint64_
   if (count == 0) return 0;
   const uint64_t elem = h->st.row_bytes();
   if (bytes < count * elem) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  FlatWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = w.s;
   Scoped<uint8_t> d_body;
   Scoped<char> d_rows;
   Scoped<uint64_t> d_tab, d_keys;
@@ -277,10 +303,7 @@ int zvec_hip_flat_load_features(zvec_hip_flat_t h, const void *features, uint64_
   a.rows = reinterpret_cast<uint8_t *>(static_cast<char *>(d_rows)); a.total = count;
   hipLaunchKernelGGL(ivf_body_rows_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, a);
   ZCHK(hipGetLastError());
-  int rc = store_append_dev(h->st, d_rows, count, keys ? static_cast<const uint64_t *>(d_keys) : nullptr, s);
-  if (rc == 0) rc = flat_holes_cover(h, s);
-  ZCHK(hipStreamSynchronize(s));
-  return rc;
+  return w.finish_synced(store_append_dev(h->st, d_rows, count, keys ? static_cast<const uint64_t *>(d_keys) : nullptr, s));
 }
 
 // FlatStreamerEntity's persisted rows (flat_streamer_entity.cc:43-47, flat_streamer_entity.h:287-311): a storage segment is a run
@@ -316,11 +339,9 @@ int zvec_hip_flat_load_blocks(zvec_hip_flat_t h, const void *blocks, uint64_t by
   }
   const uint64_t kept = src.size();
   if (kept == 0) return 0;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  FlatWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = w.s;
   // everything that can refuse comes before the first asynchronous copy out of the local arrays
   if (h->st.n + kept >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
   ZRET(h->st.reserve(h->st.n + kept, s));
@@ -329,31 +350,24 @@ int zvec_hip_flat_load_blocks(zvec_hip_flat_t h, const void *blocks, uint64_t by
   ZRET(d_rows.alloc(nblocks * rows_bytes));
   ZRET(d_src.alloc(kept));
   ZRET(d_keys.alloc(kept));
-  int rc = 0;
   auto copies = [&]() -> int {
     ZCHK(hipMemcpy2DAsync(d_rows, rows_bytes, blocks, block_size, rows_bytes, nblocks, hipMemcpyHostToDevice, s));
     ZCHK(hipMemcpyAsync(d_src, src.data(), kept * 8, hipMemcpyHostToDevice, s));
     ZCHK(hipMemcpyAsync(d_keys, keys.data(), kept * 8, hipMemcpyHostToDevice, s));
     return 0;
   };
-  rc = copies();
+  int rc = copies();
   if (rc == 0) rc = launch_pack(h->st, d_rows, kept, d_src, h->st.n, nullptr, s, h->st.keys, d_keys);
-  if (rc == 0) {
-    h->st.n += kept;
-    rc = flat_holes_cover(h, s);
-  }
-  (void)hipStreamSynchronize(s);          // on every path: the copies read `src` / `keys` / `blocks`, the device temporaries go away
-  return rc;
+  if (rc == 0) h->st.n += kept;
+  return w.finish_synced(rc);             // synchronises on every path: the copies read `src` / `keys` / `blocks`, the device temporaries go away
 }
 
 int zvec_hip_flat_append(zvec_hip_flat_t h, const void *vecs, uint64_t n, const uint64_t *keys) {
   if (!h || (!vecs && n)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  FlatWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = w.s;
   const size_t rb = h->st.row_bytes();
   if (n <= zvec_hip_flat_s::FAST_ROWS) {              // a document at a time: pinned ring, nothing to wait for
     char *prow = nullptr;
@@ -362,26 +376,24 @@ int zvec_hip_flat_append(zvec_hip_flat_t h, const void *vecs, uint64_t n, const 
     ZRET(flat_ring_slot(h, &prow, &pkey, &slot));
     memcpy(prow, vecs, (size_t)n * rb);
     if (keys) memcpy(pkey, keys, (size_t)n * 8);
-    ZRET(flat_order_after_appends(h, s));
-    int rc = store_append_dev(h->st, prow, n, keys ? pkey : nullptr, s);
-    if (rc == 0) rc = flat_holes_cover(h, s);
-    if (rc == 0) rc = flat_publish_async(h, slot, s);
-    return rc;
+    return w.finish_enqueued(store_append_dev(h->st, prow, n, keys ? pkey : nullptr, s), slot);
   }
   // stage through the device in slices of <= 1 GiB
   const uint64_t rows_per = std::max<uint64_t>(1, ((uint64_t)1 << 30) / (uint64_t)rb);
   DevBuf tmp, tk;
-  for (uint64_t o = 0; o < n; o += rows_per) {
-    uint64_t m = std::min(rows_per, n - o);
-    ZRET(tmp.ensure((size_t)m * rb));
-    if (keys) ZRET(tk.ensure((size_t)m * 8));
-    ZCHK(hipMemcpyAsync(tmp.p, reinterpret_cast<const char *>(vecs) + (size_t)o * rb, (size_t)m * rb, hipMemcpyHostToDevice, s));
-    if (keys) ZCHK(hipMemcpyAsync(tk.p, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    ZRET(store_append_dev(h->st, tmp.p, m, keys ? tk.as<uint64_t>() : nullptr, s));
-    ZRET(flat_holes_cover(h, s));
-    ZCHK(hipStreamSynchronize(s));
-  }
-  return 0;
+  auto slices = [&]() -> int {
+    for (uint64_t o = 0; o < n; o += rows_per) {
+      uint64_t m = std::min(rows_per, n - o);
+      ZRET(tmp.ensure((size_t)m * rb));
+      if (keys) ZRET(tk.ensure((size_t)m * 8));
+      ZCHK(hipMemcpyAsync(tmp.p, reinterpret_cast<const char *>(vecs) + (size_t)o * rb, (size_t)m * rb, hipMemcpyHostToDevice, s));
+      if (keys) ZCHK(hipMemcpyAsync(tk.p, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
+      ZRET(store_append_dev(h->st, tmp.p, m, keys ? tk.as<uint64_t>() : nullptr, s));
+      ZCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+  };
+  return w.finish_synced(slices());
 }
 
 // IndexStreamer::add_with_id_impl in bulk: FlatStreamerEntity::add_vector_with_id (flat_streamer_entity.cc:900-990), one row
@@ -394,11 +406,9 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
   if (n == 0) return 0;
   for (uint64_t i = 0; i < n; ++i)
     if (ids[i] >= 0xfffffff0u) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  h->shadow.drop();                                  // (any mutation: the fp16 twin no longer mirrors the store)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  FlatWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = w.s;
   Store &st = h->st;
   const size_t rb = st.row_bytes();
   const uint64_t rows_per = std::max<uint64_t>(1, ((uint64_t)1 << 28) / (uint64_t)rb);
@@ -414,7 +424,6 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
     ZRET(flat_ring_slot(h, &tmp, &tk, &slot));
     memcpy(tmp, vecs, (size_t)n * rb);
     if (keys) memcpy(tk, keys, (size_t)n * 8);
-    ZRET(flat_order_after_appends(h, s));
   } else {
     ZRET(tmp_buf.alloc((size_t)std::min<uint64_t>(n, rows_per) * rb));
     if (keys) ZRET(tk_buf.alloc(std::min<uint64_t>(n, rows_per)));
@@ -423,62 +432,50 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
   }
   uint64_t lo = ~0ull, hi = 0;                    // hole words touched
   auto touch = [&](uint64_t pos) { lo = std::min(lo, pos >> 6); hi = std::max(hi, pos >> 6); };
-  for (uint64_t o = 0; o < n; o += rows_per) {
-    const uint64_t m = std::min(rows_per, n - o);
-    if (!fast) {
-      ZCHK(hipMemcpyAsync(tmp, static_cast<const char *>(vecs) + (size_t)o * rb, (size_t)m * rb, hipMemcpyHostToDevice, s));
-      if (keys) ZCHK(hipMemcpyAsync(tk, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    }
-    for (uint64_t i = 0; i < m;) {
-      const uint64_t id = ids[o + i];
-      if (id > st.n) {                            // pad the gap with holes
-        uint64_t gap = id - st.n;
-        const uint64_t zrows = std::min<uint64_t>(gap, rows_per);
-        if (!zero.p) {
-          ZRET(zero.alloc((size_t)zrows * rb));
-          ZCHK(hipMemsetAsync(zero, 0, (size_t)zrows * rb, s));
+  auto rows = [&]() -> int {
+    for (uint64_t o = 0; o < n; o += rows_per) {
+      const uint64_t m = std::min(rows_per, n - o);
+      if (!fast) {
+        ZCHK(hipMemcpyAsync(tmp, static_cast<const char *>(vecs) + (size_t)o * rb, (size_t)m * rb, hipMemcpyHostToDevice, s));
+        if (keys) ZCHK(hipMemcpyAsync(tk, keys + o, (size_t)m * 8, hipMemcpyHostToDevice, s));
+      }
+      for (uint64_t i = 0; i < m;) {
+        const uint64_t id = ids[o + i];
+        if (id > st.n) {                            // pad the gap with holes
+          uint64_t gap = id - st.n;
+          const uint64_t zrows = std::min<uint64_t>(gap, rows_per);
+          if (!zero.p) {
+            ZRET(zero.alloc((size_t)zrows * rb));
+            ZCHK(hipMemsetAsync(zero, 0, (size_t)zrows * rb, s));
+          }
+          while (gap) {
+            const uint64_t z = std::min(gap, zrows);
+            const uint64_t pos0 = st.n;
+            ZRET(store_append_dev(st, zero, z, nullptr, s));
+            ZCHK(hipMemsetAsync(st.keys + pos0, 0xff, (size_t)z * 8, s));     // kInvalidKey (flat_index_format.h:29)
+            h->h_holes.resize((st.n + 63) / 64 + 1, 0);
+            for (uint64_t p = pos0; p < pos0 + z; ++p) { h->h_holes[p >> 6] |= 1ull << (p & 63); touch(p); }
+            h->nholes += z;
+            gap -= z;
+          }
         }
-        while (gap) {
-          const uint64_t z = std::min(gap, zrows);
-          const uint64_t pos0 = st.n;
-          ZRET(store_append_dev(st, zero, z, nullptr, s));
-          ZCHK(hipMemsetAsync(st.keys + pos0, 0xff, (size_t)z * 8, s));     // kInvalidKey (flat_index_format.h:29)
-          h->h_holes.resize((st.n + 63) / 64 + 1, 0);
-          for (uint64_t p = pos0; p < pos0 + z; ++p) { h->h_holes[p >> 6] |= 1ull << (p & 63); touch(p); }
-          h->nholes += z;
-          gap -= z;
+        if (id == st.n) {                           // a run of consecutive new ids is one append (key = position)
+          uint64_t j = i + 1;
+          while (j < m && ids[o + j] == ids[o + j - 1] + 1u) ++j;
+          ZRET(store_append_dev(st, tmp + (size_t)i * rb, j - i, keys ? tk + i : nullptr, s));
+          i = j;
+        } else {                                    // overwrite in place
+          ZRET(launch_pack(st, tmp + (size_t)i * rb, 1, nullptr, id, nullptr, s, st.keys, keys ? tk + i : nullptr));
+          if (h->is_hole(id)) { h->h_holes[id >> 6] &= ~(1ull << (id & 63)); h->nholes -= 1; touch(id); }
+          ++i;
         }
       }
-      if (id == st.n) {                           // a run of consecutive new ids is one append (key = position)
-        uint64_t j = i + 1;
-        while (j < m && ids[o + j] == ids[o + j - 1] + 1u) ++j;
-        ZRET(store_append_dev(st, tmp + (size_t)i * rb, j - i, keys ? tk + i : nullptr, s));
-        i = j;
-      } else {                                    // overwrite in place
-        ZRET(launch_pack(st, tmp + (size_t)i * rb, 1, nullptr, id, nullptr, s, st.keys, keys ? tk + i : nullptr));
-        if (h->is_hole(id)) { h->h_holes[id >> 6] &= ~(1ull << (id & 63)); h->nholes -= 1; touch(id); }
-        ++i;
-      }
+      if (!fast) ZCHK(hipStreamSynchronize(s));
     }
-    if (!fast) ZCHK(hipStreamSynchronize(s));
-  }
-  if (fast) ZRET(flat_publish_async(h, slot, s));
-  // device copy of the hole bits: everything after a reallocation, else the words that changed
-  const uint64_t words = (st.n + 63) / 64 + 1;
-  h->h_holes.resize(words, 0);
-  if (h->nholes || h->d_holes.p) {
-    if (words * 8 > h->d_holes.cap) {
-      ZRET(h->d_holes.ensure(words * 16));
-      ZCHK(hipMemsetAsync(h->d_holes.p, 0, h->d_holes.cap, s));
-      lo = 0; hi = words - 1;
-    }
-    if (lo <= hi && lo != ~0ull) {
-      ZCHK(hipMemcpyAsync(h->d_holes.as<uint64_t>() + lo, h->h_holes.data() + lo, (size_t)(std::min(hi, words - 1) - lo + 1) * 8, hipMemcpyHostToDevice, s));
-      ZCHK(hipStreamSynchronize(s));             // (h_holes is pageable and may be resized by the next call)
-      if (fast) ZRET(flat_publish_async(h, slot, s));
-    }
-  }
-  return 0;
+    return 0;
+  };
+  const int rc = rows();
+  return fast ? w.finish_enqueued(rc, slot, lo, hi) : w.finish_synced(rc, lo, hi);
 }
 
 int zvec_hip_flat_holes(zvec_hip_flat_t h, uint64_t *count) {

@@ -427,12 +427,14 @@ struct zvec_hip_flat_s {
   // extend the store holds it exclusive.  A growth reallocation frees the old arrays with hipFree, which waits for
   // the device, so kernels enqueued by earlier searches have finished with them.
   FairSharedMutex rw;
-  // zvec_hip_flat_append_dev returns with its pack kernels only enqueued: recorded after them on the append stream,
-  // waited for by every reader of the store on its own stream
-  // asynchronous mutations (append_dev, single-document adds): `append_stream` carries kernels that are only enqueued.
-  // A reader on ANOTHER stream makes its stream wait for them: it records append_ev behind them if nobody has since
-  // the last mutation (append_dirty, under ev_mu — readers run concurrently) and waits for the event; a reader on the
-  // same stream is ordered by the stream.  Writers hold `rw` exclusively, so these fields do not move under a reader.
+  // Every mutation goes through one FlatWrite (api_entry_ctx_flat.inc.h), which is the writers' protocol: mu, then rw exclusively; the
+  // device and the stream; the fp16 twin dropped; the stream ordered behind a mutation still only enqueued on another one; afterwards
+  // the device copy of the hole bits extended, and one of two endings.  finish_synced: the stream is drained, readers need nothing.
+  // finish_enqueued (append_dev, append_fp32_dev, adds of up to FAST_ROWS rows): the row count is published while kernels are only
+  // enqueued on `append_stream`.  Whoever enqueues on ANOTHER stream next — a reader or a writer — makes that stream wait: it records
+  // append_ev behind them if nobody has since the last mutation (append_dirty; readers run concurrently and do so under ev_mu) and
+  // waits for the event; the same stream orders itself.  A caller's stream may be gone by then, so its event is recorded by the
+  // ending at once.  Writers hold `rw` exclusively, so these fields do not move under a reader.  append_pending is never reset.
   hipEvent_t append_ev = nullptr;
   bool append_pending = false;
   bool append_dirty = false;
