@@ -709,7 +709,27 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     zvec_hip_sparse_get_vector read the rows themselves whether the lists are on or off.  On a ZVEC_HIP_METRIC_L2 handle
  *     zvec_hip_sparse_set_inverted returns ZVEC_HIP_ERR_UNSUPPORTED and changes nothing: the distance over the union of the index
  *     sets would need the expansion that "Score, ZVEC_HIP_METRIC_L2" rules out.  A NULL handle: ZVEC_HIP_ERR_INVALID_ARGUMENT.
- * Not served (each is the reference's to keep doing on the CPU): put / holes (add-with-id gaps), the
+ *   - Add-with-id (zvec_hip_sparse_put, zvec_hip_sparse_holes, zvec_hip_sparse_put_info): FlatSparseStreamerEntity::
+ *     add_vector_with_id (flat_sparse_streamer_entity.cc:708-783), what Index::_sparse_add calls per document, in bulk.  n rows in
+ *     CSR form as for zvec_hip_sparse_append, applied row by row in call order: the row of ids[i] lives at storage position ids[i];
+ *     id == count appends; id > count first pads [count, id) with HOLES, empty rows stored under the invalid key (all ones) that
+ *     no search returns; id < count replaces the row in place of the old one, and a hole that is written stops being one; an id
+ *     named twice in a call keeps the later row.  keys == NULL stores key = id (the reference's rule), else keys[i] with row i.
+ *     Validation is that of append (at most 4096 pairs a run, strictly ascending, NULL arrays only where there are no pairs:
+ *     ZVEC_HIP_ERR_INVALID_ARGUMENT; so is a NULL ids with n > 0); an id of 2^32 - 1, or more than 2^32 - 2 rows afterwards,
+ *     returns ZVEC_HIP_ERR_OUT_OF_RANGE.  All or nothing: a refused call, and one whose allocation fails
+ *     (ZVEC_HIP_ERR_NO_MEMORY), leaves rows, keys, holes and counts as they were.  n == 0 returns 0.  Both value types, both
+ *     metrics.  zvec_hip_sparse_count reports the pairs stored afterwards: those of a replaced row are gone.  The inverted lists
+ *     are marked out of date as by append.  Three routes, chosen per call (zvec_hip_sparse_put_info tells which): 0 tail, every
+ *     id at or behind the old count, the append path plus empty rows; 1 in place, every replaced row keeps its length and only
+ *     its pairs and key are rewritten; 2 splice, a replaced row changes its length, so the pairs behind it move: the four arrays
+ *     are written anew in one pass over the store and swapped in, and until then the store exists twice in device memory.  A put
+ *     must not overlap a zvec_hip_sparse_search_dev of the same handle that is still running on the caller's stream.
+ *     Holes: every search entry ORs the hole bits into its exclude set (the caller's pointer goes through untouched while the
+ *     handle has no hole); zvec_hip_sparse_batch_distance scores a hole +inf; zvec_hip_sparse_get_vector of a hole returns
+ *     count 0 and status 0, the empty row the reference stores; exclude bitsets and group_of_position are indexed by storage
+ *     position, holes included.  zvec_hip_sparse_append on a handle that has holes extends the hole bits with the rows.
+ * Not served (each is the reference's to keep doing on the CPU): removing a document, the
  * MipsSquaredEuclideanSparse metric, loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror
  * (zvec_hip_operator.hpp); by the inverted lists: ZVEC_HIP_METRIC_L2, listed rows and group-by. */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
@@ -731,6 +751,16 @@ int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t element
  * being counts[i] pairs; keys == NULL -> key = storage position.  All or nothing (see Row format, Index order). */
 int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const void *values,
                            uint64_t n, const uint64_t *keys);
+/* FlatSparseStreamer::add_with_id_impl in bulk: row i, counts[i] pairs, goes to storage position ids[i]; see Add-with-id above. */
+int zvec_hip_sparse_put(zvec_hip_sparse_t h, const uint32_t *ids, const uint32_t *counts, const uint32_t *indices,
+                        const void *values, uint64_t n, const uint64_t *keys);
+/* positions that are holes now */
+int zvec_hip_sparse_holes(zvec_hip_sparse_t h, uint64_t *count);
+/* The last successful zvec_hip_sparse_put of the handle.  route: -1 none yet, 0 tail only, 1 in place, 2 splice; moved_elems:
+ * (index, value) pairs the device wrote for it (routes 0 and 1: the call's own; route 2: every pair of the store); chunk_elems:
+ * destination pairs one work-group of the splice copies (a constant of the library, reported before any put); ms: wall-clock time
+ * of the call.  Every output nullable. */
+int zvec_hip_sparse_put_info(zvec_hip_sparse_t h, int *route, uint64_t *moved_elems, uint32_t *chunk_elems, double *ms);
 /* either output nullable */
 int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *elements);
 /* get_sparse_vector_by_id: row `pos` as stored, bit for bit (halves come back as halves).  *count always; indices / values
@@ -757,7 +787,7 @@ int zvec_hip_sparse_search_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const
                                   uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
 /* IndexMetric::batch_distance (index_metric.h:85-87) over sparse rows, scored as search_p_keys scores its keys
  * (flat_sparse_entity.h:63-77): one query of q_count pairs against n listed positions, scores only, in the listed order; a
- * position beyond the rows scores +inf.  n == 0 returns 0 and writes nothing. */
+ * position beyond the rows, and a hole, scores +inf.  n == 0 returns 0 and writes nothing. */
 int zvec_hip_sparse_batch_distance(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, uint32_t q_count, const uint32_t *q_indices,
                                    const void *q_values, const uint32_t *positions, uint32_t n, float *out_scores);
 /* The term-major twin of the rows; see Inverted lists above. */

@@ -58,6 +58,15 @@ streaming figure (zvec_hip_calibrate, same process) and the bytes the device bui
 
     python tools/sparse_bench.py --inverted [--out profiles/sparse_inverted.json] [--build-out profiles/sparse_inverted_build.json]
                                  [--steps 10] [--warmup 3]
+
+    --put       add-with-id (zvec_hip_sparse_put) on the full-scan mode's corpus, one call on each route: 0 tail (--put-rows new rows
+                behind the last one), 1 in place (as many random rows replaced by rows of their own length), 2 splice (the same rows
+                replaced by rows one element longer or shorter, so that everything behind the first of them moves).  Reported per
+                route: the call's wall clock (zvec_hip_sparse_put_info), the pairs the device wrote and the bytes per second they
+                make (4 + value bytes a pair, read and written: twice that), next to the box's calibrated streaming rate.  One call
+                each, not repeated; reported, not gated.
+
+    python tools/sparse_bench.py --put [--dtype fp32|fp16] [--put-rows 1000] [--out profiles/sparse_put.json]
 """
 import argparse
 import ctypes as C
@@ -433,6 +442,58 @@ def inverted(args, metric):
             "steps": args.steps, "warmup": args.warmup, "runs": runs}
 
 
+def put(args, metric):
+    import numpy as np
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    rv = (torch.rand(ri.numel(), generator=g, device=dev) * 2 - 1).cpu()
+    np_val = np.float16 if args.dtype == "fp16" else np.float32
+    width = np.dtype(np_val).itemsize
+    counts = rc_.numpy().astype(np.uint32)
+    idx, val = ri.numpy().view(np.uint32), rv.numpy().astype(np_val)
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
+    assert se.add_batch(counts, idx, val) == 0
+    rng = np.random.default_rng(3)
+    m = min(args.put_rows, args.n)
+    ids = np.sort(rng.choice(args.n, m, replace=False)).astype(np.uint32)
+
+    def rows_of(lengths):
+        """rows of the given lengths: indices 0 .. length - 1 (ascending, any length), random values"""
+        c = np.asarray(lengths, np.uint32)
+        i = np.concatenate([np.arange(x, dtype=np.uint32) for x in c])
+        return c, i, rng.uniform(-1, 1, i.size).astype(np_val)
+    legs = []
+    for name, route, put_ids, lengths in (
+            ("in place", 1, ids, counts[ids]),
+            ("splice", 2, ids, np.where(counts[ids] > 64, counts[ids] - 1, counts[ids] + 1)),
+            ("tail", 0, np.arange(args.n, args.n + m, dtype=np.uint32), np.full(m, 64, np.uint32))):
+        c, i, v = rows_of(lengths)
+        assert se.add_with_id_batch(put_ids, c, i, v) == 0
+        info = se.put_info()
+        assert info["route"] == route, (name, info)
+        nbytes = info["moved_elems"] * (4 + width)
+        legs.append({"route": route, "name": name, "rows": int(m), "ms": info["ms"], "moved_elems": info["moved_elems"],
+                     "moved_bytes": nbytes, "moved_gbs": nbytes / info["ms"] / 1e6, "read_and_written_gbs": 2 * nbytes / info["ms"] / 1e6,
+                     "elements_after": se.element_count()})
+        print(json.dumps(legs[-1]), flush=True)
+    chunk = se.put_info()["chunk_elems"]
+    del se
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    return {"workload": "flat sparse %d rows x 64-192 of %d (Zipf), %s values: one zvec_hip_sparse_put of %d rows on each route" % (
+                args.n, args.vocab, args.dtype, m),
+            "metric": metric, "timing": "zvec_hip_sparse_put_info's ms: wall clock of the call, host staging and the waits included; one call "
+            "each, not repeated", "chunk_elems": chunk, "clock_mhz": mhz.value, "stream_gbs": gbs.value, "legs": legs}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -444,6 +505,8 @@ def main():
     ap.add_argument("--by-keys", action="store_true")
     ap.add_argument("--grouped", action="store_true")
     ap.add_argument("--inverted", action="store_true")
+    ap.add_argument("--put", action="store_true")
+    ap.add_argument("--put-rows", type=int, default=1000, help="--put: rows of each call")
     ap.add_argument("--build-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                         "sparse_inverted_build.json"), help="--inverted: where the build timings go")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
@@ -454,6 +517,8 @@ def main():
         if args.metric != "ip":
             ap.error("--inverted serves InnerProductSparse only")
         mode = inverted
+    if args.put:
+        mode = put
     res = mode(args, "ip")
     if args.metric == "l2":
         res = beside(res, mode(args, "l2"), rows)

@@ -521,18 +521,26 @@ int zvec_hip_flat_get_vectors(zvec_hip_flat_t h, const uint64_t *positions, uint
   return store_get_rows(h->defctx, h->st, pos, out);
 }
 
-// the exclude set a scan of this store has to use: the caller's, plus the holes add-with-id left (caller holds h->rw)
-static int flat_effective_exclude(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
+// the exclude set a scan of this store has to use: the caller's, plus the holes add-with-id left (caller holds h->rw).  H: a flat
+// or a sparse handle, which keep their holes alike.
+extern "C++" {
+template <typename H>
+static int effective_exclude(H *h, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
   *out = d_exclude;
   if (h->nholes == 0) return 0;
-  if (!d_exclude) { *out = h->d_holes.as<uint64_t>(); return 0; }
+  const uint64_t *d_holes = static_cast<const uint64_t *>(h->d_holes.p);
+  if (!d_exclude) { *out = d_holes; return 0; }
   const uint64_t words = (h->st.n + 63) / 64;
   ZRET(c->holes_ex.ensure(words * 8 + 8));
   hipLaunchKernelGGL(or_bits_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, c->holes_ex.as<uint64_t>(), d_exclude,
-                     h->d_holes.as<uint64_t>(), words);
+                     d_holes, words);
   ZCHK(hipGetLastError());
   *out = c->holes_ex.as<uint64_t>();
   return 0;
+}
+}  // extern "C++"
+static int flat_effective_exclude(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
+  return effective_exclude(h, c, d_exclude, s, out);
 }
 
 // the flat search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments

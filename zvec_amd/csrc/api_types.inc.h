@@ -518,6 +518,21 @@ struct SparseStore {
     return 0;
   }
 
+  // the capacities reserve(rows, elements) would leave
+  void grown(uint64_t rows, uint64_t elements, uint64_t *nr, uint64_t *ne) const {
+    *nr = (rows > cap_rows || row_off == nullptr) ? std::max<uint64_t>(std::max<uint64_t>(rows, 1), cap_rows + cap_rows / 2 + 1) : cap_rows;
+    *ne = elements > cap_elems ? std::max<uint64_t>(elements, cap_elems + cap_elems / 2 + 1) : cap_elems;
+  }
+  // Four arrays written whole elsewhere (the splice of zvec_hip_sparse_put: room for nr rows and ne pairs, `rows` rows and
+  // `elements` pairs in them) take the place of the store's.  The old ones leave in the arguments and go with them: hipFree waits
+  // for the device.
+  void adopt(Scoped<uint64_t> &off, Scoped<uint64_t> &ks, Scoped<uint32_t> &ni, Scoped<void> &nv, uint64_t nr, uint64_t ne, uint64_t rows,
+             uint64_t elements) {
+    std::swap(own.row_off, off); std::swap(own.keys, ks); std::swap(own.idx, ni); std::swap(own.val, nv);
+    row_off = own.row_off; keys = own.keys; idx = own.idx; val = own.val;
+    cap_rows = nr; cap_elems = ne; n = rows; elems = elements;
+  }
+
  private:
   struct Arrays {
     Scoped<uint64_t> row_off, keys;
@@ -560,6 +575,19 @@ struct zvec_hip_sparse_s {
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)
   FairSharedMutex rw;       // searches hold it shared, anything that may move or extend the store exclusive (as zvec_hip_flat_s)
+  // add-with-id gaps (FlatSparseStreamerEntity::add_vector_with_id pads positions [count, id) with empty rows under kInvalidKey,
+  // flat_sparse_streamer_entity.cc:708-783): one bit per storage position, host copy + device copy, as zvec_hip_flat_s keeps them;
+  // every entry that takes an exclude set passes its own OR these while any hole exists (api_entry_sparse_put.inc.h)
+  std::vector<uint64_t> h_holes;
+  uint64_t nholes = 0;
+  DevBuf d_holes;
+  bool is_hole(uint64_t pos) const { return (pos >> 6) < h_holes.size() && ((h_holes[pos >> 6] >> (pos & 63)) & 1ull); }
+  // zvec_hip_sparse_put: its device workspace (tables and staged pairs of one call; kept between calls), and what the last
+  // successful call did (zvec_hip_sparse_put_info)
+  DevBuf put_ws;
+  int put_route = -1;
+  uint64_t put_moved = 0;
+  double put_ms = 0.0;
   ~zvec_hip_sparse_s() { delete defctx; }
 };
 

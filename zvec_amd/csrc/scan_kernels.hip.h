@@ -36,3 +36,4 @@
 #include "zvk_sparse.hip.h"
 #include "zvk_sparse_inv.hip.h"
 #include "zvk_sparse_invb.hip.h"
+#include "zvk_sparse_put.hip.h"

@@ -45,6 +45,7 @@ extern "C" {
 #include "api_entry_shards.inc.h"
 #include "api_entry_container.inc.h"
 #include "api_entry_sparse.inc.h"
+#include "api_entry_sparse_put.inc.h"
 #include "api_entry_sparse_inverted.inc.h"
 #include "api_entry_sparse_group.inc.h"
 

@@ -861,11 +861,72 @@ class HipFlatSparseStreamer:
             self._keys_host.append(np.arange(n0, n0 + c.size, dtype=np.uint64) if k is None else k.copy())
         return rc
 
+    INVALID_KEY = np.uint64(0xffffffffffffffff)          # kInvalidKey: what a hole is stored under
+
+    def add_with_id_impl(self, doc_id, indices, values):
+        """IndexStreamer::add_with_id_impl for one sparse document: what core_interface::Index::_sparse_add calls"""
+        i = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        return self.add_with_id_batch([doc_id], [i.size], i, values)
+
+    def add_with_id_batch(self, ids, counts, indices, values, keys=None):
+        """FlatSparseStreamerEntity::add_vector_with_id row by row (zvec_hip_sparse_put): row i goes to storage position ids[i]
+        under key ids[i] (or keys[i]); a gap is padded with holes no search returns, an id below the count replaces the row,
+        an id named twice keeps the later row.  All or nothing."""
+        runs = self._runs(counts, indices, values)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        if runs is None or ids.size != runs[0].size or (k is not None and k.size != ids.size):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        rc = _lib.lib().zvec_hip_sparse_put(self._h, _np_ptr(ids), _np_ptr(c), _np_ptr(i), _np_ptr(v), ids.size, _np_ptr(k))
+        if rc == 0 and ids.size:
+            self._put_keys(ids, ids.astype(np.uint64) if k is None else k, self.count())
+        return rc
+
+    def _put_keys(self, ids, keyvals, n):
+        """the host key column after a put that left n rows: ONE array with room to grow, of which only the new positions (the
+        invalid key) and the call's own are written, so that filling an index document by document costs the document, not the
+        index.  Rows that came through add_batch since the last put are gathered into it once."""
+        buf = getattr(self, "_key_buf", None)
+        cur = self._keys_host
+        if buf is not None and len(cur) == 1 and cur[0].base is buf:
+            have = cur[0].size
+        else:
+            allk = self._all_keys()
+            have = allk.size
+            buf = np.empty(max(n, 2 * have, 16), np.uint64)
+            buf[:have] = allk
+        if n > buf.size:
+            grown = np.empty(max(n, 2 * buf.size), np.uint64)
+            grown[:have] = buf[:have]
+            buf = grown
+        buf[have:n] = self.INVALID_KEY
+        _, first = np.unique(ids[::-1], return_index=True)          # the later row of an id wins: its last place in the call
+        last = ids.size - 1 - first
+        buf[ids[last].astype(np.int64)] = keyvals[last]
+        self._key_buf = buf
+        self._keys_host = [buf[:n]]
+
+    def holes(self):
+        c = C.c_uint64(0)
+        _lib.check(_lib.lib().zvec_hip_sparse_holes(self._h, C.byref(c)), "zvec_hip_sparse_holes")
+        return int(c.value)
+
+    def put_info(self):
+        """the last successful add_with_id_batch (zvec_hip_sparse_put_info): route -1 none yet / 0 tail / 1 in place / 2 splice"""
+        route, moved, chunk, ms = C.c_int(0), C.c_uint64(0), C.c_uint32(0), C.c_double(0.0)
+        _lib.check(_lib.lib().zvec_hip_sparse_put_info(self._h, C.byref(route), C.byref(moved), C.byref(chunk), C.byref(ms)),
+                   "zvec_hip_sparse_put_info")
+        return {"route": int(route.value), "moved_elems": int(moved.value), "chunk_elems": int(chunk.value), "ms": float(ms.value)}
+
     def _all_keys(self):
+        """the key of every storage position; a hole reports the invalid key"""
+        if len(self._keys_host) == 1:
+            return self._keys_host[0]                    # (no copy: read-only to its callers)
         return np.concatenate(self._keys_host) if self._keys_host else np.zeros(0, np.uint64)
 
     def get_vector_by_id(self, pos):
-        """(indices, values) of the row at storage position `pos` as stored, or None beyond the last row"""
+        """(indices, values) of the row at storage position `pos` as stored (a hole: empty), or None beyond the last row"""
         n = C.c_uint32(0)
         idx = np.zeros(self.MAX_COUNT, np.uint32)
         val = np.zeros(self.MAX_COUNT, self.np_dtype)
