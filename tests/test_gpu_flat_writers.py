@@ -2,7 +2,9 @@
 Every entry that changes a flat store orders its stream behind a mutation that is still only enqueued on another stream, whatever it
 does afterwards: a store that grows is copied on the writer's stream, and a row overwritten in place is packed there.  The cases put
 each writer directly behind an append_dev that waits on a caller's stream behind a few large matrix products, and then compare the
-whole store, bit for bit, with a host model.  All rows are small integers: exact in fp16 and fp32, so a row's distance to itself is 0."""
+whole store, bit for bit, with a host model.  All rows are small integers: exact in fp16 and fp32, so a row's distance to itself is 0.
+The last two tests are about the hole bits (HoleBits, api_types.inc.h): their device copy outgrown by bulk appends, and gaps that end
+at the edges of their 64-bit words."""
 import numpy as np
 import pytest
 
@@ -189,3 +191,88 @@ def test_single_row_adds_stay_ordered_across_holes_and_growth(zv):
     for qi in range(2):
         assert ctx.counts[qi] == live
         assert sorted(int(k) for k in ctx.keys[qi, :live]) == sorted(model)
+
+
+def _words_of(mask):
+    w = np.zeros((mask.size + 63) // 64, np.uint64)
+    idx = np.nonzero(mask)[0]
+    np.bitwise_or.at(w, idx // 64, np.uint64(1) << (idx % 64).astype(np.uint64))
+    return w
+
+
+def _copy_room(rows):
+    """rows the device copy of the hole bits has room for after HoleBits::reserve(rows) made it: words_for(rows) = (rows + 63) // 64
+    + 1 words are asked for as DevBuf::ensure(16 bytes a word), which allocates a quarter more and 256 bytes; one word stays spare"""
+    words = (rows + 63) // 64 + 1
+    return ((16 * words + 16 * words // 4 + 256) // 8 - 1) * 64
+
+
+@pytest.mark.parametrize("kind", ["fp32", "binary64"])
+def test_bulk_appends_to_a_handle_with_holes_across_growths_of_the_hole_copy(zv, kind):
+    """One row at id 70 leaves 70 holes and a device copy of the hole bits made for 71 rows: 3 words, 316 bytes, 39 whole words, room
+    for 2432 rows.  Appending 2500 rows (2571 > 2432) outgrows it: 42 words, 1096 bytes, 137 words, room for 8704 rows.  Appending
+    6500 more (9071 > 8704) outgrows it again.  Every search reads the copy's words for all rows, so after each call no hole may
+    come back, with and without a caller's exclude set.  Scores are exact integers on both handles (integer-valued fp32 rows at
+    dim 32 against fp64; 64-bit rows under Hamming, which reads the exclude set through its own kernel): only ties are free."""
+    from tests.hamming_ref import check_hamming_lists, hamming_reference
+    rng = np.random.default_rng(70)
+    bulks = (2500, 6500)
+    assert 71 + bulks[0] > _copy_room(71) == 2432 and 71 + sum(bulks) > _copy_room(71 + bulks[0]) == 8704
+    if kind == "fp32":
+        st = zv.HipFlatStreamer(32, L2)
+        make = lambda n: rng.integers(-8, 9, (n, 32)).astype(np.float32)
+        score = lambda b, q: ((b.astype(np.float64)[None] - q.astype(np.float64)[:, None]) ** 2).sum(-1).astype(np.int64)
+    else:
+        st = zv.HipFlatStreamer(64, "Hamming", dtype="binary64")
+        make = lambda n: rng.integers(0, 2**64, (n, 1), dtype=np.uint64)
+        score = hamming_reference
+    q = make(3)
+    q[2] = 0                                         # (nearest to the holes' zero rows)
+    stored = np.zeros((71, q.shape[1]), q.dtype)
+    stored[70] = make(1)[0]
+    assert st.add_with_id_impl(70, stored[70]) == 0
+    for step, n_new in enumerate((0,) + bulks):
+        if n_new:
+            new = make(n_new)
+            assert st.add_batch(new) == 0
+            stored = np.concatenate([stored, new])
+        n = stored.shape[0]
+        assert st.count() == n and st.holes() == 70
+        ref = score(stored, q)
+        live = np.arange(n) >= 70
+        # the caller's set: every 7th position, and each query's best live row
+        ex = np.arange(n) % 7 == 3
+        ex[[70 + int(np.argmin(ref[i, 70:])) for i in range(3)]] = True
+        for mask in (None, ex):
+            ctx = st.create_context()
+            ctx.set_topk(10)
+            if mask is not None:
+                ctx.set_exclude_bitset(_words_of(mask))
+            assert st.search_impl(q, 3, ctx) == 0
+            assert (ctx.keys[:, :10][ctx.counts[:, None] > np.arange(10)[None]] >= 70).all(), "step %d: a hole came back" % step
+            check_hamming_lists(ctx.keys, ctx.scores, ctx.counts, ref, 10, admissible=live if mask is None else live & ~mask,
+                                what="%s step %d %s" % (kind, step, "plain" if mask is None else "exclude"))
+
+
+@pytest.mark.parametrize("staged", [False, True])
+def test_put_gaps_at_the_edges_of_the_hole_words(zv, staged):
+    """Gaps [count, id) that end at positions 63, 65 and 128 on one handle and at 64 and 129 on another (a gap can end at 64 only where
+    none ended at 63), then one of more than two words, then rows put onto positions 0, 63 and 64, which are holes on one handle or
+    the other.  staged: the id is named ten times, which takes the put off the pinned ring (more than 8 rows) and overwrites the new
+    row nine times.  After each put the hole count is the model's and a search for every row returns exactly the live positions."""
+    rng = np.random.default_rng(63)
+    for ids in ([63, 65, 128, 400, 0, 63, 64], [64, 129, 300, 0, 63, 64]):
+        st = zv.HipFlatStreamer(32, L2)
+        live, n = set(), 0
+        for doc in ids:
+            rows = rng.integers(-8, 9, (10 if staged else 1, 32)).astype(np.float32)
+            assert st.add_with_id_batch(np.full(rows.shape[0], doc, np.uint32), rows) == 0
+            live.add(doc)
+            n = max(n, doc + 1)
+            assert st.count() == n and st.holes() == n - len(live), "ids %r, after %d" % (ids, doc)
+            ctx = st.create_context()
+            ctx.set_topk(n)
+            assert st.search_impl(rows[-1:], 1, ctx) == 0
+            assert ctx.counts[0] == len(live)
+            assert sorted(int(k) for k in ctx.keys[0, :len(live)]) == sorted(live), "ids %r, after %d" % (ids, doc)
+            assert ctx.keys[0, 0] == doc and ctx.scores[0, 0] == 0          # (the last row named is the one stored)

@@ -85,7 +85,7 @@ int zvec_hip_flat_append_fp32_dev(zvec_hip_flat_t h, const float *d_vecs, uint64
   FlatWrite w(h);
   ZRET(w.open(stream));
   // everything that can refuse comes before the first row is stored: all of the rows or none
-  if (h->st.n + n >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  ZRET(w.cover(h->st.n + n));
   ZRET(h->st.reserve(h->st.n + n, w.s));
   return w.finish_enqueued(flat_append_encoded(h, d_vecs, n, dim, encode_dims, threshold, d_keys, w.s));
 }
@@ -99,7 +99,7 @@ int zvec_hip_flat_append_fp32(zvec_hip_flat_t h, const float *vecs, uint64_t n, 
   FlatWrite w(h);
   ZRET(w.open());
   hipStream_t s = w.s;
-  if (h->st.n + n >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  ZRET(w.cover(h->st.n + n));
   ZRET(h->st.reserve(h->st.n + n, s));
   const uint64_t rows_per = std::max<uint64_t>(1, BENC_SLICE_BYTES / ((uint64_t)dim * 4));
   DevBuf tmp, tk;

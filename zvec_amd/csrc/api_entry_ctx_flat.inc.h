@@ -149,23 +149,6 @@ int zvec_hip_flat_destroy(zvec_hip_flat_t h) {
   return 0;
 }
 
-// The device copy of the hole bits (caller holds h->rw exclusively): it spans the store whenever holes exist, and follows the host
-// words [lo, hi] that a put changed (lo > hi: none).  After a reallocation everything is uploaded, else the changed words only.
-static int flat_holes_cover(zvec_hip_flat_s *h, hipStream_t s, uint64_t lo = ~0ull, uint64_t hi = 0) {
-  if (h->nholes == 0 && !(h->d_holes.p && lo <= hi)) return 0;       // (no hole, and no bit to clear in a copy made earlier)
-  const uint64_t words = (h->st.n + 63) / 64 + 1;
-  h->h_holes.resize(words, 0);
-  if (words * 8 > h->d_holes.cap) {
-    ZRET(h->d_holes.ensure(words * 16));
-    ZCHK(hipMemsetAsync(h->d_holes.p, 0, h->d_holes.cap, s));
-    lo = 0; hi = words - 1;
-  }
-  if (lo > hi) return 0;
-  ZCHK(hipMemcpyAsync(h->d_holes.as<uint64_t>() + lo, h->h_holes.data() + lo, (size_t)(std::min(hi, words - 1) - lo + 1) * 8, hipMemcpyHostToDevice, s));
-  ZCHK(hipStreamSynchronize(s));                 // (h_holes is pageable and may be resized by the next call)
-  return 0;
-}
-
 // a pinned slot for a tiny add: rows at *rows, keys at *keys (device-visible host memory).  Slots are handed out in
 // order; the event of a group of RING_GROUP slots is recorded behind the kernel that reads the group's last slot and
 // waited for before the group's first slot is written again — by then it is RING - RING_GROUP adds old.
@@ -214,9 +197,9 @@ static int flat_order_after_appends(zvec_hip_flat_s *h, hipStream_t s, std::mute
 static int flat_wait_appends(zvec_hip_flat_s *h, hipStream_t s) { return flat_order_after_appends(h, s, &h->ev_mu); }
 
 // One mutation of a flat store, from the locks to what readers are told (the rules: zvec_hip_flat_s::append_ev).  It holds h->mu, then
-// h->rw exclusively, while it lives.  open() readies the stream `s`; an entry that stores rows enqueues its copies and packs there and
-// returns through one of the two endings.  An ending runs whatever `rc` is — rows stored before a failure are covered and published like any others —
-// and returns the first error.
+// h->rw exclusively, while it lives.  open() readies the stream `s`; an entry that stores rows calls cover() before its first change
+// (HoleBits' protocol), enqueues its copies and packs on `s` and returns through one of the two endings.  An ending runs whatever `rc`
+// is — rows stored before a failure are published like any others, their hole bits uploaded — and returns the first error.
 struct FlatWrite {
   zvec_hip_flat_s *const h;
   hipStream_t s = nullptr;
@@ -229,18 +212,20 @@ struct FlatWrite {
     // an earlier append may still be only enqueued on another stream: a growing store is copied on `s`, rows are overwritten on `s`
     return flat_order_after_appends(h, s, nullptr);
   }
+  // the call will make the store `rows` long (positions are 32-bit, IDX_NONE reserved), padding gaps with holes if `leaves`
+  int cover(uint64_t rows, bool leaves = false) { return rows >= 0xfffffff0ull ? ZVEC_HIP_ERR_OUT_OF_RANGE : h->holes.reserve(rows, leaves, s); }
   // the call returns with work only enqueued on `s`: the row count is published now, so readers on other streams must wait for `s`.
-  // slot = the ring slot the work reads, or ~0u; [lo, hi] = the hole words it changed
-  int finish_enqueued(int rc, uint32_t slot = ~0u, uint64_t lo = ~0ull, uint64_t hi = 0) {
-    int e = flat_holes_cover(h, s, lo, hi);
+  // slot = the ring slot the work reads, or ~0u
+  int finish_enqueued(int rc, uint32_t slot = ~0u) {
+    int e = h->holes.upload_dirty(s);
     if (e == 0) e = flat_publish_async(h, slot, s);
     // a caller's stream may not outlive this call: its event is recorded now, not when a reader first needs it
     if (e == 0 && s != h->defctx->own) e = record_now();
     return rc ? rc : e;
   }
   // the call returns with `s` drained: whatever it copied out of the caller's memory or through its own temporaries is done
-  int finish_synced(int rc, uint64_t lo = ~0ull, uint64_t hi = 0) {
-    const int e = flat_holes_cover(h, s, lo, hi);
+  int finish_synced(int rc) {
+    const int e = h->holes.upload_dirty(s);
     const hipError_t he = hipStreamSynchronize(s);
     return rc ? rc : e ? e : he != hipSuccess ? ZVEC_HIP_ERR_RUNTIME : 0;
   }
@@ -268,6 +253,7 @@ int zvec_hip_flat_append_dev(zvec_hip_flat_t h, const void *d_vecs, uint64_t n, 
   FlatWrite w(h);
   ZRET(w.open(stream));
   if (n == 0) return 0;
+  ZRET(w.cover(h->st.n + n));
   return w.finish_enqueued(store_append_dev(h->st, d_vecs, n, d_keys, w.s));     // the pack kernel is only enqueued
 }
 
@@ -283,6 +269,7 @@ int zvec_hip_flat_load_features(zvec_hip_flat_t h, const void *features, uint64_
   if (bytes < count * elem) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   FlatWrite w(h);
   ZRET(w.open());
+  ZRET(w.cover(h->st.n + count));
   hipStream_t s = w.s;
   Scoped<uint8_t> d_body;
   Scoped<char> d_rows;
@@ -343,7 +330,7 @@ int zvec_hip_flat_load_blocks(zvec_hip_flat_t h, const void *blocks, uint64_t by
   ZRET(w.open());
   hipStream_t s = w.s;
   // everything that can refuse comes before the first asynchronous copy out of the local arrays
-  if (h->st.n + kept >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  ZRET(w.cover(h->st.n + kept));
   ZRET(h->st.reserve(h->st.n + kept, s));
   Scoped<char> d_rows;
   Scoped<uint64_t> d_src, d_keys;
@@ -367,6 +354,7 @@ int zvec_hip_flat_append(zvec_hip_flat_t h, const void *vecs, uint64_t n, const 
   if (n == 0) return 0;
   FlatWrite w(h);
   ZRET(w.open());
+  ZRET(w.cover(h->st.n + n));
   hipStream_t s = w.s;
   const size_t rb = h->st.row_bytes();
   if (n <= zvec_hip_flat_s::FAST_ROWS) {              // a document at a time: pinned ring, nothing to wait for
@@ -410,6 +398,10 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
   ZRET(w.open());
   hipStream_t s = w.s;
   Store &st = h->st;
+  uint64_t end = st.n;                            // the row count the call reaches, and whether it pads a gap on the way
+  bool gaps = false;
+  for (uint64_t i = 0; i < n; ++i) { gaps |= ids[i] > end; end = std::max<uint64_t>(end, (uint64_t)ids[i] + 1); }
+  ZRET(w.cover(end, gaps));
   const size_t rb = st.row_bytes();
   const uint64_t rows_per = std::max<uint64_t>(1, ((uint64_t)1 << 28) / (uint64_t)rb);
   // a document at a time (the product's ingest): the rows are read in place from a pinned ring slot, nothing is allocated
@@ -430,8 +422,6 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
     tmp = tmp_buf;
     tk = tk_buf;
   }
-  uint64_t lo = ~0ull, hi = 0;                    // hole words touched
-  auto touch = [&](uint64_t pos) { lo = std::min(lo, pos >> 6); hi = std::max(hi, pos >> 6); };
   auto rows = [&]() -> int {
     for (uint64_t o = 0; o < n; o += rows_per) {
       const uint64_t m = std::min(rows_per, n - o);
@@ -453,9 +443,7 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
             const uint64_t pos0 = st.n;
             ZRET(store_append_dev(st, zero, z, nullptr, s));
             ZCHK(hipMemsetAsync(st.keys + pos0, 0xff, (size_t)z * 8, s));     // kInvalidKey (flat_index_format.h:29)
-            h->h_holes.resize((st.n + 63) / 64 + 1, 0);
-            for (uint64_t p = pos0; p < pos0 + z; ++p) { h->h_holes[p >> 6] |= 1ull << (p & 63); touch(p); }
-            h->nholes += z;
+            h->holes.host.set_range(pos0, pos0 + z);
             gap -= z;
           }
         }
@@ -466,7 +454,7 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
           i = j;
         } else {                                    // overwrite in place
           ZRET(launch_pack(st, tmp + (size_t)i * rb, 1, nullptr, id, nullptr, s, st.keys, keys ? tk + i : nullptr));
-          if (h->is_hole(id)) { h->h_holes[id >> 6] &= ~(1ull << (id & 63)); h->nholes -= 1; touch(id); }
+          h->holes.host.clear(id);
           ++i;
         }
       }
@@ -475,12 +463,13 @@ int zvec_hip_flat_put(zvec_hip_flat_t h, const uint32_t *ids, uint64_t n, const 
     return 0;
   };
   const int rc = rows();
-  return fast ? w.finish_enqueued(rc, slot, lo, hi) : w.finish_synced(rc, lo, hi);
+  return fast ? w.finish_enqueued(rc, slot) : w.finish_synced(rc);
 }
 
 int zvec_hip_flat_holes(zvec_hip_flat_t h, uint64_t *count) {
   if (!h || !count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  *count = h->nholes;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  *count = h->holes.count();
   return 0;
 }
 
@@ -521,26 +510,18 @@ int zvec_hip_flat_get_vectors(zvec_hip_flat_t h, const uint64_t *positions, uint
   return store_get_rows(h->defctx, h->st, pos, out);
 }
 
-// the exclude set a scan of this store has to use: the caller's, plus the holes add-with-id left (caller holds h->rw).  H: a flat
-// or a sparse handle, which keep their holes alike.
-extern "C++" {
-template <typename H>
-static int effective_exclude(H *h, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
+// the exclude set a scan of `rows` rows has to use (caller holds the handle's rw): the caller's plus the holes; no hole: the caller's pointer, nothing launched
+static int effective_exclude(const HoleBits &holes, uint64_t rows, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
   *out = d_exclude;
-  if (h->nholes == 0) return 0;
-  const uint64_t *d_holes = static_cast<const uint64_t *>(h->d_holes.p);
-  if (!d_exclude) { *out = d_holes; return 0; }
-  const uint64_t words = (h->st.n + 63) / 64;
+  if (holes.count() == 0) return 0;
+  if (!d_exclude) { *out = holes.device(); return 0; }
+  const uint64_t words = (rows + 63) / 64;
   ZRET(c->holes_ex.ensure(words * 8 + 8));
   hipLaunchKernelGGL(or_bits_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, c->holes_ex.as<uint64_t>(), d_exclude,
-                     d_holes, words);
+                     holes.device(), words);
   ZCHK(hipGetLastError());
   *out = c->holes_ex.as<uint64_t>();
   return 0;
-}
-}  // extern "C++"
-static int flat_effective_exclude(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const uint64_t *d_exclude, hipStream_t s, const uint64_t **out) {
-  return effective_exclude(h, c, d_exclude, s, out);
 }
 
 // the flat search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments
@@ -549,7 +530,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
                                   uint32_t *d_out_counts, hipStream_t s, ShadowMode mode = ShadowMode()) {
   // rows appended through the asynchronous device-pointer form may still be in flight on another stream
   ZRET(flat_wait_appends(h, s));
-  ZRET(flat_effective_exclude(h, c, d_exclude_bitset, s, &d_exclude_bitset));
+  ZRET(effective_exclude(h->holes, h->st.n, c, d_exclude_bitset, s, &d_exclude_bitset));
   // the kernels address the padded query matrix with 32-bit word offsets: very large batches go in slices
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(h->st.dpad, 1u));
   c->sh.count = 0;
@@ -705,7 +686,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   std::vector<uint32_t> clean(std::max<uint32_t>(total, 1));
   for (uint32_t i = 0; i < total; ++i) {
     uint32_t id = ids[i];
-    bool ok = id < st.n && !h->is_hole(id);
+    bool ok = id < st.n && !h->holes.host.is_hole(id);
     if (ok && exclude_bitset) ok = ((exclude_bitset[id >> 6] >> (id & 63)) & 1ull) == 0;
     clean[i] = ok ? id : IDX_NONE;
   }

@@ -181,7 +181,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
   if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
   const SparseStore &st = h->st;
   if (st.n == 0) return empty_results(d_keys, d_counts, count, topk, s);
-  ZRET(effective_exclude(h, c, d_exclude, s, &d_exclude));      // (the caller's pointer untouched while the store has no hole)
+  ZRET(effective_exclude(h->holes, st.n, c, d_exclude, s, &d_exclude));      // (the caller's pointer untouched while the store has no hole)
   const SearchOut out{d_keys, d_scores, nullptr, d_counts};
   if (h->inv.ready()) return sparse_inverted_search_locked(h, c, q_counts, d_qidx, d_qval, count, topk, threshold, d_exclude, out, s);
   const bool dump = topk > SPARSE_FUSED_MAX_K;
@@ -229,7 +229,7 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
                        uint32_t count, const uint32_t *ids, const uint32_t *offsets, const uint64_t *d_exclude,
                        const uint32_t **d_list_off, hipStream_t s, uint32_t row_stride = 0) {
   const SparseStore &st = h->st;
-  ZRET(effective_exclude(h, c, d_exclude, s, &d_exclude));      // (a hole is never scored: +inf, as any excluded position)
+  ZRET(effective_exclude(h->holes, st.n, c, d_exclude, s, &d_exclude));      // (a hole is never scored: +inf, as any excluded position)
   const uint32_t total = offsets[count];
   const uint64_t want = (uint64_t)device_cus(c) * 16;
   const uint32_t slice = (uint32_t)std::min<uint64_t>(SPARSE_ROWS_SLICE, std::max<uint64_t>(1, (total + want - 1) / want));
@@ -269,32 +269,19 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   });
 }
 
-// The hole bits of a sparse handle (zvec_hip_sparse_put leaves holes; api_entry_sparse_put.inc.h), kept as zvec_hip_flat_s keeps them.
-// Whoever holds h->rw exclusively and is about to make the store `rows` rows long calls sparse_holes_reserve FIRST: while the handle
-// tracks holes (it has some, the call is about to leave some — `leaves` —, or a device copy exists) the host words and the device
-// copy are made to span `rows` positions, new words zero.  The device copy grows through a block of its own and receives the bits as
-// they are, so a failure leaves the old copy and a caller that is refused afterwards has only grown it.  Every search reads
-// (st.n + 63) / 64 words of the copy: any call that extends st.n goes through here, zvec_hip_sparse_append included.
-int sparse_holes_upload(zvec_hip_sparse_s *h, uint64_t lo, uint64_t hi, hipStream_t s) {      // host words [lo, hi] (lo > hi: none)
-  if (!h->d_holes.p || lo > hi) return 0;
-  hi = std::min<uint64_t>(hi, std::min<uint64_t>(h->h_holes.size(), h->d_holes.cap / 8) - 1);
-  if (lo > hi) return 0;
-  ZCHK(hipMemcpyAsync(h->d_holes.as<uint64_t>() + lo, h->h_holes.data() + lo, (size_t)(hi - lo + 1) * 8, hipMemcpyHostToDevice, s));
-  ZCHK(hipStreamSynchronize(s));                 // (h_holes is pageable and may be resized by the next call)
-  return 0;
-}
-int sparse_holes_reserve(zvec_hip_sparse_s *h, uint64_t rows, bool leaves, hipStream_t s) {
-  if (!leaves && h->nholes == 0 && !h->d_holes.p) return 0;
-  const uint64_t words = (rows + 63) / 64 + 1;
-  if (h->h_holes.size() < words) h->h_holes.resize((size_t)words, 0);      // (zero words: no hole)
-  if (words * 8 <= h->d_holes.cap) return 0;                               // (the copy was zeroed to its capacity when it was made)
-  DevBuf grown;
-  ZRET(grown.ensure((size_t)words * 16));
-  ZCHK(hipMemsetAsync(grown.p, 0, grown.cap, s));
-  std::swap(h->d_holes.p, grown.p);                                        // (the old block goes with the local: hipFree waits for the device)
-  std::swap(h->d_holes.cap, grown.cap);
-  return sparse_holes_upload(h, 0, h->h_holes.size() - 1, s);
-}
+// One mutation of a sparse store: FlatWrite's twin on the handle's own stream, which every entry drains itself.  It holds h->mu, then
+// h->rw exclusively, while it lives; cover() as HoleBits says; finish() ends an entry that changed the store (the next search rebuilds the twin).
+struct SparseWrite {
+  zvec_hip_sparse_s *const h;
+  hipStream_t const s;
+  explicit SparseWrite(zvec_hip_sparse_s *h_) : h(h_), s(h_->defctx->own), g(h_->mu), w(h_->rw) {}
+  int open() { ZCHK(hipSetDevice(h->device)); return 0; }
+  int cover(uint64_t rows, bool leaves = false) { return h->holes.reserve(rows, leaves, s); }
+  int finish() { h->inv.stale = true; return h->holes.upload_dirty(s); }
+ private:
+  std::lock_guard<std::mutex> g;
+  std::unique_lock<FairSharedMutex> w;
+};
 
 }  // namespace
 }  // extern "C++"
@@ -343,10 +330,9 @@ int zvec_hip_sparse_destroy(zvec_hip_sparse_t h) {
 
 int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t elements) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
-  ZCHK(hipSetDevice(h->device));
-  return h->st.reserve(rows, elements, h->defctx->own);
+  SparseWrite w(h);
+  ZRET(w.open());
+  return h->st.reserve(rows, elements, w.s);             // (no row is stored: nothing to cover, and the twin still holds the rows)
 }
 
 int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const void *values, uint64_t n,
@@ -356,13 +342,12 @@ int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const ui
   uint64_t total = 0;
   ZRET(sparse_check_runs(counts, indices, n, &total));       // (before anything is stored: a refused call stores nothing)
   if (total && (!indices || !values)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
+  SparseWrite w(h);
   SparseStore &st = h->st;
   if (st.n + n > 0xfffffffeull) return ZVEC_HIP_ERR_OUT_OF_RANGE;      // (positions are 32-bit in the partial lists)
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
-  ZRET(sparse_holes_reserve(h, st.n + n, false, s));       // (a handle with holes: their bits span the rows a search reads)
+  ZRET(w.open());
+  hipStream_t s = w.s;
+  ZRET(w.cover(st.n + n));
   ZRET(st.reserve(st.n + n, st.elems + total, s));
   // one copy per array: offsets (the first one is the old end, already there), keys, indices, values
   std::vector<uint64_t> off((size_t)n), ks;
@@ -381,8 +366,7 @@ int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const ui
   ZCHK(hipStreamSynchronize(s));
   st.n += n;
   st.elems += total;
-  h->inv.stale = true;        // (rebuilt by the next search that needs it)
-  return 0;
+  return w.finish();
 }
 
 int zvec_hip_sparse_count(zvec_hip_sparse_t h, uint64_t *rows, uint64_t *elements) {

@@ -90,7 +90,7 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
   ZRET(c->part_s.ensure((size_t)sub * st.n * 4));
   float *dump = c->part_s.as<float>();
   const uint64_t *d_ex = exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr;
-  ZRET(effective_exclude(h, c, d_ex, s, &d_ex));
+  ZRET(effective_exclude(h->holes, st.n, c, d_ex, s, &d_ex));
   const SparseOperands op = sparse_operands(st, d_ex, c->sp_plan.as<uint32_t>(), dq, dq + te);
   const uint32_t wave_rows = (uint32_t)ropts().sparse_group_rows.load(std::memory_order_relaxed);
   for (uint32_t q0 = 0; q0 < count; q0 += sub) {

@@ -18,18 +18,6 @@
 extern "C++" {
 namespace {
 
-// bits [a, b) of a host bitset, word-wise; [*lo, *hi] follows the words it changes
-void holes_set_range(std::vector<uint64_t> &w, uint64_t a, uint64_t b, uint64_t *lo, uint64_t *hi) {
-  if (a >= b) return;
-  *lo = std::min(*lo, a >> 6);
-  *hi = std::max(*hi, (b - 1) >> 6);
-  for (uint64_t p = a; p < b;) {
-    const uint64_t word = p >> 6, end = std::min(b, (word + 1) << 6), cnt = end - p;
-    w[word] |= (cnt == 64 ? ~0ull : ((1ull << cnt) - 1)) << (p & 63);
-    p = end;
-  }
-}
-
 // a stream is drained when the scope ends, however it ends: asynchronous copies out of pageable host memory declared BEFORE this
 // object have left that memory by the time it is freed
 struct DrainOnExit {
@@ -53,8 +41,7 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
     if (i && ids[i] <= ids[i - 1]) ascending = false;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(h->mu);
-  std::unique_lock<FairSharedMutex> w(h->rw);
+  SparseWrite w(h);
   SparseStore &st = h->st;
   const uint32_t width = st.width;
 
@@ -80,8 +67,8 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
   for (uint32_t j = 0; j < T; ++j) sb[j + 1] = sb[j] + counts[keep[j]];
   const uint64_t S = sb[T];
 
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  ZRET(w.open());
+  hipStream_t s = w.s;
   // The device workspace, in 8-byte words, every part on a 16-byte boundary:
   //   tid[T] u32 | gath[2m] | tkey[T] | tval[T] | tbeg[m] | sbeg[m + 1] | ds[2m + 3] | ss[2m + 2] | stage idx[S] u32 | stage val[S]
   auto even = [](uint64_t words) { return (words + 1) & ~1ull; };
@@ -110,7 +97,6 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
   int64_t *tval = reinterpret_cast<int64_t *>(ws.data() + o_tval);
   int64_t shift = 0;
   bool same = true;
-  uint64_t cleared = 0;                                              // holes that become rows
   for (uint32_t j = 0; j < m; ++j) {
     const uint64_t ob = gath[2 * (size_t)j], oe = gath[2 * (size_t)j + 1], nl = sb[j + 1] - sb[j];
     if (oe < ob || oe > old_elems) return ZVEC_HIP_ERR_RUNTIME;      // (the store's own offsets: never)
@@ -123,7 +109,6 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
     tval[j] = shift;
     tbeg[j] = ob;
     sbeg[j] = sb[j];
-    if (h->is_hole(tid[j])) ++cleared;
   }
   sbeg[m] = sb[m];
   const uint64_t tail_base = old_elems + (uint64_t)shift, new_elems = tail_base + (S - sb[m]);
@@ -146,11 +131,7 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
   }
   const int route = m == 0 ? 0 : same ? 1 : 2;
   const uint64_t gap = (new_n - old_n) - (T - m);                     // holes the call leaves behind the old rows
-  const uint64_t nholes_after = h->nholes + gap - cleared;
-
-  // the hole bits span the new rows before anything changes (sparse_holes_reserve, api_entry_sparse.inc.h)
-  ZRET(sparse_holes_reserve(h, new_n, nholes_after != 0, s));
-  const bool track = h->d_holes.p != nullptr;
+  ZRET(w.cover(new_n, gap != 0));                                     // (the hole bits span the new rows before anything changes)
 
   // the tables and the stage go up once every allocation of the route has succeeded (the ids are there already if they were gathered by)
   auto upload_ws = [&]() -> int {
@@ -220,26 +201,13 @@ int sparse_put(zvec_hip_sparse_s *h, const uint32_t *ids, const uint32_t *counts
     moved = new_elems;
   }
 
-  // the hole bits: the gaps between the old end and the call's tail rows are set, a written hole is cleared
-  uint64_t lo = ~0ull, hi = 0;
-  if (track) {
-    uint64_t from = old_n;
-    for (uint32_t j = m; j < T; ++j) {
-      holes_set_range(h->h_holes, from, tid[j], &lo, &hi);
-      from = (uint64_t)tid[j] + 1;
-    }
-    for (uint32_t j = 0; j < m && cleared; ++j)
-      if (h->is_hole(tid[j])) {
-        h->h_holes[tid[j] >> 6] &= ~(1ull << (tid[j] & 63));
-        lo = std::min<uint64_t>(lo, tid[j] >> 6);
-        hi = std::max<uint64_t>(hi, tid[j] >> 6);
-      }
-    h->nholes = nholes_after;
-  }
-  h->inv.stale = true;        // (rebuilt by the next search that needs it)
+  // the hole bits: the gaps between the old end and the call's tail rows are set, a written hole is cleared (no gap, no hole: no pass)
+  uint64_t from = old_n;
+  for (uint32_t j = m; j < T && gap; ++j) { h->holes.host.set_range(from, tid[j]); from = (uint64_t)tid[j] + 1; }
+  for (uint32_t j = 0; j < m && h->holes.count(); ++j) h->holes.host.clear(tid[j]);
   h->put_route = route;
   h->put_moved = moved;
-  const int e = sparse_holes_upload(h, lo, hi, s);
+  const int e = w.finish();
   h->put_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return e;
 }
@@ -259,7 +227,7 @@ int zvec_hip_sparse_put(zvec_hip_sparse_t h, const uint32_t *ids, const uint32_t
 int zvec_hip_sparse_holes(zvec_hip_sparse_t h, uint64_t *count) {
   if (!h || !count) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   std::shared_lock<FairSharedMutex> r(h->rw);
-  *count = h->nholes;
+  *count = h->holes.count();
   return 0;
 }
 

@@ -58,6 +58,44 @@ struct DevBuf : Scoped<void> {
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// The hole bits of a flat or a sparse handle: add-with-id pads a gap in front of an id with rows under the invalid key that no search
+// may return.  Host words (host/hole_bits.h) plus a device copy that every entry taking an exclude set ORs in while a hole exists
+// (effective_exclude), reading its words for all of the store's rows.  So the protocol is reserve-first: whoever holds the handle's rw
+// exclusively and is about to make the store `rows` long calls reserve() BEFORE the store changes — words and copy then span `rows`
+// positions, new words zero; the copy grows through a block of its own, zeroed to its capacity, that receives the words as they are and
+// takes the old one's place on success only —, sets and clears host bits while it stores, and ends with upload_dirty().  A handle TRACKS
+// holes once a device copy exists, or the count is non-zero, or the call at hand leaves some (`leaves`): until then all of this is a no-op.
+struct HoleBits {
+  HoleWords host;
+  uint64_t count() const { return host.nholes; }
+  const uint64_t *device() const { return d_holes.as<uint64_t>(); }
+  int reserve(uint64_t rows, bool leaves, hipStream_t s) {
+    if (!leaves && count() == 0 && !d_holes.p) return 0;
+    host.resize(rows);
+    if (HoleWords::words_for(rows) * 8 <= d_holes.cap) return 0;
+    DevBuf grown;
+    ZRET(grown.ensure((size_t)HoleWords::words_for(rows) * 16));
+    ZCHK(hipMemsetAsync(grown.p, 0, grown.cap, s));
+    ZRET(upload(grown, 0, ~0ull, s));
+    std::swap(d_holes, grown);                     // (the old block goes with the local: hipFree waits for the device)
+    return 0;
+  }
+  int upload_dirty(hipStream_t s) {                // the words changed since the last upload reach the copy
+    uint64_t lo, hi;
+    return host.take_dirty(&lo, &hi) ? upload(d_holes, lo, hi, s) : 0;
+  }
+
+ private:
+  DevBuf d_holes;
+  int upload(DevBuf &to, uint64_t lo, uint64_t hi, hipStream_t s) {      // host words [lo, hi], as far as both sides have them
+    const uint64_t have = std::min<uint64_t>(host.words.size(), to.cap / 8), end = hi < have ? hi + 1 : have;
+    if (lo >= end) return 0;
+    ZCHK(hipMemcpyAsync(to.as<uint64_t>() + lo, host.words.data() + lo, (size_t)(end - lo) * 8, hipMemcpyHostToDevice, s));
+    ZCHK(hipStreamSynchronize(s));                 // (the words are pageable and may be resized by the next call)
+    return 0;
+  }
+};
+
 // a typed window into somebody else's device buffer
 struct DevView {
   void *p = nullptr;
@@ -427,9 +465,7 @@ struct zvec_hip_flat_s {
   // extend the store holds it exclusive.  A growth reallocation frees the old arrays with hipFree, which waits for
   // the device, so kernels enqueued by earlier searches have finished with them.
   FairSharedMutex rw;
-  // Every mutation goes through one FlatWrite (api_entry_ctx_flat.inc.h), which is the writers' protocol: mu, then rw exclusively; the
-  // device and the stream; the fp16 twin dropped; the stream ordered behind a mutation still only enqueued on another one; afterwards
-  // the device copy of the hole bits extended, and one of two endings.  finish_synced: the stream is drained, readers need nothing.
+  // Every mutation goes through one FlatWrite (api_entry_ctx_flat.inc.h: the writers' protocol).  finish_synced: the stream is drained, readers need nothing.
   // finish_enqueued (append_dev, append_fp32_dev, adds of up to FAST_ROWS rows): the row count is published while kernels are only
   // enqueued on `append_stream`.  Whoever enqueues on ANOTHER stream next — a reader or a writer — makes that stream wait: it records
   // append_ev behind them if nobody has since the last mutation (append_dirty; readers run concurrently and do so under ev_mu) and
@@ -440,12 +476,7 @@ struct zvec_hip_flat_s {
   bool append_dirty = false;
   hipStream_t append_stream = nullptr;
   std::mutex ev_mu;
-  // add-with-id gaps (FlatStreamerEntity::add_vector_with_id pads positions [count, id) with kInvalidKey rows that no scan
-  // returns, flat_streamer_entity.cc:935-952): one bit per storage position, host copy + device copy, OR-ed into every
-  // search's exclude set while any hole exists
-  std::vector<uint64_t> h_holes;
-  uint64_t nholes = 0;
-  DevBuf d_holes;
+  HoleBits holes;           // add-with-id gaps: FlatStreamerEntity::add_vector_with_id pads [count, id) with kInvalidKey rows (flat_streamer_entity.cc:935-952)
   // single-document adds (the product ingests one add_with_id_impl per document): a ring of pinned slots that the pack
   // kernel reads in place — no staging copy, no allocation, no synchronisation per document
   static constexpr uint32_t FAST_ROWS = 8, RING = 64, RING_GROUP = 16;     // one event per group of slots
@@ -455,7 +486,6 @@ struct zvec_hip_flat_s {
   bool ring_used[RING / RING_GROUP] = {};
   uint32_t ring_next = 0;
   DevBuf enc;               // zvec_hip_flat_append_fp32[_dev]: the encoded words of a slice of rows, between the encoder and the pack kernel
-  bool is_hole(uint64_t pos) const { return (pos >> 6) < h_holes.size() && ((h_holes[pos >> 6] >> (pos & 63)) & 1ull); }
   // (zvec_hip_flat_destroy has made the device current and idle)
   ~zvec_hip_flat_s() {
     for (uint32_t i = 0; i < RING / RING_GROUP; ++i)
@@ -575,13 +605,8 @@ struct zvec_hip_sparse_s {
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;            // serialises the calls that use defctx's workspace (appends, get_vector)
   FairSharedMutex rw;       // searches hold it shared, anything that may move or extend the store exclusive (as zvec_hip_flat_s)
-  // add-with-id gaps (FlatSparseStreamerEntity::add_vector_with_id pads positions [count, id) with empty rows under kInvalidKey,
-  // flat_sparse_streamer_entity.cc:708-783): one bit per storage position, host copy + device copy, as zvec_hip_flat_s keeps them;
-  // every entry that takes an exclude set passes its own OR these while any hole exists (api_entry_sparse_put.inc.h)
-  std::vector<uint64_t> h_holes;
-  uint64_t nholes = 0;
-  DevBuf d_holes;
-  bool is_hole(uint64_t pos) const { return (pos >> 6) < h_holes.size() && ((h_holes[pos >> 6] >> (pos & 63)) & 1ull); }
+  // add-with-id gaps: FlatSparseStreamerEntity::add_vector_with_id pads [count, id) with empty rows under kInvalidKey (flat_sparse_streamer_entity.cc:708-783)
+  HoleBits holes;           // (every mutation of the store goes through one SparseWrite, api_entry_sparse.inc.h)
   // zvec_hip_sparse_put: its device workspace (tables and staged pairs of one call; kept between calls), and what the last
   // successful call did (zvec_hip_sparse_put_info)
   DevBuf put_ws;

@@ -24,6 +24,7 @@
 
 #include "../../include/zvec_hip.h"
 #include "scan_kernels.hip.h"
+#include "host/hole_bits.h"
 
 using namespace zvk;
 
