@@ -729,9 +729,33 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     handle has no hole); zvec_hip_sparse_batch_distance scores a hole +inf; zvec_hip_sparse_get_vector of a hole returns
  *     count 0 and status 0, the empty row the reference stores; exclude bitsets and group_of_position are indexed by storage
  *     position, holes included.  zvec_hip_sparse_append on a handle that has holes extends the hole bits with the rows.
+ *   - Rows and queries from device memory (zvec_hip_sparse_append_dev, zvec_hip_sparse_append_dense_dev,
+ *     zvec_hip_sparse_from_dense_dev, zvec_hip_sparse_search_dense_dev, zvec_hip_sparse_ingest_info).  The reference has no
+ *     such entry: its rows arrive in host memory.  Every array named d_* is device memory of the handle's (the context's)
+ *     device.  A DENSE matrix is n rows of `dim` elements of the handle's value type, row r at d_rows + r * ld elements
+ *     (ld >= dim); column j becomes index j.  An element is KEPT iff it is not zero: +0 and -0 are dropped, every other bit
+ *     pattern is kept as it is, subnormals included (inf and NaN too, with unspecified scores, see Value type); the kept
+ *     elements of a row stand in column order, so every run ascends strictly, and the same matrix gives the same bytes on every
+ *     call.  Neither d_rows nor ld * sizeof(value) needs to be a multiple of 16 (d_rows must be a multiple of the value's own
+ *     size).  Rows are cut into column slices of slice_cols columns (a constant of the library, zvec_hip_sparse_ingest_info), so
+ *     a call of one wide row spreads over the device as a call of many rows does.  Validation is the rule of append, done on
+ *     the device: at most 4096 pairs a row (a dense row with more non-zeros is REFUSED with the whole call, where the reference
+ *     discards the row), runs strictly ascending, and for CSR the counts summing to `elements`:
+ *     ZVEC_HIP_ERR_INVALID_ARGUMENT.  So are a NULL handle, a NULL required array with n > 0 and ld < dim; more than 2^32 - 2
+ *     rows afterwards returns ZVEC_HIP_ERR_OUT_OF_RANGE.  All or nothing: a refused call leaves rows, keys, holes, counts and
+ *     the inverted lists' state as they were.  n == 0 returns 0.  d_keys == NULL stores key = storage position.  Hole bits are
+ *     extended and the inverted lists marked out of date as by zvec_hip_sparse_append.  Waits: the two appends enqueue their
+ *     checks on `stream` (NULL: the handle's own) and WAIT for it once, to read the status word and the total before anything
+ *     of the store changes; they then write the rows on the same stream and return with the rows stored, having drained it as
+ *     zvec_hip_sparse_append does.  zvec_hip_sparse_search_dense_dev waits once for its queries' lengths, which
+ *     zvec_hip_sparse_search_dev needs on the host to cut query blocks, and then IS that call: scores, ties, threshold, exclude
+ *     bitset, topk caps, the row scan or the inverted lists, both metrics, word for word; a query with more than 4096 non-zeros
+ *     returns ZVEC_HIP_ERR_INVALID_ARGUMENT and touches no output.  zvec_hip_sparse_from_dense_dev waits once for the total.
+ *     A device append must not overlap a zvec_hip_sparse_search_dev of the same handle still running on another stream.
  * Not served (each is the reference's to keep doing on the CPU): removing a document, the
  * MipsSquaredEuclideanSparse metric, loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror
- * (zvec_hip_operator.hpp); by the inverted lists: ZVEC_HIP_METRIC_L2, listed rows and group-by. */
+ * (zvec_hip_operator.hpp); by the inverted lists: ZVEC_HIP_METRIC_L2, listed rows and group-by; from device memory:
+ * zvec_hip_sparse_put, a matrix of another type than the handle's, and any rule for keeping an element other than "not zero". */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
 /* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
  * InnerProductSparse. */
@@ -751,6 +775,28 @@ int zvec_hip_sparse_reserve(zvec_hip_sparse_t h, uint64_t rows, uint64_t element
  * being counts[i] pairs; keys == NULL -> key = storage position.  All or nothing (see Row format, Index order). */
 int zvec_hip_sparse_append(zvec_hip_sparse_t h, const uint32_t *counts, const uint32_t *indices, const void *values,
                            uint64_t n, const uint64_t *keys);
+/* zvec_hip_sparse_append with every array in device memory: d_counts[n], the runs back to back in d_indices[elements] /
+ * d_values[elements], d_keys[n] or NULL.  Validated on the device; see Rows and queries from device memory above. */
+int zvec_hip_sparse_append_dev(zvec_hip_sparse_t h, const uint32_t *d_counts, const uint32_t *d_indices, const void *d_values,
+                               uint64_t n, uint64_t elements, const uint64_t *d_keys, void *stream);
+/* n dense device rows of `dim` elements of the handle's value type, `ld` elements apart: the non-zeros of row r become the row at
+ * the next storage position, column j as index j.  dim == 0 gives empty rows.  See Rows and queries from device memory above. */
+int zvec_hip_sparse_append_dense_dev(zvec_hip_sparse_t h, const void *d_rows, uint64_t n, uint32_t dim, uint64_t ld,
+                                     const uint64_t *d_keys, void *stream);
+/* The converter alone, as zvec_hip_binary_encode_dev is for the sign bits: n dense device rows of dtype ZVEC_HIP_DT_FP32 or
+ * ZVEC_HIP_DT_FP16 (anything else: ZVEC_HIP_ERR_UNSUPPORTED) -> d_counts[n] and the runs back to back in d_indices / d_values
+ * (room for elems_cap pairs).  *elements, the pairs of the matrix, is always written (0 by a refused call).  d_indices or d_values
+ * NULL: a size query, only the counts are written.  ZVEC_HIP_ERR_OUT_OF_RANGE when elems_cap is too small: nothing but the counts
+ * is written.  A row may be longer than 4096 here: the converter does not know an index's cap.  Waits once on `stream` (NULL: the
+ * context's) for the total; the pairs are enqueued behind it.  A NULL ctx, elements, d_in or d_counts with n > 0, and ld < dim:
+ * ZVEC_HIP_ERR_INVALID_ARGUMENT. */
+int zvec_hip_sparse_from_dense_dev(zvec_hip_ctx_t ctx, int dtype, const void *d_in, uint64_t n, uint32_t dim, uint64_t ld,
+                                   uint32_t *d_counts, uint32_t *d_indices, void *d_values, uint64_t elems_cap, uint64_t *elements,
+                                   void *stream);
+/* The last successful zvec_hip_sparse_append_dev / _append_dense_dev of the handle.  route: -1 none yet, 0 CSR, 1 dense; elements:
+ * the pairs that call stored; slice_cols: columns of one work item of the dense converter (a constant of the library, reported
+ * before any call); ms: wall-clock time of the call.  Every output nullable. */
+int zvec_hip_sparse_ingest_info(zvec_hip_sparse_t h, int *route, uint64_t *elements, uint32_t *slice_cols, double *ms);
 /* FlatSparseStreamer::add_with_id_impl in bulk: row i, counts[i] pairs, goes to storage position ids[i]; see Add-with-id above. */
 int zvec_hip_sparse_put(zvec_hip_sparse_t h, const uint32_t *ids, const uint32_t *counts, const uint32_t *indices,
                         const void *values, uint64_t n, const uint64_t *keys);
@@ -777,6 +823,12 @@ int zvec_hip_sparse_search_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const ui
                                const uint32_t *d_q_indices, const void *d_q_values, uint32_t count, uint32_t topk,
                                float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                                float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* zvec_hip_sparse_search_dev for `count` DENSE device queries of `dim` elements of the handle's value type, `ld` elements apart:
+ * their non-zeros are gathered into the context's workspace, the lengths come to the host (the call's one wait), and the search
+ * above runs on them unchanged.  See Rows and queries from device memory above. */
+int zvec_hip_sparse_search_dense_dev(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count, uint32_t dim,
+                                     uint64_t ld, uint32_t topk, float threshold, const uint64_t *d_exclude_bitset,
+                                     uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
 /* FlatSparseStreamer::search_bf_by_p_keys_impl (flat_sparse_streamer.cc:324-349; FlatSparseSearcher, flat_sparse_searcher.cc:
  * 98-103; FlatSparseEntity::search_p_keys, flat_sparse_entity.h:63-77): query q against rows ids[offsets[q] .. offsets[q+1])
  * only (offsets[count + 1], offsets[0] == 0; ids may be NULL when every list is empty).  Queries and outputs as

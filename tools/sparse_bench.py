@@ -67,6 +67,17 @@ streaming figure (zvec_hip_calibrate, same process) and the bytes the device bui
                 each, not repeated; reported, not gated.
 
     python tools/sparse_bench.py --put [--dtype fp32|fp16] [--put-rows 1000] [--out profiles/sparse_put.json]
+
+    --ingest    rows and queries that are dense matrices in device memory, what a learned sparse encoder leaves there
+                (zvec_hip_sparse_append_dense_dev, zvec_hip_sparse_search_dense_dev).  The full-scan mode's corpus is scattered into
+                dense rows over the vocabulary on the device, --ingest-rows rows at a time (the whole matrix does not fit), and every
+                block is appended as it stands.  Reported: the appends' wall clock (zvec_hip_sparse_ingest_info) and the bytes of
+                the matrix they read per second (the matrix is read twice: count, then fill), one dense search at batches 1, 64
+                and 1024 (device events around the steps), and, on the first --ingest-host-blocks blocks, the host route on the same
+                data: copy the block to the host, numpy nonzero, zvec_hip_sparse_append.  All next to the box's calibrated
+                streaming rate.  Reported, not gated.
+
+    python tools/sparse_bench.py --ingest [--dtype fp32|fp16] [--ingest-rows 8192] [--out profiles/sparse_ingest.json]
 """
 import argparse
 import ctypes as C
@@ -494,6 +505,92 @@ def put(args, metric):
             "each, not repeated", "chunk_elems": chunk, "clock_mhz": mhz.value, "stream_gbs": gbs.value, "legs": legs}
 
 
+def ingest(args, metric):
+    import time
+    import numpy as np
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    tval = torch.float16 if args.dtype == "fp16" else torch.float32
+    width = 2 if args.dtype == "fp16" else 4
+    rc_, ri = zipf_runs(torch, dev, g, args.n, 64, 192, args.vocab, 768)
+    off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(rc_, 0)])
+
+    def dense(counts, idx):
+        """the runs scattered into dense rows on the device; values in [0.5, 1): no scattered element is a zero"""
+        rows = torch.repeat_interleave(torch.arange(counts.numel(), device=dev), counts.to(dev))
+        m = torch.zeros((counts.numel(), args.vocab), dtype=tval, device=dev)
+        m[rows, idx.to(dev).long()] = (torch.rand(idx.numel(), generator=g, device=dev) * 0.5 + 0.5).to(tval)
+        return m
+    se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
+    host = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
+    blocks, host_blocks = [], []
+    for b, a in enumerate(range(0, args.n, args.ingest_rows)):
+        z = min(a + args.ingest_rows, args.n)
+        m = dense(rc_[a:z], ri[off[a]:off[z]])
+        torch.cuda.synchronize()
+        assert se.add_dense(m) == 0
+        info = se.ingest_info()
+        assert info["route"] == 1 and info["elements"] == int(off[z] - off[a]), info
+        nbytes = m.numel() * width
+        blocks.append({"rows": z - a, "elements": info["elements"], "ms": info["ms"], "matrix_bytes": nbytes,
+                       "read_gbs": 2 * nbytes / info["ms"] / 1e6})
+        if b < args.ingest_host_blocks:
+            t0 = time.perf_counter()
+            hm = m.cpu().numpy()
+            t1 = time.perf_counter()
+            r, c = np.nonzero(hm)
+            hc = np.bincount(r, minlength=hm.shape[0]).astype(np.uint32)
+            hv = hm[r, c]
+            t2 = time.perf_counter()
+            assert host.add_batch(hc, c.astype(np.uint32), hv) == 0
+            t3 = time.perf_counter()
+            host_blocks.append({"rows": z - a, "copy_ms": (t1 - t0) * 1e3, "nonzero_ms": (t2 - t1) * 1e3, "append_ms": (t3 - t2) * 1e3,
+                                "ms": (t3 - t0) * 1e3})
+        del m
+    del host
+    searches = []
+    for batch in (1, 64, 1024):
+        qc, qi = zipf_runs(torch, dev, g, batch, 16, 64, args.vocab, 256)
+        qm = dense(qc, qi)
+        for _ in range(args.warmup):
+            se.search_dense(qm, args.topk)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(torch.cuda.Stream(dev)):
+            e0.record()
+            for _ in range(args.steps):
+                se.search_dense(qm, args.topk)
+            e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.steps
+        searches.append({"batch": batch, "ms": ms, "qps": batch / ms * 1e3, "query_matrix_bytes": qm.numel() * width})
+        print(json.dumps(searches[-1]), flush=True)
+    slice_cols = se.ingest_info()["slice_cols"]
+    rows, elements = se.count(), se.element_count()
+    del se
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    dev_ms, mat = sum(b["ms"] for b in blocks), sum(b["matrix_bytes"] for b in blocks)
+    res = {"workload": "flat sparse %d rows x 64-192 of %d (Zipf), %s values, as dense device rows in blocks of %d" % (
+               args.n, args.vocab, args.dtype, args.ingest_rows),
+           "metric": metric, "timing": "appends: zvec_hip_sparse_ingest_info's ms, wall clock of the call, its waits included; searches: "
+           "device events around the steps on a stream (each step waits once for the queries' lengths); host route: wall clock",
+           "slice_cols": slice_cols, "clock_mhz": mhz.value, "stream_gbs": gbs.value, "rows": rows, "elements": elements,
+           "append_dense_ms": dev_ms, "matrix_bytes": mat, "append_dense_read_gbs": 2 * mat / dev_ms / 1e6,
+           "append_dense_blocks": len(blocks), "append_dense_block_ms_median": sorted(b["ms"] for b in blocks)[len(blocks) // 2],
+           "host_route_blocks": host_blocks, "searches": searches, "steps": args.steps, "warmup": args.warmup}
+    if host_blocks:
+        res["host_route_ms_per_block"] = sum(b["ms"] for b in host_blocks) / len(host_blocks)
+        res["append_dense_ms_per_block_same_blocks"] = sum(b["ms"] for b in blocks[:len(host_blocks)]) / len(host_blocks)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -507,6 +604,9 @@ def main():
     ap.add_argument("--inverted", action="store_true")
     ap.add_argument("--put", action="store_true")
     ap.add_argument("--put-rows", type=int, default=1000, help="--put: rows of each call")
+    ap.add_argument("--ingest", action="store_true")
+    ap.add_argument("--ingest-rows", type=int, default=8192, help="--ingest: dense rows generated and appended at a time")
+    ap.add_argument("--ingest-host-blocks", type=int, default=4, help="--ingest: blocks that also go the host route")
     ap.add_argument("--build-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                         "sparse_inverted_build.json"), help="--inverted: where the build timings go")
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32")
@@ -519,6 +619,9 @@ def main():
         mode = inverted
     if args.put:
         mode = put
+    if args.ingest:
+        mode, rows = ingest, "searches"
+        args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sparse_ingest.json")
     res = mode(args, "ip")
     if args.metric == "l2":
         res = beside(res, mode(args, "l2"), rows)

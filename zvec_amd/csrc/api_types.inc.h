@@ -417,6 +417,7 @@ struct zvec_hip_ctx_s {
   DevBuf sp_plan;                                      // sparse search: query offsets | query-block table (api_entry_sparse.inc.h)
   PinnedBuf sp_pin;                                    // ... its pinned source, and the event behind its last upload
   hipEvent_t sp_ev = nullptr;
+  DevBuf sp_ing, sp_ing_pairs;                         // dense rows -> CSR: counts, offsets and status | the pairs (api_entry_sparse_ingest.inc.h)
   DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)
@@ -613,6 +614,12 @@ struct zvec_hip_sparse_s {
   int put_route = -1;
   uint64_t put_moved = 0;
   double put_ms = 0.0;
+  // zvec_hip_sparse_append_dev / _append_dense_dev: their device workspace (kept between calls), and what the last successful call
+  // did (zvec_hip_sparse_ingest_info)
+  DevBuf ing_ws;
+  int ing_route = -1;
+  uint64_t ing_elems = 0;
+  double ing_ms = 0.0;
   ~zvec_hip_sparse_s() { delete defctx; }
 };
 

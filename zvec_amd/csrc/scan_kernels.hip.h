@@ -37,3 +37,4 @@
 #include "zvk_sparse_inv.hip.h"
 #include "zvk_sparse_invb.hip.h"
 #include "zvk_sparse_put.hip.h"
+#include "zvk_sparse_ingest.hip.h"

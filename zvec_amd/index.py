@@ -1095,6 +1095,159 @@ class HipFlatSparseStreamer:
             C.c_void_p(d_exclude) if d_exclude else None, C.c_void_p(d_out_keys), C.c_void_p(d_out_scores),
             C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
 
+    # ---- rows and queries that are torch tensors on the index's device (include/zvec_hip.h, "Rows and queries from device memory") ----
+    def _keys_dev(self, keys, n):
+        return None if keys is None else _torch_array(keys, self.device, "keys", _torch_words(64), n)
+
+    def _stored_dev(self, n0, n, keys):
+        if n:
+            self._keys_host.append(np.arange(n0, n0 + n, dtype=np.uint64) if keys is None
+                                   else keys.cpu().numpy().view(np.uint64).copy())
+
+    def add_csr_dev(self, counts, indices, values, keys=None):
+        """add_batch with every array a torch tensor on the index's device (zvec_hip_sparse_append_dev): counts / indices int32 or
+        uint32, values of the index's type, keys int64 or uint64.  Validated on the device; all or nothing.  Runs on torch's
+        current stream and returns with the rows stored.  A CPU tensor or a wrong dtype raises ValueError."""
+        c = _torch_array(counts, self.device, "counts", _torch_words(32))
+        i = _torch_array(indices, self.device, "indices", _torch_words(32))
+        v = _torch_array(values, self.device, "values", (_torch_float(self.dtype),), i.numel())
+        k = self._keys_dev(keys, c.numel())
+        n0 = self.count()
+        rc = _lib.lib().zvec_hip_sparse_append_dev(self._h, _torch_ptr(c), _torch_ptr(i), _torch_ptr(v), c.numel(), i.numel(),
+                                                   _torch_ptr(k), _torch_stream(self.device))
+        if rc == 0:
+            self._stored_dev(n0, c.numel(), k)
+        return rc
+
+    def add_dense(self, matrix, keys=None):
+        """the non-zeros of every row of a dense [n, dim] torch tensor of the index's type on its device, column j as index j
+        (zvec_hip_sparse_append_dense_dev).  Rows may be `stride(0)` elements apart (a column slice of a wider matrix); columns
+        that are not adjacent are copied first.  -0.0 counts as zero; a row with more than 4096 non-zeros refuses the whole call."""
+        m, ld = _torch_matrix(matrix, self.device, _torch_float(self.dtype))
+        k = self._keys_dev(keys, m.shape[0])
+        n0 = self.count()
+        rc = _lib.lib().zvec_hip_sparse_append_dense_dev(self._h, _torch_ptr(m), m.shape[0], m.shape[1], ld, _torch_ptr(k),
+                                                         _torch_stream(self.device))
+        if rc == 0:
+            self._stored_dev(n0, m.shape[0], k)
+        return rc
+
+    def search_dense(self, matrix, topk, threshold=None, exclude=None, ctx=None):
+        """zvec_hip_sparse_search_dense_dev: the rows of a dense [count, dim] torch tensor as queries.  Returns torch tensors on the
+        device, (keys int64 [count, topk] holding the uint64 keys' bits, scores float32 [count, topk], counts int32 [count]),
+        enqueued on torch's current stream.  exclude: a device tensor of 64-bit words, bit i = storage position i."""
+        import torch
+        m, ld = _torch_matrix(matrix, self.device, _torch_float(self.dtype))
+        ex = None if exclude is None else _torch_array(exclude, self.device, "exclude", _torch_words(64))
+        count, k = m.shape[0], int(topk)
+        keys = torch.zeros((count, k), dtype=torch.int64, device=m.device)
+        scores = torch.zeros((count, k), dtype=torch.float32, device=m.device)
+        cnts = torch.zeros(count, dtype=torch.int32, device=m.device)
+        if ctx is None:
+            ctx = getattr(self, "_dense_ctx", None) or IndexContext(self.device)
+            self._dense_ctx = ctx
+        stream = _torch_stream(self.device)
+        _lib.check(_lib.lib().zvec_hip_sparse_search_dense_dev(
+            self._h, ctx._h, _torch_ptr(m), count, m.shape[1], ld, k, FLT_MAX if threshold is None else threshold,
+            _torch_ptr(ex), _torch_ptr(keys), _torch_ptr(scores), _torch_ptr(cnts), stream), "zvec_hip_sparse_search_dense_dev")
+        if not stream.value:
+            ctx.synchronize()
+        return keys, scores, cnts
+
+    def ingest_info(self):
+        """the last successful add_csr_dev / add_dense (zvec_hip_sparse_ingest_info): route -1 none yet / 0 CSR / 1 dense"""
+        route, elems, cols, ms = C.c_int(0), C.c_uint64(0), C.c_uint32(0), C.c_double(0.0)
+        _lib.check(_lib.lib().zvec_hip_sparse_ingest_info(self._h, C.byref(route), C.byref(elems), C.byref(cols), C.byref(ms)),
+                   "zvec_hip_sparse_ingest_info")
+        return {"route": int(route.value), "elements": int(elems.value), "slice_cols": int(cols.value), "ms": float(ms.value)}
+
+
+def _torch_words(bits):
+    import torch
+    names = ("int%d" % bits, "uint%d" % bits)           # (the same bits either way; older torch has no unsigned types)
+    return tuple(getattr(torch, n) for n in names if hasattr(torch, n))
+
+
+def _torch_float(dt):
+    import torch
+    return torch.float16 if dt == DT_FP16 else torch.float32
+
+
+def _torch_array(t, device, what, dtypes, numel=None):
+    """a torch tensor on cuda:`device` of one of `dtypes` (and of `numel` elements) as a contiguous 1-d one, or ValueError"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != device:
+        raise ValueError("zvec_amd: %s must be a torch tensor on cuda:%d" % (what, device))
+    if t.dtype not in dtypes:
+        raise ValueError("zvec_amd: %s must be %s, not %s" % (what, " or ".join(str(d) for d in dtypes), t.dtype))
+    if numel is not None and t.numel() != numel:
+        raise ValueError("zvec_amd: %s must hold %d elements, not %d" % (what, numel, t.numel()))
+    return t.contiguous().reshape(-1)
+
+
+def _torch_matrix(t, device, dtype):
+    """a 2-d torch tensor on cuda:`device` of `dtype` -> (the tensor with adjacent columns, its row stride in elements), or ValueError"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != device:
+        raise ValueError("zvec_amd: the matrix must be a torch tensor on cuda:%d" % device)
+    if t.dtype != dtype:
+        raise ValueError("zvec_amd: the matrix must be %s, not %s" % (dtype, t.dtype))
+    if t.dim() != 2:
+        raise ValueError("zvec_amd: the matrix must have two dimensions")
+    n, dim = t.shape
+    if (dim > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < dim):
+        t = t.contiguous()
+    return t, max(int(t.stride(0)) if n > 1 else 0, int(dim))
+
+
+def _torch_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _torch_stream(device):
+    """torch's current stream as the library takes one.  The default stream has no handle to pass: it is drained instead (the
+    tensors are complete) and the library works on a stream of its own, which the callers below drain before they return."""
+    import torch
+    s = torch.cuda.current_stream(device)
+    if not s.cuda_stream:
+        s.synchronize()
+    return C.c_void_p(s.cuda_stream)
+
+
+def sparse_from_dense(matrix, ctx=None):
+    """zvec_hip_sparse_from_dense_dev: a dense [n, dim] float32 or float16 torch tensor on a GPU -> (counts int32 [n], indices int32
+    [elements], values [elements] of the matrix's type), torch tensors on the same device: the non-zeros of every row in column
+    order, bit for bit (-0.0 counts as zero).  A size query first, then the fill, both on torch's current stream."""
+    import torch
+    if not isinstance(matrix, torch.Tensor) or not matrix.is_cuda:
+        raise ValueError("zvec_amd: the matrix must be a torch tensor on a GPU")
+    if matrix.dtype not in (torch.float32, torch.float16):
+        raise ValueError("zvec_amd: the matrix must be float32 or float16, not %s" % matrix.dtype)
+    device = matrix.device.index
+    m, ld = _torch_matrix(matrix, device, matrix.dtype)
+    ctx = ctx or IndexContext(device)
+    dt = DT_FP16 if m.dtype == torch.float16 else DT_FP32
+    n, dim = m.shape
+    counts = torch.zeros(n, dtype=torch.int32, device=m.device)
+    indices = torch.zeros(0, dtype=torch.int32, device=m.device)
+    values = torch.zeros(0, dtype=m.dtype, device=m.device)
+    if n == 0:
+        return counts, indices, values
+    total = C.c_uint64(0)
+    L = _lib.lib()
+    _lib.check(L.zvec_hip_sparse_from_dense_dev(ctx._h, dt, _torch_ptr(m), n, dim, ld, _torch_ptr(counts), None, None, 0,
+                                                C.byref(total), _torch_stream(device)), "zvec_hip_sparse_from_dense_dev")
+    if total.value:
+        indices = torch.zeros(total.value, dtype=torch.int32, device=m.device)
+        values = torch.zeros(total.value, dtype=m.dtype, device=m.device)
+        stream = _torch_stream(device)
+        _lib.check(L.zvec_hip_sparse_from_dense_dev(ctx._h, dt, _torch_ptr(m), n, dim, ld, _torch_ptr(counts), _torch_ptr(indices),
+                                                    _torch_ptr(values), total.value, C.byref(total), stream),
+                   "zvec_hip_sparse_from_dense_dev")
+        if not stream.value:
+            ctx.synchronize()
+    return counts, indices, values
+
 
 class HipIVFSearcher:
     """stands where "IVFSearcher"/"IVFStreamer" are registered (ivf_searcher.cc:183-250)."""
