@@ -730,8 +730,8 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     count 0 and status 0, the empty row the reference stores; exclude bitsets and group_of_position are indexed by storage
  *     position, holes included.  zvec_hip_sparse_append on a handle that has holes extends the hole bits with the rows.
  *   - Rows and queries from device memory (zvec_hip_sparse_append_dev, zvec_hip_sparse_append_dense_dev,
- *     zvec_hip_sparse_from_dense_dev, zvec_hip_sparse_search_dense_dev, zvec_hip_sparse_ingest_info).  The reference has no
- *     such entry: its rows arrive in host memory.  Every array named d_* is device memory of the handle's (the context's)
+ *     zvec_hip_sparse_from_dense_dev, zvec_hip_sparse_search_dense_dev, zvec_hip_sparse_ingest_info, zvec_hip_sparse_put_dev).
+ *     The reference has no such entry: its rows arrive in host memory.  Every array named d_* is device memory of the handle's (the context's)
  *     device.  A DENSE matrix is n rows of `dim` elements of the handle's value type, row r at d_rows + r * ld elements
  *     (ld >= dim); column j becomes index j.  An element is KEPT iff it is not zero: +0 and -0 are dropped, every other bit
  *     pattern is kept as it is, subnormals included (inf and NaN too, with unspecified scores, see Value type); the kept
@@ -752,10 +752,24 @@ uint32_t zvec_hip_crc32c(const void *data, uint64_t len, uint32_t crc);
  *     bitset, topk caps, the row scan or the inverted lists, both metrics, word for word; a query with more than 4096 non-zeros
  *     returns ZVEC_HIP_ERR_INVALID_ARGUMENT and touches no output.  zvec_hip_sparse_from_dense_dev waits once for the total.
  *     A device append must not overlap a zvec_hip_sparse_search_dev of the same handle still running on another stream.
+ *     zvec_hip_sparse_put_dev is zvec_hip_sparse_put with d_ids[n], d_counts[n], d_indices[elements], d_values[elements] and
+ *     d_keys[n] (or NULL: key = id) in device memory, and its contract is that entry's word for word: call order, the later row
+ *     of an id named twice, appends, holes, replacements, all or nothing, both value types and metrics, the three routes chosen
+ *     by the same rule and reported by zvec_hip_sparse_put_info, the inverted lists marked out of date; the store afterwards is
+ *     byte for byte the store after zvec_hip_sparse_put of the same arrays.  Validation is the rule of append, done on the
+ *     device as for zvec_hip_sparse_append_dev (ZVEC_HIP_ERR_INVALID_ARGUMENT, also for a NULL d_ids with n > 0); an id of
+ *     2^32 - 1, or more than 2^32 - 2 rows afterwards, returns ZVEC_HIP_ERR_OUT_OF_RANGE; a refused call leaves the last
+ *     put_info as it was too.  The pairs and the keys never cross to the host: the host reads back 12 bytes a row (id, count,
+ *     the length of the row stored at the id) and the status word, keeps the hole bits, chooses the route and sizes the
+ *     allocations; the stage that the in-place and splice kernels read, the keys and the splice's piece table are built on the
+ *     device.  Waits: the checks are enqueued on `stream` (NULL: the handle's own) and the call WAITS for it once, for those
+ *     words, before anything of the store changes; the rows are then written on the same stream and the call returns with them
+ *     stored, having drained it.  A zvec_hip_sparse_put_dev must not overlap a zvec_hip_sparse_search_dev of the same handle
+ *     still running on another stream.
  * Not served (each is the reference's to keep doing on the CPU): removing a document, the
  * MipsSquaredEuclideanSparse metric, loaders of the reference's dumped sparse segments, shards, the plugin and the C++ mirror
  * (zvec_hip_operator.hpp); by the inverted lists: ZVEC_HIP_METRIC_L2, listed rows and group-by; from device memory:
- * zvec_hip_sparse_put, a matrix of another type than the handle's, and any rule for keeping an element other than "not zero". */
+ * a matrix of another type than the handle's, and any rule for keeping an element other than "not zero". */
 int zvec_hip_sparse_create(int device, zvec_hip_sparse_t *out); /* fp32 values, InnerProductSparse */
 /* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16; anything else returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
  * InnerProductSparse. */
@@ -800,9 +814,14 @@ int zvec_hip_sparse_ingest_info(zvec_hip_sparse_t h, int *route, uint64_t *eleme
 /* FlatSparseStreamer::add_with_id_impl in bulk: row i, counts[i] pairs, goes to storage position ids[i]; see Add-with-id above. */
 int zvec_hip_sparse_put(zvec_hip_sparse_t h, const uint32_t *ids, const uint32_t *counts, const uint32_t *indices,
                         const void *values, uint64_t n, const uint64_t *keys);
+/* zvec_hip_sparse_put with every array in device memory: d_ids[n], d_counts[n], the runs back to back in d_indices[elements] /
+ * d_values[elements], d_keys[n] or NULL.  Validated on the device, one wait, the pairs stay on the device; see Rows and queries
+ * from device memory above.  zvec_hip_sparse_put_info reports it as it reports a host put. */
+int zvec_hip_sparse_put_dev(zvec_hip_sparse_t h, const uint32_t *d_ids, const uint32_t *d_counts, const uint32_t *d_indices,
+                            const void *d_values, uint64_t n, uint64_t elements, const uint64_t *d_keys, void *stream);
 /* positions that are holes now */
 int zvec_hip_sparse_holes(zvec_hip_sparse_t h, uint64_t *count);
-/* The last successful zvec_hip_sparse_put of the handle.  route: -1 none yet, 0 tail only, 1 in place, 2 splice; moved_elems:
+/* The last successful zvec_hip_sparse_put / _put_dev of the handle.  route: -1 none yet, 0 tail, 1 in place, 2 splice; moved_elems:
  * (index, value) pairs the device wrote for it (routes 0 and 1: the call's own; route 2: every pair of the store); chunk_elems:
  * destination pairs one work-group of the splice copies (a constant of the library, reported before any put); ms: wall-clock time
  * of the call.  Every output nullable. */

@@ -68,6 +68,13 @@ streaming figure (zvec_hip_calibrate, same process) and the bytes the device bui
 
     python tools/sparse_bench.py --put [--dtype fp32|fp16] [--put-rows 1000] [--out profiles/sparse_put.json]
 
+    --put --from-device   the same three calls with the call's rows already in device memory (zvec_hip_sparse_put_dev), next to the
+                host zvec_hip_sparse_put of the same rows on a second handle that holds the same corpus, in the same process.
+                Reported per route: ms per call of either entry (zvec_hip_sparse_put_info), the moved bytes per second, and the
+                box's calibrated streaming rate.  One call each, not repeated; reported, not gated.
+
+    python tools/sparse_bench.py --put --from-device [--dtype fp32|fp16] [--put-rows 1000] [--out profiles/sparse_put_dev.json]
+
     --ingest    rows and queries that are dense matrices in device memory, what a learned sparse encoder leaves there
                 (zvec_hip_sparse_append_dense_dev, zvec_hip_sparse_search_dense_dev).  The full-scan mode's corpus is scattered into
                 dense rows over the vocabulary on the device, --ingest-rows rows at a time (the whole matrix does not fit), and every
@@ -468,6 +475,10 @@ def put(args, metric):
     idx, val = ri.numpy().view(np.uint32), rv.numpy().astype(np_val)
     se = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
     assert se.add_batch(counts, idx, val) == 0
+    twin = None                                   # --from-device: the handle the host entry writes, holding the same corpus
+    if args.from_device:
+        twin = zvec_amd.HipFlatSparseStreamer(dtype=args.dtype, metric=METRIC_NAMES[metric])
+        assert twin.add_batch(counts, idx, val) == 0
     rng = np.random.default_rng(3)
     m = min(args.put_rows, args.n)
     ids = np.sort(rng.choice(args.n, m, replace=False)).astype(np.uint32)
@@ -483,22 +494,40 @@ def put(args, metric):
             ("splice", 2, ids, np.where(counts[ids] > 64, counts[ids] - 1, counts[ids] + 1)),
             ("tail", 0, np.arange(args.n, args.n + m, dtype=np.uint32), np.full(m, 64, np.uint32))):
         c, i, v = rows_of(lengths)
-        assert se.add_with_id_batch(put_ids, c, i, v) == 0
+        if twin is None:
+            assert se.add_with_id_batch(put_ids, c, i, v) == 0
+        else:
+            t = [torch.from_numpy(x.view(np.int32)).to(dev) for x in (put_ids, c, i)] + [torch.from_numpy(v).to(dev)]
+            torch.cuda.synchronize()
+            assert se.put_dev(*t) == 0
         info = se.put_info()
         assert info["route"] == route, (name, info)
         nbytes = info["moved_elems"] * (4 + width)
         legs.append({"route": route, "name": name, "rows": int(m), "ms": info["ms"], "moved_elems": info["moved_elems"],
                      "moved_bytes": nbytes, "moved_gbs": nbytes / info["ms"] / 1e6, "read_and_written_gbs": 2 * nbytes / info["ms"] / 1e6,
                      "elements_after": se.element_count()})
+        if twin is not None:
+            assert twin.add_with_id_batch(put_ids, c, i, v) == 0
+            host = twin.put_info()
+            assert host["route"] == route and host["moved_elems"] == info["moved_elems"], (name, host, info)
+            legs[-1].update({"entry": "zvec_hip_sparse_put_dev", "host_put_ms": host["ms"], "host_put_moved_gbs": nbytes / host["ms"] / 1e6,
+                             "call_pairs": int(i.size)})
         print(json.dumps(legs[-1]), flush=True)
     chunk = se.put_info()["chunk_elems"]
-    del se
+    del se, twin
     torch.cuda.synchronize()
     free, _ = torch.cuda.mem_get_info(dev)
     nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
     mhz, gbs = C.c_double(0), C.c_double(0)
     rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
     assert rc == 0, rc
+    if args.from_device:
+        return {"workload": "flat sparse %d rows x 64-192 of %d (Zipf), %s values: one zvec_hip_sparse_put_dev of %d rows on each route, the "
+                            "call's rows in device memory; host_put_*: zvec_hip_sparse_put of the same rows on a second handle" % (
+                    args.n, args.vocab, args.dtype, m),
+                "metric": metric, "timing": "zvec_hip_sparse_put_info's ms: wall clock of the call, its one wait, the plan's upload and the final "
+                "drain included (host_put_ms: host checks, staging and both waits included); one call each, not repeated",
+                "chunk_elems": chunk, "clock_mhz": mhz.value, "stream_gbs": gbs.value, "legs": legs}
     return {"workload": "flat sparse %d rows x 64-192 of %d (Zipf), %s values: one zvec_hip_sparse_put of %d rows on each route" % (
                 args.n, args.vocab, args.dtype, m),
             "metric": metric, "timing": "zvec_hip_sparse_put_info's ms: wall clock of the call, host staging and the waits included; one call "
@@ -604,6 +633,7 @@ def main():
     ap.add_argument("--inverted", action="store_true")
     ap.add_argument("--put", action="store_true")
     ap.add_argument("--put-rows", type=int, default=1000, help="--put: rows of each call")
+    ap.add_argument("--from-device", action="store_true", help="--put: the call's rows in device memory (zvec_hip_sparse_put_dev)")
     ap.add_argument("--ingest", action="store_true")
     ap.add_argument("--ingest-rows", type=int, default=8192, help="--ingest: dense rows generated and appended at a time")
     ap.add_argument("--ingest-host-blocks", type=int, default=4, help="--ingest: blocks that also go the host route")
@@ -617,8 +647,12 @@ def main():
         if args.metric != "ip":
             ap.error("--inverted serves InnerProductSparse only")
         mode = inverted
+    if args.from_device and not args.put:
+        ap.error("--from-device goes with --put")
     if args.put:
         mode = put
+        if args.from_device:
+            args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sparse_put_dev.json")
     if args.ingest:
         mode, rows = ingest, "searches"
         args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sparse_ingest.json")

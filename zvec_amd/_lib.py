@@ -171,6 +171,7 @@ SYMBOLS = {
                                                    _f32p, _u32p, C.c_void_p]),
     "zvec_hip_sparse_ingest_info": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     "zvec_hip_sparse_put": (C.c_int, [_h, _u32p, _u32p, _u32p, _valp, C.c_uint64, _u64p]),
+    "zvec_hip_sparse_put_dev": (C.c_int, [_h, _u32p, _u32p, _u32p, _valp, C.c_uint64, C.c_uint64, _u64p, C.c_void_p]),
     "zvec_hip_sparse_holes": (C.c_int, [_h, C.POINTER(C.c_uint64)]),
     "zvec_hip_sparse_put_info": (C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     "zvec_hip_sparse_count": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

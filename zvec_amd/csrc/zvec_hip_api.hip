@@ -49,6 +49,7 @@ extern "C" {
 #include "api_entry_sparse_put.inc.h"
 #include "api_entry_sparse_inverted.inc.h"
 #include "api_entry_sparse_ingest.inc.h"
+#include "api_entry_sparse_put_dev.inc.h"
 #include "api_entry_sparse_group.inc.h"
 
 }  // extern "C"

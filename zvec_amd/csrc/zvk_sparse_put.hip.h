@@ -1,4 +1,4 @@
-// zvk_sparse_put.hip.h — add-with-id on a sparse index (zvec_hip_sparse_put): the device side of the three routes.
+// zvk_sparse_put.hip.h — add-with-id on a sparse index (zvec_hip_sparse_put / _put_dev): the device side of the three routes.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // The store is a packed CSR (row_off[n + 1], idx, val, keys) and every scoring kernel relies on row_off[r] .. row_off[r + 1] being
@@ -17,6 +17,10 @@
 //   sparse_put_offsets_kernel   row_off and keys of the positions [r0, new_n): old offset + the shift behind the overwritten rows at
 //                               or below the position, the tail rows' ends, the invalid key for a hole.  Route 2 runs it over every
 //                               position into new arrays; routes 0 and 1 over the call's tail in place.
+//
+// zvec_hip_sparse_put_dev (the call's rows in device memory) makes the stage and the tables on the device instead, from a plan of a
+// few words a row: sparse_put_lens_kernel, sparse_put_stage_kernel and sparse_put_pieces_kernel at the end of this file; the four
+// kernels above then run unchanged.
 //
 // Values are moved as bits.  Halves (fp16) are moved as 32-bit words wherever the destination allows it: a piece that starts or ends
 // in the middle of a destination word writes that half alone (the other half belongs to the neighbouring piece, possibly to another
@@ -197,6 +201,110 @@ __global__ void __launch_bounds__(SPARSE_PUT_THREADS) sparse_put_offsets_kernel(
   if (j && (uint64_t)a.tid[j - 1] == r) a.new_keys[r] = a.tkey[j - 1];
   else if (r >= a.old_n) a.new_keys[r] = ~0ull;                        // kInvalidKey
   else if (a.new_keys != a.old_keys) a.new_keys[r] = a.old_keys[r];
+}
+
+// ---- the call's rows already in device memory (zvec_hip_sparse_put_dev) ----------------------------------------------------------
+// The pairs never leave the device: the host reads back three words a row (id, count, old length) with the status word of the
+// ingest check, makes the plan — the kept rows ascending by id, where each begins in the stage, the shifts — and the kernels below
+// build from it what the host put uploads: the stage, the keys of the kept rows, and the piece table of the splice.
+
+// len[i] = the pairs stored at position ids[i] now, 0 for an id at or behind the count
+__global__ void sparse_put_lens_kernel(const uint64_t *row_off, const uint32_t *ids, uint64_t n, uint64_t old_n, uint32_t *len) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t id = ids[i];
+  len[i] = id < old_n ? (uint32_t)(row_off[id + 1] - row_off[id]) : 0u;      // (a stored row has at most 4096 pairs)
+}
+
+// tbeg[m], ds[2m + 3] and ss[2m + 2] as SparsePutRowsArgs / SparsePutSpliceArgs describe them, from the store's own offsets.
+// tid[m]: the overwritten rows ascending; tval[j]: the new minus the old pairs of the overwritten rows up to and including j;
+// sb[m + 1]: where they begin in the stage.  Thread j <= m writes the untouched segment in front of row j and row j itself; the
+// last one the segment behind the last row, the call's tail rows and the end.  (m > 0)
+struct SparsePutPiecesArgs {
+  const uint64_t *row_off;
+  const uint32_t *tid;
+  const int64_t *tval;
+  const uint64_t *sb;
+  uint32_t m;
+  uint64_t tail_base, new_elems;
+  uint64_t *tbeg, *ds, *ss;
+};
+
+__global__ void __launch_bounds__(SPARSE_PUT_THREADS) sparse_put_pieces_kernel(SparsePutPiecesArgs a) {
+  const uint32_t j = blockIdx.x * SPARSE_PUT_THREADS + threadIdx.x;
+  if (j > a.m) return;
+  const uint64_t prev_end = j ? a.row_off[(uint64_t)a.tid[j - 1] + 1] : 0;
+  const uint64_t shift = j ? (uint64_t)a.tval[j - 1] : 0;
+  a.ds[2 * (size_t)j] = prev_end + shift;
+  a.ss[2 * (size_t)j] = prev_end;
+  if (j < a.m) {
+    const uint64_t ob = a.row_off[a.tid[j]];
+    a.ds[2 * (size_t)j + 1] = ob + shift;
+    a.ss[2 * (size_t)j + 1] = a.sb[j];
+    a.tbeg[j] = ob;
+  } else {
+    a.ds[2 * (size_t)j + 1] = a.tail_base;
+    a.ss[2 * (size_t)j + 1] = a.sb[j];
+    a.ds[2 * (size_t)j + 2] = a.new_elems;
+  }
+}
+
+// The stage gather.  Kept row j (ascending by id) is row src[j] of the call: its pairs, in_idx / in_val [in_off[src[j]], + len),
+// len = sb[j + 1] - sb[j], go to the stage from element sb[j] on, and its key (the caller's, or the id) to tkey[j].  A wave per row,
+// the waves stride over the rows, lane = pair.  The caller's arrays are aligned to their element only.  Indices and fp32 values move
+// as words.  Halves: the stage is word-aligned at even elements, so a row that begins at an odd one writes that half alone, and one
+// that ends at an odd one its last half; the words between are copied as words where the source run lies on the same parity, and are
+// put together from two halves where it does not.  A word of the stage that two rows share is written by each as its own half:
+// no two lanes write the same bytes, and nothing outside a row's source run is read.  Rows the keep-last rule dropped are not in src.
+struct SparsePutStageArgs {
+  const uint32_t *src, *tid;       // [T]
+  const uint64_t *sb;              // [T + 1]
+  const uint64_t *in_off;          // [n]: where the call's runs begin (the scan of its counts)
+  const uint32_t *in_idx;
+  const void *in_val;
+  const uint64_t *in_keys;         // [n] or NULL
+  uint32_t T;
+  uint32_t *stage_idx;
+  void *stage_val;
+  uint64_t *tkey;                  // [T]
+};
+
+template <typename W>
+__global__ void __launch_bounds__(SPARSE_PUT_THREADS) sparse_put_stage_kernel(SparsePutStageArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nwaves = gridDim.x * (SPARSE_PUT_THREADS / 64);
+  for (uint32_t j = blockIdx.x * (SPARSE_PUT_THREADS / 64) + (threadIdx.x >> 6); j < a.T; j += nwaves) {
+    const uint32_t r = a.src[j];
+    const uint64_t d0 = a.sb[j];
+    const uint32_t len = (uint32_t)(a.sb[j + 1] - d0);
+    if (lane == 0) a.tkey[j] = a.in_keys ? a.in_keys[r] : (uint64_t)a.tid[j];
+    if (len == 0) continue;                              // (uniform; in_off[r] may be the arrays' end)
+    const uint64_t s0 = a.in_off[r];
+    const uint32_t *si = a.in_idx + s0;
+    uint32_t *di = a.stage_idx + d0;
+    for (uint32_t e = lane; e < len; e += 64) di[e] = si[e];
+    if constexpr (sizeof(W) == 4) {
+      const uint32_t *sv = static_cast<const uint32_t *>(a.in_val) + s0;
+      uint32_t *dv = static_cast<uint32_t *>(a.stage_val) + d0;
+      for (uint32_t e = lane; e < len; e += 64) dv[e] = sv[e];
+    } else {
+      const uint16_t *sv = static_cast<const uint16_t *>(a.in_val) + s0;
+      uint16_t *dv = static_cast<uint16_t *>(a.stage_val) + d0;
+      const uint32_t head = (uint32_t)(d0 & 1);                        // halves in front of the first whole word of the stage
+      const uint32_t nw = (len - head) / 2;                            // whole words
+      const uint32_t done = head + 2 * nw;
+      if (lane == 0 && head) dv[0] = sv[0];
+      if (lane == 1 && done < len) dv[done] = sv[done];
+      uint32_t *dw = reinterpret_cast<uint32_t *>(dv + head);
+      const uint16_t *sh = sv + head;
+      if ((reinterpret_cast<uintptr_t>(sh) & 2u) == 0) {               // the same parity: words from words
+        const uint32_t *sw = reinterpret_cast<const uint32_t *>(sh);
+        for (uint32_t w = lane; w < nw; w += 64) dw[w] = sw[w];
+      } else {
+        for (uint32_t w = lane; w < nw; w += 64) dw[w] = (uint32_t)sh[2 * w] | ((uint32_t)sh[2 * w + 1] << 16);
+      }
+    }
+  }
 }
 
 }  // namespace zvk

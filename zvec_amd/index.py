@@ -1119,6 +1119,29 @@ class HipFlatSparseStreamer:
             self._stored_dev(n0, c.numel(), k)
         return rc
 
+    def put_dev(self, ids, counts, indices, values, keys=None, stream=None):
+        """add_with_id_batch with every array a torch tensor on the index's device (zvec_hip_sparse_put_dev): ids / counts /
+        indices int32 or uint32, values of the index's type, keys int64 or uint64.  Validated on the device; the pairs and the
+        keys stay there; all or nothing.  Runs on `stream` (a torch stream; None: torch's current one) and returns the status,
+        with the rows stored when it is 0.  A CPU tensor or a wrong dtype raises ValueError."""
+        c = _torch_array(counts, self.device, "counts", _torch_words(32))
+        d = _torch_array(ids, self.device, "ids", _torch_words(32), c.numel())
+        i = _torch_array(indices, self.device, "indices", _torch_words(32))
+        v = _torch_array(values, self.device, "values", (_torch_float(self.dtype),), i.numel())
+        k = self._keys_dev(keys, c.numel())
+        if stream is None:
+            s = _torch_stream(self.device)
+        else:
+            s = C.c_void_p(stream.cuda_stream)
+            if not s.value:
+                stream.synchronize()                         # (the default stream, as _torch_stream treats it)
+        rc = _lib.lib().zvec_hip_sparse_put_dev(self._h, _torch_ptr(d), _torch_ptr(c), _torch_ptr(i), _torch_ptr(v), c.numel(),
+                                                i.numel(), _torch_ptr(k), s)
+        if rc == 0 and c.numel():
+            h_ids = d.cpu().numpy().view(np.uint32)
+            self._put_keys(h_ids, h_ids.astype(np.uint64) if k is None else k.cpu().numpy().view(np.uint64), self.count())
+        return rc
+
     def add_dense(self, matrix, keys=None):
         """the non-zeros of every row of a dense [n, dim] torch tensor of the index's type on its device, column j as index j
         (zvec_hip_sparse_append_dense_dev).  Rows may be `stride(0)` elements apart (a column slice of a wider matrix); columns
