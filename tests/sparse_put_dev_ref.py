@@ -42,7 +42,7 @@ def apply_step(model, step):
 
 
 def plan(model, step):
-    """What a put makes of the call on a store that holds `model`, following api_entry_sparse_put.inc.h: the kept rows (the last one
+    """What a put makes of the call on a store that holds `model`, following csrc/host/sparse_put_plan.h: the kept rows (the last one
     of every id) ascending by id, as numbers of the call's rows; the route; per overwritten row the running shift (new minus old
     pairs up to and including it); per kept row with pairs the parity of (its place in the stage - its place in the caller's
     array), src_off included: 0 where a half keeps its place in a 32-bit word on the way into the stage, 1 where it changes it."""

@@ -211,6 +211,42 @@ def test_splice_at_the_chunk_boundaries(j, d, dtype):
         assert model.elements() in (E, E + 1, E + 3) and se.put_info()["moved_elems"] == model.elements()
 
 
+# ---- 3a. what both routes that overwrite share: the pieces kernel and the keep-last rule ------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("m", [255, 256, 257])
+@pytest.mark.parametrize("route", [1, 2])
+def test_overwritten_rows_at_the_block_edge_of_the_pieces_kernel(route, m, dtype):
+    """sparse_put_pieces_kernel runs m + 1 threads in blocks of 256 and thread m writes the closing pieces: m = 255 fills one block
+    exactly, 256 and 257 put the closing thread first and second in a block of its own.  A store of 300 rows of one or two pairs;
+    the call overwrites m of them in any order and brings two tail rows with a gap between; in place with every length kept, a
+    splice with every second overwritten row one pair longer"""
+    lengths = [1 + r % 2 for r in range(300)]
+    se, model, rng = _filled(dtype, lengths, 12)
+    over = rng.permutation(300)[:m]
+    longer = set(sorted(int(i) for i in over)[1::2]) if route == 2 else set()
+    ids = [int(i) for i in over] + [302, 300]
+    new = [lengths[i] + (i in longer) for i in ids[:m]] + [3, 2]
+    info = _put(se, model, ids, _rows(rng, new, dtype), route=route)
+    assert se.holes() == 1 and se.count() == 303
+    assert info["moved_elems"] == (sum(new) if route == 1 else model.elements())
+    assert model.elements() == sum(lengths) + len(longer) + 5
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("route", [1, 2])
+def test_ids_out_of_order_and_twice_keep_the_last_row(route, dtype):
+    """[6, 2, 6, 9, 2] on a store of 8 rows: the third and the fifth row of the call are the ones that stay, with their keys; once
+    they are as long as the stored rows (in place, whatever the first and the second row held), once not (splice)"""
+    base = [5, 9, 4, 7, 12, 3, 30, 1]
+    se, model, rng = _filled(dtype, base, 13)
+    ids = [6, 2, 6, 9, 2]
+    new = [11, 6, 30, 2, 4] if route == 1 else [30, 4, 29, 2, 6]
+    info = _put(se, model, ids, _rows(rng, new, dtype), keys=[601, 201, 602, 901, 202], route=route)
+    assert [model.keys[i] for i in (2, 6, 9)] == [202, 602, 901] and se.holes() == 1
+    assert info["moved_elems"] == (30 + 4 + 2 if route == 1 else model.elements())
+    assert model.elements() == sum(base) + 2 + (0 if route == 1 else 1)
+
+
 # ---- 4. searches after puts -----------------------------------------------------------------------------------------------------
 def _words_of(mask):
     w = np.zeros((mask.size + 63) // 64, np.uint64)

@@ -25,6 +25,7 @@
 #include "../../include/zvec_hip.h"
 #include "scan_kernels.hip.h"
 #include "host/hole_bits.h"
+#include "host/sparse_put_plan.h"
 
 using namespace zvk;
 

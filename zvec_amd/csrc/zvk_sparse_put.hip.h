@@ -2,11 +2,14 @@
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // The store is a packed CSR (row_off[n + 1], idx, val, keys) and every scoring kernel relies on row_off[r] .. row_off[r + 1] being
-// the row, so a row that changes its length moves everything behind it.  The host (api_entry_sparse_put.inc.h) sorts the rows of a
-// call by id, keeps the last one of every id and stages their pairs back to back ("the stage"); then
+// the row, so a row that changes its length moves everything behind it.  The host (host/sparse_put_plan.h) sorts the rows of a
+// call by id, keeps the last one of every id and plans where their pairs lie back to back ("the stage").  The
+// kernels, the same for both entries (the first is launched by the entry, the others by put_apply, api_entry_sparse_put.inc.h):
 //
-//   sparse_put_gather_kernel    the old offsets of the overwritten rows (2 words a row: the host learns their old lengths from these
-//                               and keeps no mirror of row_off)
+//   sparse_put_lens_kernel      before the plan: the old lengths at the call's ids (4 bytes a row: the host learns them from the
+//                               device and keeps no mirror of row_off)
+//   sparse_put_pieces_kernel    for overwritten rows: where each begins (tbeg) and the piece table of the splice (ds, ss), from the
+//                               store's own offsets and the plan's shifts
 //   sparse_put_rows_kernel      route 1: every overwritten row keeps its length -> its pairs and its key are written over the old
 //                               ones, a work-group per row
 //   sparse_put_splice_kernel    route 2: the new idx / val arrays whole, out of place.  The overwritten rows cut the old arrays into
@@ -18,9 +21,8 @@
 //                               or below the position, the tail rows' ends, the invalid key for a hole.  Route 2 runs it over every
 //                               position into new arrays; routes 0 and 1 over the call's tail in place.
 //
-// zvec_hip_sparse_put_dev (the call's rows in device memory) makes the stage and the tables on the device instead, from a plan of a
-// few words a row: sparse_put_lens_kernel, sparse_put_stage_kernel and sparse_put_pieces_kernel at the end of this file; the four
-// kernels above then run unchanged.
+// zvec_hip_sparse_put stages the pairs and the keys on the host and uploads them; zvec_hip_sparse_put_dev (the call's rows in device
+// memory) makes them on the device from the plan's tables: sparse_put_stage_kernel at the end of this file.
 //
 // Values are moved as bits.  Halves (fp16) are moved as 32-bit words wherever the destination allows it: a piece that starts or ends
 // in the middle of a destination word writes that half alone (the other half belongs to the neighbouring piece, possibly to another
@@ -101,14 +103,6 @@ template <typename W>
 __device__ __forceinline__ void put_copy_values(void *dst, const void *src, uint64_t a, uint64_t b, int64_t delta) {
   if constexpr (sizeof(W) == 4) put_copy_words(static_cast<uint32_t *>(dst), static_cast<const uint32_t *>(src), a, b, delta);
   else put_copy_halves(static_cast<uint16_t *>(dst), static_cast<const uint16_t *>(src), a, b, delta);
-}
-
-// out[2j], out[2j + 1] = row_off[ids[j]], row_off[ids[j] + 1]
-__global__ void sparse_put_gather_kernel(const uint64_t *row_off, const uint32_t *ids, uint32_t m, uint64_t *out) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  out[2 * (size_t)j] = row_off[ids[j]];
-  out[2 * (size_t)j + 1] = row_off[(uint64_t)ids[j] + 1];
 }
 
 // Route 1.  Row j of the m overwritten ones: stage[sbeg[j] .. sbeg[j + 1]) goes to the elements from tbeg[j] on (its old place,
@@ -203,10 +197,7 @@ __global__ void __launch_bounds__(SPARSE_PUT_THREADS) sparse_put_offsets_kernel(
   else if (a.new_keys != a.old_keys) a.new_keys[r] = a.old_keys[r];
 }
 
-// ---- the call's rows already in device memory (zvec_hip_sparse_put_dev) ----------------------------------------------------------
-// The pairs never leave the device: the host reads back three words a row (id, count, old length) with the status word of the
-// ingest check, makes the plan — the kept rows ascending by id, where each begins in the stage, the shifts — and the kernels below
-// build from it what the host put uploads: the stage, the keys of the kept rows, and the piece table of the splice.
+// ---- what the plan is made from, and what is made from the plan ------------------------------------------------------------------
 
 // len[i] = the pairs stored at position ids[i] now, 0 for an id at or behind the count
 __global__ void sparse_put_lens_kernel(const uint64_t *row_off, const uint32_t *ids, uint64_t n, uint64_t old_n, uint32_t *len) {
@@ -249,6 +240,8 @@ __global__ void __launch_bounds__(SPARSE_PUT_THREADS) sparse_put_pieces_kernel(S
   }
 }
 
+// The call's rows already in device memory (zvec_hip_sparse_put_dev): the pairs never leave the device, and this kernel builds from
+// the plan's tables what the host put uploads, the stage and the keys of the kept rows.
 // The stage gather.  Kept row j (ascending by id) is row src[j] of the call: its pairs, in_idx / in_val [in_off[src[j]], + len),
 // len = sb[j + 1] - sb[j], go to the stage from element sb[j] on, and its key (the caller's, or the id) to tkey[j].  A wave per row,
 // the waves stride over the rows, lane = pair.  The caller's arrays are aligned to their element only.  Indices and fp32 values move
