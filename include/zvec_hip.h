@@ -221,7 +221,9 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
 /* ---- IVF-Flat -----------------------------------------------------------------------------
  * stands behind IVFStreamer / IVFSearcher (src/core/algorithm/ivf/ivf_streamer.cc:183-250,
  * ivf_searcher.cc:183-250) with IVFCentroidIndex (ivf_centroid_index.cc:273-297) and
- * IVFEntity::search (ivf_entity.cc:587-716). */
+ * IVFEntity::search (ivf_entity.cc:587-716).
+ * Searches on separate contexts may run while another thread loads or rebuilds the index: they see the old index or the
+ * new one, or ZVEC_HIP_ERR_NO_INDEX_LOADED between begin_lists and end_lists. */
 int zvec_hip_ivf_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_ivf_t *out);
 int zvec_hip_ivf_destroy(zvec_hip_ivf_t h);
 /* load a trained index (what IVFSearcher::load reads from the ivf.* segments,

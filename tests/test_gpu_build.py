@@ -163,6 +163,111 @@ def test_streamed_build_errors(zv):
     assert se.add_dev(d.data_ptr(), 1, np.array([5], np.uint32), 0) == zv.IndexError_.InvalidArgument     # no such list
 
 
+def _search(se, ctx, q, k, nprobe):
+    """zvec_hip_ivf_search with the probe count given outright (every query probes exactly `nprobe` lists)"""
+    from zvec_amd import _lib
+    from zvec_amd.index import _np_ptr
+    nq = q.shape[0]
+    keys, scores, counts = np.zeros((nq, k), np.uint64), np.zeros((nq, k), np.float32), np.zeros(nq, np.uint32)
+    rc = _lib.lib().zvec_hip_ivf_search(se._h, ctx._h, _np_ptr(q), nq, k, 3.4e38, nprobe, 0xffffffff, None, _np_ptr(keys), _np_ptr(scores),
+                                        _np_ptr(counts))
+    return rc, keys, scores, counts
+
+
+def test_refused_add_leaves_the_fill_retriable(zv):
+    """A chunk that add_dev refuses — a label that names no list as its LAST row, or rows that overflow a list between them — has
+    stored nothing and moved no cursor: the corrected chunks go in and the index equals one given the same rows through load().
+    Before, the rows in front of the offending one were counted as stored without ever being packed."""
+    import torch
+    rng = np.random.default_rng(21)
+    dim, sizes = 8, np.array([130, 0, 5], np.uint32)                     # list 0 crosses a tile
+    n = int(sizes.sum())
+    base = rng.integers(-4, 5, (n, dim)).astype(np.float32)
+    cent = np.array([[0] * dim, [9] * dim, [-3] * dim], np.float32)
+    labels = np.zeros(n, np.uint32)
+    labels[[3, 40, 69, 70, 134]] = 2                                     # list 2's rows on both sides of the chunk boundary
+    d_base = torch.from_numpy(base).cuda()
+    se = zv.HipIVFSearcher(dim, "SquaredEuclidean")
+    assert se.set_centroids(cent) == 0
+    assert se.begin_lists(sizes) == 0
+    bad = labels[:70].copy()
+    bad[69] = 7                                                          # no such list, after 69 good rows
+    assert se.add_dev(d_base.data_ptr(), 70, bad, 0) == zv.IndexError_.InvalidArgument
+    bad = labels.copy()
+    bad[134] = 0                                                         # 131 rows for the 130 of list 0
+    assert se.add_dev(d_base.data_ptr(), n, bad, 0) == zv.IndexError_.InvalidArgument
+    assert se.end_lists() == zv.IndexError_.NoReady
+    assert se.add_dev(d_base.data_ptr(), 70, labels[:70], 0) == 0
+    assert se.add_dev(d_base[70:].data_ptr(), 65, labels[70:], 70) == 0
+    assert se.end_lists() == 0
+    # the same rows through load(): list order = stable grouping by label, keys = the original row numbers
+    order = np.argsort(labels, kind="stable")
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    ld = zv.HipIVFSearcher(dim, "SquaredEuclidean")
+    assert ld.load(cent, offs, base[order], keys=order.astype(np.uint64)) == 0
+    c1, o1, r1 = se.export()
+    c2, o2, r2 = ld.export()
+    # (a loaded index numbers its rows by their place in the loaded array: through `order` they are the streamed fill's row numbers)
+    assert np.array_equal(c1, c2) and np.array_equal(o1, o2) and np.array_equal(r1, order[r2.astype(np.int64)].astype(np.uint64))
+    assert np.array_equal(r1, order.astype(np.uint64))
+    assert se.info() == ld.info() == (n, 3)
+    pos = np.arange(n)
+    got = se.get_vectors_by_ids(pos)
+    assert np.array_equal(got, ld.get_vectors_by_ids(pos)) and np.array_equal(got, base[order])
+    q = rng.integers(-4, 5, (8, dim)).astype(np.float32)
+    rc1, k1, s1, n1 = _search(se, se.create_context(), q, 5, 3)
+    rc2, k2, s2, n2 = _search(ld, ld.create_context(), q, 5, 3)
+    assert rc1 == 0 and rc2 == 0
+    assert np.array_equal(k1, k2) and np.array_equal(s1.view(np.uint32), s2.view(np.uint32)) and np.array_equal(n1, n2)
+    assert (n1 == 5).all()
+    d = ((q[:, None, :].astype(np.int64) - base[None].astype(np.int64)) ** 2).sum(2)      # all three lists probed: the exact top 5
+    assert np.array_equal(s1, np.sort(d, 1)[:, :5].astype(np.float32))
+    assert np.array_equal(np.take_along_axis(d, k1.astype(np.int64), 1).astype(np.float32), s1)
+
+
+def test_searches_and_a_reload_exclude_each_other(zv):
+    """Searches on contexts of their own run while another thread loads the index again: load() releases and packs inside one
+    exclusive scope of the handle's reader/writer lock, so every search returns 0 with exactly the serial result — never
+    NoIndexLoaded, never rows of a store that is being released."""
+    import threading
+    rng = np.random.default_rng(22)
+    n, dim, nlist, nq, k, nprobe = 3000, 16, 12, 8, 5, 4
+    base = rng.integers(-6, 7, (n, dim)).astype(np.float32)
+    cent = rng.integers(-6, 7, (nlist, dim)).astype(np.float32)
+    b64, c64 = base.astype(np.int64), cent.astype(np.int64)
+    labels = ((b64 ** 2).sum(1)[:, None] + (c64 ** 2).sum(1)[None] - 2 * b64 @ c64.T).argmin(1)
+    order = np.argsort(labels, kind="stable")
+    offs = np.concatenate([[0], np.cumsum(np.bincount(labels, minlength=nlist))]).astype(np.uint64)
+    rows, keys = np.ascontiguousarray(base[order]), order.astype(np.uint64)
+    q = rng.integers(-6, 7, (nq, dim)).astype(np.float32)
+    se = zv.HipIVFSearcher(dim, "SquaredEuclidean")
+    assert se.load(cent, offs, rows, keys=keys) == 0
+    rc, wk, ws, wc = _search(se, se.create_context(), q, k, nprobe)
+    assert rc == 0 and (wc == k).all()
+    ctxs = [se.create_context() for _ in range(3)]
+    start = threading.Barrier(4)
+    bad = [[] for _ in ctxs]
+
+    def searcher(t):
+        start.wait()
+        for i in range(20):
+            rc, gk, gs, gc = _search(se, ctxs[t], q, k, nprobe)
+            if rc != 0 or not (np.array_equal(gk, wk) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)) and np.array_equal(gc, wc)):
+                bad[t].append((i, rc))
+
+    threads = [threading.Thread(target=searcher, args=(t,)) for t in range(3)]
+    for th in threads:
+        th.start()
+    start.wait()
+    loads = [se.load(cent, offs, rows, keys=keys) for _ in range(3)]
+    for th in threads:
+        th.join()
+    assert loads == [0, 0, 0]
+    assert bad == [[], [], []]
+    rc, gk, gs, gc = _search(se, ctxs[0], q, k, nprobe)
+    assert rc == 0 and np.array_equal(gk, wk) and np.array_equal(gs, ws) and np.array_equal(gc, wc)
+
+
 def _kmeans_quality_corpus(fx):
     c = fx["corpus"]
     rng = np.random.default_rng(c["seed"])

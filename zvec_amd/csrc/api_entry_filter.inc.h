@@ -236,9 +236,9 @@ extern "C" int zvec_hip_flat_build_filter(zvec_hip_flat_t h, zvec_hip_ctx_t ctx,
 extern "C" int zvec_hip_ivf_build_filter(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const zvec_hip_doc_filter_t *filter,
                                          uint64_t *out_words, int out_on_device, void *stream) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  std::lock_guard<std::mutex> g(c->mu);
-  return build_filter(c, h->device, h->lists.keys, h->count_local, h->tab.d_dense0.p, h->tab.d_tile0.p, h->nlist,
+  IvfRead r(h, c);
+  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
+  return build_filter(c, h->device, h->lists.keys, h->lay.count_local, h->tab.d_dense0.p, h->tab.d_tile0.p, h->lay.nlist,
                       filter, out_words, out_on_device, stream);
 }

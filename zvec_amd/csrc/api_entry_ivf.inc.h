@@ -2,6 +2,7 @@
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 // ---- IVF ------------------------------------------------------------------------------------
+static_assert(TILE_N == IVF_TILE_ROWS, "host/ivf_layout.h lays lists out in the scan's tiles");
 int zvec_hip_ivf_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_ivf_t *out) {
   if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
@@ -29,14 +30,48 @@ static void ivf_leave_coarse_space(zvec_hip_ivf_s *h) {
   h->trained = false;
 }
 
-static void ivf_release(zvec_hip_ivf_s *h) {
-  h->shadow.drop();
-  h->cent.release(); h->lists.release();
-  h->cent.n = 0; h->lists.n = 0;
-  ivf_leave_coarse_space(h);
-  h->tab = zvec_hip_ivf_s::Tables();
-  h->loaded = false; h->trained = false; h->filling = false;
-}
+// One change of an IVF index (FlatWrite's twin): it holds h->mu, then — `with_ctx`, for the entries that label rows through the
+// built-in context's workspace — that context's mutex, then h->rw exclusively, while it lives.  So no search reads the stores, the
+// tables, the twin or the layout while they change, and every state test of a writer is made under it.  Readers take a context's
+// mutex, then h->rw shared: the lock order is h->mu, a context's mu, h->rw.  Freeing a store waits for the device (hipFree), so
+// kernels that earlier searches only enqueued have finished with it.
+struct IvfWrite {
+  zvec_hip_ivf_s *const h;
+  explicit IvfWrite(zvec_hip_ivf_s *h_, bool with_ctx = false) : h(h_), g(h_->mu), gc(h_->defctx->mu, std::defer_lock), w(h_->rw, std::defer_lock) {
+    if (with_ctx) gc.lock();
+    w.lock();
+  }
+  int open() { ZCHK(hipSetDevice(h->device)); return 0; }
+  // release whatever is loaded, filling or in a separate coarse space: the handle is as created, but for its shard
+  void reset() {
+    if (!h->loaded && !h->filling && !h->coarse_sep) return;
+    h->shadow.drop();
+    h->cent.release(); h->lists.release();
+    h->cent.n = 0; h->lists.n = 0;
+    ivf_leave_coarse_space(h);
+    h->tab = zvec_hip_ivf_s::Tables();
+    h->loaded = false; h->trained = false; h->filling = false;
+  }
+
+ private:
+  std::lock_guard<std::mutex> g;
+  std::unique_lock<std::mutex> gc;
+  std::unique_lock<FairSharedMutex> w;
+};
+
+// One reader of an IVF index: the mutex of the context it works through, then h->rw shared, while it lives; `loaded`, `trained` and
+// `coarse_sep` are tested under it.  The entries that use the built-in context's workspace on their own behalf (label_dev,
+// get_vector, get_vectors) take h->mu in front, as the writers do.  FairSharedMutex is not recursive: what a reader calls
+// (ivf_search_dev_locked, ivf_shadow_certify_locked, ivf_search_core) takes nothing.
+struct IvfRead {
+  IvfRead(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c) : gc(c->mu), r(h->rw) {}
+  explicit IvfRead(zvec_hip_ivf_s *h) : g(h->mu), gc(h->defctx->mu), r(h->rw) {}
+
+ private:
+  std::unique_lock<std::mutex> g;
+  std::lock_guard<std::mutex> gc;
+  std::shared_lock<FairSharedMutex> r;
+};
 
 int zvec_hip_ivf_destroy(zvec_hip_ivf_t h) {
   if (!h) return 0;
@@ -44,31 +79,6 @@ int zvec_hip_ivf_destroy(zvec_hip_ivf_t h) {
   (void)hipDeviceSynchronize();
   delete h;
   return 0;
-}
-
-// Greedy largest-first (LPT) assignment of inverted lists to shards, weighted by the 128-row tiles a list occupies in
-// HBM (= the bytes a scan streams).  Deterministic: lists ordered by (tiles desc, list id asc), each given to the shard
-// with the least tiles so far (lowest shard id on ties) — every rank computes the same map from the global list sizes.
-// "whole inverted lists assigned to GPUs (balanced by bytes, list->GPU map)".
-static void ivf_lpt_owner(const uint32_t *sizes, uint32_t nlist, uint32_t nshards, uint32_t *owner, uint64_t *rows_out) {
-  std::vector<uint64_t> load(nshards, 0), rows(nshards, 0);
-  if (nshards <= 1) {
-    for (uint32_t l = 0; l < nlist; ++l) { owner[l] = 0; rows[0] += sizes[l]; }
-  } else {
-    std::vector<uint32_t> order(nlist);
-    for (uint32_t l = 0; l < nlist; ++l) order[l] = l;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return sizes[x] > sizes[y]; });
-    for (uint32_t i = 0; i < nlist; ++i) {
-      const uint32_t l = order[i];
-      uint32_t best = 0;
-      for (uint32_t g = 1; g < nshards; ++g)
-        if (load[g] < load[best]) best = g;
-      owner[l] = best;
-      load[best] += (sizes[l] + TILE_N - 1) / TILE_N;
-      rows[best] += sizes[l];
-    }
-  }
-  if (rows_out) for (uint32_t g = 0; g < nshards; ++g) rows_out[g] = rows[g];
 }
 
 int zvec_hip_ivf_shard_map(const uint32_t *list_sizes, uint32_t nlist, uint32_t nshards, uint32_t *owner_out,
@@ -80,92 +90,63 @@ int zvec_hip_ivf_shard_map(const uint32_t *list_sizes, uint32_t nlist, uint32_t 
 
 int zvec_hip_ivf_keep_shard(zvec_hip_ivf_t h, uint32_t shard, uint32_t nshards) {
   if (!h || nshards == 0 || shard >= nshards) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfWrite w(h);
   if (h->loaded || h->filling) return ZVEC_HIP_ERR_NO_READY;   // must be set before load/build
-  h->shard = shard; h->nshards = nshards;
+  h->lay.shard = shard; h->lay.nshards = nshards;
   return 0;
 }
 
 int zvec_hip_ivf_list_owners(zvec_hip_ivf_t h, uint32_t *owner_out) {
   if (!h || !owner_out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
   if (!h->loaded && !h->filling) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-  memcpy(owner_out, h->h_owner.data(), (size_t)h->nlist * 4);
+  memcpy(owner_out, h->lay.owner.data(), (size_t)h->lay.nlist * 4);
   return 0;
 }
 
-// (re)build the centroid store from host rows; the index is "trained" afterwards
-static int ivf_set_centroids(zvec_hip_ivf_s *h, const void *h_centroids, uint32_t nlist, hipStream_t s) {
-  ivf_leave_coarse_space(h);            // centroids handed over here are rows of the index's own space
-  const size_t rb = h->lists.row_bytes();
-  h->nlist = nlist;
+// nlist host rows of the centroid store's configured space -> h_centroids and the store; the index is "trained" afterwards
+static int ivf_upload_centroids(zvec_hip_ivf_s *h, const void *h_centroids, uint32_t nlist, hipStream_t s) {
+  const size_t bytes = (size_t)nlist * h->cent.row_bytes();
+  h->trained = false;
+  h->lay.nlist = nlist;
   if (h_centroids != h->h_centroids.data())
-    h->h_centroids.assign(reinterpret_cast<const char *>(h_centroids), reinterpret_cast<const char *>(h_centroids) + (size_t)nlist * rb);
+    h->h_centroids.assign(reinterpret_cast<const char *>(h_centroids), reinterpret_cast<const char *>(h_centroids) + bytes);
   h->cent.n = 0;
   Scoped<char> d_c;
-  ZRET(d_c.alloc((size_t)nlist * rb));
-  ZCHK(hipMemcpyAsync(d_c, h->h_centroids.data(), (size_t)nlist * rb, hipMemcpyHostToDevice, s));
+  ZRET(d_c.alloc(bytes));
+  ZCHK(hipMemcpyAsync(d_c, h->h_centroids.data(), bytes, hipMemcpyHostToDevice, s));
   ZRET(store_append_dev(h->cent, d_c, nlist, nullptr, s));
   ZCHK(hipStreamSynchronize(s));
   h->trained = true;
   return 0;
 }
 
+// (re)build the centroid store from host rows of the index's own space
+static int ivf_set_centroids(zvec_hip_ivf_s *h, const void *h_centroids, uint32_t nlist, hipStream_t s) {
+  ivf_leave_coarse_space(h);
+  return ivf_upload_centroids(h, h_centroids, nlist, s);
+}
+
 // IVFDumper's job, step 1 (ivf_dumper.h:33-160: every list's extent is known before its blocks are written): lay out
 // the lists this shard owns from the GLOBAL list sizes, allocate the blocked store, reset the per-list cursors.
 static int ivf_begin_lists(zvec_hip_ivf_s *h, const uint32_t *sizes_global, hipStream_t s) {
-  const uint32_t nlist = h->nlist;
-  h->h_size_global.assign(sizes_global, sizes_global + nlist);
-  h->h_owner.assign(nlist, 0);
-  ivf_lpt_owner(sizes_global, nlist, h->nshards, h->h_owner.data(), nullptr);
-  h->h_size.assign(nlist, 0);
-  uint64_t total = 0;
-  for (uint32_t l = 0; l < nlist; ++l) {
-    total += sizes_global[l];
-    if (h->h_owner[l] == h->shard) h->h_size[l] = sizes_global[l];
-  }
-  h->h_tile0.assign(nlist, 0);
-  h->h_dense0.assign(nlist + 1, 0);
-  uint64_t tiles = 0, dense = 0;
-  for (uint32_t l = 0; l < nlist; ++l) {
-    h->h_tile0[l] = (uint32_t)tiles;
-    h->h_dense0[l] = dense;
-    tiles += (h->h_size[l] + TILE_N - 1) / TILE_N;
-    dense += h->h_size[l];
-  }
-  h->h_dense0[nlist] = dense;
-  h->count_local = dense;
-  h->count_global = total;
-  h->local_tiles = tiles;
-  if (tiles * TILE_N >= 0xffffffffull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  h->h_cursor.assign(h->h_dense0.begin(), h->h_dense0.end() - 1);
-  h->h_row_ids.assign(dense, 0);
+  ZRET(h->lay.begin(sizes_global, h->lay.nlist));
+  const uint64_t rows = h->lay.local_tiles * TILE_N;
   h->lists.n = 0;
-  ZRET(h->lists.reserve(std::max<uint64_t>(tiles * TILE_N, 1), s));
-  h->lists.n = tiles * TILE_N;
-  if (tiles) ZCHK(hipMemsetAsync(h->lists.keys, 0xff, (size_t)tiles * TILE_N * 8, s));   // padding rows: invalid key
+  ZRET(h->lists.reserve(std::max<uint64_t>(rows, 1), s));
+  h->lists.n = rows;
+  if (rows) ZCHK(hipMemsetAsync(h->lists.keys, 0xff, (size_t)rows * 8, s));   // padding rows: invalid key
   h->filling = true;
   return 0;
 }
 
-// step 2: rows (device, row-major [n][dim]) with their labels (host); the rows of owned lists are appended to those
-// lists in arrival order (stable, like the reference's per-list append).  `first_row` = global number of d_rows[0];
-// keys: host, per row of this call, NULL -> global row number.
+// step 2: rows (device, row-major [n][dim]) with their labels (host), planned by IvfLayout::place — a refused chunk has changed
+// nothing and may be sent again — then packed into their lists, their keys scattered beside them
 static int ivf_add_rows(zvec_hip_ivf_s *h, const void *d_rows, uint64_t n, const uint32_t *labels, const uint64_t *keys,
                         uint64_t first_row, hipStream_t s) {
   if (n == 0) return 0;
   std::vector<uint64_t> src, dst, kv;
-  src.reserve(n / h->nshards + 16); dst.reserve(n / h->nshards + 16); kv.reserve(n / h->nshards + 16);
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint32_t l = labels[i];
-    if (l >= h->nlist) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-    if (h->h_owner[l] != h->shard) continue;
-    const uint64_t d = h->h_cursor[l];
-    if (d >= h->h_dense0[l + 1]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;   // more rows than begin_lists was told
-    h->h_cursor[l] = d + 1;
-    h->h_row_ids[d] = first_row + i;
-    src.push_back(i);
-    dst.push_back((uint64_t)h->h_tile0[l] * TILE_N + (d - h->h_dense0[l]));
-    kv.push_back(keys ? keys[i] : first_row + i);
-  }
+  ZRET(h->lay.place(labels, n, keys, first_row, src, dst, kv));
   const uint64_t kept = src.size();
   if (kept == 0) return 0;
   Scoped<uint64_t> d_src, d_dst, d_kv;
@@ -185,103 +166,61 @@ static int ivf_add_rows(zvec_hip_ivf_s *h, const void *d_rows, uint64_t n, const
 
 // step 3: every list must be complete; upload the list tables and the deal order of the scan's work queue
 static int ivf_end_lists(zvec_hip_ivf_s *h) {
-  const uint32_t nlist = h->nlist;
-  for (uint32_t l = 0; l < nlist; ++l)
-    if (h->h_cursor[l] != h->h_dense0[l + 1]) return ZVEC_HIP_ERR_NO_READY;   // fewer rows than announced
-  const uint64_t tiles = h->local_tiles;
-  // largest lists are dealt first by the scan's work queue; chunk length adapts to the index size so
-  // that a search has a few items per resident work-group yet long runs per top-k warm-up
-  std::vector<uint32_t> order(nlist);
-  for (uint32_t l = 0; l < nlist; ++l) order[l] = l;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h->h_size[x] > h->h_size[y]; });
-  {
-    uint64_t tpc = tiles / (4ull * 256ull * 3ull);
-    h->tiles_per_chunk = (uint32_t)std::min<uint64_t>(32, std::max<uint64_t>(4, tpc));
-    if (knobs().ivf_tpc) h->tiles_per_chunk = (uint32_t)knobs().ivf_tpc;
-    // The queue deals lists largest first, so the lists at the END of the order are the tail of every search: one
-    // work-group streams only ~7 GB/s (5.7 TB/s over ~768 resident groups), i.e. a 4-tile item lasts ~200 us, and a
-    // tail of such items leaves most of the chip idle.  Guided self-scheduling in three levels of the deal order:
-    // the first half of the tiles (level 0) in chunks twice as long (fewer top-k warm-ups and list write-outs per byte
-    // while everybody is busy anyway), the next quarter (level 1) at the base length, the last quarter (level 2) in
-    // chunks a quarter as long.  Measured (head share 0 / 25 / 50 / 75 %): 1/8 shard 0.691 / 0.700 / 0.706 / 0.67 of
-    // peak, whole 10M index 0.758 / 0.767 / 0.775 / 0.770 on one box.
-    h->h_tail.assign(nlist, 1);
-    const uint64_t head_num = knobs().ivf_head_pct;         // per cent of the tiles dealt in double-length chunks
-    uint64_t acc = 0;
-    for (uint32_t i = nlist; i-- > 0;) {
-      const uint32_t l = order[i];
-      if (acc * 4 >= tiles) break;
-      h->h_tail[l] = 2;
-      acc += (h->h_size[l] + TILE_N - 1) / TILE_N;
-    }
-    acc = 0;
-    for (uint32_t i = 0; i < nlist; ++i) {
-      const uint32_t l = order[i];
-      if (acc * 100 >= tiles * head_num || h->h_tail[l] == 2) break;
-      h->h_tail[l] = 0;
-      acc += (h->h_size[l] + TILE_N - 1) / TILE_N;
-    }
-  }
+  IvfLayout &lay = h->lay;
+  ZRET(lay.finish((uint32_t)knobs().ivf_head_pct, (uint32_t)knobs().ivf_tpc));
+  const uint32_t nlist = lay.nlist;
   zvec_hip_ivf_s::Tables t;              // the new tables first, all of them: a failure leaves the old ones in place
-  ZRET(upload(t.d_tail, h->h_tail.data(), nlist));
-  ZRET(upload(t.d_order, order.data(), nlist));
-  ZRET(upload(t.d_size, h->h_size.data(), nlist));
-  ZRET(upload(t.d_size_global, h->h_size_global.data(), nlist));
-  ZRET(upload(t.d_tile0, h->h_tile0.data(), nlist));
-  ZRET(upload(t.d_dense0, h->h_dense0.data(), (size_t)nlist + 1));
+  ZRET(upload(t.d_tail, lay.tail.data(), nlist));
+  ZRET(upload(t.d_order, lay.order.data(), nlist));
+  ZRET(upload(t.d_size, lay.size.data(), nlist));
+  ZRET(upload(t.d_size_global, lay.size_global.data(), nlist));
+  ZRET(upload(t.d_tile0, lay.tile0.data(), nlist));
+  ZRET(upload(t.d_dense0, lay.dense0.data(), (size_t)nlist + 1));
   h->tab = std::move(t);
   h->filling = false;
-  // rows of the i largest local lists: the bound of what i probes can scan (small-batch route); computed here, once,
-  // because searches on different contexts read it concurrently
-  {
-    std::vector<uint32_t> sz(h->h_size);
-    std::sort(sz.begin(), sz.end(), std::greater<uint32_t>());
-    h->h_rows_of_largest.assign((size_t)h->nlist + 1, 0);
-    for (uint32_t i = 0; i < h->nlist; ++i) h->h_rows_of_largest[i + 1] = h->h_rows_of_largest[i] + sz[i];
-  }
   h->loaded = true;
   return 0;
 }
 
-// all rows at once (load, load_segments, the one-call build): centroids + layout + rows + tables
-static int ivf_pack(zvec_hip_ivf_s *h, const void *d_rows, uint64_t n, const uint64_t *keys,
-                    const std::vector<uint32_t> &labels, const void *h_centroids, uint32_t nlist, hipStream_t s) {
-  if (h_centroids) {
-    ZRET(ivf_set_centroids(h, h_centroids, nlist, s));
-  } else {                               // (load_segments without centroids: zvec_hip_ivf_set_coarse_space brings them)
-    h->nlist = nlist;
-    h->cent.n = 0;
-    h->trained = false;
-  }
-  std::vector<uint32_t> sizes(nlist, 0);
-  for (uint64_t i = 0; i < n; ++i) {
-    if (labels[i] >= nlist) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-    sizes[labels[i]] += 1;
-  }
+// all rows at once, labelled (load, load_segments, the one-call build): layout + rows + tables
+static int ivf_fill(zvec_hip_ivf_s *h, const void *d_rows, uint64_t n, const uint64_t *keys, const std::vector<uint32_t> &labels,
+                    hipStream_t s) {
+  std::vector<uint32_t> sizes;
+  ZRET(IvfLayout::count_sizes(labels.data(), n, h->lay.nlist, sizes));
   ZRET(ivf_begin_lists(h, sizes.data(), s));
   ZRET(ivf_add_rows(h, d_rows, n, labels.data(), keys, 0, s));
   return ivf_end_lists(h);
 }
 
+// load, load_segments: centroids, then the lists
+static int ivf_pack(zvec_hip_ivf_s *h, const void *d_rows, uint64_t n, const uint64_t *keys,
+                    const std::vector<uint32_t> &labels, const void *h_centroids, uint32_t nlist, hipStream_t s) {
+  if (h_centroids) {
+    ZRET(ivf_set_centroids(h, h_centroids, nlist, s));
+  } else {                               // (load_segments without centroids: zvec_hip_ivf_set_coarse_space brings them)
+    h->lay.nlist = nlist;
+    h->cent.n = 0;
+    h->trained = false;
+  }
+  return ivf_fill(h, d_rows, n, keys, labels, s);
+}
+
 int zvec_hip_ivf_load(zvec_hip_ivf_t h, const void *centroids, uint32_t nlist, const uint64_t *list_offsets,
                       const void *vecs, const uint64_t *keys) {
   if (!h || !centroids || nlist == 0 || !list_offsets) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
-  uint64_t n = list_offsets[nlist];
+  const uint64_t n = list_offsets[nlist];
   if (n && !vecs) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::vector<uint32_t> labels(n);
-  for (uint32_t l = 0; l < nlist; ++l) {
-    if (list_offsets[l + 1] < list_offsets[l]) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-    for (uint64_t i = list_offsets[l]; i < list_offsets[l + 1]; ++i) labels[i] = l;
-  }
+  std::vector<uint32_t> labels;
+  ZRET(IvfLayout::labels_of_offsets(list_offsets, nlist, labels));
+  IvfWrite w(h);
+  ZRET(w.open());
+  hipStream_t s = h->defctx->own;
   Scoped<char> d_rows;
   if (n) {
     ZRET(d_rows.alloc((size_t)n * h->lists.row_bytes()));
     ZCHK(hipMemcpyAsync(d_rows, vecs, (size_t)n * h->lists.row_bytes(), hipMemcpyHostToDevice, s));
   }
-  if (h->loaded || h->filling || h->coarse_sep) ivf_release(h);
+  w.reset();
   return ivf_pack(h, d_rows, n, keys, labels, centroids, nlist, s);
 }
 
@@ -333,7 +272,7 @@ int zvec_hip_ivf_load_segments(zvec_hip_ivf_t h, const void *inverted_header, ui
   const uint64_t block_size = (bvc * elem + 31) / 32 * 32;                   // IVFUtility::AlignedSize
   if (hd.block_size != 0 && hd.block_size != block_size) return load_fail(7, ZVEC_HIP_ERR_INVALID_ARGUMENT);
   const bool column_major = im.major_order == 2;
-  std::vector<uint64_t> list_off(nlist), row0(nlist + 1), list_offsets(nlist + 1);
+  std::vector<uint64_t> list_off(nlist), row0(nlist + 1);
   uint64_t seen = 0;
   for (uint32_t l = 0; l < nlist; ++l) {
     RefInvertedListMeta m;
@@ -347,15 +286,15 @@ int zvec_hip_ivf_load_segments(zvec_hip_ivf_t h, const void *inverted_header, ui
     if (m.vector_count && (m.offset > body_bytes || bytes > body_bytes - m.offset)) return load_fail(9, ZVEC_HIP_ERR_INVALID_ARGUMENT);
     list_off[l] = m.offset;
     row0[l] = seen;
-    list_offsets[l] = seen;
     seen += m.vector_count;
   }
   row0[nlist] = seen;
-  list_offsets[nlist] = seen;
   if (seen != total) return load_fail(10, ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  std::vector<uint32_t> labels;
+  ZRET(IvfLayout::labels_of_offsets(row0.data(), nlist, labels));
 
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  IvfWrite w(h);
+  ZRET(w.open());
   hipStream_t s = h->defctx->own;
   Scoped<char> d_rows;
   if (total) {
@@ -376,10 +315,7 @@ int zvec_hip_ivf_load_segments(zvec_hip_ivf_t h, const void *inverted_header, ui
     ZCHK(hipGetLastError());
     ZCHK(hipStreamSynchronize(s));      // the uploaded body and tables are freed here
   }
-  std::vector<uint32_t> labels(total);
-  for (uint32_t l = 0; l < nlist; ++l)
-    for (uint64_t i = list_offsets[l]; i < list_offsets[l + 1]; ++i) labels[i] = l;
-  if (h->loaded || h->filling || h->coarse_sep) ivf_release(h);
+  w.reset();
   return ivf_pack(h, d_rows, total, static_cast<const uint64_t *>(keys), labels, centroids, nlist, s);
 }
 
@@ -498,15 +434,14 @@ int zvec_hip_ivf_build_dev(zvec_hip_ivf_t h, const void *d_vecs, uint64_t n, con
                            uint32_t kmeans_iters, uint32_t sample_per_list, uint64_t seed, void *stream) {
   if (!h || !d_vecs || n == 0 || nlist == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (nlist > n) nlist = (uint32_t)n;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  IvfWrite w(h, true);                   // (labelling goes through the built-in context's workspace)
+  ZRET(w.open());
   zvec_hip_ctx_s *c = h->defctx;
-  std::lock_guard<std::mutex> gc(c->mu);
   hipStream_t s = pick_stream(c, stream);
   const char *rows = reinterpret_cast<const char *>(d_vecs);
   const size_t rb = h->lists.row_bytes();
   if (sample_per_list == 0) sample_per_list = 256;
-  if (h->loaded || h->filling || h->coarse_sep) ivf_release(h);
+  w.reset();
 
   // ---- sample (deterministic stride) ----
   uint64_t S = std::min<uint64_t>(n, (uint64_t)sample_per_list * nlist);
@@ -531,11 +466,7 @@ int zvec_hip_ivf_build_dev(zvec_hip_ivf_t h, const void *d_vecs, uint64_t n, con
     ZCHK(hipMemcpy(lab.data(), d_lab, n * 4, hipMemcpyDeviceToHost));
   }
   for (uint64_t i = 0; i < n; ++i) if (lab[i] >= nlist) lab[i] = 0;
-  std::vector<uint32_t> sizes(nlist, 0);
-  for (uint64_t i = 0; i < n; ++i) sizes[lab[i]] += 1;
-  ZRET(ivf_begin_lists(h, sizes.data(), s));
-  ZRET(ivf_add_rows(h, rows, n, lab.data(), keys, 0, s));
-  return ivf_end_lists(h);
+  return ivf_fill(h, rows, n, keys, lab, s);
 }
 
 int zvec_hip_ivf_build(zvec_hip_ivf_t h, const void *vecs, uint64_t n, const uint64_t *keys, uint32_t nlist,
@@ -554,53 +485,52 @@ int zvec_hip_ivf_build(zvec_hip_ivf_t h, const void *vecs, uint64_t n, const uin
 int zvec_hip_ivf_train_dev(zvec_hip_ivf_t h, const void *d_sample, uint64_t n_sample, uint32_t nlist, uint32_t kmeans_iters,
                            uint64_t seed, void *stream) {
   if (!h || !d_sample || n_sample == 0 || nlist == 0 || nlist > n_sample) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  IvfWrite w(h, true);
+  ZRET(w.open());
+  w.reset();
   zvec_hip_ctx_s *c = h->defctx;
-  std::lock_guard<std::mutex> gc(c->mu);
-  if (h->loaded || h->filling || h->coarse_sep) ivf_release(h);
   return ivf_train(h, c, reinterpret_cast<const char *>(d_sample), n_sample, nlist, kmeans_iters, seed, pick_stream(c, stream));
 }
 
 int zvec_hip_ivf_set_centroids(zvec_hip_ivf_t h, const void *centroids, uint32_t nlist) {
   if (!h || !centroids || nlist == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
-  if (h->loaded || h->filling || h->coarse_sep) ivf_release(h);
+  IvfWrite w(h);
+  ZRET(w.open());
+  w.reset();
   return ivf_set_centroids(h, centroids, nlist, h->defctx->own);
 }
 
 int zvec_hip_ivf_get_centroids(zvec_hip_ivf_t h, void *centroids, uint32_t *nlist) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
   if (!h->trained) return ZVEC_HIP_ERR_NO_TRAINED;
   if (centroids && h->coarse_sep) return ZVEC_HIP_ERR_UNSUPPORTED;      // (rows of another width than the caller's [nlist][dim])
-  if (nlist) *nlist = h->nlist;
+  if (nlist) *nlist = h->lay.nlist;
   if (centroids) memcpy(centroids, h->h_centroids.data(), h->h_centroids.size());
   return 0;
 }
 
 int zvec_hip_ivf_label_dev(zvec_hip_ivf_t h, const void *d_rows, uint64_t n, uint32_t *d_labels, void *stream) {
   if (!h || (n && (!d_rows || !d_labels))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfRead r(h);
   if (!h->trained) return ZVEC_HIP_ERR_NO_TRAINED;
   if (h->coarse_sep) return ZVEC_HIP_ERR_UNSUPPORTED;      // the centroid store is not in the rows' space: nothing to label against
   if (n == 0) return 0;
-  std::lock_guard<std::mutex> g(h->mu);
   ZCHK(hipSetDevice(h->device));
   zvec_hip_ctx_s *c = h->defctx;
-  std::lock_guard<std::mutex> gc(c->mu);
   return ivf_label_rows(h, c, h->cent, reinterpret_cast<const char *>(d_rows), n, d_labels, pick_stream(c, stream));
 }
 
 int zvec_hip_ivf_begin_lists(zvec_hip_ivf_t h, const uint32_t *list_sizes) {
   if (!h || !list_sizes) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfWrite w(h);
   if (!h->trained) return ZVEC_HIP_ERR_NO_TRAINED;
   if (h->coarse_sep) return ZVEC_HIP_ERR_UNSUPPORTED;      // (a streamed fill labels against centroids of the rows' own space)
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  ZRET(w.open());
   if (h->loaded) {                       // a new fill replaces the lists, the centroids stay
     std::vector<char> keep(h->h_centroids);
-    const uint32_t nl = h->nlist;
-    ivf_release(h);
+    const uint32_t nl = h->lay.nlist;
+    w.reset();
     ZRET(ivf_set_centroids(h, keep.data(), nl, h->defctx->own));
   }
   int rc = ivf_begin_lists(h, list_sizes, h->defctx->own);
@@ -611,46 +541,46 @@ int zvec_hip_ivf_begin_lists(zvec_hip_ivf_t h, const uint32_t *list_sizes) {
 int zvec_hip_ivf_add_dev(zvec_hip_ivf_t h, const void *d_rows, uint64_t n, const uint32_t *labels, const uint64_t *keys,
                          uint64_t first_row, void *stream) {
   if (!h || (n && (!d_rows || !labels))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfWrite w(h);
   if (!h->filling) return ZVEC_HIP_ERR_NO_READY;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  ZRET(w.open());
   return ivf_add_rows(h, d_rows, n, labels, keys, first_row, pick_stream(h->defctx, stream));
 }
 
 int zvec_hip_ivf_end_lists(zvec_hip_ivf_t h) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfWrite w(h);
   if (!h->filling) return ZVEC_HIP_ERR_NO_READY;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  ZRET(w.open());
   return ivf_end_lists(h);
 }
 
 int zvec_hip_ivf_info(zvec_hip_ivf_t h, uint64_t *count, uint32_t *nlist) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (count) *count = h->count_local;
-  if (nlist) *nlist = h->nlist;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (count) *count = h->lay.count_local;
+  if (nlist) *nlist = h->lay.nlist;
   return 0;
 }
 
 int zvec_hip_ivf_export(zvec_hip_ivf_t h, void *centroids, uint64_t *list_offsets, uint64_t *row_ids) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   if (centroids && h->coarse_sep) return ZVEC_HIP_ERR_UNSUPPORTED;      // (rows of another width than the caller's [nlist][dim])
   if (centroids) memcpy(centroids, h->h_centroids.data(), h->h_centroids.size());
-  if (list_offsets) memcpy(list_offsets, h->h_dense0.data(), h->h_dense0.size() * 8);
-  if (row_ids) memcpy(row_ids, h->h_row_ids.data(), h->h_row_ids.size() * 8);
+  if (list_offsets) memcpy(list_offsets, h->lay.dense0.data(), h->lay.dense0.size() * 8);
+  if (row_ids) memcpy(row_ids, h->lay.row_ids.data(), h->lay.row_ids.size() * 8);
   return 0;
 }
 
 int zvec_hip_ivf_get_vector(zvec_hip_ivf_t h, uint64_t list_pos, void *out) {
   if (!h || !out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfRead r(h);                    // (io_q is the built-in context's staging buffer)
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-  if (list_pos >= h->count_local) return ZVEC_HIP_ERR_NO_EXIST;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::lock_guard<std::mutex> gc(h->defctx->mu);     // io_q is the built-in context's staging buffer
+  uint64_t pos = 0;
+  if (!h->lay.store_pos(list_pos, &pos)) return ZVEC_HIP_ERR_NO_EXIST;
   ZCHK(hipSetDevice(h->device));
-  uint32_t l = (uint32_t)(std::upper_bound(h->h_dense0.begin(), h->h_dense0.end(), list_pos) - h->h_dense0.begin()) - 1;
-  uint64_t pos = (uint64_t)h->h_tile0[l] * TILE_N + (list_pos - h->h_dense0[l]);
   zvec_hip_ctx_s *c = h->defctx;
   ZRET(c->io_q.ensure(h->lists.row_bytes()));
   ZRET(launch_unpack(h->lists, pos, c->io_q.p, c->own));
@@ -661,30 +591,25 @@ int zvec_hip_ivf_get_vector(zvec_hip_ivf_t h, uint64_t list_pos, void *out) {
 
 int zvec_hip_ivf_get_vectors(zvec_hip_ivf_t h, const uint64_t *list_positions, uint64_t n, void *out) {
   if (!h || (n && (!list_positions || !out))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  IvfRead r(h);
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   if (n == 0) return 0;
   if (n > 0x7fffffffull) return ZVEC_HIP_ERR_OUT_OF_RANGE;
-  std::lock_guard<std::mutex> g(h->mu);
-  std::lock_guard<std::mutex> gc(h->defctx->mu);
   std::vector<uint64_t> pos(n);
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t lp = list_positions[i];
-    if (lp >= h->count_local) return ZVEC_HIP_ERR_NO_EXIST;
-    const uint32_t l = (uint32_t)(std::upper_bound(h->h_dense0.begin(), h->h_dense0.end(), lp) - h->h_dense0.begin()) - 1;
-    pos[i] = (uint64_t)h->h_tile0[l] * TILE_N + (lp - h->h_dense0[l]);
-  }
+  for (uint64_t i = 0; i < n; ++i)
+    if (!h->lay.store_pos(list_positions[i], &pos[i])) return ZVEC_HIP_ERR_NO_EXIST;
   ZCHK(hipSetDevice(h->device));
   return store_get_rows(h->defctx, h->lists, pos, out);
 }
 
-// the IVF search proper; the caller holds c->mu and has validated the arguments
+// the IVF search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments
 static int ivf_search_dev_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk,
                                  float threshold, uint32_t nprobe, uint32_t max_scan_count, int brute_force,
                                  const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts,
                                  hipStream_t s, const void *d_coarse_queries = nullptr, const CoarseSplit &coarse = CoarseSplit(),
                                  ShadowMode mode = ShadowMode()) {
   if (!h->trained && !brute_force) return ZVEC_HIP_ERR_NO_TRAINED;      // (segments loaded, coarse space still to be set)
-  const uint32_t np = std::max<uint32_t>(1u, std::min(nprobe, h->nlist));      // (the row stride of the probe lists)
+  const uint32_t np = std::max<uint32_t>(1u, std::min(nprobe, h->lay.nlist));      // (the row stride of the probe lists)
   // 32-bit word offsets into the padded query matrix: very large batches go in slices
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(std::max(h->lists.dpad, h->cent.dpad), 1u));
   // (the flags of a shadow search belong to ONE call of the core: a sliced batch reads the fp32 lists)
@@ -713,11 +638,11 @@ static int ivf_search_dev_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const voi
 int zvec_hip_ivf_coarse_dev(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count, uint32_t nprobe,
                             uint32_t *d_probe_idx, uint32_t *d_probe_cnt, void *stream) {
   if (!h || !d_queries || !d_probe_idx || !d_probe_cnt) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  IvfRead r(h, c);
   if (!h->trained) return ZVEC_HIP_ERR_NO_TRAINED;
   if (h->coarse_sep) return ZVEC_HIP_ERR_UNSUPPORTED;
   if (count == 0) return 0;
-  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
   CoarseSplit cs;
   cs.out_idx = d_probe_idx;
@@ -731,11 +656,11 @@ int zvec_hip_ivf_search_probes_dev(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const v
                                    const uint32_t *d_probe_cnt, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                                    float *d_out_scores, uint32_t *d_out_counts, void *stream) {
   if (!h || !d_queries || !d_probe_idx || !d_probe_cnt || !d_out_keys || !d_out_scores || !d_out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  IvfRead r(h, c);
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
   CoarseSplit cs;
   cs.given_idx = d_probe_idx;
@@ -748,18 +673,18 @@ int zvec_hip_ivf_search_dev(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void *d_
                             float threshold, uint32_t nprobe, uint32_t max_scan_count, const uint64_t *d_exclude_bitset,
                             uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream) {
   if (!h || !d_queries || !d_out_keys || !d_out_scores || !d_out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  IvfRead r(h, c);
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;   // ivf_searcher.cc:197-200
-  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
   return ivf_search_dev_locked(h, c, d_queries, count, topk, threshold, nprobe, max_scan_count, 0, d_exclude_bitset,
                                d_out_keys, d_out_scores, d_out_counts, pick_stream(c, stream));
 }
 
 // the certify step of an IVF search through the twin (shadow_certify): the flagged queries are searched again with the same probe
-// rule and exclude set.  The caller holds c->mu.
+// rule and exclude set.  The caller holds c->mu and h->rw (shared).
 static int ivf_shadow_certify_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk,
                                      uint32_t nprobe, uint32_t max_scan_count, const uint64_t *d_exclude, uint64_t *d_out_keys,
                                      float *d_out_scores, uint32_t *d_out_counts, hipStream_t s, const void *d_coarse_queries,
@@ -774,8 +699,8 @@ static int ivf_shadow_certify_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const
 
 int zvec_hip_ivf_set_shadow(zvec_hip_ivf_t h, int enable, uint32_t preselect) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
+  IvfWrite w(h);
+  ZRET(w.open());
   if (!enable) {
     ZCHK(hipDeviceSynchronize());
     h->shadow.drop();
@@ -785,20 +710,21 @@ int zvec_hip_ivf_set_shadow(zvec_hip_ivf_t h, int enable, uint32_t preselect) {
   if (h->dtype != ZVEC_HIP_DT_FP32 || h->metric == ZVEC_HIP_METRIC_COSINE) return ZVEC_HIP_ERR_UNSUPPORTED;
   if (preselect > 64) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (h->shadow.on) { h->shadow.kp = preselect; h->shadow.gov.reset(); return 0; }
-  const uint64_t tiles = (h->lists.n + TILE_N - 1) / TILE_N;
+  const uint64_t tiles = h->lay.local_tiles;      // (the lists fill whole tiles: lists.n == tiles x TILE_N)
   if (tiles == 0) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-  return h->shadow.build(h->lists, tiles * TILE_N, 0, h->tab.d_tile0.p, h->tab.d_size.p, h->nlist, preselect, h->defctx->own);
+  return h->shadow.build(h->lists, tiles * TILE_N, 0, h->tab.d_tile0.p, h->tab.d_size.p, h->lay.nlist, preselect, h->defctx->own);
 }
 
 int zvec_hip_ivf_shadow_info(zvec_hip_ivf_t h, int *enabled, uint64_t *bytes, float *max_row_error, float *max_row_norm) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> g(h->mu);
+  std::shared_lock<FairSharedMutex> r(h->rw);
   h->shadow.info(enabled, bytes, max_row_error, max_row_norm);
   return 0;
 }
 
 int zvec_hip_ivf_shadow_width(zvec_hip_ivf_t h, uint32_t topk, uint32_t *rows) {
   if (!h || !rows) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
   *rows = h->shadow.width(topk);
   return 0;
 }
@@ -807,9 +733,9 @@ int zvec_hip_ivf_shadow_certify(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void
                                 uint32_t nprobe, uint32_t max_scan_count, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                                 float *d_out_scores, uint32_t *d_out_counts, void *stream, uint32_t *rerun) {
   if (!h || !d_queries || !d_out_keys || !d_out_scores || !d_out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  std::lock_guard<std::mutex> g(c->mu);
+  IvfRead r(h, c);
+  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   ZCHK(hipSetDevice(h->device));
   return ivf_shadow_certify_locked(h, c, d_queries, count, topk, nprobe, max_scan_count, d_exclude_bitset, d_out_keys, d_out_scores,
                                    d_out_counts, pick_stream(c, stream), nullptr, rerun);
@@ -820,16 +746,17 @@ static int ivf_search_host_impl(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void
                                 const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
                                 uint32_t *out_counts, const void *coarse_queries = nullptr) {
   if (!h || !queries || !out_keys || !out_scores || !out_counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  // ONE critical section from the upload to the copy-out (see zvec_hip_flat_search)
+  IvfRead r(h, c);
+  if (coarse_queries && !h->coarse_sep) return ZVEC_HIP_ERR_INVALID_ARGUMENT;      // (zvec_hip_ivf_search_coarse without a coarse space)
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
   if (count == 0) return 0;
   if (topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
-  // ONE critical section from the upload to the copy-out (see zvec_hip_flat_search)
-  std::lock_guard<std::mutex> g(c->mu);
   ZCHK(hipSetDevice(h->device));
-  ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->lists.row_bytes(), exclude_bitset, h->count_local, count, topk, c->cur));
+  ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->lists.row_bytes(), exclude_bitset, h->lay.count_local, count, topk, c->cur));
   const void *d_cq = nullptr;
-  if (coarse_queries && h->coarse_sep) {
+  if (coarse_queries) {
     const size_t cb = (size_t)count * h->cent.row_bytes();
     ZRET(c->io_cq.ensure(cb));
     ZCHK(hipMemcpyAsync(c->io_cq.p, coarse_queries, cb, hipMemcpyHostToDevice, c->cur));
@@ -853,30 +780,20 @@ static int ivf_search_host_impl(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void
 int zvec_hip_ivf_set_coarse_space(zvec_hip_ivf_t h, uint32_t coarse_dim, int coarse_metric, const void *centroids, uint32_t nlist) {
   if (!h || !centroids || coarse_dim == 0 || nlist == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (coarse_metric != ZVEC_HIP_METRIC_L2 && coarse_metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (h->loaded && nlist != h->nlist) return ZVEC_HIP_ERR_MISMATCH;
-  std::lock_guard<std::mutex> g(h->mu);
-  ZCHK(hipSetDevice(h->device));
-  hipStream_t s = h->defctx->own;
+  IvfWrite w(h);
+  if (h->loaded && nlist != h->lay.nlist) return ZVEC_HIP_ERR_MISMATCH;
+  ZRET(w.open());
   h->cent.release();
   h->cent.n = 0;                          // (centroids of the rows' own space may have been loaded before)
   h->cent.configure(coarse_dim, coarse_metric, h->dtype);
-  const size_t rb = h->cent.row_bytes();
-  h->h_centroids.assign(static_cast<const char *>(centroids), static_cast<const char *>(centroids) + (size_t)nlist * rb);
-  Scoped<char> d_c;
-  ZRET(d_c.alloc((size_t)nlist * rb));
-  ZCHK(hipMemcpyAsync(d_c, centroids, (size_t)nlist * rb, hipMemcpyHostToDevice, s));
-  ZRET(store_append_dev(h->cent, d_c, nlist, nullptr, s));
-  ZCHK(hipStreamSynchronize(s));
-  h->nlist = nlist;
   h->coarse_sep = true;
-  h->trained = true;
-  return 0;
+  return ivf_upload_centroids(h, centroids, nlist, h->defctx->own);
 }
 
 int zvec_hip_ivf_search_coarse(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void *queries, const void *coarse_queries, uint32_t count,
                                uint32_t topk, float threshold, uint32_t nprobe, uint32_t max_scan_count,
                                const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores, uint32_t *out_counts) {
-  if (!h || !h->coarse_sep || !coarse_queries) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (!h || !coarse_queries) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   return ivf_search_host_impl(h, ctx, queries, count, topk, threshold, nprobe, max_scan_count, 0, exclude_bitset, out_keys,
                               out_scores, out_counts, coarse_queries);
 }

@@ -193,7 +193,7 @@ int zvec_hip_shards_count(zvec_hip_shards_t h, uint64_t *total, uint64_t *per_sh
   for (uint32_t g = 0; g < h->G; ++g) {
     uint64_t n = 0;
     if (h->kind == ZVEC_HIP_SHARDS_FLAT) ZRET(zvec_hip_flat_count(h->flat[g], &n));
-    else if (h->ivf[g]->loaded) n = h->ivf[g]->count_local;
+    else if (h->ivf[g]->loaded) n = h->ivf[g]->lay.count_local;
     if (per_shard) per_shard[g] = n;
     sum += n;
   }
@@ -381,7 +381,7 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
   // [g x per, (g + 1) x per) against its replica of the centroids and peer-copies that slice of the probe lists (ids, then counts)
   // into every shard's table; the search proper then plans from the table instead of running the whole coarse pass G times.
   const bool dealt = is_ivf && h->deal_coarse && h->G > 1 && !h->ivf[0]->coarse_sep;
-  const uint32_t np = is_ivf ? std::max<uint32_t>(1u, std::min(nprobe, h->ivf[0]->nlist)) : 0;
+  const uint32_t np = is_ivf ? std::max<uint32_t>(1u, std::min(nprobe, h->ivf[0]->lay.nlist)) : 0;
   const uint32_t per = (count + h->G - 1) / h->G;
   if (dealt) {
     for (uint32_t g = 0; g < h->G; ++g) {          // every table exists before the first peer copy into it
@@ -430,12 +430,12 @@ int zvec_hip_shards_search(zvec_hip_shards_t h, const void *queries, uint32_t co
       if (is_ivf) {                      // owned lists: global list-order run -> local list-order run
         const zvec_hip_ivf_s *v = h->ivf[g];
         uint64_t gd = 0;
-        for (uint32_t l = 0; l < v->nlist; ++l) {
-          if (v->h_size[l]) tmp.push_back(ShardRange{gd, v->h_dense0[l], v->h_size[l]});
-          gd += v->h_size_global[l];
+        for (uint32_t l = 0; l < v->lay.nlist; ++l) {
+          if (v->lay.size[l]) tmp.push_back(ShardRange{gd, v->lay.dense0[l], v->lay.size[l]});
+          gd += v->lay.size_global[l];
         }
         rs = &tmp;
-        local_n = v->count_local;
+        local_n = v->lay.count_local;
       } else {
         for (const auto &r : *rs) local_n += r.len;
       }

@@ -24,14 +24,14 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   if ((given || coarse_only) && brute_force) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (h->coarse_sep && !brute_force && !given && d_coarse_queries == nullptr) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   const int cus = device_cus(ctx);
-  const uint32_t nlist = h->nlist;
+  const uint32_t nlist = h->lay.nlist;
   if (nprobe < 1) nprobe = 1;
   if (nprobe > nlist) nprobe = nlist;
 
   // A handful of queries (the product's count = 1 calls): both steps go wave-per-row instead of through the MFMA tile
   // kernels, whose few work items would each be a chain of dependent HBM round trips (1 query, 2M x 768, nprobe 32:
   // coarse 90 us + list scan 113 us for 6 + 96 MB).  Bound of the rows one query can scan: the nprobe largest lists.
-  const uint64_t direct_rows = h->h_rows_of_largest.size() > nprobe ? std::max<uint64_t>(1, h->h_rows_of_largest[nprobe]) : ~0ull;
+  const uint64_t direct_rows = h->lay.rows_of_largest.size() > nprobe ? std::max<uint64_t>(1, h->lay.rows_of_largest[nprobe]) : ~0ull;
   // (measured, 2M x 768 fp32, nprobe 32 of 2048 lists, host-pointer calls: 1 query 223 -> 116 us, 2: 244 -> 153, 4: 290 -> 222,
   // 8: 390 -> 369, 16: 586 -> 655 — the direct route costs the same for every query, the tile route shares the lists)
   const bool direct = !brute_force && !coarse_only && count <= (uint32_t)knobs().ivf_direct_q && (uint64_t)count * direct_rows <= (4u << 20) &&
@@ -191,7 +191,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     // upper bound of the rows one query scans here: the np largest local lists
     uint64_t maxlen = 0;
     {
-      std::vector<uint32_t> sz(h->h_size);
+      std::vector<uint32_t> sz(h->lay.size);
       const uint32_t np = brute_force ? nlist : nprobe;
       std::partial_sort(sz.begin(), sz.begin() + np, sz.end(), std::greater<uint32_t>());
       for (uint32_t i = 0; i < np; ++i) maxlen += sz[i];
@@ -252,15 +252,15 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   // chunk length of this search: the lists it can touch (at most count x nprobe of them) should give a few items per
   // resident work-group — a single query probing 40 lists needs one-tile items to use the chip at all, a batch of
   // 1024 the index-wide default
-  uint32_t tpc = h->tiles_per_chunk;
+  uint32_t tpc = h->lay.tiles_per_chunk;
   {
     const uint64_t lists_touched = std::min<uint64_t>(nlist, (uint64_t)count * (brute_force ? nlist : nprobe));
-    const uint64_t est_tiles = std::max<uint64_t>(1, h->local_tiles * lists_touched / std::max<uint32_t>(nlist, 1));
+    const uint64_t est_tiles = std::max<uint64_t>(1, h->lay.local_tiles * lists_touched / std::max<uint32_t>(nlist, 1));
     const uint64_t t = est_tiles / (4ull * (uint64_t)device_cus(ctx) * 3ull);
     // never one-tile items: they double the slots the merge has to fold for nothing (measured, 10M x 768, nprobe 38:
     // batch 1 best at 2 tiles, batch 8 at 4, batch 32 at 4-8, batch 1024 at the index default)
     const uint64_t lo = est_tiles >= 4096 ? 4 : 2;
-    tpc = (uint32_t)std::min<uint64_t>(h->tiles_per_chunk, std::max<uint64_t>(lo, t));
+    tpc = (uint32_t)std::min<uint64_t>(h->lay.tiles_per_chunk, std::max<uint64_t>(lo, t));
     if (knobs().ivf_tpc) tpc = (uint32_t)knobs().ivf_tpc;
   }
   {
@@ -295,14 +295,14 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
 
   // 3. scan.  Upper bound of slots: every probed list contributes its chunks; the worst case is a query that
   //    probes the nprobe lists with the most chunks.
-  std::vector<uint32_t> &sz = h->h_size;
+  const std::vector<uint32_t> &sz = h->lay.size;
   uint64_t slots_bound;
   {
     std::vector<uint32_t> chunks(nlist);
     for (uint32_t l = 0; l < nlist; ++l)
     {
-      const uint32_t t = level_tpc(h->h_tail[l], tpc);
-      chunks[l] = sz[l] ? (((sz[l] + TILE_N - 1) / TILE_N + t - 1) / t) : 0;
+      const uint32_t t = level_tpc(h->lay.tail[l], tpc);
+      chunks[l] = sz[l] ? (uint32_t)((ivf_tiles(sz[l]) + t - 1) / t) : 0;
     }
     uint32_t np = brute_force ? nlist : nprobe;
     std::partial_sort(chunks.begin(), chunks.begin() + np, chunks.end(), std::greater<uint32_t>());
@@ -320,7 +320,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     ZRET(shadow_prep_queries(ctx, sst, d_queries, count, stream));
     a.queries = ctx->sh.q16.as<float>(); a.qnorm = ctx->sh.qn16.as<float>();
   }
-  a.k = ks; a.mode = 1; a.nq = count; a.n = h->lists.n; a.ndense = h->count_local; a.tiles_per_chunk = tpc; a.list_tpc = pb + o_ltpc;
+  a.k = ks; a.mode = 1; a.nq = count; a.n = h->lists.n; a.ndense = h->lay.count_local; a.tiles_per_chunk = tpc; a.list_tpc = pb + o_ltpc;
   a.total_items = p.total_items; a.queue = pb + o_queue; a.list_order = h->tab.d_order.p; a.item_off = p.item_off; a.list_tile0 = h->tab.d_tile0.p; a.list_size = h->tab.d_size.p;
   a.list_dense0 = h->tab.d_dense0.p; a.list_qoff = p.list_qoff; a.csr_q = p.csr_q; a.csr_slot = p.csr_slot; a.nlist = nlist;
   a.part_s = ctx->part_s.as<float>(); a.part_i = ctx->part_i.as<uint32_t>();

@@ -628,31 +628,21 @@ struct zvec_hip_ivf_s {
   int dtype = 0;
   uint32_t dim = 0;
   int metric = 0;
-  uint32_t nlist = 0;
-  uint32_t shard = 0, nshards = 1;
   bool loaded = false;
   bool trained = false;                // centroids present (h_centroids + cent store): labelling possible
   bool filling = false;                // between begin_lists and end_lists of a streamed build
-  std::vector<uint32_t> h_owner;       // list -> shard (byte-balanced, identical on every rank)
-  std::vector<uint64_t> h_cursor;      // streamed build: next dense position of each list
-  Store cent;     // centroids as a flat store
   bool coarse_sep = false;             // the centroid store lives in a space of its own (dimension / metric): zvec_hip_ivf_set_coarse_space
+  IvfLayout lay;  // which lists are kept, where they lie in `lists`, the fill's cursors, the deal order (host/ivf_layout.h)
+  Store cent;     // centroids as a flat store
   Store lists;    // inverted lists, each padded to whole tiles
   ShadowTwin shadow;                   // fp16 twin of `lists` (zvec_hip_ivf_set_shadow)
-  uint64_t count_local = 0, count_global = 0;
-  std::vector<uint32_t> h_size, h_size_global, h_tile0;
-  std::vector<uint64_t> h_rows_of_largest;   // [i] = rows of the i largest local lists (bound of what i probes can scan)
-  std::vector<uint64_t> h_dense0;      // local dense offsets (nlist+1)
-  std::vector<uint64_t> h_row_ids;     // local dense position -> original row
   std::vector<char> h_centroids;       // [nlist][dim] in the index element type
   struct Tables {                      // the list tables on the device: built whole by ivf_end_lists, replaced whole
     Scoped<uint32_t> d_size, d_size_global, d_tile0, d_order, d_tail;
     Scoped<uint64_t> d_dense0;
   } tab;
-  uint32_t tiles_per_chunk = 8;
-  std::vector<uint32_t> h_tail;        // 1 = list belongs to the tail of the deal order (shorter chunks)
-  uint64_t local_tiles = 0;            // tiles of the lists held by this shard
   zvec_hip_ctx_s *defctx = nullptr;
-  std::mutex mu;
+  std::mutex mu;            // serialises the calls that change the index or use defctx's workspace (label_dev, get_vector)
+  FairSharedMutex rw;       // searches hold it shared, anything that may move or extend the store exclusive (as zvec_hip_flat_s)
   ~zvec_hip_ivf_s() { delete defctx; }
 };

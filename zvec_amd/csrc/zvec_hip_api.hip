@@ -26,6 +26,7 @@
 #include "scan_kernels.hip.h"
 #include "host/hole_bits.h"
 #include "host/sparse_put_plan.h"
+#include "host/ivf_layout.h"
 
 using namespace zvk;
 
