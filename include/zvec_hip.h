@@ -456,6 +456,39 @@ int zvec_hip_ctx_profile_read(zvec_hip_ctx_t ctx, uint64_t *launches, double *sc
  *   bits 16..25  seeding 2 only: bits 0..9 of the prefix scan itself */
 int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route);
 
+/* The plan of the last IVF search on ctx (zvec_hip_ivf_search / _search_bf / _search_dev / _search_probes_dev): which route the host
+ * dispatched and, for the tile route, the arrays the plan kernels left for the list scan — the only view of them that does not go
+ * through the final top-k.  A test and debugging hook: the searches themselves only remember a few host words (no launch, copy or
+ * wait is added to them); this call waits for the context's stream and copies the plan buffer out once.  A search that was handed a
+ * caller's stream must have been waited for by the caller.
+ *   info      always filled: route, and for the tile route every scalar below
+ *   arrays    each may be NULL; filled for the tile route only: q_nprobe, q_scanned, q_nslots [nq], slot_begin [nq + 1],
+ *             list_count, list_tpc [nlist], list_qoff, item_off [nlist + 1] (item_off in the deal order: lists largest first),
+ *             csr_q, csr_slot [csr_len <= nq x nprobe] (list-major; the order inside a list is not defined)
+ * Returns 0 for the tile route, ZVEC_HIP_ERR_NO_READY ("nothing to report", info->route says why) when the last search took the
+ * direct or the large-k route, was cut short by an error, or was not an IVF search (a flat, group-by or by-ids search on the
+ * context in between; other search kinds leave the plan of the last IVF search readable). */
+#define ZVEC_HIP_IVF_ROUTE_NONE 0u
+#define ZVEC_HIP_IVF_ROUTE_DIRECT_BLOCK_TOPK 1u /* a few queries, wave per row: the scoring blocks keep their own top-k lists */
+#define ZVEC_HIP_IVF_ROUTE_DIRECT_SELECT 2u     /* a few queries, wave per row: score matrix, selected in one run or two steps */
+#define ZVEC_HIP_IVF_ROUTE_TILE 3u              /* list-major work items on the matrix tile */
+#define ZVEC_HIP_IVF_ROUTE_LARGE_K 4u           /* k beyond the scan's resident lists: expanded positions, scored pair by pair */
+typedef struct zvec_hip_ivf_plan_info {
+  uint32_t route;          /* ZVEC_HIP_IVF_ROUTE_* */
+  uint32_t scan_threads;   /* threads of the plan's single-group scan kernel: 1024 on the context's own stream, 256 beside another lane */
+  uint32_t nq, nlist;
+  uint32_t nprobe;         /* probe ranks per query (nlist under brute force) */
+  uint32_t brute_force;
+  uint32_t tpc;            /* base tiles per chunk of this search (a list's own: list_tpc) */
+  uint32_t rows_per_group; /* query rows of one work item */
+  uint32_t total_items;
+  uint32_t csr_len;        /* = list_qoff[nlist] */
+  uint64_t slots_bound;    /* result slots the host sized the partial lists for; >= slot_begin[nq] */
+} zvec_hip_ivf_plan_info;
+int zvec_hip_ctx_last_ivf_plan(zvec_hip_ctx_t ctx, zvec_hip_ivf_plan_info *info, uint32_t *q_nprobe, uint32_t *q_scanned,
+                               uint32_t *q_nslots, uint32_t *slot_begin, uint32_t *list_count, uint32_t *list_qoff,
+                               uint32_t *item_off, uint32_t *list_tpc, uint32_t *csr_q, uint32_t *csr_slot);
+
 /* Per-box calibration for the measurement line (bench.py `roofline.box_clock_mhz` / `box_stream_gbs`): what this box's HBM delivers
  * to a pure streaming reader (16-byte non-temporal loads over `bytes` of device memory: d_buf, or a scratch allocation when NULL),
  * best of `reps` launches, and the shader clock held under that load (s_memtime against the constant 100 MHz s_memrealtime).  So a

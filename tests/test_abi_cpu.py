@@ -191,6 +191,33 @@ def test_route_read_back_validates_its_arguments_without_a_gpu():
     assert L.zvec_hip_ctx_last_route(None, None) == -31
 
 
+def test_ivf_plan_read_back_validates_its_arguments_without_a_gpu():
+    """zvec_hip_ctx_last_ivf_plan is declared, bound and exported; it refuses a null context or a null info block before touching
+    anything, and the ctypes mirror of zvec_hip_ivf_plan_info has the header's fields in the header's order and size"""
+    import ctypes as C
+    from zvec_amd import _lib
+    L = _lib.lib()
+    assert "zvec_hip_ctx_last_ivf_plan" in _declared_symbols() and "zvec_hip_ctx_last_ivf_plan" in _lib.SYMBOLS
+    info = _lib.IvfPlanInfo()
+    info.route, info.slots_bound = 77, 5
+    nulls = [None] * 10
+    assert L.zvec_hip_ctx_last_ivf_plan(None, C.byref(info), *nulls) == -31 and info.route == 77 and info.slots_bound == 5
+    assert L.zvec_hip_ctx_last_ivf_plan(None, None, *nulls) == -31
+    text = open(os.path.join(ROOT, "include", "zvec_hip.h")).read()
+    body = re.search(r"typedef struct zvec_hip_ivf_plan_info \{(.*?)\} zvec_hip_ivf_plan_info;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for typ, names in re.findall(r"(uint32_t|uint64_t)\s+([a-z_, ]+);", body):
+        fields += [(n.strip(), typ) for n in names.split(",")]
+    assert fields == [(n, "uint64_t" if t is C.c_uint64 else "uint32_t") for n, t in _lib.IvfPlanInfo._fields_]
+    assert C.sizeof(_lib.IvfPlanInfo) == 4 * 10 + 8
+    routes = dict(re.findall(r"#define ZVEC_HIP_IVF_ROUTE_([A-Z_]+) (\d)u", text))
+    assert {k: int(v) for k, v in routes.items()} == {
+        "NONE": _lib.IVF_ROUTE_NONE, "DIRECT_BLOCK_TOPK": _lib.IVF_ROUTE_DIRECT_BLOCK_TOPK, "DIRECT_SELECT": _lib.IVF_ROUTE_DIRECT_SELECT,
+        "TILE": _lib.IVF_ROUTE_TILE, "LARGE_K": _lib.IVF_ROUTE_LARGE_K}
+    assert re.search(r"ZVEC_HIP_ERR_NO_READY = (-\d+)", text).group(1) == str(_lib.ERR_NO_READY)
+
+
 def test_shadow_entry_points_refuse_null_handles_without_a_gpu():
     """the half-width pre-selection entry points (zvec_hip_ivf_set_shadow / zvec_hip_flat_set_shadow and their _info / _certify
     companions) validate their arguments before any device call"""

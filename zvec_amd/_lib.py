@@ -21,6 +21,13 @@ class DocFilterDesc(C.Structure):
                 ("forward_bits", C.c_void_p), ("forward_len", C.c_uint64)]
 
 
+class IvfPlanInfo(C.Structure):
+    """zvec_hip_ivf_plan_info: route and scalars of the last IVF search's plan (zvec_hip_ctx_last_ivf_plan)"""
+    _fields_ = [("route", C.c_uint32), ("scan_threads", C.c_uint32), ("nq", C.c_uint32), ("nlist", C.c_uint32), ("nprobe", C.c_uint32),
+                ("brute_force", C.c_uint32), ("tpc", C.c_uint32), ("rows_per_group", C.c_uint32), ("total_items", C.c_uint32),
+                ("csr_len", C.c_uint32), ("slots_bound", C.c_uint64)]
+
+
 class Segment(C.Structure):
     """zvec_hip_segment_t: one segment of a dumped index file"""
     _fields_ = [("id", C.c_char * 64), ("offset", C.c_uint64), ("size", C.c_uint64), ("padding", C.c_uint64),
@@ -32,6 +39,9 @@ ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 # ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes only)
 DT_FP32, DT_FP16, DT_BINARY32, DT_BINARY64 = 0, 1, 2, 3
 METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING = 0, 1, 2, 3
+# ZVEC_HIP_IVF_ROUTE_*
+IVF_ROUTE_NONE, IVF_ROUTE_DIRECT_BLOCK_TOPK, IVF_ROUTE_DIRECT_SELECT, IVF_ROUTE_TILE, IVF_ROUTE_LARGE_K = 0, 1, 2, 3, 4
+ERR_NO_READY = -21
 
 # every symbol include/zvec_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -197,6 +207,7 @@ SYMBOLS = {
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
     "zvec_hip_ctx_last_route": (C.c_int, [_h, C.POINTER(C.c_uint32)]),
+    "zvec_hip_ctx_last_ivf_plan": (C.c_int, [_h, C.POINTER(IvfPlanInfo)] + [_u32p] * 10),
 }
 
 _LIB = None

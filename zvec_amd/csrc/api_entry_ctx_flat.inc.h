@@ -535,6 +535,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(h->st.dpad, 1u));
   c->sh.count = 0;
   c->route = 0;                 // (zvec_hip_ctx_last_route: what this search launches)
+  c->ivf_plan.route = 0;        // (zvec_hip_ctx_last_ivf_plan: not an IVF search)
   // Half-width pre-selection (zvk_shadow.hip.h, as for the IVF lists): the scan streams the fp16 twin of the store for k' rows per
   // query — half the bytes of a small batch's HBM-bound scan, and fp16 matrix work instead of fp32 for a wide one —, those are
   // re-scored on the fp32 rows, the k best certified; zvec_hip_flat_shadow_certify re-runs what fails.
@@ -692,6 +693,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   }
   ZRET(host_search_wrap_begin(c, queries, (size_t)count * st.row_bytes(), nullptr, 0, count, topk, s));
   ZRET(prep_queries(c, st, c->io_qp, count, threshold, s));
+  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(((size_t)total + count + 8) * sizeof(uint32_t)));
   uint32_t *d_pos = c->plan.as<uint32_t>();
   uint32_t *d_off = d_pos + std::max<uint32_t>(total, 1);
@@ -728,6 +730,7 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   ZRET(c->io_q.ensure(st.row_bytes()));
   ZCHK(hipMemcpyAsync(c->io_q.p, query, st.row_bytes(), hipMemcpyHostToDevice, s));
   ZRET(prep_queries(c, st, c->io_q.p, 1, FLT_MAX, s));
+  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(((size_t)n + 8) * sizeof(uint32_t)));
   uint32_t *d_pos = c->plan.as<uint32_t>(), *d_off = d_pos + n;
   ZCHK(hipMemcpyAsync(d_pos, clean.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));

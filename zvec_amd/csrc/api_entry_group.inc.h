@@ -200,6 +200,7 @@ int zvec_hip_flat_search_grouped_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, c
   if (st.n) ZCHK(hipMemcpyAsync(c->grp_of.p, group_of_position, (size_t)st.n * 4, hipMemcpyHostToDevice, s));
   ZRET(host_search_wrap_begin(c, queries, (size_t)count * st.row_bytes(), nullptr, 0, count, 1, s));
   ZRET(prep_queries(c, st, c->io_qp, count, threshold, s));
+  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(((size_t)total + count + 8) * sizeof(uint32_t)));
   uint32_t *d_pos = c->plan.as<uint32_t>();
   uint32_t *d_off = d_pos + std::max<uint32_t>(total, 1);

@@ -94,6 +94,35 @@ int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route) {
   return 0;
 }
 
+// the route and (tile route) the plan arrays of the context's last IVF search: ivf_search_core left word offsets into ctx->plan
+// (IvfPlanMark); one wait and one copy here, nothing in the search
+int zvec_hip_ctx_last_ivf_plan(zvec_hip_ctx_t ctx, zvec_hip_ivf_plan_info *info, uint32_t *q_nprobe, uint32_t *q_scanned,
+                               uint32_t *q_nslots, uint32_t *slot_begin, uint32_t *list_count, uint32_t *list_qoff,
+                               uint32_t *item_off, uint32_t *list_tpc, uint32_t *csr_q, uint32_t *csr_slot) {
+  if (!ctx || !info) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const IvfPlanMark &m = ctx->ivf_plan;
+  *info = zvec_hip_ivf_plan_info();
+  info->route = m.route; info->nq = m.nq; info->nlist = m.nlist; info->nprobe = m.nprobe; info->brute_force = m.brute_force;
+  if (m.route != ZVEC_HIP_IVF_ROUTE_TILE) return ZVEC_HIP_ERR_NO_READY;
+  if (!ctx->plan.p || m.words == 0) { info->route = ZVEC_HIP_IVF_ROUTE_NONE; return ZVEC_HIP_ERR_NO_READY; }
+  info->scan_threads = m.scan_threads; info->tpc = m.tpc; info->rows_per_group = m.rows_per_group; info->slots_bound = m.slots_bound;
+  ZCHK(hipSetDevice(ctx->device));
+  ZCHK(hipStreamSynchronize(ctx->cur));
+  std::vector<uint32_t> w(m.words);
+  ZCHK(hipMemcpy(w.data(), ctx->plan.p, m.words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  info->total_items = w[m.o_total];
+  info->csr_len = w[m.o_lqoff + m.nlist];
+  auto put = [&](uint32_t *dst, size_t o, size_t n) { if (dst && n) memcpy(dst, w.data() + o, n * sizeof(uint32_t)); };
+  const size_t ncsr = (size_t)std::min<uint64_t>(info->csr_len, m.npairs);       // (never beyond what the search reserved)
+  put(q_nprobe, m.o_qnprobe, m.nq); put(q_scanned, m.o_qscanned, m.nq); put(q_nslots, m.o_qnslots, m.nq);
+  put(slot_begin, m.o_slotbegin, (size_t)m.nq + 1);
+  put(list_count, m.o_lcount, m.nlist); put(list_tpc, m.o_ltpc, m.nlist);
+  put(list_qoff, m.o_lqoff, (size_t)m.nlist + 1); put(item_off, m.o_itemoff, (size_t)m.nlist + 1);
+  put(csr_q, m.o_csrq, ncsr); put(csr_slot, m.o_csrslot, ncsr);
+  return 0;
+}
+
 int zvec_hip_ctx_profile_read(zvec_hip_ctx_t ctx, uint64_t *launches, double *scan_ms, double *algorithmic_bytes,
                               double *algorithmic_flops, int reset) {
   if (!ctx) return ZVEC_HIP_ERR_INVALID_ARGUMENT;

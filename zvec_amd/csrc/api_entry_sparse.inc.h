@@ -249,6 +249,7 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   const uint32_t items = (uint32_t)item_e0.size();
   plan.insert(plan.end(), item_e0.begin(), item_e0.end());
   ZRET(sparse_upload_plan(c, plan, s));
+  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(std::max<size_t>(total, 1) * 4));
   const size_t cells = row_stride ? (size_t)count * row_stride : std::max<size_t>(total, 1);
   ZRET(c->part_s.ensure(cells * 4));

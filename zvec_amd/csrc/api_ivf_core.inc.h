@@ -25,6 +25,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   if (h->coarse_sep && !brute_force && !given && d_coarse_queries == nullptr) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   const int cus = device_cus(ctx);
   const uint32_t nlist = h->lay.nlist;
+  ctx->ivf_plan = IvfPlanMark();       // (zvec_hip_ctx_last_ivf_plan: set again where a route has enqueued all of its work)
   if (nprobe < 1) nprobe = 1;
   if (nprobe > nlist) nprobe = nlist;
 
@@ -150,6 +151,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       ZRET(launch_merge(merge_stream(ctx->direct_scores.as<float>(), ctx->direct_idx.as<uint32_t>(), bpq, topk, true, topk, threshold,
                                      h->lists.keys, out), count, 256, stream));
       ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
+      ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_DIRECT_BLOCK_TOPK; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist; ctx->ivf_plan.nprobe = nprobe;
       return 0;
     }
     // equal scores keep the reference's order — probe rank, then position in the list — which here is the ORDER of the
@@ -171,6 +173,7 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       ZRET(launch_merge(merge_stream(ps, ppos, 1, stride, true, topk, threshold, h->lists.keys, out), count, 64, stream));
     }
     ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
+    ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_DIRECT_SELECT; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist; ctx->ivf_plan.nprobe = nprobe;
     return 0;
   }
 
@@ -221,6 +224,8 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
                                    h->lists.keys, out), count, 64, stream));
     ZCHK(hipStreamSynchronize(stream));    // d_pos is freed on return
     ctx->q_nprobe = nullptr; ctx->q_scanned = nullptr; ctx->last_count = 0;
+    ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_LARGE_K; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist;
+    ctx->ivf_plan.nprobe = brute_force ? nlist : nprobe; ctx->ivf_plan.brute_force = brute_force ? 1u : 0u;
     return 0;
   }
   // Half-width pre-selection (zvk_shadow.hip.h): the scan reads the fp16 twin of the lists and keeps k' > k rows per query, which
@@ -289,7 +294,8 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   // resident list scan: a 1024-thread work-group is not dispatched until that scan drains — 714 us for this 20 us kernel
   // in the round-2 trace — four waves are)
   const bool pipelined = ctx->gate != nullptr || stream != ctx->own;
-  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(pipelined ? 256 : 1024), 0, stream, p);
+  const uint32_t scan_threads = pipelined ? 256 : 1024;
+  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(scan_threads), 0, stream, p);
   hipLaunchKernelGGL(plan_wave_kernel<true>, dim3((count + 3) / 4), dim3(256), 0, stream, p);
   ZCHK(hipGetLastError());
 
@@ -333,6 +339,15 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   prof_end(ctx, stream, pi);
   gate_leave(ctx, stream);
   ZRET(lrc);
+  {
+    // the plan is complete on the stream from here on: remember where its arrays lie (host words only, nothing enqueued)
+    IvfPlanMark &m = ctx->ivf_plan;
+    m.route = ZVEC_HIP_IVF_ROUTE_TILE; m.scan_threads = scan_threads; m.nq = count; m.nlist = nlist;
+    m.nprobe = brute_force ? nlist : nprobe; m.tpc = tpc; m.rows_per_group = rows_per_group; m.brute_force = brute_force ? 1u : 0u;
+    m.slots_bound = slots_bound; m.npairs = npairs; m.words = off;
+    m.o_qnprobe = o_qnprobe; m.o_qscanned = o_qscanned; m.o_qnslots = o_qnslots; m.o_slotbegin = o_slotbegin; m.o_lcount = o_lcount;
+    m.o_lqoff = o_lqoff; m.o_itemoff = o_itemoff; m.o_ltpc = o_ltpc; m.o_total = o_total; m.o_csrq = o_csrq; m.o_csrslot = o_csrslot;
+  }
 
   // 4. merge the per-(query, probe, chunk) partial lists in probe order
   if (use_shadow) {

@@ -396,6 +396,20 @@ struct zvec_hip_gate_s {
   std::mutex mu;
 };
 
+// What the last IVF search on a context planned (zvec_hip_ctx_last_ivf_plan): the route it took and, for the tile route, where
+// its arrays lie inside ctx->plan (u32 word offsets: the buffer may be reallocated, the offsets hold).  Host bookkeeping only.
+struct IvfPlanMark {
+  uint32_t route = 0;                      // ZVEC_HIP_IVF_ROUTE_*; 0 = the last search planned nothing that can be read back
+  uint32_t scan_threads = 0;               // threads of plan_scan_kernel (tile route)
+  uint32_t nq = 0, nlist = 0, nprobe = 0;  // nprobe: probe ranks per query (nlist under brute force)
+  uint32_t tpc = 0, rows_per_group = 0, brute_force = 0;
+  uint64_t slots_bound = 0;                // what part_s / part_i were sized from
+  uint64_t npairs = 0;                     // capacity of csr_q / csr_slot
+  size_t words = 0;                        // words of the plan buffer in use
+  size_t o_qnprobe = 0, o_qscanned = 0, o_qnslots = 0, o_slotbegin = 0, o_lcount = 0, o_lqoff = 0, o_itemoff = 0, o_ltpc = 0,
+         o_total = 0, o_csrq = 0, o_csrslot = 0;
+};
+
 struct zvec_hip_ctx_s {
   int device = 0;
   zvec_hip_gate_s *gate = nullptr;
@@ -431,6 +445,7 @@ struct zvec_hip_ctx_s {
   uint32_t *q_scanned = nullptr, *q_nprobe = nullptr;  // inside plan
   uint32_t *last_list_count = nullptr;                 // inside plan
   uint32_t last_count = 0;
+  IvfPlanMark ivf_plan;                                // the last IVF search's route and plan layout (zvec_hip_ctx_last_ivf_plan)
   // profiling
   bool profile = false;
   std::vector<hipEvent_t> ev0, ev1;

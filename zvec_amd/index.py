@@ -377,6 +377,24 @@ class IndexContext:
         _lib.check(_lib.lib().zvec_hip_ctx_last_route(self._h, C.byref(r)), "zvec_hip_ctx_last_route")
         return int(r.value)
 
+    def last_ivf_plan(self):
+        """route and plan of the last IVF search on this context (zvec_hip_ctx_last_ivf_plan): a dict of the scalars — `route` is one of
+        _lib.IVF_ROUTE_* — and, after a tile-route search only, of the plan arrays (uint32); a test and debugging hook"""
+        info = _lib.IvfPlanInfo()
+        fn = _lib.lib().zvec_hip_ctx_last_ivf_plan
+        rc = fn(self._h, C.byref(info), *([None] * 10))
+        out = {name: int(getattr(info, name)) for name, _ in _lib.IvfPlanInfo._fields_}
+        if rc == _lib.ERR_NO_READY:
+            return out
+        _lib.check(rc, "zvec_hip_ctx_last_ivf_plan")
+        nq, nlist, ncsr = out["nq"], out["nlist"], min(out["csr_len"], out["nq"] * out["nprobe"])
+        sizes = (("q_nprobe", nq), ("q_scanned", nq), ("q_nslots", nq), ("slot_begin", nq + 1), ("list_count", nlist),
+                 ("list_qoff", nlist + 1), ("item_off", nlist + 1), ("list_tpc", nlist), ("csr_q", ncsr), ("csr_slot", ncsr))
+        arrays = [np.zeros(max(n, 1), np.uint32) for _, n in sizes]
+        _lib.check(fn(self._h, C.byref(info), *[_np_ptr(a) for a in arrays]), "zvec_hip_ctx_last_ivf_plan")
+        out.update({name: a[:n] for (name, n), a in zip(sizes, arrays)})
+        return out
+
 
 def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
