@@ -46,7 +46,7 @@ enum {
   ZVEC_HIP_METRIC_HAMMING = 3 /* "Hamming" (src/core/metric/hamming_metric.cc:236) */
 };
 
-/* Binary rows (flat indexes only).  HammingMetric accepts DT_BINARY32 / DT_BINARY64 and nothing else (hamming_metric.cc:146-147)
+/* Binary rows (flat indexes, and inverted lists through the zvec_hip_bivf_* family below).  HammingMetric accepts DT_BINARY32 / DT_BINARY64 and nothing else (hamming_metric.cc:146-147)
  * and scores a pair with HammingDistanceMatrix<uint32_t / uint64_t> (src/ailego/math/hamming_distance_matrix.h:41, :339):
  *   - `dim` counts BITS; a row is dim / 32 uint32_t (BINARY32) or dim / 64 uint64_t (BINARY64) words in the host's byte order,
  *     dim / 8 bytes either way; dim must be a non-zero multiple of 32 resp. 64 (the reference asserts !(dim & 31) / !(dim & 63))
@@ -58,7 +58,8 @@ enum {
  *     search_dev, search_by_ids, batch_distance, build_filter (exclude_bitset and threshold mean what they mean elsewhere: a
  *     document is dropped iff score > threshold), and — DT_BINARY32 only, fed with fp32 rows / queries that are turned into sign
  *     bits on the device ("fp32 -> sign bits" below) — append_fp32, append_fp32_dev, search_fp32, search_fp32_dev;  ZVEC_HIP_ERR_UNSUPPORTED: search_grouped*, the shadow entries, load_features,
- *     load_blocks, zvec_hip_shards_create and zvec_hip_ivf_create with a binary dtype;
+ *     load_blocks, zvec_hip_shards_create and zvec_hip_ivf_create with a binary dtype (inverted lists over binary rows are a handle
+ *     family of their own: zvec_hip_bivf_create);
  *   - lists are ascending by score; which of several equal scores are returned at the k-th place, and their order, is unspecified
  *     (the reference's heap resolves ties arbitrarily). */
 
@@ -83,6 +84,7 @@ typedef struct zvec_hip_ctx_s *zvec_hip_ctx_t;
 typedef struct zvec_hip_shards_s *zvec_hip_shards_t;
 typedef struct zvec_hip_gate_s *zvec_hip_gate_t;
 typedef struct zvec_hip_sparse_s *zvec_hip_sparse_t;
+typedef struct zvec_hip_bivf_s *zvec_hip_bivf_t;
 
 /* library / device ------------------------------------------------------------------------- */
 int zvec_hip_abi_version(void);
@@ -109,6 +111,8 @@ const char *zvec_hip_error_string(int code); /* IndexError::What analogue */
  *   "sparse_inverted_build"  1 (default) = the inverted lists of a sparse index are built on the device; 0 = on the host, the
  *               reference of the device build.  Read when a build starts.  The same bytes, and so the same search results,
  *               either way.
+ *   "bivf_part_bytes"  1024 .. 2^30 (default 2^30): a zvec_hip_bivf_search keeps the partial lists of one slice of its batch within
+ *               this many bytes and answers a batch that needs more in slices of queries.  Same results either way.
  * Unsupported (-12) for an unknown name, invalid argument (-1) for a value outside the option's range. */
 int zvec_hip_set_option(const char *name, int value);
 int zvec_hip_get_option(const char *name, int *value);
@@ -361,6 +365,59 @@ int zvec_hip_ivf_end_lists(zvec_hip_ivf_t h);
  * scanned[q] = total_scan_count, probes[q] = lists actually probed.  Host arrays, nullable. */
 int zvec_hip_ivf_last_stats(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, uint32_t count,
                             uint32_t *scanned, uint32_t *probes);
+
+/* ---- Hamming IVF: binary rows through inverted lists ------------------------------------------
+ * The reference's IVF is metric-generic: IVFStreamer::search_impl (src/core/algorithm/ivf/ivf_streamer.cc:183-250) never looks
+ * at the data type, IVFCentroidIndex (ivf_centroid_index.cc:273-297) is a flat index over the centroids under the rows' own
+ * metric, and the trainer has a binary branch, BinaryKmeansAlgorithm<uint32_t / uint64_t> (src/core/algorithm/cluster/
+ * opt_kmeans_cluster.cc:760-851, 1319-1326) over BinaryVectorMean (cluster/vector_mean.h:538-650).  zvec_hip_ivf_* keeps refusing
+ * binary rows; this family stands beside it.  Score = (float) popcount(row ^ query).
+ *   Probe set: the min(nprobe, nlist) centroids smallest by the pair (distance, centroid index), in that ascending order — the
+ *   centroid index's heap admits with a strict `<` (heap.h:103-114), so the centroid seen first wins a tie.
+ *   max_scan_count: lists are probed in that order while the running scanned count < max_scan_count; every probed list adds its
+ *   whole length (ivf_streamer.cc:223-237), as in zvec_hip_ivf_search.
+ *   Result: the topk best rows of the probed lists that are not excluded and score <= threshold, ascending; which of several equal
+ *   scores sit at the k-th place, and their order, is unspecified.  topk > 128: ZVEC_HIP_ERR_UNSUPPORTED.
+ * Searches take the handle's reader side, load and build the writer side; a context's mutex is taken first. */
+/* dtype / dim rules of zvec_hip_flat_create for binary rows: Mismatch (-24) for an fp dtype, InvalidArgument (-31) for a dim that
+ * is not a multiple of 32 (BINARY32) / 64 (BINARY64) or above 2^20 (hamming_metric.cc:146-147) */
+int zvec_hip_bivf_create(uint32_t dim_bits, int dtype, int device, zvec_hip_bivf_t *out);
+int zvec_hip_bivf_destroy(zvec_hip_bivf_t h);
+/* as zvec_hip_ivf_load (what IVFSearcher::load reads, ivf_index_format.h:26-60,152-164): centroids [nlist] rows; `rows` in
+ * inverted-list order, list l owning positions [list_offsets[l], list_offsets[l+1]); keys per row (NULL -> list-order position) */
+int zvec_hip_bivf_load(zvec_hip_bivf_t h, const void *centroids, uint32_t nlist, const uint64_t *list_offsets, const void *rows,
+                       const uint64_t *keys);
+/* IVFBuilder::train + build (ivf_builder.cc:212-403) with the binary trainer: the initial centroids are nlist distinct rows (a
+ * partial Fisher-Yates shuffle of the row numbers driven by splitmix64 seeded with `seed`, draws reduced by `% (n - i)`); each of
+ * the kmeans_iters iterations labels every row with its nearest centroid by (distance, index) and replaces every centroid that has
+ * members by their bitwise majority — bit i set iff ones_i > (members >> 1), BinaryVectorMean::mean (vector_mean.h:599-613) —;
+ * then the rows are labelled once more and packed, inside a list in ascending original row number.  kmeans_iters == 0 leaves the
+ * initial rows as centroids.  The same arguments always give the same index.  rows: host, [n] rows; keys: host, NULL -> the
+ * original row number.  InvalidArgument unless 0 < nlist <= n. */
+int zvec_hip_bivf_build(zvec_hip_bivf_t h, const void *rows, uint64_t n, const uint64_t *keys, uint32_t nlist, uint32_t kmeans_iters,
+                        uint64_t seed);
+/* the same from DEVICE rows; keys stay a host array.  Returns after the index is complete. */
+int zvec_hip_bivf_build_dev(zvec_hip_bivf_t h, const void *d_rows, uint64_t n, const uint64_t *keys, uint32_t nlist,
+                            uint32_t kmeans_iters, uint64_t seed, void *stream);
+int zvec_hip_bivf_info(zvec_hip_bivf_t h, uint64_t *count, uint32_t *nlist);
+/* read back as zvec_hip_ivf_export: centroids [nlist] rows, list_offsets [nlist+1], row_ids [count] = original row number (build) /
+ * load-order row (load) of each list-order position; any pointer may be NULL.  NoIndexLoaded (-204) before load / build. */
+int zvec_hip_bivf_export(zvec_hip_bivf_t h, void *centroids, uint64_t *list_offsets, uint64_t *row_ids);
+/* IVFEntity::get_vector by list-order position (ivf_entity.cc:587-716 addresses rows the same way); NoExist beyond the count */
+int zvec_hip_bivf_get_vectors(zvec_hip_bivf_t h, const uint64_t *list_positions, uint64_t n, void *out);
+/* IVFStreamer::search_impl (ivf_streamer.cc:183-250) under the rules above.  exclude_bitset is over list-order positions, one bit
+ * per position, as in zvec_hip_ivf_search.  NoIndexLoaded (-204) before load / build; InvalidArgument for topk == 0 or nprobe == 0. */
+int zvec_hip_bivf_search(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, const void *queries, uint32_t count, uint32_t topk, float threshold,
+                         uint32_t nprobe, uint32_t max_scan_count, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
+                         uint32_t *out_counts);
+int zvec_hip_bivf_search_dev(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count, uint32_t topk,
+                             float threshold, uint32_t nprobe, uint32_t max_scan_count, const uint64_t *d_exclude_bitset,
+                             uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* what the last search of this index on ctx probed (IndexContext::Stats, index_context.h:67-111, and the coarse result behind it):
+ * probe_idx [count][min(nprobe, nlist)] the probe order, probe_cnt [count] the lists probed under the max-scan rule, scanned
+ * [count] their rows.  Host arrays, nullable; waits for the context's stream.  NoReady (-21) without such a search. */
+int zvec_hip_bivf_last_probes(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *probe_idx, uint32_t *probe_cnt,
+                              uint32_t *scanned);
 
 /* ---- partial top-k merge ------------------------------------------------------------------
  * CombinedVectorColumnIndexer::Search concat + sort + truncate

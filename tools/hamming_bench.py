@@ -12,6 +12,14 @@ alone and the fp32 append in GB/s of fp32 input against the box's streaming figu
 bit-fed search at the same batches.  Reported, not gated.
 
     python tools/hamming_bench.py --from-fp32 [--out profiles/hamming_from_fp32.json]
+
+--ivf measures the same rows through inverted lists (zvec_hip_bivf_*): the index is built with nlist 1024 on the GPU, batches 1 / 256 /
+1024 are timed at nprobe 8 / 32 / 128 next to the flat scan of the same rows IN THE SAME PROCESS — the yardstick —, with recall@10
+against the flat answer (tie-aware: a returned score at or below the flat k-th score counts), the bytes of the probed lists per step
+over the box's streaming figure, and the build time.  The rows are 1024 random prototypes with one bit in eight flipped at random, so
+that there is something to cluster.  Reported, not gated.
+
+    python tools/hamming_bench.py --ivf [--out profiles/hamming_ivf.json]
 """
 import argparse
 import ctypes as C
@@ -31,9 +39,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--from-fp32", action="store_true", help="feed the index with fp32 rows / queries (encoder, fp32 append, search_fp32)")
+    ap.add_argument("--ivf", action="store_true", help="the rows through inverted lists next to the flat scan (zvec_hip_bivf_*)")
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--kmeans-iters", type=int, default=5)
     args = ap.parse_args()
     if args.from_fp32:
         return from_fp32(args)
+    if args.ivf:
+        return ivf(args)
     import torch
     import zvec_amd
     dev = torch.device("cuda:0")
@@ -178,6 +191,72 @@ def from_fp32(args):
            "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup,
            "encode": {"ms": enc_ms, "input_gbs": enc_gbs, "stream_fraction": enc_gbs / gbs.value},
            "append_fp32": {"ms": app_ms, "input_gbs": app_gbs, "stream_fraction": app_gbs / gbs.value},
+           "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def ivf(args):
+    import time
+    import numpy as np
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    n, words, k = args.n, args.bits // 32, args.topk
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+
+    def rand(rows):
+        return torch.randint(-2**31, 2**31 - 1, (rows, words), generator=g, device=dev, dtype=torch.int32)
+
+    def noisy(src):                                   # one bit in eight flipped
+        return src ^ (rand(src.shape[0]) & rand(src.shape[0]) & rand(src.shape[0]))
+    proto = rand(1024)
+    base = noisy(proto[torch.randint(0, 1024, (n,), generator=g, device=dev)])
+    flat = zvec_amd.HipFlatSearcher(args.bits, "Hamming", dtype="binary32")
+    se = zvec_amd.HipHammingIVFSearcher(args.bits, dtype="binary32")
+    torch.cuda.synchronize()
+    assert flat.add_batch_dev(base.data_ptr(), n) == 0
+    t0 = time.perf_counter()
+    assert se.build_dev(base.data_ptr(), n, args.nlist, kmeans_iters=args.kmeans_iters) == 0
+    build_s = time.perf_counter() - t0
+    ctx = se.create_context()
+    row_bytes = (words + 3) // 4 * 16
+    ts = torch.cuda.Stream(device=dev)
+    ts.wait_stream(torch.cuda.current_stream(dev))
+    stream = ts.cuda_stream
+    legs = []
+    for batch in (1, 256, 1024):
+        q = noisy(base[torch.randint(0, n, (batch,), generator=g, device=dev)])
+        out = [(torch.empty((batch, k), dtype=torch.int64, device=dev), torch.empty((batch, k), dtype=torch.float32, device=dev),
+                torch.empty((batch,), dtype=torch.int32, device=dev)) for _ in range(2)]
+        (fk, fs, fc), (ik, is_, ic) = out
+        torch.cuda.synchronize()
+        flat_ms = _timed(torch, ts, args.steps, args.warmup, lambda: flat.search_dev(
+            q.data_ptr(), batch, k, fk.data_ptr(), fs.data_ptr(), fc.data_ptr(), ctx, stream=stream))
+        for nprobe in (8, 32, 128):
+            ms = _timed(torch, ts, args.steps, args.warmup, lambda: se.search_dev(
+                q.data_ptr(), batch, k, nprobe, 0xffffffff, ik.data_ptr(), is_.data_ptr(), ic.data_ptr(), ctx, stream=stream))
+            _, _, scanned = se.last_probes(ctx, batch, nprobe)
+            hit = (is_ <= fs[:, k - 1:k]) & (torch.arange(k, device=dev)[None, :] < ic[:, None])
+            legs.append({"batch": batch, "nprobe": nprobe, "ms_per_step": ms, "qps": batch / ms * 1e3, "flat_ms_per_step": flat_ms,
+                         "flat_qps": batch / flat_ms * 1e3, "recall_at_k": float(hit.sum()) / (batch * k),
+                         "probed_bytes": float(scanned.astype(np.float64).sum()) * row_bytes})
+    del base
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for leg in legs:
+        leg["stream_bound_ms"] = leg["probed_bytes"] / (gbs.value * 1e9) * 1e3
+        leg["stream_fraction"] = leg["stream_bound_ms"] / leg["ms_per_step"]
+    res = {"workload": "hamming ivf %d x %d bits, nlist=%d, k=%d" % (n, args.bits, args.nlist, k), "build_seconds": build_s,
+           "kmeans_iters": args.kmeans_iters, "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup,
            "legs": legs}
     print(json.dumps(res))
     if args.out:

@@ -36,7 +36,7 @@ class Segment(C.Structure):
 
 ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 
-# ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes only)
+# ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes and zvec_hip_bivf_*)
 DT_FP32, DT_FP16, DT_BINARY32, DT_BINARY64 = 0, 1, 2, 3
 METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING = 0, 1, 2, 3
 # ZVEC_HIP_IVF_ROUTE_*
@@ -130,6 +130,19 @@ SYMBOLS = {
     "zvec_hip_ivf_add_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, _u32p, _u64p, C.c_uint64, C.c_void_p]),
     "zvec_hip_ivf_end_lists": (C.c_int, [_h]),
     "zvec_hip_ivf_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p]),
+    "zvec_hip_bivf_create": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_bivf_destroy": (C.c_int, [_h]),
+    "zvec_hip_bivf_load": (C.c_int, [_h, C.c_void_p, C.c_uint32, _u64p, C.c_void_p, _u64p]),
+    "zvec_hip_bivf_build": (C.c_int, [_h, C.c_void_p, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "zvec_hip_bivf_build_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "zvec_hip_bivf_info": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "zvec_hip_bivf_export": (C.c_int, [_h, C.c_void_p, _u64p, _u64p]),
+    "zvec_hip_bivf_get_vectors": (C.c_int, [_h, _u64p, C.c_uint64, C.c_void_p]),
+    "zvec_hip_bivf_search": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _u64p, _u64p, _f32p,
+                                       _u32p]),
+    "zvec_hip_bivf_search_dev": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _u64p, _u64p,
+                                           _f32p, _u32p, C.c_void_p]),
+    "zvec_hip_bivf_last_probes": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, _u32p]),
     "zvec_hip_merge_topk": (C.c_int, [_h, _u64p, _f32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                       _u64p, _f32p, _u32p]),
     "zvec_hip_merge_topk_dev": (C.c_int, [_h, _u64p, _f32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,

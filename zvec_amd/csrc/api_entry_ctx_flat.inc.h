@@ -56,6 +56,11 @@ int zvec_hip_set_option(const char *name, int value) {
     ropts().sparse_inverted_build = value;
     return 0;
   }
+  if (strcmp(name, "bivf_part_bytes") == 0) {
+    if (value < 1024 || value > (1 << 30)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    ropts().bivf_part_bytes = value;
+    return 0;
+  }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 int zvec_hip_get_option(const char *name, int *value) {
@@ -66,6 +71,7 @@ int zvec_hip_get_option(const char *name, int *value) {
   if (strcmp(name, "scan256") == 0) { *value = ropts().scan256; return 0; }
   if (strcmp(name, "sparse_group_rows") == 0) { *value = ropts().sparse_group_rows; return 0; }
   if (strcmp(name, "sparse_inverted_build") == 0) { *value = ropts().sparse_inverted_build; return 0; }
+  if (strcmp(name, "bivf_part_bytes") == 0) { *value = ropts().bivf_part_bytes; return 0; }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 

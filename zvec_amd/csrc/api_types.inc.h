@@ -144,6 +144,9 @@ struct RuntimeOpts {
   // how a stale term-major twin of a sparse index is rebuilt: 1 = on the device (zvk_sparse_invb.hip.h), 0 = on the host (the
   // reference of the device build: the same bytes).  Read when a build starts.  DESIGN §3b "Inverted lists"
   std::atomic<int> sparse_inverted_build{1};
+  // Hamming IVF search (api_entry_hamming_ivf.inc.h): the partial lists of one slice of a batch stay within this many bytes; a batch
+  // that needs more goes in slices of queries.  1 GiB like dense_sub_batch; tests lower it to reach a second slice at small shapes.
+  std::atomic<int> bivf_part_bytes{1 << 30};
   RuntimeOpts() {
     if (const char *e = getenv("ZVEC_HIP_SCAN256")) scan256 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("ZVEC_HIP_WAIT")) wait = std::max(0, std::min(2, atoi(e)));
@@ -432,6 +435,11 @@ struct zvec_hip_ctx_s {
   PinnedBuf sp_pin;                                    // ... its pinned source, and the event behind its last upload
   hipEvent_t sp_ev = nullptr;
   DevBuf sp_ing, sp_ing_pairs;                         // dense rows -> CSR: counts, offsets and status | the pairs (api_entry_sparse_ingest.inc.h)
+  // Hamming IVF (api_entry_hamming_ivf.inc.h): probe lists [count][np] | probed lists [count] | rows scanned [count] of the last
+  // search, kept for zvec_hip_bivf_last_probes; the plan arrays of its current slice
+  DevBuf bivf_probe, bivf_plan;
+  const void *bivf_owner = nullptr;                    // the index of that search
+  uint32_t bivf_count = 0, bivf_np = 0;
   DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)

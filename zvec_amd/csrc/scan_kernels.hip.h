@@ -33,6 +33,7 @@
 #include "zvk_build.hip.h"
 #include "zvk_group.hip.h"
 #include "zvk_hamming.hip.h"
+#include "zvk_hamming_ivf.hip.h"
 #include "zvk_sparse.hip.h"
 #include "zvk_sparse_inv.hip.h"
 #include "zvk_sparse_invb.hip.h"

@@ -58,9 +58,11 @@ __host__ __device__ inline size_t ham_lds_bytes(uint32_t k) { return ((size_t)HA
 // CH chunks of both rows of the lane against every query of the block.  The words of query j + 1 are fetched (scalar loads) in
 // front of the popcounts of query j; the uniform guards keep the fetches of the queries after that from being scheduled early too,
 // which would take 16 SGPRs per query.
-template <int CH>
+// INDIRECT (the list scan, zvk_hamming_ivf.hip.h): query j of the block does not start at chunk j * qstride of `q` but at the chunk
+// lane j of `qv` names — a v_readlane away from a scalar, so nothing else changes.
+template <int CH, bool INDIRECT = false>
 __device__ __forceinline__ void ham_accumulate(const uint32_t *tile, ham_qptr q, uint32_t qstride, uint32_t c0, uint32_t nqb, int lane,
-                                               uint32_t (&acc)[HAM_QB][2]) {
+                                               uint32_t (&acc)[HAM_QB][2], uint32_t qv = 0) {
   // (the query words do not depend on the tile: without this the compiler hoists the loads of the last chunks of all 32 queries
   // out of the tile loop, into SGPRs that do not exist)
   asm volatile("" : "+s"(c0), "+s"(nqb));        // (nqb: the 32 guards below are compared where they branch, not kept in 64 SGPRs)
@@ -70,14 +72,18 @@ __device__ __forceinline__ void ham_accumulate(const uint32_t *tile, ham_qptr q,
     const uint32_t *p = tile + (size_t)(c0 + c) * (TILE_N * 4) + lane * 4;
     r0[c] = *reinterpret_cast<const u32x4 *>(p);
     r1[c] = *reinterpret_cast<const u32x4 *>(p + 64 * 4);
-    cur[c] = q[c0 + c];
+    if constexpr (INDIRECT) cur[c] = q[bcast_u(qv, 0) + c0 + c];
+    else cur[c] = q[c0 + c];
   }
 #pragma unroll
   for (int j = 0; j < HAM_QB; ++j) {
     if ((uint32_t)j < nqb) {                       // (uniform)
       const uint32_t jn = min((uint32_t)j + 1, nqb - 1);
 #pragma unroll
-      for (int c = 0; c < CH; ++c) nxt[c] = q[(size_t)jn * qstride + c0 + c];
+      for (int c = 0; c < CH; ++c) {
+        if constexpr (INDIRECT) nxt[c] = q[bcast_u(qv, (int)jn) + c0 + c];
+        else nxt[c] = q[(size_t)jn * qstride + c0 + c];
+      }
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
 #pragma unroll

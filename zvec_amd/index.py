@@ -1592,6 +1592,157 @@ class HipIVFSearcher:
 HipIVFStreamer = HipIVFSearcher
 
 
+class HipHammingIVFSearcher:
+    """Binary rows under the Hamming metric through inverted lists (zvec_hip_bivf_*): what IVFStreamer / IVFSearcher are over a
+    binary meta (ivf_streamer.cc:183-250 never looks at the data type).  Shaped like HipIVFSearcher; dim counts bits, rows are
+    dim // 32 uint32 ("binary32") or dim // 64 uint64 ("binary64") words."""
+
+    def __init__(self, dim, device=0, dtype="binary32", scan_ratio=0.1, brute_force_threshold=1000):
+        self.dim = int(dim)
+        self.metric = METRIC_HAMMING
+        self.device = device
+        self.dtype, self.np_dtype = _dtype_of(dtype)
+        self.row_words = _row_words(self.dim, self.dtype)
+        self.scan_ratio = float(scan_ratio)
+        self.brute_force_threshold = int(brute_force_threshold)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().zvec_hip_bivf_create(self.dim, self.dtype, device, C.byref(self._h)), "zvec_hip_bivf_create")
+        self._list_keys = None
+        self._orig_keys = None
+        self.total_count = 0
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().zvec_hip_bivf_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def create_context(self):
+        return IndexContext(self.device)
+
+    def _loaded(self, rc, n, keys):
+        if rc == 0:
+            self.total_count = int(n)
+            self._orig_keys = keys
+            self._list_keys = None
+        return rc
+
+    def load(self, centroids, list_offsets, rows, keys=None):
+        cent = np.ascontiguousarray(centroids, self.np_dtype)
+        lo = np.ascontiguousarray(list_offsets, np.uint64)
+        rows = np.ascontiguousarray(rows, self.np_dtype)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        if cent.ndim != 2 or cent.shape[1] != self.row_words or lo.size != cent.shape[0] + 1 or rows.size != int(lo[-1]) * self.row_words:
+            return IndexError_.InvalidArgument
+        rc = _lib.lib().zvec_hip_bivf_load(self._h, _np_ptr(cent), cent.shape[0], _np_ptr(lo), _np_ptr(rows), _np_ptr(k))
+        # (keys are given per list-order position: keys_in_list_order is them, or the positions)
+        return self._loaded(rc, lo[-1], None if k is None else ("list", k))
+
+    def build(self, rows, nlist, keys=None, kmeans_iters=10, seed=20260320):
+        rows = np.ascontiguousarray(rows, self.np_dtype)
+        if rows.ndim != 2 or rows.shape[1] != self.row_words:
+            return IndexError_.InvalidArgument
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        rc = _lib.lib().zvec_hip_bivf_build(self._h, _np_ptr(rows), rows.shape[0], _np_ptr(k), int(nlist), int(kmeans_iters), int(seed))
+        return self._loaded(rc, rows.shape[0], None if k is None else ("row", k))
+
+    def build_dev(self, d_rows, n, nlist, keys=None, kmeans_iters=10, seed=20260320, stream=None):
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        rc = _lib.lib().zvec_hip_bivf_build_dev(self._h, C.c_void_p(d_rows), int(n), _np_ptr(k), int(nlist), int(kmeans_iters), int(seed),
+                                                C.c_void_p(stream) if stream else None)
+        return self._loaded(rc, n, None if k is None else ("row", k))
+
+    def info(self):
+        n = C.c_uint64(0)
+        nl = C.c_uint32(0)
+        _lib.check(_lib.lib().zvec_hip_bivf_info(self._h, C.byref(n), C.byref(nl)), "zvec_hip_bivf_info")
+        return int(n.value), int(nl.value)
+
+    def export(self):
+        """centroids [nlist][words], list_offsets [nlist + 1], row_ids [count] (original row of every list-order position)"""
+        n, nlist = self.info()
+        cent = np.zeros((nlist, self.row_words), self.np_dtype)
+        lo = np.zeros(nlist + 1, np.uint64)
+        rows = np.zeros(n, np.uint64)
+        _lib.check(_lib.lib().zvec_hip_bivf_export(self._h, _np_ptr(cent), _np_ptr(lo), _np_ptr(rows)), "zvec_hip_bivf_export")
+        return cent, lo, rows
+
+    def get_vectors_by_ids(self, list_positions):
+        pos = np.ascontiguousarray(list_positions, np.uint64)
+        out = np.zeros((pos.size, self.row_words), self.np_dtype)
+        _lib.check(_lib.lib().zvec_hip_bivf_get_vectors(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_bivf_get_vectors")
+        return out
+
+    def keys_in_list_order(self):
+        if self._list_keys is None:
+            _, _, rows = self.export()
+            if self._orig_keys is None:
+                self._list_keys = rows
+            else:
+                kind, k = self._orig_keys
+                self._list_keys = k if kind == "list" else k[rows.astype(np.int64)]
+        return self._list_keys
+
+    def _vectors_of_keys(self, keys):
+        lk = self.keys_in_list_order()
+        order = np.argsort(lk, kind="stable")
+        return self.get_vectors_by_ids(order[np.searchsorted(lk[order], keys)])
+
+    # IVFSearcherContext::update (ivf_searcher_context.h:61-79)
+    def probe_params(self, ctx=None):
+        ratio = self.scan_ratio if ctx is None or ctx._scan_ratio is None else ctx._scan_ratio
+        bft = self.brute_force_threshold if ctx is None or ctx._bf_threshold is None else ctx._bf_threshold
+        return ivf_probe_params(self.info()[1], self.total_count, ratio, bft)
+
+    def set_nprobe(self, nprobe, exact=True):
+        """as HipIVFSearcher.set_nprobe: scan_ratio = nprobe / nlist; exact=True keeps max_scan_count from cutting the probe loop"""
+        self.scan_ratio = float(np.float32(nprobe) / np.float32(max(self.info()[1], 1)))
+        if exact:
+            self.brute_force_threshold = max(self.total_count - 1, 0)
+
+    def search_impl(self, query, count, ctx, nprobe=None, max_scan=None):
+        """IndexRunner::search_impl over the probed lists; nprobe / max_scan default to probe_params(ctx)"""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(query, self.np_dtype).reshape(-1)
+        if q.size != int(count) * self.row_words:
+            return IndexError_.InvalidArgument
+        k = ctx.topk()
+        pp = self.probe_params(ctx) if nprobe is None or max_scan is None else (nprobe, max_scan)
+        nprobe = pp[0] if nprobe is None else nprobe
+        max_scan = pp[1] if max_scan is None else max_scan
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        counts = np.zeros(count, np.uint32)
+        if ctx._exclude is not None:
+            ex = ctx._exclude
+        else:
+            ex = ctx._exclude_for(self.keys_in_list_order()) if ctx._filter_fn else None
+        rc = _lib.lib().zvec_hip_bivf_search(self._h, ctx._h, _np_ptr(q), count, k, ctx.threshold(), int(nprobe), int(max_scan),
+                                             _np_ptr(ex), _np_ptr(keys), _np_ptr(scores), _np_ptr(counts))
+        if rc == 0:
+            ctx._set_results(keys, scores, counts, self._vectors_of_keys)
+        return rc
+
+    def search_dev(self, d_queries, count, topk, nprobe, max_scan, d_out_keys, d_out_scores, d_out_counts, ctx, threshold=FLT_MAX,
+                   d_exclude=None, stream=None):
+        return _lib.lib().zvec_hip_bivf_search_dev(
+            self._h, ctx._h, C.c_void_p(d_queries), count, topk, threshold, nprobe, max_scan, C.c_void_p(d_exclude) if d_exclude else None,
+            C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
+
+    def last_probes(self, ctx, count, nprobe):
+        """(probe_idx [count][min(nprobe, nlist)], probe_cnt [count], scanned [count]) of the last search of this index on ctx,
+        which was made with this nprobe"""
+        idx = np.zeros((count, min(int(nprobe), self.info()[1])), np.uint32)
+        cnt = np.zeros(count, np.uint32)
+        scanned = np.zeros(count, np.uint32)
+        _lib.check(_lib.lib().zvec_hip_bivf_last_probes(self._h, ctx._h, count, _np_ptr(idx), _np_ptr(cnt), _np_ptr(scanned)),
+                   "zvec_hip_bivf_last_probes")
+        return idx, cnt, scanned
+
+
 def container_segments(image, checksum=False):
     """segment table of a dumped index FILE image (zvec_hip_container_segments): {id: (offset, size)} in file order"""
     image = bytes(image)
