@@ -419,6 +419,67 @@ int zvec_hip_bivf_search_dev(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, const void *
 int zvec_hip_bivf_last_probes(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *probe_idx, uint32_t *probe_cnt,
                               uint32_t *scanned);
 
+/* ---- Hamming IVF fed with fp32: rows kept in list order, candidates re-ranked on them ------------------------
+ * The reference's pipeline for a binary index over fp32 documents is BinaryConverter on the rows (src/core/quantizer/
+ * binary_converter.cc:25-128) -> IVFBuilder (ivf_builder.cc:212-403) -> BinaryReformer on every query (binary_reformer.cc:46-68) ->
+ * IVFStreamer::search_impl (ivf_streamer.cc:183-250); a deployment then re-scores the survivors on the original values.  A
+ * ZVEC_HIP_DT_BINARY32 handle of 32 * ceil(dim / 32) bits may own the documents' fp32 rows, row-major [count][dim] in LIST ORDER (row
+ * p is the document at list-order position p), and a re-score metric, ZVEC_HIP_METRIC_L2 or ZVEC_HIP_METRIC_IP.  The rows cost
+ * dim * 4 bytes per document, 32 times the dim / 8 bytes of its bits.  destroy, and the next load or build of any kind, free them;
+ * a handle that never sees these calls is unchanged.  Every entry: Mismatch (-24) for a DT_BINARY64 handle (the converter never
+ * emits one, binary_converter.cc:100-102) or another width, Unsupported (-12) for a metric other than L2 / IP, InvalidArgument (-31)
+ * for dim == 0 or dim > 2^20. */
+/* zvec_hip_binary_encode_dev of the rows (encode_dims = dim: bit i = rows[i] >= bin_threshold), zvec_hip_bivf_build of those bits
+ * — the same arguments give the same index as the plain build of the same bits —, and the fp32 rows gathered into list order on
+ * the device with the build's packing permutation.  rows: host, [n][dim]; keys: host, NULL -> the original row number.  A refused
+ * call leaves the handle as it was; everything the fp32 side needs is allocated before the index is touched, and a failure after
+ * that point leaves the handle without an index, as one of zvec_hip_bivf_build does. */
+int zvec_hip_bivf_build_fp32(zvec_hip_bivf_t h, const float *rows, uint64_t n, uint32_t dim, int metric, const uint64_t *keys,
+                             uint32_t nlist, uint32_t kmeans_iters, uint64_t seed, float bin_threshold);
+/* the same from DEVICE rows; keys stay a host array.  Returns after the index is complete. */
+int zvec_hip_bivf_build_fp32_dev(zvec_hip_bivf_t h, const float *d_rows, uint64_t n, uint32_t dim, int metric, const uint64_t *keys,
+                                 uint32_t nlist, uint32_t kmeans_iters, uint64_t seed, float bin_threshold, void *stream);
+/* for a handle filled by zvec_hip_bivf_load or the plain build (what IVFSearcher::load leaves, ivf_index_format.h:26-60): rows is
+ * [count][dim], ALREADY in list order (zvec_hip_bivf_export's row_ids maps a build's positions to the original rows), and is copied
+ * in; calling it again replaces the rows, and a failed call keeps the old ones.  The bits of the index are NOT re-derived from the
+ * rows and NOT checked against them: the caller vouches that row p belongs to the bits at position p.  NoIndexLoaded (-204) before
+ * load / build.  The _dev form copies from device memory on `stream` (NULL: the handle's) and returns after the copy. */
+int zvec_hip_bivf_attach_rows(zvec_hip_bivf_t h, const float *rows, uint32_t dim, int metric);
+int zvec_hip_bivf_attach_rows_dev(zvec_hip_bivf_t h, const float *d_rows, uint32_t dim, int metric, void *stream);
+/* the fp32 rows of the listed list-order positions, out: host [n][dim] (IVFEntity::get_vector addresses rows the same way,
+ * ivf_entity.cc:587-716); NoExist (-22) beyond the count, NoReady (-21) when the handle holds no rows */
+int zvec_hip_bivf_get_rows(zvec_hip_bivf_t h, const uint64_t *list_positions, uint64_t n, float *out);
+/* dim (0: no rows), the re-score metric and the bytes of the array; any pointer may be NULL */
+int zvec_hip_bivf_rows_info(zvec_hip_bivf_t h, uint32_t *dim, int *metric, uint64_t *bytes);
+/* BinaryReformer::transform of every query (binary_reformer.cc:46-68: all `dim` values against bin_threshold, as
+ * zvec_hip_flat_search_fp32), then two stages that both stay on the device.
+ *   Stage 1: zvec_hip_bivf_search's chain (ivf_streamer.cc:183-250) with kc = min(topk * refine, 128) and no radius; nprobe,
+ *   max_scan_count and exclude_bitset (over list-order positions) mean what they mean there.  Its result — list-order positions and
+ *   Hamming scores, ascending — stays in the context; which of several equal Hamming scores sit at the kc-th place is unspecified.
+ *   Stage 2: every candidate is re-scored on its fp32 row: L2 = the fp32 sum of (q_i - b_i)^2, the difference rounded once, each
+ *   step an fma; IP = minus the fp32 sum of q_i * b_i; the order of the sum is the library's, values must be finite.  The topk best
+ *   by the pair (fp32 score, rank in stage 1's list) are written ascending — a tie in the fp32 score has one answer given the
+ *   candidates — and a document with score > threshold is dropped: the radius applies to the fp32 score only.  out_counts[q] can be
+ *   below topk (short probed lists, the radius); ONLY the first out_counts[q] entries of a query's output rows are written.
+ * Checked before any output is touched: InvalidArgument (-31) for topk, refine or nprobe == 0; Unsupported (-12) for topk > 128;
+ * NoIndexLoaded (-204); NoReady (-21) when the handle holds no rows; Mismatch (-24) when dim differs from the rows'; Unsupported
+ * for dim > 16128 — a work-group keeps its query in LDS, and 63 KiB of query plus the 528 bytes of scores behind it is what a
+ * launch may take without a raised limit.  Batches are sliced under "bivf_part_bytes" as zvec_hip_bivf_search slices them; a slice
+ * runs both stages.  keys come from the handle's key column. */
+int zvec_hip_bivf_search_fp32(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t count, uint32_t dim, uint32_t topk,
+                              uint32_t refine, float threshold, float bin_threshold, uint32_t nprobe, uint32_t max_scan_count,
+                              const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+int zvec_hip_bivf_search_fp32_dev(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t count, uint32_t dim,
+                                  uint32_t topk, uint32_t refine, float threshold, float bin_threshold, uint32_t nprobe,
+                                  uint32_t max_scan_count, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
+                                  float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* stage 1 of the last zvec_hip_bivf_search_fp32[_dev] of this index on ctx, which ran with this kc = min(topk * refine, 128):
+ * positions [count][kc] list-order positions ascending by Hamming score, hamming_scores [count][kc], counts [count] the candidates
+ * of each query (entries beyond them are unspecified).  Host arrays, nullable; waits for the context's stream.  NoReady (-21)
+ * without such a search. */
+int zvec_hip_bivf_last_candidates(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t kc, uint32_t *positions,
+                                  float *hamming_scores, uint32_t *counts);
+
 /* ---- partial top-k merge ------------------------------------------------------------------
  * CombinedVectorColumnIndexer::Search concat + sort + truncate
  * (src/db/index/column/vector_column/combined_vector_column_indexer.cc:91-232); also the merge

@@ -20,6 +20,13 @@ over the box's streaming figure, and the build time.  The rows are 1024 random p
 that there is something to cluster.  Reported, not gated.
 
     python tools/hamming_bench.py --ivf [--out profiles/hamming_ivf.json]
+
+--ivf --from-fp32 generates the --ivf corpus as fp32 (1024 normal prototypes plus noise that flips one sign in eight), builds it with
+zvec_hip_bivf_build_fp32_dev and times search_fp32 at batches 1 / 256 / 1024, k = 10, refine 1 / 2 / 4 / 8 / 12: QPS, recall@10
+against an exact fp32 flat search of the same rows, and the re-rank's time (the fp32 search minus the bit-fed search at topk = kc,
+which also holds the query encoder) beside the bound its gathered bytes set at the box's streaming figure.  Reported, not gated.
+
+    python tools/hamming_bench.py --ivf --from-fp32 [--out profiles/hamming_ivf_fp32.json]
 """
 import argparse
 import ctypes as C
@@ -42,7 +49,10 @@ def main():
     ap.add_argument("--ivf", action="store_true", help="the rows through inverted lists next to the flat scan (zvec_hip_bivf_*)")
     ap.add_argument("--nlist", type=int, default=1024)
     ap.add_argument("--kmeans-iters", type=int, default=5)
+    ap.add_argument("--nprobe", type=int, default=32, help="--ivf --from-fp32: lists probed")
     args = ap.parse_args()
+    if args.ivf and args.from_fp32:
+        return ivf_fp32(args)
     if args.from_fp32:
         return from_fp32(args)
     if args.ivf:
@@ -258,6 +268,76 @@ def ivf(args):
     res = {"workload": "hamming ivf %d x %d bits, nlist=%d, k=%d" % (n, args.bits, args.nlist, k), "build_seconds": build_s,
            "kmeans_iters": args.kmeans_iters, "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup,
            "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def ivf_fp32(args):
+    import time
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    n, dim, k = args.n, args.bits, args.topk
+    words = (dim + 31) // 32
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    sigma = 0.41421356                                # tan(pi / 8): one sign in eight flips, as one bit in eight of --ivf
+
+    def noisy(src):
+        return src + sigma * torch.randn(src.shape, generator=g, device=dev, dtype=torch.float32)
+    proto = torch.randn((1024, dim), generator=g, device=dev, dtype=torch.float32)
+    base = noisy(proto[torch.randint(0, 1024, (n,), generator=g, device=dev)])
+    exact = zvec_amd.HipFlatSearcher(dim, "SquaredEuclidean")
+    se = zvec_amd.HipHammingIVFSearcher(words * 32, dtype="binary32")
+    torch.cuda.synchronize()
+    assert exact.add_batch_dev(base.data_ptr(), n) == 0
+    t0 = time.perf_counter()
+    assert se.build_fp32_dev(base.data_ptr(), n, dim, args.nlist, "SquaredEuclidean", kmeans_iters=args.kmeans_iters) == 0
+    build_s = time.perf_counter() - t0
+    del base                                          # (both indexes hold their copy)
+    ctx, ectx = se.create_context(), exact.create_context()
+    ts = torch.cuda.Stream(device=dev)
+    ts.wait_stream(torch.cuda.current_stream(dev))
+    stream = ts.cuda_stream
+    nprobe = args.nprobe
+    legs = []
+    for batch in (1, 256, 1024):
+        q = noisy(proto[torch.randint(0, 1024, (batch,), generator=g, device=dev)])
+        qw = torch.empty((batch, words), dtype=torch.int32, device=dev)
+        ek, es, ec = (torch.empty((batch, k), dtype=torch.int64, device=dev), torch.empty((batch, k), dtype=torch.float32, device=dev),
+                      torch.empty((batch,), dtype=torch.int32, device=dev))
+        rk, rs, rc_ = torch.full_like(ek, -1), torch.empty_like(es), torch.empty_like(ec)
+        torch.cuda.synchronize()
+        assert exact.search_dev(q.data_ptr(), batch, k, ek.data_ptr(), es.data_ptr(), ec.data_ptr(), ectx, stream=stream) == 0
+        ctx.binary_encode_dev(q.data_ptr(), batch, dim, qw.data_ptr(), stream=stream)
+        for refine in (1, 2, 4, 8, 12):
+            kc = min(k * refine, 128)
+            hk, hs = torch.empty((batch, kc), dtype=torch.int64, device=dev), torch.empty((batch, kc), dtype=torch.float32, device=dev)
+            rk.fill_(-1)
+            ms = _timed(torch, ts, args.steps, args.warmup, lambda: se.search_fp32_dev(
+                q.data_ptr(), dim, batch, k, refine, nprobe, 0xffffffff, rk.data_ptr(), rs.data_ptr(), rc_.data_ptr(), ctx, stream=stream))
+            hit = (rk[:, :, None] == ek[:, None, :]).any(dim=2) & (torch.arange(k, device=dev)[None, :] < rc_[:, None])
+            # stage 1 alone at the same width: the bit-fed search with topk = kc; the difference is the encoder plus the re-rank
+            ms_bits = _timed(torch, ts, args.steps, args.warmup, lambda: se.search_dev(
+                qw.data_ptr(), batch, kc, nprobe, 0xffffffff, hk.data_ptr(), hs.data_ptr(), rc_.data_ptr(), ctx, stream=stream))
+            legs.append({"batch": batch, "refine": refine, "kc": kc, "nprobe": nprobe, "ms_per_step": ms, "qps": batch / ms * 1e3,
+                         "recall_at_k": float(hit.sum()) / (batch * k), "stage1_ms_per_step": ms_bits,
+                         "rerank_ms_estimate": ms - ms_bits, "gathered_bytes": float(batch) * kc * dim * 4})
+    del exact
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for leg in legs:
+        leg["rerank_stream_bound_ms"] = leg["gathered_bytes"] / (gbs.value * 1e9) * 1e3
+    res = {"workload": "hamming ivf fed with fp32: %d x %d values, nlist=%d, nprobe=%d, k=%d, re-ranked by squared L2" % (n, dim, args.nlist, nprobe, k),
+           "build_seconds": build_s, "kmeans_iters": args.kmeans_iters, "rows_bytes": float(n) * dim * 4, "stream_gbs": gbs.value,
+           "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:

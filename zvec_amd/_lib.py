@@ -143,6 +143,19 @@ SYMBOLS = {
     "zvec_hip_bivf_search_dev": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, _u64p, _u64p,
                                            _f32p, _u32p, C.c_void_p]),
     "zvec_hip_bivf_last_probes": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, _u32p]),
+    "zvec_hip_bivf_build_fp32": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, _u64p, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_float]),
+    "zvec_hip_bivf_build_fp32_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, _u64p, C.c_uint32, C.c_uint32, C.c_uint64,
+                                               C.c_float, C.c_void_p]),
+    "zvec_hip_bivf_attach_rows": (C.c_int, [_h, C.c_void_p, C.c_uint32, C.c_int]),
+    "zvec_hip_bivf_attach_rows_dev": (C.c_int, [_h, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "zvec_hip_bivf_get_rows": (C.c_int, [_h, _u64p, C.c_uint64, C.c_void_p]),
+    "zvec_hip_bivf_rows_info": (C.c_int, [_h, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "zvec_hip_bivf_search_fp32": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                            C.c_uint32, C.c_uint32, _u64p, _u64p, _f32p, _u32p]),
+    "zvec_hip_bivf_search_fp32_dev": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                                C.c_uint32, C.c_uint32, _u64p, _u64p, _f32p, _u32p, C.c_void_p]),
+    "zvec_hip_bivf_last_candidates": (C.c_int, [_h, _h, C.c_uint32, C.c_uint32, _u32p, _f32p, _u32p]),
     "zvec_hip_merge_topk": (C.c_int, [_h, _u64p, _f32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                       _u64p, _f32p, _u32p]),
     "zvec_hip_merge_topk_dev": (C.c_int, [_h, _u64p, _f32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,

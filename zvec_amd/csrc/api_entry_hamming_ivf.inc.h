@@ -16,6 +16,9 @@ struct zvec_hip_bivf_s {
   std::vector<uint64_t> h_off;         // ... on the host (export)
   std::vector<uint64_t> h_row_ids;     // original row of every position (build); empty: the identity (load)
   std::vector<uint32_t> h_cent;        // [nlist][words]
+  Scoped<float> frows;                 // optional: the documents' fp32 rows [count][fdim] in list order (zvec_hip_bivf_build_fp32 / _attach_rows)
+  uint32_t fdim = 0;                   // ... their dimension (0: no rows) and the metric of the re-score (L2 or IP)
+  int fmetric = 0;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;                  // searches hold it shared, load and build exclusive (as zvec_hip_flat_s); a context's mutex is taken first
@@ -106,12 +109,15 @@ struct BivfWrite {
   void clear_rows() {
     h->lists.release();
     h->lists.n = 0;
+    h->frows.release();                  // (the fp32 rows belong to the rows that go)
+    h->fdim = 0;
   }
   int done(int rc, hipStream_t s) {
     const hipError_t he = hipStreamSynchronize(s);
     if (rc == 0 && he != hipSuccess) rc = ZVEC_HIP_ERR_RUNTIME;
     h->loaded = rc == 0;
     h->defctx->bivf_count = 0;
+    h->defctx->bivf_cand_count = 0;
     return rc;
   }
 
@@ -191,8 +197,9 @@ static std::vector<uint64_t> bivf_initial_rows(uint64_t n, uint32_t nlist, uint6
 }
 
 // the build proper: plain DEVICE rows -> centroids, labels, packed lists.  The caller holds the write scope.
+// perm_out: receives the packing permutation on the device (list-order position -> original row)
 static int bivf_build_locked(BivfWrite &w, const void *d_rows, uint64_t n, const uint64_t *keys, uint32_t nlist, uint32_t iters,
-                             uint64_t seed, hipStream_t s) {
+                             uint64_t seed, hipStream_t s, Scoped<uint64_t> *perm_out = nullptr) {
   zvec_hip_bivf_s *h = w.h;
   zvec_hip_ctx_s *c = h->defctx;
   const uint32_t words = h->lists.bin_words(), dim = words * 32;
@@ -255,6 +262,7 @@ static int bivf_build_locked(BivfWrite &w, const void *d_rows, uint64_t n, const
   h->lists.n = n;
   ZCHK(hipStreamSynchronize(s));         // (the tables are locals)
   h->h_row_ids = std::move(perm);
+  if (perm_out) *perm_out = std::move(d_perm);
   return 0;
 }
 
@@ -346,22 +354,54 @@ static BivfSlices bivf_slices(uint32_t count, uint32_t np, uint32_t topk, uint32
   return b;
 }
 
-// the search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments
+// Stage 2 of zvec_hip_bivf_search_fp32: what the caller asked for, while the search proper runs with topk = kc and no radius.  The
+// outputs of the search proper are then the caller's, [count][topk] long.
+struct BivfRerank {
+  const float *d_queries;       // [count][dim] fp32
+  uint32_t dim, topk;
+  float threshold;
+};
+
+// the candidate arrays of a re-ranked search inside c->bivf_cand: the scratch keys of one slice in front (8-byte aligned)
+struct BivfCand {
+  uint64_t *keys;
+  uint32_t *pos;
+  float *scores;
+  uint32_t *counts;
+};
+static BivfCand bivf_cand_arrays(const zvec_hip_ctx_s *c, uint32_t count, uint32_t kc, uint32_t slice) {
+  BivfCand b;
+  b.keys = c->bivf_cand.as<uint64_t>();
+  b.pos = reinterpret_cast<uint32_t *>(b.keys + (size_t)slice * kc);
+  b.scores = reinterpret_cast<float *>(b.pos + (size_t)count * kc);
+  b.counts = reinterpret_cast<uint32_t *>(b.scores + (size_t)count * kc);
+  return b;
+}
+
+// the search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments.  rr: the merge of every slice keeps
+// list-order positions and Hamming scores in the context, and bivf_rerank_kernel writes the slice's outputs from them.
 static int bivf_search_dev_locked(zvec_hip_bivf_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk,
                                   float threshold, uint32_t nprobe, uint32_t max_scan_count, const uint64_t *d_exclude,
-                                  uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, hipStream_t s) {
+                                  uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, hipStream_t s,
+                                  const BivfRerank *rr = nullptr) {
   const StoreView &st = h->lists;
   const uint32_t nlist = h->nlist, np = std::min(nprobe, nlist);
   c->sh.count = 0;              // (no certify step is pending, no flat route and no fp IVF plan to read back)
   c->route = 0;
   c->ivf_plan.route = 0;
   c->bivf_count = 0;
+  c->bivf_cand_count = 0;
   const int cus = device_cus(c);
   const BivfSlices cutq = bivf_slices(count, np, topk, h->max_tiles, nlist, st.bin_chunks(), cus, (uint64_t)ropts().bivf_part_bytes.load(std::memory_order_relaxed));
   const uint32_t nsplit = cutq.nsplit;
   if ((uint64_t)cutq.slice * np * nsplit >= 0xffffffffull) return ZVEC_HIP_ERR_UNSUPPORTED;       // (slots are 32-bit)
   ZRET(c->bivf_probe.ensure(((size_t)count * np + 2 * (size_t)count) * sizeof(uint32_t)));
   uint32_t *pidx = c->bivf_probe.as<uint32_t>(), *pcnt = pidx + (size_t)count * np, *pscan = pcnt + count;
+  BivfCand cand{};
+  if (rr) {
+    ZRET(c->bivf_cand.ensure((size_t)cutq.slice * topk * 8 + (size_t)count * topk * 8 + (size_t)count * 4));
+    cand = bivf_cand_arrays(c, count, topk, cutq.slice);
+  }
   for (uint32_t q0 = 0; q0 < count; q0 += cutq.slice) {
     const uint32_t m = std::min(cutq.slice, count - q0);
     const uint64_t pairs = (uint64_t)m * np;
@@ -403,12 +443,30 @@ static int bivf_search_dev_locked(zvec_hip_bivf_s *h, zvec_hip_ctx_s *c, const v
     if (a.exclude) hipLaunchKernelGGL(hamming_list_scan_kernel<true>, dim3((unsigned)bound), dim3(64), ham_lds_bytes(topk), s, a);
     else hipLaunchKernelGGL(hamming_list_scan_kernel<false>, dim3((unsigned)bound), dim3(64), ham_lds_bytes(topk), s, a);
     ZCHK(hipGetLastError());
-    const SearchOut out{d_out_keys + (size_t)q0 * topk, d_out_scores + (size_t)q0 * topk, nullptr, d_out_counts + q0};
-    ZRET(launch_merge(merge_partials(a.part_s, a.part_i, np * nsplit, a.gtau, topk, threshold, st.keys, out), m, merge_threads(m), s));
+    if (!rr) {
+      const SearchOut out{d_out_keys + (size_t)q0 * topk, d_out_scores + (size_t)q0 * topk, nullptr, d_out_counts + q0};
+      ZRET(launch_merge(merge_partials(a.part_s, a.part_i, np * nsplit, a.gtau, topk, threshold, st.keys, out), m, merge_threads(m), s));
+      continue;
+    }
+    // stage 1 ends as positions (the merge's key column is scratch), stage 2 re-scores them on the fp32 rows
+    const SearchOut out{cand.keys, cand.scores + (size_t)q0 * topk, cand.pos + (size_t)q0 * topk, cand.counts + q0};
+    ZRET(launch_merge(merge_partials(a.part_s, a.part_i, np * nsplit, a.gtau, topk, threshold, nullptr, out), m, merge_threads(m), s));
+    BivfRerankArgs r{};
+    r.rows = h->frows; r.queries = rr->d_queries + (size_t)q0 * rr->dim; r.cand = out.idx; r.cand_cnt = out.counts; r.keymap = st.keys;
+    r.dim = rr->dim; r.kc = topk; r.topk = rr->topk; r.ip = h->fmetric == ZVEC_HIP_METRIC_IP ? 1u : 0u;
+    r.threshold = std::min(rr->threshold, FLT_MAX);
+    r.out_keys = d_out_keys + (size_t)q0 * rr->topk; r.out_scores = d_out_scores + (size_t)q0 * rr->topk; r.out_counts = d_out_counts + q0;
+    hipLaunchKernelGGL(bivf_rerank_kernel, dim3(m), dim3(256), bivf_rerank_lds_bytes(rr->dim), s, r);
+    ZCHK(hipGetLastError());
   }
   c->bivf_owner = h;
   c->bivf_count = count;
   c->bivf_np = np;
+  if (rr) {
+    c->bivf_cand_count = count;
+    c->bivf_cand_kc = topk;
+    c->bivf_cand_slice = cutq.slice;
+  }
   return 0;
 }
 

@@ -440,6 +440,10 @@ struct zvec_hip_ctx_s {
   DevBuf bivf_probe, bivf_plan;
   const void *bivf_owner = nullptr;                    // the index of that search
   uint32_t bivf_count = 0, bivf_np = 0;
+  // ... and stage 1 of the last zvec_hip_bivf_search_fp32 (zvec_hip_bivf_last_candidates): a slice's scratch keys [slice][kc] u64 |
+  // positions [count][kc] | Hamming scores [count][kc] | counts [count]
+  DevBuf bivf_cand;
+  uint32_t bivf_cand_count = 0, bivf_cand_kc = 0, bivf_cand_slice = 0;
   DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)

@@ -34,6 +34,7 @@
 #include "zvk_group.hip.h"
 #include "zvk_hamming.hip.h"
 #include "zvk_hamming_ivf.hip.h"
+#include "zvk_hamming_rerank.hip.h"
 #include "zvk_sparse.hip.h"
 #include "zvk_sparse_inv.hip.h"
 #include "zvk_sparse_invb.hip.h"

@@ -45,6 +45,7 @@ extern "C" {
 #include "api_entry_filter.inc.h"
 #include "api_entry_binary_quant.inc.h"
 #include "api_entry_hamming_ivf.inc.h"
+#include "api_entry_hamming_ivf_fp32.inc.h"
 #include "api_entry_group.inc.h"
 #include "api_entry_shards.inc.h"
 #include "api_entry_container.inc.h"

@@ -1742,6 +1742,92 @@ class HipHammingIVFSearcher:
                    "zvec_hip_bivf_last_probes")
         return idx, cnt, scanned
 
+    # ---- fed with fp32: rows kept in list order, candidates re-ranked on them (zvec_hip_bivf_*_fp32) ----
+    def build_fp32(self, rows, nlist, metric="SquaredEuclidean", keys=None, kmeans_iters=10, seed=20260320, bin_threshold=0.0):
+        """BinaryConverter + build + the fp32 rows gathered into list order; rows: [n][dim] fp32, self.dim == 32 * ceil(dim / 32)"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2:
+            return IndexError_.InvalidArgument
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        rc = _lib.lib().zvec_hip_bivf_build_fp32(self._h, _np_ptr(rows), rows.shape[0], rows.shape[1], metric_from_name(metric), _np_ptr(k),
+                                                 int(nlist), int(kmeans_iters), int(seed), float(bin_threshold))
+        return self._loaded(rc, rows.shape[0], None if k is None else ("row", k))
+
+    def build_fp32_dev(self, d_rows, n, dim, nlist, metric="SquaredEuclidean", keys=None, kmeans_iters=10, seed=20260320,
+                       bin_threshold=0.0, stream=None):
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        rc = _lib.lib().zvec_hip_bivf_build_fp32_dev(self._h, C.c_void_p(d_rows), int(n), int(dim), metric_from_name(metric), _np_ptr(k),
+                                                     int(nlist), int(kmeans_iters), int(seed), float(bin_threshold),
+                                                     C.c_void_p(stream) if stream else None)
+        return self._loaded(rc, n, None if k is None else ("row", k))
+
+    def attach_rows(self, rows, metric="SquaredEuclidean"):
+        """fp32 rows [count][dim], already in list order, for an index made by load or build; the bits are not checked against them"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[0] != self.info()[0]:
+            return IndexError_.InvalidArgument
+        return _lib.lib().zvec_hip_bivf_attach_rows(self._h, _np_ptr(rows), rows.shape[1], metric_from_name(metric))
+
+    def attach_rows_dev(self, d_rows, dim, metric="SquaredEuclidean", stream=None):
+        return _lib.lib().zvec_hip_bivf_attach_rows_dev(self._h, C.c_void_p(d_rows), int(dim), metric_from_name(metric),
+                                                        C.c_void_p(stream) if stream else None)
+
+    def rows_info(self):
+        """(dim, metric, bytes) of the fp32 rows; dim 0: none"""
+        d, m, b = C.c_uint32(0), C.c_int(0), C.c_uint64(0)
+        _lib.check(_lib.lib().zvec_hip_bivf_rows_info(self._h, C.byref(d), C.byref(m), C.byref(b)), "zvec_hip_bivf_rows_info")
+        return int(d.value), int(m.value), int(b.value)
+
+    def get_rows_by_ids(self, list_positions):
+        pos = np.ascontiguousarray(list_positions, np.uint64)
+        out = np.zeros((pos.size, self.rows_info()[0]), np.float32)
+        _lib.check(_lib.lib().zvec_hip_bivf_get_rows(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_bivf_get_rows")
+        return out
+
+    def search_impl_fp32(self, queries, count, ctx, refine=4, bin_threshold=0.0, nprobe=None, max_scan=None):
+        """fp32 queries ([count][dim]): BinaryReformer::transform, the Hamming search for min(topk * refine, 128) candidates and their
+        re-rank on the fp32 rows, all on the GPU.  Results, filter and threshold (on the fp32 score) as search_impl."""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim != 2 or q.shape[0] != int(count):
+            return IndexError_.InvalidArgument
+        k = ctx.topk()
+        pp = self.probe_params(ctx) if nprobe is None or max_scan is None else (nprobe, max_scan)
+        nprobe = pp[0] if nprobe is None else nprobe
+        max_scan = pp[1] if max_scan is None else max_scan
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        counts = np.zeros(count, np.uint32)
+        if ctx._exclude is not None:
+            ex = ctx._exclude
+        else:
+            ex = ctx._exclude_for(self.keys_in_list_order()) if ctx._filter_fn else None
+        rc = _lib.lib().zvec_hip_bivf_search_fp32(self._h, ctx._h, _np_ptr(q), count, q.shape[1], k, int(refine), ctx.threshold(),
+                                                  float(bin_threshold), int(nprobe), int(max_scan), _np_ptr(ex), _np_ptr(keys),
+                                                  _np_ptr(scores), _np_ptr(counts))
+        if rc == 0:
+            ctx._set_results(keys, scores, counts, self._vectors_of_keys)
+        return rc
+
+    def search_fp32_dev(self, d_queries, dim, count, topk, refine, nprobe, max_scan, d_out_keys, d_out_scores, d_out_counts, ctx,
+                        bin_threshold=0.0, threshold=FLT_MAX, d_exclude=None, stream=None):
+        """device-pointer form of search_impl_fp32 (async): all arguments are raw device pointers (ints)."""
+        return _lib.lib().zvec_hip_bivf_search_fp32_dev(
+            self._h, ctx._h, C.c_void_p(d_queries), count, int(dim), topk, int(refine), threshold, float(bin_threshold), nprobe, max_scan,
+            C.c_void_p(d_exclude) if d_exclude else None, C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts),
+            C.c_void_p(stream) if stream else None)
+
+    def last_candidates(self, ctx, count, kc):
+        """(positions [count][kc], hamming_scores [count][kc], counts [count]): stage 1 of the last fp32 search of this index on ctx,
+        which ran with kc = min(topk * refine, 128)"""
+        pos = np.zeros((count, kc), np.uint32)
+        sc = np.zeros((count, kc), np.float32)
+        cnt = np.zeros(count, np.uint32)
+        _lib.check(_lib.lib().zvec_hip_bivf_last_candidates(self._h, ctx._h, count, kc, _np_ptr(pos), _np_ptr(sc), _np_ptr(cnt)),
+                   "zvec_hip_bivf_last_candidates")
+        return pos, sc, cnt
+
 
 def container_segments(image, checksum=False):
     """segment table of a dumped index FILE image (zvec_hip_container_segments): {id: (offset, size)} in file order"""
