@@ -113,6 +113,8 @@ const char *zvec_hip_error_string(int code); /* IndexError::What analogue */
  *               either way.
  *   "bivf_part_bytes"  1024 .. 2^30 (default 2^30): a zvec_hip_bivf_search keeps the partial lists of one slice of its batch within
  *               this many bytes and answers a batch that needs more in slices of queries.  Same results either way.
+ *   "hnsw_ws_bytes"  1024 .. 2^30 (default 2^30): a zvec_hip_hnsw_search keeps the visited bits and candidate regions of one slice of
+ *               its batch within this many bytes and answers a batch that needs more in slices of queries.  Same results either way.
  * Unsupported (-12) for an unknown name, invalid argument (-1) for a value outside the option's range. */
 int zvec_hip_set_option(const char *name, int value);
 int zvec_hip_get_option(const char *name, int *value);
@@ -1047,6 +1049,54 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
                                           uint32_t group_num, uint32_t group_topk, float threshold,
                                           const uint64_t *exclude_bitset, uint32_t *out_groups, uint32_t *out_ngroups,
                                           uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+
+/* ---- HNSW: search on a built graph ----------------------------------------------------------
+ * stands behind HnswSearcher::search_impl (src/core/algorithm/hnsw/hnsw_searcher.cc) above its brute-force hand-over: the walk of
+ * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
+ * query.  The handle loads a graph that is already built; building one, reading the reference's dumped HNSW segments
+ * (hnsw_searcher_entity.cc), fp16 rows, the cosine metric and group-by are not served.  Small indexes
+ * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
+ *   - fp32 rows; ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
+ *     index); every other dtype or metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
+ *   - a node is its position 0 .. n-1; exclude_bitset, threshold, out_counts and the fill of the places past out_counts[q]
+ *     (key 2^64 - 1, score +inf) are those of zvec_hip_flat_search; an excluded node is walked through but never returned;
+ *   - lists are ascending by (score, node); of two candidates or results at one distance the one with the smaller node comes first,
+ *     and the largest by (distance, node) leaves a full set — the reference's KeyValueHeap leaves equal keys in heap order. */
+typedef struct zvec_hip_hnsw_s *zvec_hip_hnsw_t;
+int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
+int zvec_hip_hnsw_destroy(zvec_hip_hnsw_t h);
+/* HnswSearcher::load in the shape of plain host arrays — what HnswEntity serves the algorithm: get_vector / get_key (rows [n][dim],
+ * keys [n], NULL = the position), get_neighbors(0, id) (nbr0 [n][m0] with cnt0 [n] valid entries each), get_neighbors(level >= 1, id)
+ * (upper_of [n]: index into the upper table or 0xffffffff for a node of level 0 only; nbr_up [n_upper][max_level][m] with
+ * cnt_up [n_upper][max_level], level l at slot l - 1, count 0 above a node's own level), entry_point() and cur_max_level().
+ * max_level == 0: the upper arrays are not read.  InvalidArgument (-31), the handle untouched, for: a neighbour >= n, a count above
+ * m0 / m, entry_point >= n, upper_of beyond n_upper, and — with max_level >= 1 — an entry point or an upper-level neighbour without
+ * upper lists.  A second load replaces the first; n == 0 is a valid empty index (every search answers with empty lists). */
+int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
+                       const uint32_t *cnt0, uint32_t max_level, uint32_t m, uint32_t n_upper, const uint32_t *upper_of,
+                       const uint32_t *nbr_up, const uint32_t *cnt_up, uint32_t entry_point);
+/* what load took, read back (every pointer nullable): the shape, rows by position (HnswEntity::get_vector), the other arrays */
+int zvec_hip_hnsw_info(zvec_hip_hnsw_t h, uint64_t *n, uint32_t *dim, uint32_t *m0, uint32_t *max_level, uint32_t *m, uint32_t *n_upper,
+                       uint32_t *entry_point);
+int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, float *out);
+int zvec_hip_hnsw_export(zvec_hip_hnsw_t h, uint64_t *keys, uint32_t *nbr0, uint32_t *cnt0, uint32_t *upper_of, uint32_t *nbr_up,
+                         uint32_t *cnt_up);
+/* HnswSearcher::search_impl(query, qmeta, count, ctx): queries [count][dim] fp32.  ef: HnswContext's ef (kDefaultEf = 500,
+ * hnsw_params.h); the walk runs with max(ef, topk), above 512 Unsupported (-12).  max_scan: the context's scan limit
+ * (reach_scan_limit), counted in distances computed, 0 = n.  Batches go in slices of queries that keep the walk's workspace within
+ * the "hnsw_ws_bytes" option (1024 .. 2^30, default 2^30): ceil(n / 32) * 4 bytes per query, plus 8 * min(max_scan, n) bytes per
+ * query when min(max_scan, n) > 1024; the same results either way. */
+int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t count, uint32_t topk, uint32_t ef,
+                         uint32_t max_scan, float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
+                         uint32_t *out_counts);
+int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+                             uint32_t max_scan, float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
+                             float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* HnswContext's debugging counters of the last search of `h` on the context (stats_get_vector's rows, stats_get_neighbors at level 0),
+ * for its first `count` queries: distances computed, nodes expanded on level 0, and the slices the batch went in (each nullable).
+ * Waits for the context's stream.  NoReady (-21) when the context's last search was not one of `h` or was shorter. */
+int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
+                             uint32_t *out_slices);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,151 @@
+"""HNSW graph search measured (reported, not gated): ms per step, recall@10 against the exact flat search, distances computed per
+query, and the gathered bytes per second (distances x row bytes / time) beside the box's calibrated streaming rate.
+
+The corpus is n x dim fp32 from the generator tools/hamming_bench.py --from-fp32 uses.  A real HNSW build at that size is out of
+reach of the Python model, so the graph is a k-NN graph made on the GPU with the existing flat search: level 0 holds every row's
+m0 / 2 nearest rows plus reverse edges up to m0 = 32; a 1-in-32 sample is level 1, built the same way with m = 16; the entry point
+is the sample's first row.
+
+    python tools/hnsw_bench.py [--n 1000000 --dim 768] [--out profiles/hnsw_1m.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _timed(torch, stream, steps, warmup, step):
+    """ms per step, events on `stream` around `steps` calls"""
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(steps):
+        step()
+    e1.record(stream)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def knn_dev(torch, zvec_amd, rows, k, stream, chunk=8192):
+    """positions of every row's k nearest other rows ([n][k] int64 on the host), by the exact flat search"""
+    n, dim = rows.shape
+    flat = zvec_amd.HipFlatSearcher(dim, "SquaredEuclidean")
+    assert flat.add_batch_dev(rows.data_ptr(), n) == 0
+    ctx = flat.create_context()
+    dev = rows.device
+    keys = torch.empty((chunk, k + 1), dtype=torch.int64, device=dev)
+    scores = torch.empty((chunk, k + 1), dtype=torch.float32, device=dev)
+    counts = torch.empty((chunk,), dtype=torch.int32, device=dev)
+    out = np.zeros((n, k), np.int64)
+    torch.cuda.synchronize()
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        assert flat.search_dev(rows[o:o + m].data_ptr(), m, k + 1, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx, stream=stream) == 0
+        torch.cuda.synchronize()
+        got = keys[:m].cpu().numpy()
+        own = got == np.arange(o, o + m)[:, None]          # a row is its own nearest row: drop it (or the last place on a tie)
+        own[~own.any(1), -1] = True
+        out[o:o + m] = got[~own].reshape(m, k)
+    return out, flat
+
+
+def with_reverse_edges(knn, cap):
+    """lists of up to `cap`: the k forward edges of every node, then reverse edges that are not forward ones, in source order"""
+    n, k = knn.shape
+    nbr = np.zeros((n, cap), np.uint32)
+    nbr[:, :k] = knn
+    cnt = np.full(n, k, np.uint32)
+    src = np.repeat(np.arange(n, dtype=np.int64), k)
+    dst = knn.reshape(-1)
+    mutual = np.isin(dst * n + src, src * n + dst)         # dst already lists src
+    src, dst = src[~mutual], dst[~mutual]
+    order = np.argsort(dst, kind="stable")
+    src, dst = src[order], dst[order]
+    first = np.searchsorted(dst, np.arange(n))
+    rank = np.arange(dst.size) - first[dst]
+    keep = rank < cap - k
+    nbr[dst[keep], k + rank[keep]] = src[keep]
+    np.add.at(cnt, dst[keep], 1)
+    return nbr, cnt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1000000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--topk", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import zvec_amd
+    dev = torch.device("cuda:0")
+    n, dim, m0, m = args.n, args.dim, 32, 16
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    rows = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
+    ts = torch.cuda.Stream(device=dev)
+    ts.wait_stream(torch.cuda.current_stream(dev))
+    stream = ts.cuda_stream
+    torch.cuda.synchronize()
+    knn0, flat = knn_dev(torch, zvec_amd, rows, m0 // 2, stream)
+    nbr0, cnt0 = with_reverse_edges(knn0, m0)
+    sample = np.arange(0, n, 32)
+    knn1, _ = knn_dev(torch, zvec_amd, rows[::32].contiguous(), min(m // 2, sample.size - 1), stream)
+    nbr1, cnt1 = with_reverse_edges(knn1, m)
+    upper_of = np.full(n, 0xffffffff, np.uint32)
+    upper_of[sample] = np.arange(sample.size, dtype=np.uint32)
+    nbr_up = sample[nbr1.astype(np.int64)].astype(np.uint32).reshape(sample.size, 1, m)
+    se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+    assert se.load(rows.cpu().numpy(), nbr0, cnt0, 0, None, upper_of, nbr_up, cnt1.reshape(-1, 1)) == 0
+    ctx, fctx = se.create_context(), flat.create_context()
+    legs = []
+    for batch in (1, 64, 1024):
+        q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+        keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        exact = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        assert flat.search_dev(q.data_ptr(), batch, args.topk, exact.data_ptr(), scores.data_ptr(), counts.data_ptr(), fctx, stream=stream) == 0
+        torch.cuda.synchronize()
+        truth = exact.cpu().numpy()
+        for ef in (64, 128, 256):
+            def step():
+                assert se.search_dev(q.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx,
+                                     stream=stream) == 0
+            ms = _timed(torch, ts, args.steps, args.warmup, step)
+            scanned, hops, _ = se.last_stats(ctx, batch)
+            got = keys.cpu().numpy()
+            recall = float(np.mean([len(set(got[i]) & set(truth[i])) / float(args.topk) for i in range(batch)]))
+            gathered = float(scanned.sum()) * dim * 4
+            legs.append({"batch": batch, "ef": ef, "ms_per_step": ms, "qps": batch / ms * 1e3, "recall_at_%d" % args.topk: recall,
+                         "mean_scanned": float(scanned.mean()), "mean_hops": float(hops.mean()), "gathered_gbs": gathered / ms / 1e6})
+    del rows, flat
+    torch.cuda.synchronize()
+    free, _ = torch.cuda.mem_get_info(dev)
+    nbytes = int(min(30e9, free * 0.8)) // 4096 * 4096
+    mhz, gbs = C.c_double(0), C.c_double(0)
+    rc = zvec_amd._lib.lib().zvec_hip_calibrate(0, None, nbytes, 3, C.byref(mhz), C.byref(gbs))
+    assert rc == 0, rc
+    for leg in legs:
+        leg["stream_fraction"] = leg["gathered_gbs"] / gbs.value
+    res = {"workload": "hnsw search %d x %d fp32, k-NN graph m0=%d (+ 1-in-32 level 1, m=%d), k=%d" % (n, dim, m0, m, args.topk),
+           "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

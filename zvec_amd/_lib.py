@@ -229,6 +229,18 @@ SYMBOLS = {
                                                  C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
     "zvec_hip_sparse_search_grouped_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32,
                                                         C.c_uint32, C.c_uint32, C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
+    "zvec_hip_hnsw_create": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_hnsw_destroy": (C.c_int, [_h]),
+    "zvec_hip_hnsw_load": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p,
+                                     _u32p, _u32p, C.c_uint32]),
+    "zvec_hip_hnsw_info": (C.c_int, [_h, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 6),
+    "zvec_hip_hnsw_get_vectors": (C.c_int, [_h, _u64p, C.c_uint64, _f32p]),
+    "zvec_hip_hnsw_export": (C.c_int, [_h, _u64p, _u32p, _u32p, _u32p, _u32p, _u32p]),
+    "zvec_hip_hnsw_search": (C.c_int, [_h, _h, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
+                                       _u32p]),
+    "zvec_hip_hnsw_search_dev": (C.c_int, [_h, _h, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
+                                           _u32p, C.c_void_p]),
+    "zvec_hip_hnsw_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

@@ -61,6 +61,11 @@ int zvec_hip_set_option(const char *name, int value) {
     ropts().bivf_part_bytes = value;
     return 0;
   }
+  if (strcmp(name, "hnsw_ws_bytes") == 0) {
+    if (value < 1024 || value > (1 << 30)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    ropts().hnsw_ws_bytes = value;
+    return 0;
+  }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 int zvec_hip_get_option(const char *name, int *value) {
@@ -72,6 +77,7 @@ int zvec_hip_get_option(const char *name, int *value) {
   if (strcmp(name, "sparse_group_rows") == 0) { *value = ropts().sparse_group_rows; return 0; }
   if (strcmp(name, "sparse_inverted_build") == 0) { *value = ropts().sparse_inverted_build; return 0; }
   if (strcmp(name, "bivf_part_bytes") == 0) { *value = ropts().bivf_part_bytes; return 0; }
+  if (strcmp(name, "hnsw_ws_bytes") == 0) { *value = ropts().hnsw_ws_bytes; return 0; }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 

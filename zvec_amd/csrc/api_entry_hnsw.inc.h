@@ -1,0 +1,275 @@
+// api_entry_hnsw.inc.h — C ABI entry points: batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*; inside extern "C").
+// Device code: zvk_hnsw.hip.h.  A handle family of its own beside the flat and IVF handles: it loads a graph somebody else built
+// and walks it by the rule of DESIGN §3c (HnswAlgorithm::search, hnsw_algorithm.cc:83-278).  Nothing here builds a graph.
+// Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
+
+struct zvec_hip_hnsw_s {
+  int device = 0;
+  int metric = 0;
+  uint32_t dim = 0, dpad = 0;          // dpad: floats per stored row, dim rounded up to 4 (a lane of the kernel loads 16 bytes)
+  bool loaded = false;
+  uint64_t n = 0;
+  uint32_t m0 = 0, m = 0, max_level = 0, n_upper = 0, entry = 0;
+  struct Arrays {                      // everything a load replaces, whole
+    Scoped<float> rows;                // [n][dpad]
+    Scoped<uint64_t> keys;             // [n]
+    Scoped<uint32_t> nbr0, cnt0, upper_of, nbr_up, cnt_up;
+  } arr;
+  zvec_hip_ctx_s *defctx = nullptr;
+  std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
+  FairSharedMutex rw;                  // searches hold it shared, load exclusive (as zvec_hip_flat_s); a context's mutex is taken first
+  ~zvec_hip_hnsw_s() { delete defctx; }
+};
+
+int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
+  if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype != ZVEC_HIP_DT_FP32) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (metric != ZVEC_HIP_METRIC_L2 && metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS)
+  zvec_hip_ctx_s *c = nullptr;
+  ZRET(ctx_new(device, &c));
+  zvec_hip_hnsw_s *h = new (std::nothrow) zvec_hip_hnsw_s();
+  if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
+  h->device = device; h->metric = metric; h->dim = dim; h->dpad = (dim + 3) / 4 * 4; h->defctx = c;
+  *out = h;
+  return 0;
+}
+
+int zvec_hip_hnsw_destroy(zvec_hip_hnsw_t h) {
+  if (!h) return 0;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  delete h;
+  return 0;
+}
+
+// what zvec_hip_hnsw_load refuses before it touches the handle
+static int hnsw_validate(uint64_t n, const void *rows, uint32_t m0, const uint32_t *nbr0, const uint32_t *cnt0, uint32_t max_level,
+                         uint32_t m, uint32_t n_upper, const uint32_t *upper_of, const uint32_t *nbr_up, const uint32_t *cnt_up,
+                         uint32_t entry_point) {
+  if (n == 0) return 0;
+  if (n >= 0xfffffff0ull) return ZVEC_HIP_ERR_OUT_OF_RANGE;         // node ids are 32-bit (IDX_NONE reserved)
+  if (!rows || !cnt0 || (m0 && !nbr0) || entry_point >= n) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  const bool up = max_level >= 1;
+  if (up && (!upper_of || n_upper == 0 || !cnt_up || (m && !nbr_up) || n_upper > n)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (cnt0[i] > m0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    for (uint32_t j = 0; j < cnt0[i]; ++j)
+      if (nbr0[i * m0 + j] >= n) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    if (up && upper_of[i] != IDX_NONE && upper_of[i] >= n_upper) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  }
+  if (!up) return 0;
+  if (upper_of[entry_point] == IDX_NONE) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  for (uint64_t s = 0; s < (uint64_t)n_upper * max_level; ++s) {
+    if (cnt_up[s] > m) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    for (uint32_t j = 0; j < cnt_up[s]; ++j) {
+      const uint32_t v = nbr_up[s * m + j];
+      // (the walk reads the upper lists of every node it moves to: a neighbour on an upper level has them)
+      if (v >= n || upper_of[v] == IDX_NONE) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    }
+  }
+  return 0;
+}
+
+// HnswSearcher::load (hnsw_searcher.cc) in the shape of plain arrays: the graph as HnswEntity serves it to the algorithm
+// (get_neighbors(level, id), get_vector(id), get_key(id), entry_point(), cur_max_level())
+int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
+                       const uint32_t *cnt0, uint32_t max_level, uint32_t m, uint32_t n_upper, const uint32_t *upper_of,
+                       const uint32_t *nbr_up, const uint32_t *cnt_up, uint32_t entry_point) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  ZRET(hnsw_validate(n, rows, m0, nbr0, cnt0, max_level, m, n_upper, upper_of, nbr_up, cnt_up, entry_point));
+  ZCHK(hipSetDevice(h->device));
+  std::lock_guard<std::mutex> g(h->mu);
+  std::lock_guard<std::mutex> gc(h->defctx->mu);
+  std::unique_lock<FairSharedMutex> w(h->rw);
+  ZCHK(hipDeviceSynchronize());                  // (searches enqueued on other contexts have finished with the old arrays)
+  zvec_hip_hnsw_s::Arrays a;
+  const bool up = n && max_level >= 1;
+  if (n) {
+    ZRET(a.rows.alloc((size_t)n * h->dpad));
+    ZRET(a.keys.alloc(n));
+    ZRET(a.cnt0.alloc(n));
+    ZRET(a.nbr0.alloc(std::max<size_t>((size_t)n * m0, 1)));
+    if (h->dpad != h->dim) ZCHK(hipMemset(a.rows, 0, (size_t)n * h->dpad * 4));
+    ZCHK(hipMemcpy2D(a.rows, (size_t)h->dpad * 4, rows, (size_t)h->dim * 4, (size_t)h->dim * 4, n, hipMemcpyHostToDevice));
+    if (keys) {
+      ZCHK(hipMemcpy(a.keys, keys, (size_t)n * 8, hipMemcpyHostToDevice));
+    } else {
+      std::vector<uint64_t> id(n);
+      for (uint64_t i = 0; i < n; ++i) id[i] = i;
+      ZCHK(hipMemcpy(a.keys, id.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    ZCHK(hipMemcpy(a.cnt0, cnt0, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (m0) ZCHK(hipMemcpy(a.nbr0, nbr0, (size_t)n * m0 * 4, hipMemcpyHostToDevice));
+  }
+  if (up) {
+    const size_t slots = (size_t)n_upper * max_level;
+    ZRET(a.upper_of.alloc(n));
+    ZRET(a.cnt_up.alloc(slots));
+    ZRET(a.nbr_up.alloc(std::max<size_t>(slots * m, 1)));
+    ZCHK(hipMemcpy(a.upper_of, upper_of, (size_t)n * 4, hipMemcpyHostToDevice));
+    ZCHK(hipMemcpy(a.cnt_up, cnt_up, slots * 4, hipMemcpyHostToDevice));
+    if (m) ZCHK(hipMemcpy(a.nbr_up, nbr_up, slots * m * 4, hipMemcpyHostToDevice));
+  }
+  std::swap(h->arr, a);                          // the old arrays go with the local
+  h->n = n; h->m0 = m0; h->m = up ? m : 0; h->max_level = up ? max_level : 0; h->n_upper = up ? n_upper : 0;
+  h->entry = n ? entry_point : 0;
+  h->loaded = true;
+  h->defctx->hnsw_count = 0;
+  return 0;
+}
+
+int zvec_hip_hnsw_info(zvec_hip_hnsw_t h, uint64_t *n, uint32_t *dim, uint32_t *m0, uint32_t *max_level, uint32_t *m, uint32_t *n_upper,
+                       uint32_t *entry_point) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (n) *n = h->n;
+  if (dim) *dim = h->dim;
+  if (m0) *m0 = h->m0;
+  if (max_level) *max_level = h->max_level;
+  if (m) *m = h->m;
+  if (n_upper) *n_upper = h->n_upper;
+  if (entry_point) *entry_point = h->entry;
+  return 0;
+}
+
+int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, float *out) {
+  if (!h || (n && (!positions || !out))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (n == 0) return 0;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
+  for (uint64_t i = 0; i < n; ++i)
+    if (positions[i] >= h->n) return ZVEC_HIP_ERR_NO_EXIST;
+  ZCHK(hipSetDevice(h->device));
+  for (uint64_t i = 0; i < n; ++i)
+    ZCHK(hipMemcpy(out + (size_t)i * h->dim, h->arr.rows.p + (size_t)positions[i] * h->dpad, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int zvec_hip_hnsw_export(zvec_hip_hnsw_t h, uint64_t *keys, uint32_t *nbr0, uint32_t *cnt0, uint32_t *upper_of, uint32_t *nbr_up,
+                         uint32_t *cnt_up) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
+  if (h->n == 0) return 0;
+  ZCHK(hipSetDevice(h->device));
+  const size_t n = h->n, slots = (size_t)h->n_upper * h->max_level;
+  if (keys) ZCHK(hipMemcpy(keys, h->arr.keys, n * 8, hipMemcpyDeviceToHost));
+  if (nbr0 && h->m0) ZCHK(hipMemcpy(nbr0, h->arr.nbr0, n * h->m0 * 4, hipMemcpyDeviceToHost));
+  if (cnt0) ZCHK(hipMemcpy(cnt0, h->arr.cnt0, n * 4, hipMemcpyDeviceToHost));
+  if (h->max_level == 0) return 0;
+  if (upper_of) ZCHK(hipMemcpy(upper_of, h->arr.upper_of, n * 4, hipMemcpyDeviceToHost));
+  if (nbr_up && h->m) ZCHK(hipMemcpy(nbr_up, h->arr.nbr_up, slots * h->m * 4, hipMemcpyDeviceToHost));
+  if (cnt_up) ZCHK(hipMemcpy(cnt_up, h->arr.cnt_up, slots * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments.  A batch goes in slices of queries so
+// that the visited bits (ceil(n / 32) words per query) and the candidate regions (min(max_scan, n) words of 8 bytes per query, only
+// when that is more than the kernel holds in LDS) stay within the "hnsw_ws_bytes" option; a query's walk does not depend on its slice.
+static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+                                  uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
+                                  uint32_t *d_out_counts, hipStream_t s) {
+  c->sh.count = 0;              // (no certify step is pending, no flat route and no IVF plan to read back)
+  c->route = 0;
+  c->ivf_plan.route = 0;
+  c->hnsw_count = 0;
+  ZRET(c->hnsw_stats.ensure((size_t)count * 8));
+  uint32_t slices = 0;
+  if (h->n == 0) {
+    hipLaunchKernelGGL(hnsw_empty_kernel, dim3((count * std::max(topk, 2u) + 255) / 256), dim3(256), 0, s, d_out_keys, d_out_scores,
+                       d_out_counts, c->hnsw_stats.as<uint32_t>(), count, topk);
+    ZCHK(hipGetLastError());
+  } else {
+    const uint32_t n = (uint32_t)h->n;
+    HnswArgs a{};
+    a.rows = h->arr.rows; a.keys = h->arr.keys; a.nbr0 = h->arr.nbr0; a.cnt0 = h->arr.cnt0; a.upper_of = h->arr.upper_of;
+    a.nbr_up = h->arr.nbr_up; a.cnt_up = h->arr.cnt_up;
+    a.n = n; a.dim = h->dim; a.dpad = h->dpad; a.m0 = h->m0; a.m = h->m; a.max_level = h->max_level; a.entry = h->entry;
+    a.ip = h->metric == ZVEC_HIP_METRIC_IP ? 1 : 0;
+    a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
+    a.topk = topk; a.ef = std::max(ef, topk); a.max_scan = max_scan ? max_scan : n; a.threshold = threshold;
+    a.vis_words = (n + 31) / 32;
+    a.ccap = std::min(a.max_scan, n);
+    const bool spill = a.ccap > HNSW_C_LDS;
+    const uint64_t per_q = (uint64_t)a.vis_words * 4 + (spill ? (uint64_t)a.ccap * 8 : 0);
+    const uint64_t budget = (uint64_t)ropts().hnsw_ws_bytes.load(std::memory_order_relaxed);
+    const uint32_t slice = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(count, budget / per_q));
+    ZRET(c->hnsw_ws.ensure((size_t)slice * per_q));
+    uint64_t *cand = spill ? c->hnsw_ws.as<uint64_t>() : nullptr;
+    uint32_t *vis = reinterpret_cast<uint32_t *>(c->hnsw_ws.as<uint64_t>() + (spill ? (size_t)slice * a.ccap : 0));
+    for (uint32_t q0 = 0; q0 < count; q0 += slice, ++slices) {
+      const uint32_t mq = std::min(slice, count - q0);
+      ZCHK(hipMemsetAsync(vis, 0, (size_t)mq * a.vis_words * 4, s));
+      a.queries = d_queries + (size_t)q0 * h->dim;
+      a.visited = vis; a.cand_ws = cand;
+      a.out_keys = d_out_keys + (size_t)q0 * topk; a.out_scores = d_out_scores + (size_t)q0 * topk; a.out_counts = d_out_counts + q0;
+      a.stats = c->hnsw_stats.as<uint32_t>() + 2 * (size_t)q0;
+      hipLaunchKernelGGL(hnsw_search_kernel, dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
+      ZCHK(hipGetLastError());
+    }
+  }
+  c->hnsw_owner = h;
+  c->hnsw_count = count;
+  c->hnsw_slices = slices;
+  return 0;
+}
+
+static int hnsw_search_args(zvec_hip_hnsw_t h, const void *queries, uint32_t count, uint32_t topk, uint32_t ef, const void *keys,
+                            const void *scores, const void *counts) {
+  if (!h || !queries || !keys || !scores || !counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (count && topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  return std::max(ef, topk) > HNSW_MAX_EF ? ZVEC_HIP_ERR_UNSUPPORTED : 0;
+}
+
+// HnswSearcher::search_impl (hnsw_searcher.cc) above the brute-force hand-over, which stays with the caller
+int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+                             uint32_t max_scan, float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
+                             float *d_out_scores, uint32_t *d_out_counts, void *stream) {
+  ZRET(hnsw_search_args(h, d_queries, count, topk, ef, d_out_keys, d_out_scores, d_out_counts));
+  if (count == 0) return 0;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  std::shared_lock<FairSharedMutex> r(h->rw);
+  if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
+  ZCHK(hipSetDevice(h->device));
+  return hnsw_search_dev_locked(h, c, d_queries, count, topk, ef, max_scan, threshold, d_exclude_bitset, d_out_keys, d_out_scores,
+                                d_out_counts, pick_stream(c, stream));
+}
+
+int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t count, uint32_t topk, uint32_t ef,
+                         uint32_t max_scan, float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
+                         uint32_t *out_counts) {
+  ZRET(hnsw_search_args(h, queries, count, topk, ef, out_keys, out_scores, out_counts));
+  if (count == 0) return 0;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);                // ONE critical section from the upload to the copy-out (zvec_hip_flat_search)
+  ZCHK(hipSetDevice(h->device));
+  {
+    std::shared_lock<FairSharedMutex> r(h->rw);        // the row count the bitset is sized for == the nodes of the graph
+    if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
+    ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->dim * 4, h->n ? exclude_bitset : nullptr, h->n, count, topk, c->cur));
+    ZRET(hnsw_search_dev_locked(h, c, static_cast<const float *>(c->io_qp), count, topk, ef, max_scan, threshold,
+                                exclude_bitset && h->n ? c->io_ex.as<uint64_t>() : nullptr, c->io_keys.as<uint64_t>(),
+                                c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur));
+  }
+  return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
+}
+
+int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
+                             uint32_t *out_slices) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->hnsw_owner != h || c->hnsw_count == 0 || count > c->hnsw_count) return ZVEC_HIP_ERR_NO_READY;
+  ZCHK(hipSetDevice(h->device));
+  ZCHK(hipStreamSynchronize(c->cur));
+  std::vector<uint32_t> st((size_t)count * 2);
+  ZCHK(hipMemcpy(st.data(), c->hnsw_stats.p, st.size() * 4, hipMemcpyDeviceToHost));
+  for (uint32_t q = 0; q < count; ++q) {
+    if (out_scanned) out_scanned[q] = st[2 * (size_t)q];
+    if (out_hops) out_hops[q] = st[2 * (size_t)q + 1];
+  }
+  if (out_slices) *out_slices = c->hnsw_slices;
+  return 0;
+}

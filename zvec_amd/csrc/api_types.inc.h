@@ -147,6 +147,9 @@ struct RuntimeOpts {
   // Hamming IVF search (api_entry_hamming_ivf.inc.h): the partial lists of one slice of a batch stay within this many bytes; a batch
   // that needs more goes in slices of queries.  1 GiB like dense_sub_batch; tests lower it to reach a second slice at small shapes.
   std::atomic<int> bivf_part_bytes{1 << 30};
+  // HNSW search (api_entry_hnsw.inc.h): the visited bits and candidate regions of one slice of a batch stay within this many bytes;
+  // a batch that needs more goes in slices of queries.  Tests lower it to reach a second slice at small shapes.
+  std::atomic<int> hnsw_ws_bytes{1 << 30};
   RuntimeOpts() {
     if (const char *e = getenv("ZVEC_HIP_SCAN256")) scan256 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("ZVEC_HIP_WAIT")) wait = std::max(0, std::min(2, atoi(e)));
@@ -444,6 +447,11 @@ struct zvec_hip_ctx_s {
   // positions [count][kc] | Hamming scores [count][kc] | counts [count]
   DevBuf bivf_cand;
   uint32_t bivf_cand_count = 0, bivf_cand_kc = 0, bivf_cand_slice = 0;
+  // HNSW search (api_entry_hnsw.inc.h): candidate regions | visited bits of the current slice; {distances computed, nodes expanded}
+  // per query of the last search, kept for zvec_hip_hnsw_last_stats
+  DevBuf hnsw_ws, hnsw_stats;
+  const void *hnsw_owner = nullptr;
+  uint32_t hnsw_count = 0, hnsw_slices = 0;
   DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)

@@ -40,3 +40,4 @@
 #include "zvk_sparse_invb.hip.h"
 #include "zvk_sparse_put.hip.h"
 #include "zvk_sparse_ingest.hip.h"
+#include "zvk_hnsw.hip.h"

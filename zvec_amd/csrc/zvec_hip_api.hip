@@ -55,5 +55,6 @@ extern "C" {
 #include "api_entry_sparse_ingest.inc.h"
 #include "api_entry_sparse_put_dev.inc.h"
 #include "api_entry_sparse_group.inc.h"
+#include "api_entry_hnsw.inc.h"
 
 }  // extern "C"

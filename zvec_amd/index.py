@@ -1829,6 +1829,116 @@ class HipHammingIVFSearcher:
         return pos, sc, cnt
 
 
+class HipHnswSearcher:
+    """Batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*): what HnswSearcher::search_impl is above its brute-force
+    hand-over.  fp32 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays; nothing here builds one."""
+
+    def __init__(self, dim, metric="SquaredEuclidean", device=0, dtype="fp32"):
+        self.dim = int(dim)
+        self.metric = metric_from_name(metric) if isinstance(metric, str) else int(metric)
+        self.device = device
+        self.dtype, _ = _dtype_of(dtype)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().zvec_hip_hnsw_create(self.dim, self.dtype, self.metric, device, C.byref(self._h)), "zvec_hip_hnsw_create")
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().zvec_hip_hnsw_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def create_context(self):
+        return IndexContext(self.device)
+
+    def load(self, rows, nbr0, cnt0, entry_point=0, keys=None, upper_of=None, nbr_up=None, cnt_up=None):
+        """rows [n][dim]; nbr0 [n][m0] with cnt0 [n]; upper levels (all three or none): upper_of [n], nbr_up [n_upper][max_level][m],
+        cnt_up [n_upper][max_level]"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        n = rows.shape[0]
+        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+            return IndexError_.Mismatch
+        nbr0 = np.ascontiguousarray(nbr0, np.uint32).reshape(n, -1) if n else np.zeros((0, 1), np.uint32)
+        cnt0 = np.ascontiguousarray(cnt0, np.uint32)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        if cnt0.size != n or (k is not None and k.size != n):
+            return IndexError_.InvalidArgument
+        max_level = m = n_upper = 0
+        if nbr_up is not None and n:
+            upper_of = np.ascontiguousarray(upper_of, np.uint32)
+            nbr_up = np.ascontiguousarray(nbr_up, np.uint32)
+            cnt_up = np.ascontiguousarray(cnt_up, np.uint32)
+            if nbr_up.ndim != 3 or cnt_up.shape != nbr_up.shape[:2] or upper_of.size != n:
+                return IndexError_.InvalidArgument
+            n_upper, max_level, m = nbr_up.shape
+        if max_level == 0:
+            upper_of = nbr_up = cnt_up = None
+        return _lib.lib().zvec_hip_hnsw_load(self._h, n, _np_ptr(rows), _np_ptr(k), nbr0.shape[1], _np_ptr(nbr0), _np_ptr(cnt0), max_level, m,
+                                             n_upper, _np_ptr(upper_of), _np_ptr(nbr_up), _np_ptr(cnt_up), int(entry_point))
+
+    def info(self):
+        """{n, dim, m0, max_level, m, n_upper, entry_point}"""
+        n = C.c_uint64(0)
+        v = [C.c_uint32(0) for _ in range(6)]
+        _lib.check(_lib.lib().zvec_hip_hnsw_info(self._h, C.byref(n), *[C.byref(x) for x in v]), "zvec_hip_hnsw_info")
+        names = ("dim", "m0", "max_level", "m", "n_upper", "entry_point")
+        return dict([("n", int(n.value))] + [(k, int(x.value)) for k, x in zip(names, v)])
+
+    def get_vectors_by_ids(self, positions):
+        pos = np.ascontiguousarray(positions, np.uint64)
+        out = np.zeros((pos.size, self.dim), np.float32)
+        _lib.check(_lib.lib().zvec_hip_hnsw_get_vectors(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_hnsw_get_vectors")
+        return out
+
+    def export(self):
+        """keys, nbr0, cnt0, upper_of, nbr_up, cnt_up as load took them (the upper three None without upper levels)"""
+        i = self.info()
+        n = i["n"]
+        keys, nbr0, cnt0 = np.zeros(n, np.uint64), np.zeros((n, i["m0"]), np.uint32), np.zeros(n, np.uint32)
+        up = i["max_level"] > 0
+        upper_of = np.zeros(n, np.uint32) if up else None
+        nbr_up = np.zeros((i["n_upper"], i["max_level"], i["m"]), np.uint32) if up else None
+        cnt_up = np.zeros((i["n_upper"], i["max_level"]), np.uint32) if up else None
+        _lib.check(_lib.lib().zvec_hip_hnsw_export(self._h, _np_ptr(keys), _np_ptr(nbr0), _np_ptr(cnt0), _np_ptr(upper_of), _np_ptr(nbr_up),
+                                                   _np_ptr(cnt_up)), "zvec_hip_hnsw_export")
+        return keys, nbr0, cnt0, upper_of, nbr_up, cnt_up
+
+    def search(self, query, count, ctx, ef, max_scan=0):
+        """HnswSearcher::search_impl: topk, threshold and the exclude bitset (1 bit per node) come from ctx; ef and max_scan are
+        HnswContext's.  Fills ctx like search_impl of the other searchers and returns 0 or a negative IndexError value."""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(query, np.float32).reshape(int(count), -1)
+        if q.shape[1] != self.dim:
+            return IndexError_.Mismatch
+        k = ctx.topk()
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        counts = np.zeros(count, np.uint32)
+        rc = _lib.lib().zvec_hip_hnsw_search(self._h, ctx._h, _np_ptr(q), count, k, int(ef), int(max_scan), ctx.threshold(),
+                                             _np_ptr(ctx._exclude), _np_ptr(keys), _np_ptr(scores), _np_ptr(counts))
+        if rc == 0:
+            ctx._set_results(keys, scores, counts)
+        return rc
+
+    def search_dev(self, d_queries, count, topk, ef, max_scan, d_out_keys, d_out_scores, d_out_counts, ctx, threshold=FLT_MAX,
+                   d_exclude=None, stream=None):
+        """device-pointer form (async): all arguments are raw device pointers (ints)"""
+        return _lib.lib().zvec_hip_hnsw_search_dev(
+            self._h, ctx._h, C.c_void_p(d_queries), count, topk, int(ef), int(max_scan), threshold, C.c_void_p(d_exclude) if d_exclude else None,
+            C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
+
+    def last_stats(self, ctx, count):
+        """(distances computed [count], nodes expanded on level 0 [count], slices) of the last search of this index on ctx"""
+        scanned = np.zeros(count, np.uint32)
+        hops = np.zeros(count, np.uint32)
+        slices = C.c_uint32(0)
+        _lib.check(_lib.lib().zvec_hip_hnsw_last_stats(self._h, ctx._h, count, _np_ptr(scanned), _np_ptr(hops), C.byref(slices)),
+                   "zvec_hip_hnsw_last_stats")
+        return scanned, hops, int(slices.value)
+
+
 def container_segments(image, checksum=False):
     """segment table of a dumped index FILE image (zvec_hip_container_segments): {id: (offset, size)} in file order"""
     image = bytes(image)
