@@ -113,6 +113,7 @@ const char *zvec_hip_error_string(int code); /* IndexError::What analogue */
  *               either way.
  *   "bivf_part_bytes"  1024 .. 2^30 (default 2^30): a zvec_hip_bivf_search keeps the partial lists of one slice of its batch within
  *               this many bytes and answers a batch that needs more in slices of queries.  Same results either way.
+ *   "hnsw_build_round_div"  0 .. 2^20 (default 16), "hnsw_build_round_max"  1 .. 2^20 (default 4096): the rounds of zvec_hip_hnsw_build
  *   "hnsw_ws_bytes"  1024 .. 2^30 (default 2^30): a zvec_hip_hnsw_search keeps the visited bits and candidate regions of one slice of
  *               its batch within this many bytes and answers a batch that needs more in slices of queries.  Same results either way.
  * Unsupported (-12) for an unknown name, invalid argument (-1) for a value outside the option's range. */
@@ -1053,8 +1054,8 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
 /* ---- HNSW: search on a built graph ----------------------------------------------------------
  * stands behind HnswSearcher::search_impl (src/core/algorithm/hnsw/hnsw_searcher.cc) above its brute-force hand-over: the walk of
  * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
- * query.  The handle loads a graph that is already built; building one, reading the reference's dumped HNSW segments
- * (hnsw_searcher_entity.cc), fp16 rows, the cosine metric and group-by are not served.  Small indexes
+ * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below); reading the
+ * reference's dumped HNSW segments (hnsw_searcher_entity.cc), fp16 rows, the cosine metric and group-by are not served.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - fp32 rows; ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
  *     index); every other dtype or metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
@@ -1097,6 +1098,49 @@ int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float 
  * Waits for the context's stream.  NoReady (-21) when the context's last search was not one of `h` or was shorter. */
 int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
                              uint32_t *out_slices);
+
+/* ---- HNSW: building a graph from rows --------------------------------------------------------
+ * stands behind HnswBuilder::train / build (hnsw_builder.cc) and HnswAlgorithm::add_node (hnsw_algorithm.cc:31-81).  The reference
+ * inserts node by node under locks and its graph depends on thread timing; this build inserts in ROUNDS: every node of a round
+ * searches the graph as it stood when the round began, then the links are written (DESIGN §3c "Building" is the specification).
+ * With s nodes in the graph a round takes clamp(s / round_div, 1, round_max) nodes in index order — options "hnsw_build_round_div"
+ * (0 .. 2^20, default 16; 0 = one node per round, the sequential order) and "hnsw_build_round_max" (1 .. 2^20, default 4096) —
+ * and a node above the current top level is a round of its own.  The result depends on nothing but the arguments and the two options.
+ * A field of the parameters left 0 takes the reference's default (hnsw_builder.cc:36-99, hnsw_entity.h): m 50 (upper levels),
+ * m0 2 * m, ef_construction 500, prune_cnt m, scaling_factor m; min_neighbors 0 is its default. */
+typedef struct zvec_hip_hnsw_build_params {
+  uint32_t m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor;
+  uint64_t seed;                       /* of the level generator, when no levels are passed */
+} zvec_hip_hnsw_build_params;
+typedef struct zvec_hip_hnsw_build_info {
+  uint32_t rounds;                     /* after the seed node */
+  uint32_t slices;                     /* the most slices one round's insert phase went in ("hnsw_ws_bytes") */
+  uint32_t top, entry_point;           /* HnswEntity::cur_max_level(), entry_point() after the build */
+  uint64_t dists;                      /* distances the insert phase computed: walks, and candidate-to-kept pairs of the selections */
+  uint64_t requests;                   /* reverse links asked for = neighbours selected */
+  uint64_t prunes;                     /* requests that met a full list (reverse_update_neighbors past its early return) */
+  double insert_ms, reverse_ms;        /* device time of the insert kernels / of sort, grouping and the reverse kernels */
+} zvec_hip_hnsw_build_info;
+#define ZVEC_HIP_HNSW_BUILD_MAX_LEVEL 15
+/* HnswAlgorithm::get_random_level in integer arithmetic (the same levels from C and from Python): with
+ * r = splitmix64(seed + i * 0x9E3779B97F4A7C15) >> 11, where splitmix64(x) is the output of the SplitMix64 generator whose state
+ * before the call is x, the level of node i is the number of k >= 1 with r * scaling_factor^k < 2^53, at most 15:
+ * P(level >= k) = scaling_factor^-k.  Host only.  InvalidArgument for a scaling_factor outside 5 .. 1000 (hnsw_builder.cc:84). */
+int zvec_hip_hnsw_build_levels(uint64_t n, uint32_t scaling_factor, uint64_t seed, uint32_t *out_levels);
+/* HnswBuilder::build: rows [n][dim] fp32 (host), keys [n] or NULL = the position, levels [n] (each <= 15) or NULL = generated.
+ * Replaces the handle's arrays whole under its exclusive lock, like load; search, info, export and get_vectors then serve the built
+ * graph (upper table: upper_of = rank among the nodes of level >= 1, stride = the largest level).  n == 0 and n == 1 are valid.
+ * Unsupported (-12): ef_construction > 512, m0 > 256, m > 128.  InvalidArgument (-31): min_neighbors above m or m0, a level above 15,
+ * a generated level asked for with scaling_factor outside 5 .. 1000.  The insert phase of a round goes in slices of nodes whose
+ * visited bits (ceil(s / 32) * 4 bytes a node with s nodes in the graph) and candidate regions (8 * s bytes a node once s > 1024)
+ * stay within "hnsw_ws_bytes"; the same graph either way. */
+int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+                        const uint32_t *levels);
+/* the same with rows [n][dim] in device memory (keys and levels stay host arrays); synchronous */
+int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const float *d_rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+                            const uint32_t *levels);
+/* what the last build of `h` did; NoReady (-21) before the first one */
+int zvec_hip_hnsw_last_build_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_build_info *out);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,13 @@ reach of the Python model, so the graph is a k-NN graph made on the GPU with the
 m0 / 2 nearest rows plus reverse edges up to m0 = 32; a 1-in-32 sample is level 1, built the same way with m = 16; the entry point
 is the sample's first row.
 
+With --build the graph is a real one: zvec_hip_hnsw_build_dev inserts the rows in rounds on the device (m0 32, m 16,
+--ef-construction, generated levels), and the result carries the build's seconds, rounds and counters beside the same legs.
+
     python tools/hnsw_bench.py [--n 1000000 --dim 768] [--out profiles/hnsw_1m.json]
+    python tools/hnsw_bench.py --build [--ef-construction 200] [--out profiles/hnsw_build_1m.json]
 """
+import time
 import argparse
 import ctypes as C
 import json
@@ -84,6 +89,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--build", action="store_true", help="build the graph with zvec_hip_hnsw_build_dev instead of the k-NN stand-in")
+    ap.add_argument("--ef-construction", type=int, default=200)
     args = ap.parse_args()
     import torch
     import zvec_amd
@@ -96,16 +103,28 @@ def main():
     ts.wait_stream(torch.cuda.current_stream(dev))
     stream = ts.cuda_stream
     torch.cuda.synchronize()
-    knn0, flat = knn_dev(torch, zvec_amd, rows, m0 // 2, stream)
-    nbr0, cnt0 = with_reverse_edges(knn0, m0)
-    sample = np.arange(0, n, 32)
-    knn1, _ = knn_dev(torch, zvec_amd, rows[::32].contiguous(), min(m // 2, sample.size - 1), stream)
-    nbr1, cnt1 = with_reverse_edges(knn1, m)
-    upper_of = np.full(n, 0xffffffff, np.uint32)
-    upper_of[sample] = np.arange(sample.size, dtype=np.uint32)
-    nbr_up = sample[nbr1.astype(np.int64)].astype(np.uint32).reshape(sample.size, 1, m)
     se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
-    assert se.load(rows.cpu().numpy(), nbr0, cnt0, 0, None, upper_of, nbr_up, cnt1.reshape(-1, 1)) == 0
+    built = None
+    if args.build:
+        flat = zvec_amd.HipFlatSearcher(dim, "SquaredEuclidean")
+        assert flat.add_batch_dev(rows.data_ptr(), n) == 0
+        t0 = time.perf_counter()
+        assert se.build_dev(rows.data_ptr(), n, m=m, m0=m0, ef_construction=args.ef_construction, seed=1) == 0
+        built = dict(se.build_info(), build_seconds=time.perf_counter() - t0, ef_construction=args.ef_construction)
+        for name in ("hnsw_build_round_div", "hnsw_build_round_max"):
+            v = C.c_int(0)
+            assert zvec_amd._lib.lib().zvec_hip_get_option(name.encode(), C.byref(v)) == 0
+            built[name] = v.value
+    else:
+        knn0, flat = knn_dev(torch, zvec_amd, rows, m0 // 2, stream)
+        nbr0, cnt0 = with_reverse_edges(knn0, m0)
+        sample = np.arange(0, n, 32)
+        knn1, _ = knn_dev(torch, zvec_amd, rows[::32].contiguous(), min(m // 2, sample.size - 1), stream)
+        nbr1, cnt1 = with_reverse_edges(knn1, m)
+        upper_of = np.full(n, 0xffffffff, np.uint32)
+        upper_of[sample] = np.arange(sample.size, dtype=np.uint32)
+        nbr_up = sample[nbr1.astype(np.int64)].astype(np.uint32).reshape(sample.size, 1, m)
+        assert se.load(rows.cpu().numpy(), nbr0, cnt0, 0, None, upper_of, nbr_up, cnt1.reshape(-1, 1)) == 0
     ctx, fctx = se.create_context(), flat.create_context()
     legs = []
     for batch in (1, 64, 1024):
@@ -138,8 +157,11 @@ def main():
     assert rc == 0, rc
     for leg in legs:
         leg["stream_fraction"] = leg["gathered_gbs"] / gbs.value
-    res = {"workload": "hnsw search %d x %d fp32, k-NN graph m0=%d (+ 1-in-32 level 1, m=%d), k=%d" % (n, dim, m0, m, args.topk),
+    graph = "graph built on the device m0=%d m=%d" % (m0, m) if args.build else "k-NN graph m0=%d (+ 1-in-32 level 1, m=%d)" % (m0, m)
+    res = {"workload": "hnsw search %d x %d fp32, %s, k=%d" % (n, dim, graph, args.topk),
            "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
+    if built is not None:
+        res["build"] = built
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:

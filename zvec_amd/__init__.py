@@ -10,5 +10,5 @@ Package layout (only what the hot path needs):
 from .index import (  # noqa: F401
     DocFilter, Gate, HipBinaryPreselectFlat, HipFlatSearcher, HipShardedIndex, HipFlatStreamer, HipFlatSparseStreamer, HipHammingIVFSearcher, HipHnswSearcher, HipIVFSearcher, HipIVFStreamer, IndexContext, IndexDocument, IndexError_,
     METRIC_L2, METRIC_IP, METRIC_COSINE, metric_from_name, shard_map, container_segments, open_flat_file, open_ivf_file,
-    sparse_from_dense,
+    sparse_from_dense, hnsw_levels,
 )

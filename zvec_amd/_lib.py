@@ -34,6 +34,19 @@ class Segment(C.Structure):
                 ("crc", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class HnswBuildParams(C.Structure):
+    """zvec_hip_hnsw_build_params: a field left 0 takes the reference's default"""
+    _fields_ = [("m", C.c_uint32), ("m0", C.c_uint32), ("ef_construction", C.c_uint32), ("prune_cnt", C.c_uint32),
+                ("min_neighbors", C.c_uint32), ("scaling_factor", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class HnswBuildInfo(C.Structure):
+    """zvec_hip_hnsw_build_info"""
+    _fields_ = [("rounds", C.c_uint32), ("slices", C.c_uint32), ("top", C.c_uint32), ("entry_point", C.c_uint32),
+                ("dists", C.c_uint64), ("requests", C.c_uint64), ("prunes", C.c_uint64), ("insert_ms", C.c_double),
+                ("reverse_ms", C.c_double)]
+
+
 ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 
 # ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes and zvec_hip_bivf_*)
@@ -241,6 +254,10 @@ SYMBOLS = {
     "zvec_hip_hnsw_search_dev": (C.c_int, [_h, _h, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
                                            _u32p, C.c_void_p]),
     "zvec_hip_hnsw_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "zvec_hip_hnsw_build_levels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, _u32p]),
+    "zvec_hip_hnsw_build": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_build_dev": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_last_build_info": (C.c_int, [_h, C.c_void_p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

@@ -66,6 +66,16 @@ int zvec_hip_set_option(const char *name, int value) {
     ropts().hnsw_ws_bytes = value;
     return 0;
   }
+  if (strcmp(name, "hnsw_build_round_div") == 0) {
+    if (value < 0 || value > (1 << 20)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    ropts().hnsw_build_round_div = value;
+    return 0;
+  }
+  if (strcmp(name, "hnsw_build_round_max") == 0) {
+    if (value < 1 || value > (1 << 20)) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+    ropts().hnsw_build_round_max = value;
+    return 0;
+  }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 int zvec_hip_get_option(const char *name, int *value) {
@@ -78,6 +88,8 @@ int zvec_hip_get_option(const char *name, int *value) {
   if (strcmp(name, "sparse_inverted_build") == 0) { *value = ropts().sparse_inverted_build; return 0; }
   if (strcmp(name, "bivf_part_bytes") == 0) { *value = ropts().bivf_part_bytes; return 0; }
   if (strcmp(name, "hnsw_ws_bytes") == 0) { *value = ropts().hnsw_ws_bytes; return 0; }
+  if (strcmp(name, "hnsw_build_round_div") == 0) { *value = ropts().hnsw_build_round_div; return 0; }
+  if (strcmp(name, "hnsw_build_round_max") == 0) { *value = ropts().hnsw_build_round_max; return 0; }
   return ZVEC_HIP_ERR_UNSUPPORTED;
 }
 

@@ -1,6 +1,6 @@
 // api_entry_hnsw.inc.h — C ABI entry points: batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*; inside extern "C").
 // Device code: zvk_hnsw.hip.h.  A handle family of its own beside the flat and IVF handles: it loads a graph somebody else built
-// and walks it by the rule of DESIGN §3c (HnswAlgorithm::search, hnsw_algorithm.cc:83-278).  Nothing here builds a graph.
+// and walks it by the rule of DESIGN §3c (HnswAlgorithm::search, hnsw_algorithm.cc:83-278).  api_entry_hnsw_build.inc.h builds one.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 struct zvec_hip_hnsw_s {
@@ -10,11 +10,13 @@ struct zvec_hip_hnsw_s {
   bool loaded = false;
   uint64_t n = 0;
   uint32_t m0 = 0, m = 0, max_level = 0, n_upper = 0, entry = 0;
-  struct Arrays {                      // everything a load replaces, whole
+  struct Arrays {                      // everything a load or a build replaces, whole
     Scoped<float> rows;                // [n][dpad]
     Scoped<uint64_t> keys;             // [n]
     Scoped<uint32_t> nbr0, cnt0, upper_of, nbr_up, cnt_up;
   } arr;
+  bool built = false;                  // binfo is the last build's
+  zvec_hip_hnsw_build_info binfo{};
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;                  // searches hold it shared, load exclusive (as zvec_hip_flat_s); a context's mutex is taken first

@@ -150,6 +150,10 @@ struct RuntimeOpts {
   // HNSW search (api_entry_hnsw.inc.h): the visited bits and candidate regions of one slice of a batch stay within this many bytes;
   // a batch that needs more goes in slices of queries.  Tests lower it to reach a second slice at small shapes.
   std::atomic<int> hnsw_ws_bytes{1 << 30};
+  // HNSW build (api_entry_hnsw_build.inc.h): with s nodes in the graph the next round inserts clamp(s / round_div, 1, round_max) nodes
+  // against the graph as it stands; round_div 0 = one node per round (the reference's sequential order).  DESIGN §3c "Building".
+  std::atomic<int> hnsw_build_round_div{16};
+  std::atomic<int> hnsw_build_round_max{4096};
   RuntimeOpts() {
     if (const char *e = getenv("ZVEC_HIP_SCAN256")) scan256 = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("ZVEC_HIP_WAIT")) wait = std::max(0, std::min(2, atoi(e)));

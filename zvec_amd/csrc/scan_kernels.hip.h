@@ -41,3 +41,4 @@
 #include "zvk_sparse_put.hip.h"
 #include "zvk_sparse_ingest.hip.h"
 #include "zvk_hnsw.hip.h"
+#include "zvk_hnsw_build.hip.h"

@@ -56,5 +56,6 @@ extern "C" {
 #include "api_entry_sparse_put_dev.inc.h"
 #include "api_entry_sparse_group.inc.h"
 #include "api_entry_hnsw.inc.h"
+#include "api_entry_hnsw_build.inc.h"
 
 }  // extern "C"

@@ -138,59 +138,54 @@ __device__ __forceinline__ bool hnsw_excluded(const HnswArgs &a, uint32_t id) {
   return a.exclude != nullptr && ((a.exclude[id >> 5] >> (id & 31u)) & 1u) != 0;
 }
 
-__global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  const int lane = (int)threadIdx.x;
-  const uint32_t q = blockIdx.x;
-  float *qv = reinterpret_cast<float *>(hnsw_smem);
-  uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
-  uint64_t *C = R + a.ef;
-  uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
-  float *cdist = reinterpret_cast<float *>(coll + 64);
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? a.queries[(size_t)q * a.dim + i] : 0.f;
-  if (lane == 0) coll[0] = a.entry;
-  hnsw_sync(false);
+// the list of node c on level l: level 0 is nbr0 / cnt0, level l >= 1 is slot l - 1 of c's place in the upper table
+__device__ __forceinline__ const uint32_t *hnsw_list(const HnswArgs &a, uint32_t l, uint32_t c, uint32_t &cnt) {
+  if (l == 0) {
+    cnt = hnsw_uni(a.cnt0[c]);
+    return a.nbr0 + (size_t)c * a.m0;
+  }
+  const size_t slot = (size_t)hnsw_uni(a.upper_of[c]) * a.max_level + (l - 1);
+  cnt = hnsw_uni(a.cnt_up[slot]);
+  return a.nbr_up + slot * a.m;
+}
 
-  // 1. the entry point
-  uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances(a, qv, coll, cdist, 1, lane);
-  float dist = cdist[0];
-  hnsw_sync(false);
-
-  // 2. the upper levels: greedy, no visited set, no scan limit
-  for (uint32_t l = a.max_level; l >= 1; --l) {
-    bool changed = true;
-    while (changed) {
-      changed = false;
-      const uint32_t u = hnsw_uni(a.upper_of[ep]);
-      const size_t slot = (size_t)u * a.max_level + (l - 1);
-      const uint32_t cnt = hnsw_uni(a.cnt_up[slot]);
-      const uint32_t *lst = a.nbr_up + slot * a.m;
-      for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
-        const uint32_t nc = min(64u, cnt - c0);
-        uint32_t id = 0;
-        if ((uint32_t)lane < nc) { id = lst[c0 + lane]; coll[lane] = id; }
-        hnsw_sync(false);
-        hnsw_distances(a, qv, coll, cdist, nc, lane);
-        scanned += nc;
-        const float d = (uint32_t)lane < nc ? cdist[lane] : __builtin_inff();
-        float mn = d;
-        for (int o = 32; o >= 1; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
-        if (mn < dist) {                                 // stored order, strict: the first row at the pass's smallest distance
-          const uint64_t at = __ballot((uint32_t)lane < nc && d == mn);
-          if (at != 0) {
-            dist = mn;
-            ep = bcast_u(id, __builtin_ctzll(at));
-            changed = true;
-          }
+// step 2 of the rule on level l >= 1: greedy, no visited set, no scan limit; moves ep / dist
+__device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const float *qv, uint32_t *coll, float *cdist, uint32_t &ep,
+                                            float &dist, uint32_t &scanned, int lane) {
+  bool changed = true;
+  while (changed) {
+    changed = false;
+    uint32_t cnt;
+    const uint32_t *lst = hnsw_list(a, l, ep, cnt);
+    for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
+      const uint32_t nc = min(64u, cnt - c0);
+      uint32_t id = 0;
+      if ((uint32_t)lane < nc) { id = lst[c0 + lane]; coll[lane] = id; }
+      hnsw_sync(false);
+      hnsw_distances(a, qv, coll, cdist, nc, lane);
+      scanned += nc;
+      const float d = (uint32_t)lane < nc ? cdist[lane] : __builtin_inff();
+      float mn = d;
+      for (int o = 32; o >= 1; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
+      if (mn < dist) {                                   // stored order, strict: the first row at the pass's smallest distance
+        const uint64_t at = __ballot((uint32_t)lane < nc && d == mn);
+        if (at != 0) {
+          dist = mn;
+          ep = bcast_u(id, __builtin_ctzll(at));
+          changed = true;
         }
-        hnsw_sync(false);
       }
+      hnsw_sync(false);
     }
   }
+}
 
-  // 3. level 0
-  uint32_t *vis = a.visited + (size_t)q * a.vis_words;
+// step 3 of the rule on level l from ep (at distance dist): fills R (capacity a.ef, ascending) and returns its size.  C is the
+// HNSW_C_LDS words in LDS, G the walk's region of a.ccap words in the workspace (null when a.ccap fits LDS); vis is the walk's
+// visited bits, zero on entry.  The search kernel calls it on level 0, the build (zvk_hnsw_build.hip.h) on every level.
+__device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, const float *qv, uint64_t *R, uint64_t *C, uint64_t *G,
+                                              uint32_t *coll, float *cdist, uint32_t *vis, uint32_t ep, float dist, uint32_t &scanned,
+                                              uint32_t &hops, int lane) {
   if (lane == 0) atomicOr(&vis[ep >> 5], 1u << (ep & 31u));
   uint32_t rsize = 0, csize = 1, chead = 0, cbuf = min(HNSW_C_LDS, a.ccap);
   bool cglob = false;
@@ -204,9 +199,8 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
     const uint64_t top = hnsw_uni64(C[chead]);
     if (rsize == a.ef && (uint32_t)(top >> 32) > (uint32_t)(hnsw_uni64(R[a.ef - 1]) >> 32)) break;
     ++chead; --csize; ++hops;
-    const uint32_t c = (uint32_t)top;
-    const uint32_t cnt = hnsw_uni(a.cnt0[c]);
-    const uint32_t *lst = a.nbr0 + (size_t)c * a.m0;
+    uint32_t cnt;
+    const uint32_t *lst = hnsw_list(a, l, (uint32_t)top, cnt);
     for (uint32_t c0 = 0; c0 < cnt; c0 += 64) {
       const uint32_t nl = min(64u, cnt - c0);
       const bool valid = (uint32_t)lane < nl;
@@ -246,8 +240,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
               hnsw_sync(cglob);
             }
             chead = 0;
-          } else if (!cglob && a.cand_ws != nullptr) {   // LDS is full of live candidates: go on in the query's workspace region
-            uint64_t *G = a.cand_ws + (size_t)q * a.ccap;
+          } else if (!cglob && G != nullptr) {           // LDS is full of live candidates: go on in the walk's workspace region
             for (uint32_t jj = (uint32_t)lane; jj < csize; jj += 64) G[jj] = C[jj];
             C = G;
             cbuf = a.ccap;
@@ -266,6 +259,34 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
       while (csize > 0 && (uint32_t)(hnsw_uni64(C[chead + csize - 1]) >> 32) > worst) --csize;
     }
   }
+  return rsize;
+}
+
+__global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+  const int lane = (int)threadIdx.x;
+  const uint32_t q = blockIdx.x;
+  float *qv = reinterpret_cast<float *>(hnsw_smem);
+  uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
+  uint64_t *C = R + a.ef;
+  uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
+  float *cdist = reinterpret_cast<float *>(coll + 64);
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? a.queries[(size_t)q * a.dim + i] : 0.f;
+  if (lane == 0) coll[0] = a.entry;
+  hnsw_sync(false);
+
+  // 1. the entry point
+  uint32_t scanned = 1, hops = 0, ep = a.entry;
+  hnsw_distances(a, qv, coll, cdist, 1, lane);
+  float dist = cdist[0];
+  hnsw_sync(false);
+
+  // 2. the upper levels
+  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, qv, coll, cdist, ep, dist, scanned, lane);
+
+  // 3. level 0
+  const uint32_t rsize = hnsw_beam(a, 0, qv, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
+                                   a.visited + (size_t)q * a.vis_words, ep, dist, scanned, hops, lane);
 
   // 4. the first topk of R within the threshold
   const uint32_t lim = min(a.topk, rsize);

@@ -1831,7 +1831,7 @@ class HipHammingIVFSearcher:
 
 class HipHnswSearcher:
     """Batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*): what HnswSearcher::search_impl is above its brute-force
-    hand-over.  fp32 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays; nothing here builds one."""
+    hand-over.  fp32 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays, or built from rows (build)."""
 
     def __init__(self, dim, metric="SquaredEuclidean", device=0, dtype="fp32"):
         self.dim = int(dim)
@@ -1876,6 +1876,44 @@ class HipHnswSearcher:
             upper_of = nbr_up = cnt_up = None
         return _lib.lib().zvec_hip_hnsw_load(self._h, n, _np_ptr(rows), _np_ptr(k), nbr0.shape[1], _np_ptr(nbr0), _np_ptr(cnt0), max_level, m,
                                              n_upper, _np_ptr(upper_of), _np_ptr(nbr_up), _np_ptr(cnt_up), int(entry_point))
+
+    def _build_args(self, n, keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed):
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        lv = None if levels is None else np.ascontiguousarray(levels, np.uint32)
+        if (k is not None and k.size != n) or (lv is not None and lv.size != n):
+            return None
+        p = _lib.HnswBuildParams(int(m), int(m0), int(ef_construction), int(prune_cnt), int(min_neighbors), int(scaling_factor),
+                                 int(seed) & 0xffffffffffffffff)
+        return k, lv, p
+
+    def build(self, rows, keys=None, levels=None, m=0, m0=0, ef_construction=0, prune_cnt=0, min_neighbors=0, scaling_factor=0, seed=0):
+        """HnswBuilder::build: rows [n][dim] in, searchable graph out, by the rounds of DESIGN §3c.  An argument left 0 takes the
+        reference's default (m 50, m0 2m, ef_construction 500, prune_cnt m, scaling_factor m); levels [n] or None = generated
+        (hnsw_levels).  Returns 0 or a negative IndexError value."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        n = rows.shape[0]
+        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+            return IndexError_.Mismatch
+        args = self._build_args(n, keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed)
+        if args is None:
+            return IndexError_.InvalidArgument
+        k, lv, p = args
+        return _lib.lib().zvec_hip_hnsw_build(self._h, n, _np_ptr(rows), _np_ptr(k), C.byref(p), _np_ptr(lv))
+
+    def build_dev(self, d_rows, n, keys=None, levels=None, m=0, m0=0, ef_construction=0, prune_cnt=0, min_neighbors=0, scaling_factor=0,
+                  seed=0):
+        """build with rows [n][dim] fp32 in device memory (a raw device pointer); keys and levels stay host arrays"""
+        args = self._build_args(int(n), keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed)
+        if args is None:
+            return IndexError_.InvalidArgument
+        k, lv, p = args
+        return _lib.lib().zvec_hip_hnsw_build_dev(self._h, int(n), C.c_void_p(d_rows), _np_ptr(k), C.byref(p), _np_ptr(lv))
+
+    def build_info(self):
+        """{rounds, slices, top, entry_point, dists, requests, prunes, insert_ms, reverse_ms} of the last build"""
+        out = _lib.HnswBuildInfo()
+        _lib.check(_lib.lib().zvec_hip_hnsw_last_build_info(self._h, C.byref(out)), "zvec_hip_hnsw_last_build_info")
+        return {k: getattr(out, k) for k, _ in out._fields_}
 
     def info(self):
         """{n, dim, m0, max_level, m, n_upper, entry_point}"""
@@ -1937,6 +1975,14 @@ class HipHnswSearcher:
         _lib.check(_lib.lib().zvec_hip_hnsw_last_stats(self._h, ctx._h, count, _np_ptr(scanned), _np_ptr(hops), C.byref(slices)),
                    "zvec_hip_hnsw_last_stats")
         return scanned, hops, int(slices.value)
+
+
+def hnsw_levels(n, scaling_factor, seed=0):
+    """the levels zvec_hip_hnsw_build gives n nodes when it is passed none (zvec_hip_hnsw_build_levels; host only)"""
+    out = np.zeros(int(n), np.uint32)
+    _lib.check(_lib.lib().zvec_hip_hnsw_build_levels(int(n), int(scaling_factor), int(seed) & 0xffffffffffffffff, _np_ptr(out)),
+               "zvec_hip_hnsw_build_levels")
+    return out
 
 
 def container_segments(image, checksum=False):
