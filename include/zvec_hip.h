@@ -1054,7 +1054,8 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
 /* ---- HNSW: search on a built graph ----------------------------------------------------------
  * stands behind HnswSearcher::search_impl (src/core/algorithm/hnsw/hnsw_searcher.cc) above its brute-force hand-over: the walk of
  * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
- * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below); reading the
+ * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below), and takes more rows
+ * afterwards (zvec_hip_hnsw_add, below); deleting nodes, reading the
  * reference's dumped HNSW segments (hnsw_searcher_entity.cc), fp16 rows, the cosine metric and group-by are not served.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - fp32 rows; ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
@@ -1133,7 +1134,7 @@ int zvec_hip_hnsw_build_levels(uint64_t n, uint32_t scaling_factor, uint64_t see
  * Unsupported (-12): ef_construction > 512, m0 > 256, m > 128.  InvalidArgument (-31): min_neighbors above m or m0, a level above 15,
  * a generated level asked for with scaling_factor outside 5 .. 1000.  The insert phase of a round goes in slices of nodes whose
  * visited bits (ceil(s / 32) * 4 bytes a node with s nodes in the graph) and candidate regions (8 * s bytes a node once s > 1024)
- * stay within "hnsw_ws_bytes"; the same graph either way. */
+ * stay within "hnsw_ws_bytes"; the same graph either way.  The handle remembers the parameters for later adds. */
 int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                         const uint32_t *levels);
 /* the same with rows [n][dim] in device memory (keys and levels stay host arrays); synchronous */
@@ -1141,6 +1142,47 @@ int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const float *d_rows, 
                             const uint32_t *levels);
 /* what the last build of `h` did; NoReady (-21) before the first one */
 int zvec_hip_hnsw_last_build_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_build_info *out);
+
+/* ---- HNSW: appending rows to a graph ---------------------------------------------------------
+ * stands behind HnswStreamer::add_impl / add_with_id_impl (src/core/algorithm/hnsw/hnsw_streamer.cc:426-585), which end in
+ * HnswAlgorithm::add_node(id, level, ctx): documents arrive after the index exists, and searches run between the arrivals.  The new
+ * rows take the positions n .. n + count - 1 and are inserted by the build's own rounds, started at s = n nodes (DESIGN §3c
+ * "Appending" is the specification): build(A) then add(B) gives the graph of one build of all rows, except that a round ends at the
+ * call boundary.  With "hnsw_build_round_div" 0, or one row per call, that is the sequential graph.  A call does no work in
+ * proportion to n unless an array must grow or the upper table must be re-strided.  A round of one node applies its reverse links
+ * without sorting them (its targets are distinct and have one source each).  Adds and searches on one handle exclude each other. */
+typedef struct zvec_hip_hnsw_add_info {
+  uint32_t rounds, slices, top, entry_point;       /* as zvec_hip_hnsw_build_info, for this call alone; top / entry_point after it */
+  uint64_t dists, requests, prunes;
+  double insert_ms, reverse_ms;
+  uint64_t first, count;               /* the call's rows took the positions first .. first + count - 1 */
+  uint32_t rounds_one;                 /* of `rounds`, those of one node: reverse links applied without sort and grouping */
+  uint32_t grew_rows, grew_upper;      /* 1: the arrays per row / per upper node were moved into larger ones by this call */
+  uint32_t restrided;                  /* 1: the call held a node above the largest level, and the upper table was re-strided (or made) */
+  uint64_t cap_rows, cap_upper;        /* rows / upper nodes the arrays have room for after the call */
+} zvec_hip_hnsw_add_info;
+/* HnswStreamer::add_impl for count rows at once: rows [count][dim] fp32 (host), keys [count] or NULL = the position, levels [count]
+ * (each <= 15) or NULL = the level zvec_hip_hnsw_build_levels(n + count, scaling_factor, seed) gives each global position, which does
+ * not depend on how the rows were split into calls.  p: NULL, or a field left 0, means the value of the handle's last build, and on a
+ * handle that load filled the reference's default (as zvec_hip_hnsw_build).  InvalidArgument (-31): an m0 that is neither 0 nor the
+ * graph's once it has nodes, an m that is neither 0 nor the graph's once it has upper lists, min_neighbors above m or m0, a level
+ * above 15, rows NULL with count > 0.  Unsupported (-12): the build's limits.  OutOfRange (-17): n + count >=
+ * 0xfffffff0.  Every argument is validated before the handle is touched.  count == 0 succeeds and changes nothing.  On a handle that
+ * holds no graph the call is a build of these rows (node 0 is the seed).  The arrays grow geometrically (device-to-device copies);
+ * a call with a node above the largest level re-strides the upper table once, before its first round, so that export always has the
+ * layout of a build: upper_of = rank among the nodes of level >= 1, stride = the largest level. */
+int zvec_hip_hnsw_add(zvec_hip_hnsw_t h, uint64_t count, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+                      const uint32_t *levels);
+/* the same with rows [count][dim] in device memory (keys and levels stay host arrays); synchronous like build_dev */
+int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const float *d_rows, const uint64_t *keys,
+                          const zvec_hip_hnsw_build_params *p, const uint32_t *levels);
+/* HnswStreamerEntity's chunked storage in one step: room for `rows` rows and `upper_nodes` nodes of level >= 1, so that adds up to
+ * there move nothing.  Never shrinks.  upper_nodes == 0: min(rows, rows / (scaling_factor - 1) + 64) with the scaling_factor of the
+ * last build (the reference's default, m, on a loaded handle) — the expectation rows / scaling_factor times sf / (sf - 1), plus 64.
+ * On a handle that holds no graph yet the sizes are kept for the first add.  load and build allocate exactly what they need. */
+int zvec_hip_hnsw_reserve(zvec_hip_hnsw_t h, uint64_t rows, uint64_t upper_nodes);
+/* what the last add of `h` did; NoReady (-21) before the first one.  zvec_hip_hnsw_last_build_info keeps describing the last build. */
+int zvec_hip_hnsw_last_add_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_add_info *out);
 
 #ifdef __cplusplus
 }

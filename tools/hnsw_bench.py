@@ -11,6 +11,12 @@ With --build the graph is a real one: zvec_hip_hnsw_build_dev inserts the rows i
 
     python tools/hnsw_bench.py [--n 1000000 --dim 768] [--out profiles/hnsw_1m.json]
     python tools/hnsw_bench.py --build [--ef-construction 200] [--out profiles/hnsw_build_1m.json]
+
+With --append the first 90 % of the corpus are built and the last 10 % appended (zvec_hip_hnsw_add_dev) in calls of 1, 64 and 4096
+rows, each call size on a fresh copy of the 90 % graph: rows per second, device ms of the insert and reverse phases, the share of
+rounds that took the one-node path, wall time per call, and recall@10 at ef 128 beside that of one build of all rows.
+
+    python tools/hnsw_bench.py --append [--n 1000000 --dim 768] [--out profiles/hnsw_append_1m.json]
 """
 import time
 import argparse
@@ -81,8 +87,89 @@ def with_reverse_edges(knn, cap):
     return nbr, cnt
 
 
+def append_bench(args, torch, zvec_amd, rows, g, stream):
+    """--append: 90 % of the corpus built, the last 10 % appended in calls of 1, 64 and 4096 rows, each call size on a fresh copy of
+    the 90 % graph (its exported arrays loaded into a new handle); recall@10 at ef 128 beside one build of all rows"""
+    n, dim = rows.shape
+    m0, m, efc = 32, 16, args.ef_construction
+    kw = dict(m=m, m0=m0, ef_construction=efc, scaling_factor=m, seed=1)
+    base = n - n // 10
+    flat = zvec_amd.HipFlatSearcher(dim, "SquaredEuclidean")
+    assert flat.add_batch_dev(rows.data_ptr(), n) == 0
+    batch, ef = 1024, 128
+    dev = rows.device
+    q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+    keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+    scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+    counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    assert flat.search_dev(q.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), flat.create_context(),
+                           stream=stream) == 0
+    torch.cuda.synchronize()
+    truth = keys.cpu().numpy()
+    del flat
+
+    def recall_of(se):
+        assert se.search_dev(q.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), se.create_context(),
+                             stream=stream) == 0
+        torch.cuda.synchronize()
+        got = keys.cpu().numpy()
+        return float(np.mean([len(set(got[i]) & set(truth[i])) / float(args.topk) for i in range(batch)]))
+
+    whole = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+    t0 = time.perf_counter()
+    assert whole.build_dev(rows.data_ptr(), n, **kw) == 0
+    one_build = dict(whole.build_info(), build_seconds=time.perf_counter() - t0, recall=recall_of(whole))
+    del whole
+    part = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+    t0 = time.perf_counter()
+    assert part.build_dev(rows.data_ptr(), base, **kw) == 0
+    part_seconds = time.perf_counter() - t0
+    arrays = part.export()
+    host_rows = rows[:base].cpu().numpy()
+    entry = part.info()["entry_point"]
+    del part
+    legs = []
+    for size in (1, 64, 4096):
+        se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+        k_, nbr0, cnt0, upper_of, nbr_up, cnt_up = arrays
+        assert se.load(host_rows, nbr0, cnt0, entry, k_, upper_of, nbr_up, cnt_up) == 0
+        end = n if size > 1 or args.append_one_rows <= 0 else min(n, base + args.append_one_rows)
+        walls, acc = [], dict(rounds=0, rounds_one=0, insert_ms=0.0, reverse_ms=0.0, dists=0, requests=0, prunes=0, grew=0)
+        torch.cuda.synchronize()
+        t_all = time.perf_counter()
+        for a in range(base, end, size):
+            c = min(size, end - a)
+            t0 = time.perf_counter()
+            assert se.add_dev(rows[a:a + c].data_ptr(), c, **kw) == 0                  # synchronous
+            walls.append(time.perf_counter() - t0)
+            i = se.add_info()
+            for k in ("rounds", "rounds_one", "insert_ms", "reverse_ms", "dists", "requests", "prunes"):
+                acc[k] += i[k]
+            acc["grew"] += int(i["grew_rows"] or i["grew_upper"])
+        total = time.perf_counter() - t_all
+        w = np.array(walls)
+        leg = dict(acc, call_rows=size, rows=end - base, calls=len(walls), seconds=total, rows_per_s=(end - base) / total,
+                   one_node_share=acc["rounds_one"] / max(acc["rounds"], 1), wall_ms_per_call_mean=float(w.mean() * 1e3),
+                   wall_ms_per_call_median=float(np.median(w) * 1e3), wall_ms_per_call_max=float(w.max() * 1e3))
+        if end == n:
+            leg["recall"] = recall_of(se)
+        legs.append(leg)
+        del se
+    res = {"workload": "hnsw append %d x %d fp32: %d rows built (m0=%d m=%d ef_construction=%d), %d appended; recall@%d at ef %d, batch %d"
+                       % (n, dim, base, m0, m, efc, n - base, args.topk, ef, batch),
+           "measured": "once", "build_of_the_first_rows_seconds": part_seconds, "one_build_of_all_rows": one_build, "legs": legs}
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--append", action="store_true", help="90 %% built, 10 %% appended in calls of 1, 64 and 4096 rows (zvec_hip_hnsw_add_dev)")
+    ap.add_argument("--append-one-rows", type=int, default=0, help="rows the one-row-per-call leg appends (0 = the whole 10 %%)")
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--topk", type=int, default=10)
@@ -103,6 +190,8 @@ def main():
     ts.wait_stream(torch.cuda.current_stream(dev))
     stream = ts.cuda_stream
     torch.cuda.synchronize()
+    if args.append:
+        return append_bench(args, torch, zvec_amd, rows, g, stream)
     se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
     built = None
     if args.build:

@@ -47,6 +47,13 @@ class HnswBuildInfo(C.Structure):
                 ("reverse_ms", C.c_double)]
 
 
+class HnswAddInfo(C.Structure):
+    """zvec_hip_hnsw_add_info"""
+    _fields_ = HnswBuildInfo._fields_ + [
+        ("first", C.c_uint64), ("count", C.c_uint64), ("rounds_one", C.c_uint32), ("grew_rows", C.c_uint32), ("grew_upper", C.c_uint32),
+        ("restrided", C.c_uint32), ("cap_rows", C.c_uint64), ("cap_upper", C.c_uint64)]
+
+
 ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 
 # ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes and zvec_hip_bivf_*)
@@ -258,6 +265,10 @@ SYMBOLS = {
     "zvec_hip_hnsw_build": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
     "zvec_hip_hnsw_build_dev": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
     "zvec_hip_hnsw_last_build_info": (C.c_int, [_h, C.c_void_p]),
+    "zvec_hip_hnsw_add": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_add_dev": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_reserve": (C.c_int, [_h, C.c_uint64, C.c_uint64]),
+    "zvec_hip_hnsw_last_add_info": (C.c_int, [_h, C.c_void_p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

@@ -10,13 +10,20 @@ struct zvec_hip_hnsw_s {
   bool loaded = false;
   uint64_t n = 0;
   uint32_t m0 = 0, m = 0, max_level = 0, n_upper = 0, entry = 0;
-  struct Arrays {                      // everything a load or a build replaces, whole
-    Scoped<float> rows;                // [n][dpad]
-    Scoped<uint64_t> keys;             // [n]
-    Scoped<uint32_t> nbr0, cnt0, upper_of, nbr_up, cnt_up;
+  struct Arrays {                      // everything a load or a build replaces, whole, and an add (api_entry_hnsw_add.inc.h) grows
+    Scoped<float> rows;                // [cap_rows][dpad]
+    Scoped<uint64_t> keys;             // [cap_rows]
+    Scoped<uint32_t> nbr0, cnt0, upper_of, nbr_up, cnt_up;      // [cap_rows] each per row; the upper two [cap_upper][max_level]
   } arr;
+  // Room of the arrays, in rows and in nodes of level >= 1 (cap_upper is 0 without upper lists): n and n_upper after a load or a
+  // build, more after an add or a reserve.  Behind n / n_upper the lists and counts are zero and upper_of is IDX_NONE.
+  uint64_t cap_rows = 0, cap_upper = 0;
+  uint64_t want_rows = 0, want_upper = 0;        // what zvec_hip_hnsw_reserve asked for: the least an add grows to
+  zvec_hip_hnsw_build_params params{};           // of the last build (an add on an empty handle is one); all zero after a load
   bool built = false;                  // binfo is the last build's
   zvec_hip_hnsw_build_info binfo{};
+  bool added = false;                  // ainfo is the last add's
+  zvec_hip_hnsw_add_info ainfo{};
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;                  // searches hold it shared, load exclusive (as zvec_hip_flat_s); a context's mutex is taken first
@@ -116,6 +123,8 @@ int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const u
   std::swap(h->arr, a);                          // the old arrays go with the local
   h->n = n; h->m0 = m0; h->m = up ? m : 0; h->max_level = up ? max_level : 0; h->n_upper = up ? n_upper : 0;
   h->entry = n ? entry_point : 0;
+  h->cap_rows = n; h->cap_upper = up ? n_upper : 0;
+  h->params = zvec_hip_hnsw_build_params();
   h->loaded = true;
   h->defctx->hnsw_count = 0;
   return 0;

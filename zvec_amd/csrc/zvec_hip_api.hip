@@ -27,6 +27,7 @@
 #include "host/hole_bits.h"
 #include "host/sparse_put_plan.h"
 #include "host/ivf_layout.h"
+#include "host/hnsw_add_plan.h"
 
 using namespace zvk;
 
@@ -57,5 +58,6 @@ extern "C" {
 #include "api_entry_sparse_group.inc.h"
 #include "api_entry_hnsw.inc.h"
 #include "api_entry_hnsw_build.inc.h"
+#include "api_entry_hnsw_add.inc.h"
 
 }  // extern "C"

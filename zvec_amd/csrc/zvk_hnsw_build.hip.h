@@ -6,6 +6,8 @@
 //   (device radix sort of the request words: level, target, source)
 //   hnsw_groups_kernel   the first word of every (level, target) group
 //   hnsw_reverse_kernel  one wave per group applies its requests in ascending source
+//   hnsw_reverse_one_kernel  a round of ONE node: every used request word is a group of one, no sort and no grouping
+//   hnsw_restride_kernel the upper table under a larger stride (zvec_hip_hnsw_add, api_entry_hnsw_add.inc.h)
 // The walk is the search's own (hnsw_greedy, hnsw_beam, hnsw_put, hnsw_distances of zvk_hnsw.hip.h).
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 #pragma once
@@ -24,8 +26,9 @@ struct HnswBuildArgs {
   HnswArgs g;                   // the frozen graph: ef = ef_construction, max_scan = 2^32 - 1, no exclude bits, entry = the round's
                                 // entry point, ccap = nodes in the graph; visited / cand_ws are the slice's regions, one per wave
   uint32_t *nbr0, *cnt0, *nbr_up, *cnt_up;       // the same lists, writable
-  const uint32_t *levels;       // [n]
-  const uint64_t *req_off;      // [n + 1] first request slot of every node, counted from node 0
+  uint32_t node_base;           // levels and req_off cover the nodes from this one on: 0 in a build, the old node count in an append
+  const uint32_t *levels;       // [nodes from node_base]
+  const uint64_t *req_off;      // [nodes from node_base + 1] first request slot of every such node, counted from node node_base
   uint64_t req_base;            // req_off[first node of the round]
   uint64_t *req;                // the round buffer
   uint32_t round_first, first, top;              // first: the first node of this slice
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
   float *cdist = reinterpret_cast<float *>(coll + 64);
   uint32_t *kept = reinterpret_cast<uint32_t *>(cdist + 64);
   uint32_t *mask = kept + HNSW_BUILD_MAX_M0;
-  const uint32_t li = hnsw_uni(b.levels[i]);
+  const uint32_t li = hnsw_uni(b.levels[i - b.node_base]);
   for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) qv[t] = a.rows[(size_t)i * a.dpad + t];
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
 
   uint32_t *vis = a.visited + (size_t)wv * a.vis_words;
   uint64_t *G = a.cand_ws != nullptr ? a.cand_ws + (size_t)wv * a.ccap : nullptr;
-  uint64_t *req = b.req + (hnsw_uni64(b.req_off[i]) - b.req_base);
+  uint64_t *req = b.req + (hnsw_uni64(b.req_off[i - b.node_base]) - b.req_base);
   uint32_t nreq = 0;
   for (int l = (int)min(li, b.top); l >= 0; --l) {
     const uint32_t cap = l == 0 ? a.m0 : a.m;
@@ -171,82 +174,119 @@ __global__ void hnsw_groups_kernel(const uint64_t *req, uint64_t slots, uint32_t
   if (j == 0 || (req[j - 1] >> HNSW_REQ_SRC_BITS) != (w >> HNSW_REQ_SRC_BITS)) gstart[atomicAdd(ngroups, 1u)] = (uint32_t)j;
 }
 
-// One wave per (level, target) group, grid-stride: the requests of the group in ascending source.  A list with room takes the source
-// at its end; a full list plus the source is sorted by (distance to the target, id) and goes through the keep rule, no shortcut and
-// no fill.  Targets are older than the round and every (level, target) is one group, so no two waves touch one list.
+// The LDS of a reverse wave (hnsw_reverse_lds_bytes)
+struct HnswReverseLds {
+  float *qv, *cv, *cdist;
+  uint64_t *S;
+  uint32_t *coll, *kept;
+  __device__ explicit HnswReverseLds(unsigned char *smem, uint32_t dpad) {
+    qv = reinterpret_cast<float *>(smem);
+    cv = qv + dpad;
+    S = reinterpret_cast<uint64_t *>(cv + dpad);
+    coll = reinterpret_cast<uint32_t *>(S + HNSW_BUILD_MAX_M0 + 2);
+    cdist = reinterpret_cast<float *>(coll + 64);
+    kept = reinterpret_cast<uint32_t *>(cdist + 64);
+  }
+};
+
+// One (level, target) group, by one wave: the words req[j0 .. ) that share req[j0]'s level and target, at most up to jend, in
+// ascending source.  A list with room takes the source at its end; a full list plus the source is sorted by (distance to the target,
+// id) and goes through the keep rule, no shortcut and no fill, and the places the prune emptied are zeroed, so that a list never keeps
+// anything behind its count.  Returns the prunes run.
+__device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, const HnswReverseLds &m, const uint64_t *req, uint64_t j0,
+                                                       uint64_t jend, int lane) {
+  const HnswArgs &a = b.g;
+  const uint64_t head = hnsw_uni64(req[j0]) >> HNSW_REQ_SRC_BITS;
+  const uint32_t l = (uint32_t)(head >> 32), t = (uint32_t)head;
+  const uint32_t cap = l == 0 ? a.m0 : a.m;
+  uint32_t *lst, *lcnt;
+  if (l == 0) {
+    lst = b.nbr0 + (size_t)t * a.m0;
+    lcnt = b.cnt0 + t;
+  } else {
+    const size_t slot = (size_t)hnsw_uni(a.upper_of[t]) * a.max_level + (l - 1);
+    lst = b.nbr_up + slot * a.m;
+    lcnt = b.cnt_up + slot;
+  }
+  uint32_t cnt = hnsw_uni(*lcnt), nprune = 0;
+  bool have_row = false;
+  for (uint64_t j = j0; j < jend; ++j) {
+    const uint64_t w = hnsw_uni64(req[j]);
+    if ((w >> HNSW_REQ_SRC_BITS) != head) break;
+    const uint32_t src = b.round_first + (uint32_t)(w & ((1ull << HNSW_REQ_SRC_BITS) - 1ull));
+    if (cnt < cap) {
+      if (lane == 0) lst[cnt] = src;
+      ++cnt;
+      hnsw_sync(true);
+      continue;
+    }
+    if (!have_row) {
+      for (uint32_t x = (uint32_t)lane; x < a.dpad; x += 64) m.qv[x] = a.rows[(size_t)t * a.dpad + x];
+      have_row = true;
+      hnsw_sync(false);
+    }
+    uint32_t ssize = 0;
+    for (uint32_t c0 = 0; c0 < cap + 1; c0 += 64) {
+      const uint32_t nc = min(64u, cap + 1 - c0);
+      if ((uint32_t)lane < nc) m.coll[lane] = c0 + (uint32_t)lane < cap ? lst[c0 + lane] : src;
+      hnsw_sync(false);
+      hnsw_distances(a, m.qv, m.coll, m.cdist, nc, lane);
+      for (uint32_t jj = 0; jj < nc; ++jj) {
+        const uint64_t word = hnsw_pack(__builtin_bit_cast(float, hnsw_uni(__builtin_bit_cast(uint32_t, m.cdist[jj]))), hnsw_uni(m.coll[jj]));
+        ssize = hnsw_put(m.S, ssize, cap + 1, word, lane, false);
+      }
+      hnsw_sync(false);
+    }
+    uint32_t unused = 0;
+    const uint32_t nk = hnsw_keep(a, m.S, ssize, cap, m.cv, m.kept, nullptr, m.cdist, unused, lane);
+    for (uint32_t x = (uint32_t)lane; x < cap; x += 64) lst[x] = x < nk ? m.kept[x] : 0u;
+    cnt = nk;
+    ++nprune;
+    hnsw_sync(true);
+  }
+  if (lane == 0) *lcnt = cnt;
+  return nprune;
+}
+
+// One wave per (level, target) group of the sorted round buffer, grid-stride.  Targets are older than the round and every
+// (level, target) is one group, so no two waves touch one list.
 __global__ __launch_bounds__(64) void hnsw_reverse_kernel(HnswBuildArgs b, const uint64_t *req, uint64_t slots, const uint32_t *gstart,
                                                           const uint32_t *ngroups) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  const HnswArgs &a = b.g;
   const int lane = (int)threadIdx.x;
-  float *qv = reinterpret_cast<float *>(hnsw_smem);
-  float *cv = qv + a.dpad;
-  uint64_t *S = reinterpret_cast<uint64_t *>(cv + a.dpad);
-  uint32_t *coll = reinterpret_cast<uint32_t *>(S + HNSW_BUILD_MAX_M0 + 2);
-  float *cdist = reinterpret_cast<float *>(coll + 64);
-  uint32_t *kept = reinterpret_cast<uint32_t *>(cdist + 64);
+  const HnswReverseLds m(hnsw_smem, b.g.dpad);
   const uint32_t ng = hnsw_uni(*ngroups);
   uint32_t nprune = 0;
-  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) {
-    const uint64_t j0 = hnsw_uni(gstart[g]);
-    const uint64_t head = hnsw_uni64(req[j0]) >> HNSW_REQ_SRC_BITS;
-    const uint32_t l = (uint32_t)(head >> 32), t = (uint32_t)head;
-    const uint32_t cap = l == 0 ? a.m0 : a.m;
-    uint32_t *lst, *lcnt;
-    if (l == 0) {
-      lst = b.nbr0 + (size_t)t * a.m0;
-      lcnt = b.cnt0 + t;
-    } else {
-      const size_t slot = (size_t)hnsw_uni(a.upper_of[t]) * a.max_level + (l - 1);
-      lst = b.nbr_up + slot * a.m;
-      lcnt = b.cnt_up + slot;
-    }
-    uint32_t cnt = hnsw_uni(*lcnt);
-    bool have_row = false;
-    for (uint64_t j = j0; j < slots; ++j) {
-      const uint64_t w = hnsw_uni64(req[j]);
-      if ((w >> HNSW_REQ_SRC_BITS) != head) break;
-      const uint32_t src = b.round_first + (uint32_t)(w & ((1ull << HNSW_REQ_SRC_BITS) - 1ull));
-      if (cnt < cap) {
-        if (lane == 0) lst[cnt] = src;
-        ++cnt;
-        hnsw_sync(true);
-        continue;
-      }
-      if (!have_row) {
-        for (uint32_t x = (uint32_t)lane; x < a.dpad; x += 64) qv[x] = a.rows[(size_t)t * a.dpad + x];
-        have_row = true;
-        hnsw_sync(false);
-      }
-      uint32_t ssize = 0;
-      for (uint32_t c0 = 0; c0 < cap + 1; c0 += 64) {
-        const uint32_t nc = min(64u, cap + 1 - c0);
-        if ((uint32_t)lane < nc) coll[lane] = c0 + (uint32_t)lane < cap ? lst[c0 + lane] : src;
-        hnsw_sync(false);
-        hnsw_distances(a, qv, coll, cdist, nc, lane);
-        for (uint32_t jj = 0; jj < nc; ++jj) {
-          const uint64_t word = hnsw_pack(__builtin_bit_cast(float, hnsw_uni(__builtin_bit_cast(uint32_t, cdist[jj]))), hnsw_uni(coll[jj]));
-          ssize = hnsw_put(S, ssize, cap + 1, word, lane, false);
-        }
-        hnsw_sync(false);
-      }
-      uint32_t unused = 0;
-      const uint32_t nk = hnsw_keep(a, S, ssize, cap, cv, kept, nullptr, cdist, unused, lane);
-      for (uint32_t x = (uint32_t)lane; x < nk; x += 64) lst[x] = kept[x];
-      cnt = nk;
-      ++nprune;
-      hnsw_sync(true);
-    }
-    if (lane == 0) *lcnt = cnt;
+  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) nprune += hnsw_reverse_group(b, m, req, hnsw_uni(gstart[g]), slots, lane);
+  if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
+}
+
+// The reverse phase of a round of ONE node, on the round buffer as the insert kernel left it: one wave per request slot, grid-stride.
+// The selection of one node on one level holds distinct targets, so the used words are distinct (level, target) pairs with one source
+// each: every used word is a whole group, and no two waves touch one list.
+__global__ __launch_bounds__(64) void hnsw_reverse_one_kernel(HnswBuildArgs b, uint64_t slots) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+  const int lane = (int)threadIdx.x;
+  const HnswReverseLds m(hnsw_smem, b.g.dpad);
+  uint32_t nprune = 0;
+  for (uint64_t j = blockIdx.x; j < slots; j += gridDim.x) {
+    if (hnsw_uni64(b.req[j]) == HNSW_REQ_NONE) continue;
+    nprune += hnsw_reverse_group(b, m, b.req, j, j + 1, lane);
   }
   if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
 }
 
-// after the last round: the places behind a list's count (what a prune left there) read zero, so that a graph exports the same
-// however its lists came to their length
-__global__ void hnsw_tidy_kernel(uint32_t *nbr, const uint32_t *cnt, uint64_t lists, uint32_t width) {
+// The upper table under a larger stride: old slot (u, l) goes to new slot (u, l); the new arrays are zero on entry.  One thread per
+// old neighbour place, and per old count.
+__global__ void hnsw_restride_kernel(const uint32_t *old_nbr, const uint32_t *old_cnt, uint32_t *new_nbr, uint32_t *new_cnt, uint64_t n_upper,
+                                     uint32_t old_stride, uint32_t new_stride, uint32_t m) {
+  const uint64_t per = (uint64_t)old_stride * m;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < lists * width && (uint32_t)(i % width) >= cnt[i / width]) nbr[i] = 0;
+  if (i < n_upper * per) {
+    const uint64_t u = i / per, r = i % per;           // r = l * m + place
+    new_nbr[u * new_stride * m + r] = old_nbr[i];
+  }
+  if (i < n_upper * old_stride) new_cnt[(i / old_stride) * new_stride + i % old_stride] = old_cnt[i];
 }
 
 }  // namespace zvk

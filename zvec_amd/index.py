@@ -1915,6 +1915,55 @@ class HipHnswSearcher:
         _lib.check(_lib.lib().zvec_hip_hnsw_last_build_info(self._h, C.byref(out)), "zvec_hip_hnsw_last_build_info")
         return {k: getattr(out, k) for k, _ in out._fields_}
 
+    def _add_args(self, n, keys, levels, params):
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        lv = None if levels is None else np.ascontiguousarray(levels, np.uint32)
+        if (k is not None and k.size != n) or (lv is not None and lv.size != n):
+            return None
+        names = [f for f, _ in _lib.HnswBuildParams._fields_]
+        if any(x not in names for x in params):
+            raise TypeError("unknown HNSW parameter among %s" % sorted(params))
+        p = None
+        if params:
+            p = _lib.HnswBuildParams(*[int(params.get(f, 0)) & (0xffffffffffffffff if f == "seed" else 0xffffffff) for f in names])
+        return k, lv, p
+
+    def add(self, rows, keys=None, levels=None, **params):
+        """HnswStreamer::add_impl for rows [count][dim] at once: they take the positions n .. n + count - 1 and are inserted by the
+        rounds of DESIGN §3c "Appending".  params (m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed): one left
+        out or 0 takes the value of the last build (the reference's default on a loaded handle).  Returns 0 or a negative
+        IndexError value."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        n = rows.shape[0]
+        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+            return IndexError_.Mismatch
+        args = self._add_args(n, keys, levels, params)
+        if args is None:
+            return IndexError_.InvalidArgument
+        k, lv, p = args
+        return _lib.lib().zvec_hip_hnsw_add(self._h, n, _np_ptr(rows), _np_ptr(k), C.byref(p) if p is not None else None, _np_ptr(lv))
+
+    def add_dev(self, d_rows, n, keys=None, levels=None, **params):
+        """add with rows [n][dim] fp32 in device memory (a raw device pointer); keys and levels stay host arrays"""
+        args = self._add_args(int(n), keys, levels, params)
+        if args is None:
+            return IndexError_.InvalidArgument
+        k, lv, p = args
+        return _lib.lib().zvec_hip_hnsw_add_dev(self._h, int(n), C.c_void_p(d_rows), _np_ptr(k), C.byref(p) if p is not None else None,
+                                                _np_ptr(lv))
+
+    def reserve(self, rows, upper_nodes=0):
+        """room for `rows` rows and `upper_nodes` nodes of level >= 1 (0: chosen from the scaling factor), so that adds up to there
+        move nothing; never shrinks"""
+        return _lib.lib().zvec_hip_hnsw_reserve(self._h, int(rows), int(upper_nodes))
+
+    def add_info(self):
+        """the fields of build_info for the last add alone, and {first, count, rounds_one, grew_rows, grew_upper, restrided,
+        cap_rows, cap_upper}"""
+        out = _lib.HnswAddInfo()
+        _lib.check(_lib.lib().zvec_hip_hnsw_last_add_info(self._h, C.byref(out)), "zvec_hip_hnsw_last_add_info")
+        return {k: getattr(out, k) for k, _ in out._fields_}
+
     def info(self):
         """{n, dim, m0, max_level, m, n_upper, entry_point}"""
         n = C.c_uint64(0)
