@@ -1056,16 +1056,33 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
  * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below), and takes more rows
  * afterwards (zvec_hip_hnsw_add, below); deleting nodes, reading the
- * reference's dumped HNSW segments (hnsw_searcher_entity.cc), fp16 rows, the cosine metric and group-by are not served.  Small indexes
+ * reference's dumped HNSW segments (hnsw_searcher_entity.cc), the cosine metric and group-by are not served.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
- *   - fp32 rows; ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
- *     index); every other dtype or metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
+ *   - ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
+ *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
+ *   - Element type.  A handle serves ONE element type: ZVEC_HIP_DT_FP32 (float) or, through zvec_hip_hnsw_create_typed,
+ *     ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes) — the reference's HNSW after HalfFloatConverter / HalfFloatReformer.  Every `rows`,
+ *     `queries` and get_vectors `out` pointer below, host or device, is a `const void *` / `void *` read as elements of the handle's
+ *     type, the way zvec_hip_flat_* treats `vecs`; scores are fp32 for either type.  Halves are stored as halves (half the bytes
+ *     held, half the bytes a distance fetches).  Each is widened to fp32 where it is read, which is exact (subnormals included,
+ *     nothing flushed), and from there on the arithmetic is the fp32 handle's, operation for operation and in the same order
+ *     (the reference widens too: distance_matrix_fp16.i, _mm256_cvtph_ps into fp32 accumulators).  So an fp16 handle answers — lists,
+ *     counts, statistics, built and appended graphs and their counters — bit for bit as an fp32 handle given the widened rows and
+ *     queries would.  No half-precision arithmetic.  Values must be finite: inf and NaN are not checked for and give unspecified
+ *     results.  DESIGN §3c "fp16 rows".
  *   - a node is its position 0 .. n-1; exclude_bitset, threshold, out_counts and the fill of the places past out_counts[q]
  *     (key 2^64 - 1, score +inf) are those of zvec_hip_flat_search; an excluded node is walked through but never returned;
  *   - lists are ascending by (score, node); of two candidates or results at one distance the one with the smaller node comes first,
  *     and the largest by (distance, node) leaves a full set — the reference's KeyValueHeap leaves equal keys in heap order. */
 typedef struct zvec_hip_hnsw_s *zvec_hip_hnsw_t;
+/* the fp32 creator: dtype must be ZVEC_HIP_DT_FP32; every other type is ZVEC_HIP_ERR_UNSUPPORTED here, ZVEC_HIP_DT_FP16 included
+ * (callers of this entry hand over float pointers; that behaviour is kept exactly) */
 int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
+/* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16.  Any other type or metric returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
+ * With ZVEC_HIP_DT_FP32 this is zvec_hip_hnsw_create. */
+int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
+/* the element type the handle was created with */
+int zvec_hip_hnsw_dtype(zvec_hip_hnsw_t h, int *dtype);
 int zvec_hip_hnsw_destroy(zvec_hip_hnsw_t h);
 /* HnswSearcher::load in the shape of plain host arrays — what HnswEntity serves the algorithm: get_vector / get_key (rows [n][dim],
  * keys [n], NULL = the position), get_neighbors(0, id) (nbr0 [n][m0] with cnt0 [n] valid entries each), get_neighbors(level >= 1, id)
@@ -1074,24 +1091,24 @@ int zvec_hip_hnsw_destroy(zvec_hip_hnsw_t h);
  * max_level == 0: the upper arrays are not read.  InvalidArgument (-31), the handle untouched, for: a neighbour >= n, a count above
  * m0 / m, entry_point >= n, upper_of beyond n_upper, and — with max_level >= 1 — an entry point or an upper-level neighbour without
  * upper lists.  A second load replaces the first; n == 0 is a valid empty index (every search answers with empty lists). */
-int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
+int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const void *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
                        const uint32_t *cnt0, uint32_t max_level, uint32_t m, uint32_t n_upper, const uint32_t *upper_of,
                        const uint32_t *nbr_up, const uint32_t *cnt_up, uint32_t entry_point);
 /* what load took, read back (every pointer nullable): the shape, rows by position (HnswEntity::get_vector), the other arrays */
 int zvec_hip_hnsw_info(zvec_hip_hnsw_t h, uint64_t *n, uint32_t *dim, uint32_t *m0, uint32_t *max_level, uint32_t *m, uint32_t *n_upper,
                        uint32_t *entry_point);
-int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, float *out);
+int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, void *out);
 int zvec_hip_hnsw_export(zvec_hip_hnsw_t h, uint64_t *keys, uint32_t *nbr0, uint32_t *cnt0, uint32_t *upper_of, uint32_t *nbr_up,
                          uint32_t *cnt_up);
-/* HnswSearcher::search_impl(query, qmeta, count, ctx): queries [count][dim] fp32.  ef: HnswContext's ef (kDefaultEf = 500,
+/* HnswSearcher::search_impl(query, qmeta, count, ctx): queries [count][dim] of the handle's element type.  ef: HnswContext's ef (kDefaultEf = 500,
  * hnsw_params.h); the walk runs with max(ef, topk), above 512 Unsupported (-12).  max_scan: the context's scan limit
  * (reach_scan_limit), counted in distances computed, 0 = n.  Batches go in slices of queries that keep the walk's workspace within
  * the "hnsw_ws_bytes" option (1024 .. 2^30, default 2^30): ceil(n / 32) * 4 bytes per query, plus 8 * min(max_scan, n) bytes per
  * query when min(max_scan, n) > 1024; the same results either way. */
-int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t count, uint32_t topk, uint32_t ef,
+int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *queries, uint32_t count, uint32_t topk, uint32_t ef,
                          uint32_t max_scan, float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
                          uint32_t *out_counts);
-int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
                              uint32_t max_scan, float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                              float *d_out_scores, uint32_t *d_out_counts, void *stream);
 /* HnswContext's debugging counters of the last search of `h` on the context (stats_get_vector's rows, stats_get_neighbors at level 0),
@@ -1128,17 +1145,17 @@ typedef struct zvec_hip_hnsw_build_info {
  * before the call is x, the level of node i is the number of k >= 1 with r * scaling_factor^k < 2^53, at most 15:
  * P(level >= k) = scaling_factor^-k.  Host only.  InvalidArgument for a scaling_factor outside 5 .. 1000 (hnsw_builder.cc:84). */
 int zvec_hip_hnsw_build_levels(uint64_t n, uint32_t scaling_factor, uint64_t seed, uint32_t *out_levels);
-/* HnswBuilder::build: rows [n][dim] fp32 (host), keys [n] or NULL = the position, levels [n] (each <= 15) or NULL = generated.
+/* HnswBuilder::build: rows [n][dim] of the handle's element type (host), keys [n] or NULL = the position, levels [n] (each <= 15) or NULL = generated.
  * Replaces the handle's arrays whole under its exclusive lock, like load; search, info, export and get_vectors then serve the built
  * graph (upper table: upper_of = rank among the nodes of level >= 1, stride = the largest level).  n == 0 and n == 1 are valid.
  * Unsupported (-12): ef_construction > 512, m0 > 256, m > 128.  InvalidArgument (-31): min_neighbors above m or m0, a level above 15,
  * a generated level asked for with scaling_factor outside 5 .. 1000.  The insert phase of a round goes in slices of nodes whose
  * visited bits (ceil(s / 32) * 4 bytes a node with s nodes in the graph) and candidate regions (8 * s bytes a node once s > 1024)
  * stay within "hnsw_ws_bytes"; the same graph either way.  The handle remembers the parameters for later adds. */
-int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const void *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                         const uint32_t *levels);
 /* the same with rows [n][dim] in device memory (keys and levels stay host arrays); synchronous */
-int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const float *d_rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const void *d_rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                             const uint32_t *levels);
 /* what the last build of `h` did; NoReady (-21) before the first one */
 int zvec_hip_hnsw_last_build_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_build_info *out);
@@ -1161,7 +1178,7 @@ typedef struct zvec_hip_hnsw_add_info {
   uint32_t restrided;                  /* 1: the call held a node above the largest level, and the upper table was re-strided (or made) */
   uint64_t cap_rows, cap_upper;        /* rows / upper nodes the arrays have room for after the call */
 } zvec_hip_hnsw_add_info;
-/* HnswStreamer::add_impl for count rows at once: rows [count][dim] fp32 (host), keys [count] or NULL = the position, levels [count]
+/* HnswStreamer::add_impl for count rows at once: rows [count][dim] of the handle's element type (host), keys [count] or NULL = the position, levels [count]
  * (each <= 15) or NULL = the level zvec_hip_hnsw_build_levels(n + count, scaling_factor, seed) gives each global position, which does
  * not depend on how the rows were split into calls.  p: NULL, or a field left 0, means the value of the handle's last build, and on a
  * handle that load filled the reference's default (as zvec_hip_hnsw_build).  InvalidArgument (-31): an m0 that is neither 0 nor the
@@ -1171,10 +1188,10 @@ typedef struct zvec_hip_hnsw_add_info {
  * holds no graph the call is a build of these rows (node 0 is the seed).  The arrays grow geometrically (device-to-device copies);
  * a call with a node above the largest level re-strides the upper table once, before its first round, so that export always has the
  * layout of a build: upper_of = rank among the nodes of level >= 1, stride = the largest level. */
-int zvec_hip_hnsw_add(zvec_hip_hnsw_t h, uint64_t count, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_add(zvec_hip_hnsw_t h, uint64_t count, const void *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                       const uint32_t *levels);
 /* the same with rows [count][dim] in device memory (keys and levels stay host arrays); synchronous like build_dev */
-int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const float *d_rows, const uint64_t *keys,
+int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const void *d_rows, const uint64_t *keys,
                           const zvec_hip_hnsw_build_params *p, const uint32_t *levels);
 /* HnswStreamerEntity's chunked storage in one step: room for `rows` rows and `upper_nodes` nodes of level >= 1, so that adds up to
  * there move nothing.  Never shrinks.  upper_nodes == 0: min(rows, rows / (scaling_factor - 1) + 64) with the scaling_factor of the

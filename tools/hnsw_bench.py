@@ -17,6 +17,17 @@ rows, each call size on a fresh copy of the 90 % graph: rows per second, device 
 rounds that took the one-node path, wall time per call, and recall@10 at ef 128 beside that of one build of all rows.
 
     python tools/hnsw_bench.py --append [--n 1000000 --dim 768] [--out profiles/hnsw_append_1m.json]
+
+With --dtype fp16 (alone, or with --build or --append) the corpus and the queries are rounded to IEEE binary16 first, and the same
+values go through two handles in one process: the fp32 handle (the values widened) and the fp16 handle
+(zvec_hip_hnsw_create_typed(ZVEC_HIP_DT_FP16), the halves as they are).  By the contract of DESIGN §3c "fp16 rows" both walk the same
+graph to the same answers, so the legs differ in time and in bytes alone: ms per step, QPS and the bytes of rows held are reported
+for both, and recall@10 of each against the exact search.  The parent of this option has no fp16 to compare with: the comparison is
+fp16 beside fp32 in the same run.
+
+    python tools/hnsw_bench.py --dtype fp16 [--n 100000 --dim 128] [--out profiles/hnsw_1m_fp16.json]
+    python tools/hnsw_bench.py --dtype fp16 --build [--out profiles/hnsw_build_1m_fp16.json]
+    python tools/hnsw_bench.py --dtype fp16 --append [--out profiles/hnsw_append_1m_fp16.json]
 """
 import time
 import argparse
@@ -87,8 +98,8 @@ def with_reverse_edges(knn, cap):
     return nbr, cnt
 
 
-def append_bench(args, torch, zvec_amd, rows, g, stream):
-    """--append: 90 % of the corpus built, the last 10 % appended in calls of 1, 64 and 4096 rows, each call size on a fresh copy of
+def append_bench(args, torch, zvec_amd, rows, g, stream, dtype="fp32"):
+    """--append (dtype: of the handles; rows and queries hold values of that type, as fp32): 90 % of the corpus built, the last 10 % appended in calls of 1, 64 and 4096 rows, each call size on a fresh copy of
     the 90 % graph (its exported arrays loaded into a new handle); recall@10 at ef 128 beside one build of all rows"""
     n, dim = rows.shape
     m0, m, efc = 32, 16, args.ef_construction
@@ -99,6 +110,8 @@ def append_bench(args, torch, zvec_amd, rows, g, stream):
     batch, ef = 1024, 128
     dev = rows.device
     q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+    if dtype == "fp16":
+        q = q.half().float()
     keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
     scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
     counts = torch.empty((batch,), dtype=torch.int32, device=dev)
@@ -108,6 +121,8 @@ def append_bench(args, torch, zvec_amd, rows, g, stream):
     torch.cuda.synchronize()
     truth = keys.cpu().numpy()
     del flat
+    if dtype == "fp16":                            # what the handles take: the halves themselves
+        rows, q = rows.half(), q.half()
 
     def recall_of(se):
         assert se.search_dev(q.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), se.create_context(),
@@ -116,12 +131,12 @@ def append_bench(args, torch, zvec_amd, rows, g, stream):
         got = keys.cpu().numpy()
         return float(np.mean([len(set(got[i]) & set(truth[i])) / float(args.topk) for i in range(batch)]))
 
-    whole = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+    whole = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean", dtype=dtype)
     t0 = time.perf_counter()
     assert whole.build_dev(rows.data_ptr(), n, **kw) == 0
     one_build = dict(whole.build_info(), build_seconds=time.perf_counter() - t0, recall=recall_of(whole))
     del whole
-    part = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+    part = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean", dtype=dtype)
     t0 = time.perf_counter()
     assert part.build_dev(rows.data_ptr(), base, **kw) == 0
     part_seconds = time.perf_counter() - t0
@@ -131,7 +146,7 @@ def append_bench(args, torch, zvec_amd, rows, g, stream):
     del part
     legs = []
     for size in (1, 64, 4096):
-        se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
+        se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean", dtype=dtype)
         k_, nbr0, cnt0, upper_of, nbr_up, cnt_up = arrays
         assert se.load(host_rows, nbr0, cnt0, entry, k_, upper_of, nbr_up, cnt_up) == 0
         end = n if size > 1 or args.append_one_rows <= 0 else min(n, base + args.append_one_rows)
@@ -156,9 +171,13 @@ def append_bench(args, torch, zvec_amd, rows, g, stream):
             leg["recall"] = recall_of(se)
         legs.append(leg)
         del se
-    res = {"workload": "hnsw append %d x %d fp32: %d rows built (m0=%d m=%d ef_construction=%d), %d appended; recall@%d at ef %d, batch %d"
-                       % (n, dim, base, m0, m, efc, n - base, args.topk, ef, batch),
-           "measured": "once", "build_of_the_first_rows_seconds": part_seconds, "one_build_of_all_rows": one_build, "legs": legs}
+    return {"workload": "hnsw append %d x %d %s: %d rows built (m0=%d m=%d ef_construction=%d), %d appended; recall@%d at ef %d, batch %d"
+                        % (n, dim, dtype, base, m0, m, efc, n - base, args.topk, ef, batch),
+            "measured": "once", "row_bytes_held": n * ((dim + 3) // 4 * 4) * (2 if dtype == "fp16" else 4),
+            "build_of_the_first_rows_seconds": part_seconds, "one_build_of_all_rows": one_build, "legs": legs}
+
+
+def _emit(args, res):
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:
@@ -178,6 +197,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--build", action="store_true", help="build the graph with zvec_hip_hnsw_build_dev instead of the k-NN stand-in")
     ap.add_argument("--ef-construction", type=int, default=200)
+    ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32",
+                    help="fp16: a binary16-representable corpus through the fp32 handle and the fp16 handle, side by side")
     args = ap.parse_args()
     import torch
     import zvec_amd
@@ -186,12 +207,22 @@ def main():
     g = torch.Generator(device=dev)
     g.manual_seed(1)
     rows = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
+    f16 = args.dtype == "fp16"
+    if f16:
+        rows = rows.half().float()                 # every value is a binary16 value: both handles see the same numbers
     ts = torch.cuda.Stream(device=dev)
     ts.wait_stream(torch.cuda.current_stream(dev))
     stream = ts.cuda_stream
     torch.cuda.synchronize()
     if args.append:
-        return append_bench(args, torch, zvec_amd, rows, g, stream)
+        if not f16:
+            return _emit(args, append_bench(args, torch, zvec_amd, rows, g, stream))
+        state = g.get_state()
+        both = {}
+        for dt in ("fp32", "fp16"):
+            g.set_state(state)                     # (the same queries for both)
+            both[dt] = append_bench(args, torch, zvec_amd, rows, g, stream, dt)
+        return _emit(args, {"workload": "hnsw append %d x %d, fp16 beside fp32 on one binary16-representable corpus" % (n, dim), **both})
     se = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean")
     built = None
     if args.build:
@@ -214,10 +245,21 @@ def main():
         upper_of[sample] = np.arange(sample.size, dtype=np.uint32)
         nbr_up = sample[nbr1.astype(np.int64)].astype(np.uint32).reshape(sample.size, 1, m)
         assert se.load(rows.cpu().numpy(), nbr0, cnt0, 0, None, upper_of, nbr_up, cnt1.reshape(-1, 1)) == 0
-    ctx, fctx = se.create_context(), flat.create_context()
+    handles = [("fp32", se, 4)]
+    if f16:
+        # the same graph in an fp16 handle: what the fp32 handle exports, over the halves (with --build the contract says a build of
+        # the halves gives this graph; loading it keeps the bench to one build)
+        se16 = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean", dtype="fp16")
+        k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_ = se.export()
+        assert se16.load(rows.half().cpu().numpy(), nbr0_, cnt0_, se.info()["entry_point"], k_, upper_of_, nbr_up_, cnt_up_) == 0
+        handles.append(("fp16", se16, 2))
+        del k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_
+    fctx = flat.create_context()
     legs = []
     for batch in (1, 64, 1024):
         q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+        if f16:
+            q = q.half().float()
         keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
         scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
         counts = torch.empty((batch,), dtype=torch.int32, device=dev)
@@ -227,16 +269,23 @@ def main():
         torch.cuda.synchronize()
         truth = exact.cpu().numpy()
         for ef in (64, 128, 256):
-            def step():
-                assert se.search_dev(q.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx,
-                                     stream=stream) == 0
-            ms = _timed(torch, ts, args.steps, args.warmup, step)
-            scanned, hops, _ = se.last_stats(ctx, batch)
-            got = keys.cpu().numpy()
-            recall = float(np.mean([len(set(got[i]) & set(truth[i])) / float(args.topk) for i in range(batch)]))
-            gathered = float(scanned.sum()) * dim * 4
-            legs.append({"batch": batch, "ef": ef, "ms_per_step": ms, "qps": batch / ms * 1e3, "recall_at_%d" % args.topk: recall,
-                         "mean_scanned": float(scanned.mean()), "mean_hops": float(hops.mean()), "gathered_gbs": gathered / ms / 1e6})
+            for name, hs, esz in handles:
+                hq = q.half() if esz == 2 else q
+                hctx = hs.create_context()
+
+                def step():
+                    assert hs.search_dev(hq.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), hctx,
+                                         stream=stream) == 0
+                ms = _timed(torch, ts, args.steps, args.warmup, step)
+                scanned, hops, _ = hs.last_stats(hctx, batch)
+                got = keys.cpu().numpy()
+                recall = float(np.mean([len(set(got[i]) & set(truth[i])) / float(args.topk) for i in range(batch)]))
+                gathered = float(scanned.sum()) * dim * esz
+                leg = {"batch": batch, "ef": ef, "ms_per_step": ms, "qps": batch / ms * 1e3, "recall_at_%d" % args.topk: recall,
+                       "mean_scanned": float(scanned.mean()), "mean_hops": float(hops.mean()), "gathered_gbs": gathered / ms / 1e6}
+                if f16:
+                    leg = dict(dtype=name, row_bytes_held=n * ((dim + 3) // 4 * 4) * esz, **leg)
+                legs.append(leg)
     del rows, flat
     torch.cuda.synchronize()
     free, _ = torch.cuda.mem_get_info(dev)
@@ -247,15 +296,12 @@ def main():
     for leg in legs:
         leg["stream_fraction"] = leg["gathered_gbs"] / gbs.value
     graph = "graph built on the device m0=%d m=%d" % (m0, m) if args.build else "k-NN graph m0=%d (+ 1-in-32 level 1, m=%d)" % (m0, m)
-    res = {"workload": "hnsw search %d x %d fp32, %s, k=%d" % (n, dim, graph, args.topk),
+    what = "fp16 beside fp32 on one binary16-representable corpus" if f16 else "fp32"
+    res = {"workload": "hnsw search %d x %d %s, %s, k=%d" % (n, dim, what, graph, args.topk),
            "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
     if built is not None:
         res["build"] = built
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    _emit(args, res)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ import os
 from . import build as _build
 
 _f32p = C.c_void_p
-_valp = C.c_void_p    # sparse values: elements of the handle's type (float or IEEE binary16), `void *` in the header
+_valp = C.c_void_p    # sparse values, HNSW rows and queries: elements of the handle's type (float or IEEE binary16), `void *` in the header
 _u64p = C.c_void_p
 _u32p = C.c_void_p
 _h = C.c_void_p
@@ -250,23 +250,25 @@ SYMBOLS = {
     "zvec_hip_sparse_search_grouped_by_ids": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32,
                                                         C.c_uint32, C.c_uint32, C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
     "zvec_hip_hnsw_create": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_hnsw_create_typed": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_hnsw_dtype": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "zvec_hip_hnsw_destroy": (C.c_int, [_h]),
-    "zvec_hip_hnsw_load": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p,
+    "zvec_hip_hnsw_load": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p,
                                      _u32p, _u32p, C.c_uint32]),
     "zvec_hip_hnsw_info": (C.c_int, [_h, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint32)] * 6),
-    "zvec_hip_hnsw_get_vectors": (C.c_int, [_h, _u64p, C.c_uint64, _f32p]),
+    "zvec_hip_hnsw_get_vectors": (C.c_int, [_h, _u64p, C.c_uint64, _valp]),
     "zvec_hip_hnsw_export": (C.c_int, [_h, _u64p, _u32p, _u32p, _u32p, _u32p, _u32p]),
-    "zvec_hip_hnsw_search": (C.c_int, [_h, _h, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
+    "zvec_hip_hnsw_search": (C.c_int, [_h, _h, _valp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
                                        _u32p]),
-    "zvec_hip_hnsw_search_dev": (C.c_int, [_h, _h, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
+    "zvec_hip_hnsw_search_dev": (C.c_int, [_h, _h, _valp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
                                            _u32p, C.c_void_p]),
     "zvec_hip_hnsw_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "zvec_hip_hnsw_build_levels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, _u32p]),
-    "zvec_hip_hnsw_build": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
-    "zvec_hip_hnsw_build_dev": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_build": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_build_dev": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_void_p, _u32p]),
     "zvec_hip_hnsw_last_build_info": (C.c_int, [_h, C.c_void_p]),
-    "zvec_hip_hnsw_add": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
-    "zvec_hip_hnsw_add_dev": (C.c_int, [_h, C.c_uint64, _f32p, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_add": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_add_dev": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_void_p, _u32p]),
     "zvec_hip_hnsw_reserve": (C.c_int, [_h, C.c_uint64, C.c_uint64]),
     "zvec_hip_hnsw_last_add_info": (C.c_int, [_h, C.c_void_p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),

@@ -6,12 +6,14 @@
 struct zvec_hip_hnsw_s {
   int device = 0;
   int metric = 0;
-  uint32_t dim = 0, dpad = 0;          // dpad: floats per stored row, dim rounded up to 4 (a lane of the kernel loads 16 bytes)
+  int dtype = ZVEC_HIP_DT_FP32;        // of rows and queries: fp32, or fp16 (zvec_hip_hnsw_create_typed); halves are stored as halves
+  uint32_t esz = 4;                    // bytes per element
+  uint32_t dim = 0, dpad = 0;          // dpad: elements per stored row, dim rounded up to 4 (a lane of the kernel loads four elements)
   bool loaded = false;
   uint64_t n = 0;
   uint32_t m0 = 0, m = 0, max_level = 0, n_upper = 0, entry = 0;
   struct Arrays {                      // everything a load or a build replaces, whole, and an add (api_entry_hnsw_add.inc.h) grows
-    Scoped<float> rows;                // [cap_rows][dpad]
+    Scoped<unsigned char> rows;        // [cap_rows][dpad] elements of esz bytes
     Scoped<uint64_t> keys;             // [cap_rows]
     Scoped<uint32_t> nbr0, cnt0, upper_of, nbr_up, cnt_up;      // [cap_rows] each per row; the upper two [cap_upper][max_level]
   } arr;
@@ -27,12 +29,15 @@ struct zvec_hip_hnsw_s {
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;                  // searches hold it shared, load exclusive (as zvec_hip_flat_s); a context's mutex is taken first
+  bool f16() const { return dtype == ZVEC_HIP_DT_FP16; }
+  size_t row_bytes() const { return (size_t)dim * esz; }           // of a row as callers pass it
+  size_t pad_bytes() const { return (size_t)dpad * esz; }          // of a row as it is stored
   ~zvec_hip_hnsw_s() { delete defctx; }
 };
 
-int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
+int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
   if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (dtype != ZVEC_HIP_DT_FP32) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
   if (metric != ZVEC_HIP_METRIC_L2 && metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
   if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS)
   zvec_hip_ctx_s *c = nullptr;
@@ -40,7 +45,21 @@ int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_h
   zvec_hip_hnsw_s *h = new (std::nothrow) zvec_hip_hnsw_s();
   if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
   h->device = device; h->metric = metric; h->dim = dim; h->dpad = (dim + 3) / 4 * 4; h->defctx = c;
+  h->dtype = dtype; h->esz = dtype == ZVEC_HIP_DT_FP16 ? 2 : 4;
   *out = h;
+  return 0;
+}
+
+// the fp32 creator: every other type stays Unsupported here, fp16 included (zvec_hip_hnsw_create_typed takes it)
+int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
+  if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype != ZVEC_HIP_DT_FP32) return ZVEC_HIP_ERR_UNSUPPORTED;
+  return zvec_hip_hnsw_create_typed(dim, dtype, metric, device, out);
+}
+
+int zvec_hip_hnsw_dtype(zvec_hip_hnsw_t h, int *dtype) {
+  if (!h || !dtype) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  *dtype = h->dtype;
   return 0;
 }
 
@@ -82,7 +101,7 @@ static int hnsw_validate(uint64_t n, const void *rows, uint32_t m0, const uint32
 
 // HnswSearcher::load (hnsw_searcher.cc) in the shape of plain arrays: the graph as HnswEntity serves it to the algorithm
 // (get_neighbors(level, id), get_vector(id), get_key(id), entry_point(), cur_max_level())
-int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
+int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const void *rows, const uint64_t *keys, uint32_t m0, const uint32_t *nbr0,
                        const uint32_t *cnt0, uint32_t max_level, uint32_t m, uint32_t n_upper, const uint32_t *upper_of,
                        const uint32_t *nbr_up, const uint32_t *cnt_up, uint32_t entry_point) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -95,12 +114,12 @@ int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const u
   zvec_hip_hnsw_s::Arrays a;
   const bool up = n && max_level >= 1;
   if (n) {
-    ZRET(a.rows.alloc((size_t)n * h->dpad));
+    ZRET(a.rows.alloc((size_t)n * h->pad_bytes()));
     ZRET(a.keys.alloc(n));
     ZRET(a.cnt0.alloc(n));
     ZRET(a.nbr0.alloc(std::max<size_t>((size_t)n * m0, 1)));
-    if (h->dpad != h->dim) ZCHK(hipMemset(a.rows, 0, (size_t)n * h->dpad * 4));
-    ZCHK(hipMemcpy2D(a.rows, (size_t)h->dpad * 4, rows, (size_t)h->dim * 4, (size_t)h->dim * 4, n, hipMemcpyHostToDevice));
+    if (h->dpad != h->dim) ZCHK(hipMemset(a.rows, 0, (size_t)n * h->pad_bytes()));
+    ZCHK(hipMemcpy2D(a.rows, h->pad_bytes(), rows, h->row_bytes(), h->row_bytes(), n, hipMemcpyHostToDevice));
     if (keys) {
       ZCHK(hipMemcpy(a.keys, keys, (size_t)n * 8, hipMemcpyHostToDevice));
     } else {
@@ -144,7 +163,7 @@ int zvec_hip_hnsw_info(zvec_hip_hnsw_t h, uint64_t *n, uint32_t *dim, uint32_t *
   return 0;
 }
 
-int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, float *out) {
+int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint64_t n, void *out) {
   if (!h || (n && (!positions || !out))) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
   std::shared_lock<FairSharedMutex> r(h->rw);
@@ -153,7 +172,8 @@ int zvec_hip_hnsw_get_vectors(zvec_hip_hnsw_t h, const uint64_t *positions, uint
     if (positions[i] >= h->n) return ZVEC_HIP_ERR_NO_EXIST;
   ZCHK(hipSetDevice(h->device));
   for (uint64_t i = 0; i < n; ++i)
-    ZCHK(hipMemcpy(out + (size_t)i * h->dim, h->arr.rows.p + (size_t)positions[i] * h->dpad, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
+    ZCHK(hipMemcpy(static_cast<unsigned char *>(out) + (size_t)i * h->row_bytes(), h->arr.rows.p + (size_t)positions[i] * h->pad_bytes(),
+                   h->row_bytes(), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -178,7 +198,7 @@ int zvec_hip_hnsw_export(zvec_hip_hnsw_t h, uint64_t *keys, uint32_t *nbr0, uint
 // The search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments.  A batch goes in slices of queries so
 // that the visited bits (ceil(n / 32) words per query) and the candidate regions (min(max_scan, n) words of 8 bytes per query, only
 // when that is more than the kernel holds in LDS) stay within the "hnsw_ws_bytes" option; a query's walk does not depend on its slice.
-static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
                                   uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
                                   uint32_t *d_out_counts, hipStream_t s) {
   c->sh.count = 0;              // (no certify step is pending, no flat route and no IVF plan to read back)
@@ -212,11 +232,11 @@ static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const f
     for (uint32_t q0 = 0; q0 < count; q0 += slice, ++slices) {
       const uint32_t mq = std::min(slice, count - q0);
       ZCHK(hipMemsetAsync(vis, 0, (size_t)mq * a.vis_words * 4, s));
-      a.queries = d_queries + (size_t)q0 * h->dim;
+      a.queries = static_cast<const unsigned char *>(d_queries) + (size_t)q0 * h->row_bytes();
       a.visited = vis; a.cand_ws = cand;
       a.out_keys = d_out_keys + (size_t)q0 * topk; a.out_scores = d_out_scores + (size_t)q0 * topk; a.out_counts = d_out_counts + q0;
       a.stats = c->hnsw_stats.as<uint32_t>() + 2 * (size_t)q0;
-      hipLaunchKernelGGL(hnsw_search_kernel, dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
+      hipLaunchKernelGGL(h->f16() ? hnsw_search_kernel<true> : hnsw_search_kernel<false>, dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
       ZCHK(hipGetLastError());
     }
   }
@@ -234,7 +254,7 @@ static int hnsw_search_args(zvec_hip_hnsw_t h, const void *queries, uint32_t cou
 }
 
 // HnswSearcher::search_impl (hnsw_searcher.cc) above the brute-force hand-over, which stays with the caller
-int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
                              uint32_t max_scan, float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys,
                              float *d_out_scores, uint32_t *d_out_counts, void *stream) {
   ZRET(hnsw_search_args(h, d_queries, count, topk, ef, d_out_keys, d_out_scores, d_out_counts));
@@ -248,7 +268,7 @@ int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float 
                                 d_out_counts, pick_stream(c, stream));
 }
 
-int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *queries, uint32_t count, uint32_t topk, uint32_t ef,
+int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *queries, uint32_t count, uint32_t topk, uint32_t ef,
                          uint32_t max_scan, float threshold, const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores,
                          uint32_t *out_counts) {
   ZRET(hnsw_search_args(h, queries, count, topk, ef, out_keys, out_scores, out_counts));
@@ -259,8 +279,8 @@ int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const float *que
   {
     std::shared_lock<FairSharedMutex> r(h->rw);        // the row count the bitset is sized for == the nodes of the graph
     if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-    ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->dim * 4, h->n ? exclude_bitset : nullptr, h->n, count, topk, c->cur));
-    ZRET(hnsw_search_dev_locked(h, c, static_cast<const float *>(c->io_qp), count, topk, ef, max_scan, threshold,
+    ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->row_bytes(), h->n ? exclude_bitset : nullptr, h->n, count, topk, c->cur));
+    ZRET(hnsw_search_dev_locked(h, c, c->io_qp, count, topk, ef, max_scan, threshold,
                                 exclude_bitset && h->n ? c->io_ex.as<uint64_t>() : nullptr, c->io_keys.as<uint64_t>(),
                                 c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur));
   }

@@ -30,7 +30,7 @@ static int hnsw_resize(zvec_hip_hnsw_s *h, uint64_t cap_rows, uint64_t cap_upper
   zvec_hip_hnsw_s::Arrays g;
   hipStream_t s = h->defctx->cur;
   if (grew_rows) {
-    ZRET(hnsw_regrow(g.rows, h->arr.rows, n * h->dpad, (size_t)cap_rows * h->dpad, 0, s));
+    ZRET(hnsw_regrow(g.rows, h->arr.rows, n * h->pad_bytes(), (size_t)cap_rows * h->pad_bytes(), 0, s));
     ZRET(hnsw_regrow(g.keys, h->arr.keys, n, (size_t)cap_rows, 0, s));
     ZRET(hnsw_regrow(g.cnt0, h->arr.cnt0, n, (size_t)cap_rows, 0, s));
     ZRET(hnsw_regrow(g.nbr0, h->arr.nbr0, n * m0, (size_t)cap_rows * m0, 0, s));
@@ -58,7 +58,7 @@ static int hnsw_resize(zvec_hip_hnsw_s *h, uint64_t cap_rows, uint64_t cap_upper
 }
 
 // the caller holds h->mu, the default context's mutex and h->rw exclusively; rows: [count][dim], on the device or on the host
-static int hnsw_add_locked(zvec_hip_hnsw_s *h, uint64_t count64, const float *rows, bool rows_on_device, const uint64_t *keys,
+static int hnsw_add_locked(zvec_hip_hnsw_s *h, uint64_t count64, const void *rows, bool rows_on_device, const uint64_t *keys,
                            const zvec_hip_hnsw_build_params *p, const uint32_t *levels) {
   const bool has = h->loaded && h->n > 0;        // without a graph the call is a build of these rows
   const uint64_t n = has ? h->n : 0;
@@ -94,7 +94,7 @@ static int hnsw_add_locked(zvec_hip_hnsw_s *h, uint64_t count64, const float *ro
   ZRET(hnsw_resize(h, hnsw_grow(h->cap_rows, n + count, h->want_rows), shape.stride ? hnsw_grow(h->cap_upper, shape.n_upper, h->want_upper) : 0,
                    shape.stride, q.m0, q.m, grew_rows, grew_upper));
   // the new rows behind the old ones; their lists and counts are zero already
-  ZCHK(hipMemcpy2D(h->arr.rows.p + (size_t)n * h->dpad, (size_t)h->dpad * 4, rows, (size_t)h->dim * 4, (size_t)h->dim * 4, count,
+  ZCHK(hipMemcpy2D(h->arr.rows.p + (size_t)n * h->pad_bytes(), h->pad_bytes(), rows, h->row_bytes(), h->row_bytes(), count,
                    rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   if (keys) {
     ZCHK(hipMemcpy(h->arr.keys.p + n, keys, (size_t)count * 8, hipMemcpyHostToDevice));
@@ -124,7 +124,7 @@ static int hnsw_add_locked(zvec_hip_hnsw_s *h, uint64_t count64, const float *ro
   return 0;
 }
 
-static int hnsw_add_entry(zvec_hip_hnsw_t h, uint64_t count, const float *rows, bool rows_on_device, const uint64_t *keys,
+static int hnsw_add_entry(zvec_hip_hnsw_t h, uint64_t count, const void *rows, bool rows_on_device, const uint64_t *keys,
                           const zvec_hip_hnsw_build_params *p, const uint32_t *levels) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   ZCHK(hipSetDevice(h->device));
@@ -135,13 +135,13 @@ static int hnsw_add_entry(zvec_hip_hnsw_t h, uint64_t count, const float *rows, 
 }
 
 // HnswStreamer::add_impl (hnsw_streamer.cc:426-503) for count rows: each ends in HnswAlgorithm::add_node(id, level, ctx)
-int zvec_hip_hnsw_add(zvec_hip_hnsw_t h, uint64_t count, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_add(zvec_hip_hnsw_t h, uint64_t count, const void *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                       const uint32_t *levels) {
   return hnsw_add_entry(h, count, rows, false, keys, p, levels);
 }
 
 // the same behind a holder whose rows are in device memory already
-int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const float *d_rows, const uint64_t *keys,
+int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const void *d_rows, const uint64_t *keys,
                           const zvec_hip_hnsw_build_params *p, const uint32_t *levels) {
   return hnsw_add_entry(h, count, d_rows, true, keys, p, levels);
 }

@@ -79,7 +79,7 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const zvec_hip_hnsw_s::Arrays &ar
     uint32_t slices = 0;
     for (uint32_t f = r.first; f < r.end; f += slice, ++slices) {     // (the graph is frozen: a slice sees what every slice sees)
       b.first = f;
-      hipLaunchKernelGGL(hnsw_insert_kernel, dim3(std::min(slice, r.end - f)), dim3(64), lds_ins, s, b);
+      hipLaunchKernelGGL(h->f16() ? hnsw_insert_kernel<true> : hnsw_insert_kernel<false>, dim3(std::min(slice, r.end - f)), dim3(64), lds_ins, s, b);
       ZCHK(hipGetLastError());
     }
     done.slices = std::max(done.slices, slices);
@@ -87,7 +87,7 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const zvec_hip_hnsw_s::Arrays &ar
     const uint64_t slots = req_off[r.end - node_base] - req_off[r.first - node_base];
     if (r.end - r.first == 1) {
       // the reverse phase of one node: every used request word is a (level, target) group of its own
-      hipLaunchKernelGGL(hnsw_reverse_one_kernel, dim3((uint32_t)std::min<uint64_t>(slots, 4096)), dim3(64), lds_rev, s, b, slots);
+      hipLaunchKernelGGL(h->f16() ? hnsw_reverse_one_kernel<true> : hnsw_reverse_one_kernel<false>, dim3((uint32_t)std::min<uint64_t>(slots, 4096)), dim3(64), lds_rev, s, b, slots);
       ZCHK(hipGetLastError());
       ++done.one;
     } else {
@@ -96,8 +96,8 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const zvec_hip_hnsw_s::Arrays &ar
       ZCHK(hipMemsetAsync(ngroups, 0, 4, s));
       hipLaunchKernelGGL(hnsw_groups_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, req_b.p, slots, gstart.p, ngroups.p);
       ZCHK(hipGetLastError());
-      hipLaunchKernelGGL(hnsw_reverse_kernel, dim3((uint32_t)std::min<uint64_t>(slots, 4096)), dim3(64), lds_rev, s, b, req_b.p, slots,
-                         gstart.p, ngroups.p);
+      hipLaunchKernelGGL(h->f16() ? hnsw_reverse_kernel<true> : hnsw_reverse_kernel<false>, dim3((uint32_t)std::min<uint64_t>(slots, 4096)),
+                         dim3(64), lds_rev, s, b, req_b.p, slots, gstart.p, ngroups.p);
       ZCHK(hipGetLastError());
     }
     ZCHK(hipEventRecord(ev[2].e, s));
@@ -116,7 +116,7 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const zvec_hip_hnsw_s::Arrays &ar
 }
 
 // the caller holds h->mu, the default context's mutex and h->rw exclusively; rows: [n][dim], on the device or on the host
-static int hnsw_build_locked(zvec_hip_hnsw_s *h, uint64_t n64, const float *rows, bool rows_on_device, const uint64_t *keys,
+static int hnsw_build_locked(zvec_hip_hnsw_s *h, uint64_t n64, const void *rows, bool rows_on_device, const uint64_t *keys,
                              const zvec_hip_hnsw_build_params *p, const uint32_t *levels) {
   zvec_hip_hnsw_build_params q{};
   ZRET(hnsw_add_params(p, zvec_hip_hnsw_build_params(), 0, 0, 0, q));      // (a build remembers nothing and finds no graph)
@@ -148,12 +148,12 @@ static int hnsw_build_locked(zvec_hip_hnsw_s *h, uint64_t n64, const float *rows
   info.top = top;
   info.entry_point = entry;
   if (n) {
-    ZRET(arr.rows.alloc((size_t)n * h->dpad));
+    ZRET(arr.rows.alloc((size_t)n * h->pad_bytes()));
     ZRET(arr.keys.alloc(n));
     ZRET(arr.cnt0.alloc(n));
     ZRET(arr.nbr0.alloc(std::max<size_t>((size_t)n * q.m0, 1)));
-    if (h->dpad != h->dim) ZCHK(hipMemset(arr.rows, 0, (size_t)n * h->dpad * 4));
-    ZCHK(hipMemcpy2D(arr.rows, (size_t)h->dpad * 4, rows, (size_t)h->dim * 4, (size_t)h->dim * 4, n,
+    if (h->dpad != h->dim) ZCHK(hipMemset(arr.rows, 0, (size_t)n * h->pad_bytes()));
+    ZCHK(hipMemcpy2D(arr.rows, h->pad_bytes(), rows, h->row_bytes(), h->row_bytes(), n,
                      rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     if (keys) {
       ZCHK(hipMemcpy(arr.keys, keys, (size_t)n * 8, hipMemcpyHostToDevice));
@@ -191,7 +191,7 @@ static int hnsw_build_locked(zvec_hip_hnsw_s *h, uint64_t n64, const float *rows
   return 0;
 }
 
-static int hnsw_build_entry(zvec_hip_hnsw_t h, uint64_t n, const float *rows, bool rows_on_device, const uint64_t *keys,
+static int hnsw_build_entry(zvec_hip_hnsw_t h, uint64_t n, const void *rows, bool rows_on_device, const uint64_t *keys,
                             const zvec_hip_hnsw_build_params *p, const uint32_t *levels) {
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   ZCHK(hipSetDevice(h->device));
@@ -202,13 +202,13 @@ static int hnsw_build_entry(zvec_hip_hnsw_t h, uint64_t n, const float *rows, bo
 }
 
 // HnswBuilder::train + build (hnsw_builder.cc): every row goes through HnswAlgorithm::add_node (hnsw_algorithm.cc:31-81)
-int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const float *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_build(zvec_hip_hnsw_t h, uint64_t n, const void *rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                         const uint32_t *levels) {
   return hnsw_build_entry(h, n, rows, false, keys, p, levels);
 }
 
 // the same behind a holder whose rows are in device memory already
-int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const float *d_rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+int zvec_hip_hnsw_build_dev(zvec_hip_hnsw_t h, uint64_t n, const void *d_rows, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
                             const uint32_t *levels) {
   return hnsw_build_entry(h, n, d_rows, true, keys, p, levels);
 }

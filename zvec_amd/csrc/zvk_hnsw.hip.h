@@ -8,6 +8,11 @@
 // are arrays of such words sorted ascending.  R lives in LDS.  C starts in LDS (HNSW_C_LDS words) and moves, once, into the query's
 // region of the context workspace when more than that many candidates are alive at the same time (rows excluded by the caller's
 // bitset are traversed but never fill R, so nothing bounds C below the row count then).
+//
+// Rows and queries are fp32 or IEEE binary16 (template parameter H of everything that touches their memory: H = true, halves).  A half
+// is widened to fp32 where it is read, which is exact (subnormals included, nothing flushed); from there on the arithmetic is the
+// fp32 kernel's own, operation for operation and in the same order, so an fp16 handle answers bit for bit as an fp32 handle given the
+// widened values would (DESIGN §3c "fp16 rows").  LDS holds the query, and the build's candidate row, as fp32 either way.
 #pragma once
 #include "zvk_common.hip.h"
 
@@ -18,7 +23,8 @@ constexpr uint32_t HNSW_C_LDS = 1024;      // words of C held in LDS: 8 KiB per 
 constexpr uint32_t HNSW_MAX_DIM = 4096;    // the query row is kept in LDS
 
 struct HnswArgs {
-  const float *rows;          // [n][dpad] row-major, zero padded; dpad is a multiple of 4 floats (a lane loads 16 bytes)
+  const void *rows;           // [n][dpad] row-major, zero padded; dpad is a multiple of 4 elements (a lane loads 16 bytes of
+                              // fp32, 8 bytes of fp16: the same four elements; an fp16 row is 8-byte aligned and no more)
   const uint64_t *keys;       // [n]
   const uint32_t *nbr0;       // [n][m0]
   const uint32_t *cnt0;       // [n]
@@ -27,7 +33,7 @@ struct HnswArgs {
   const uint32_t *cnt_up;     // [n_upper][max_level]
   uint32_t n, dim, dpad, m0, m, max_level, entry;
   int ip;                     // 0: squared L2, 1: minus the dot product
-  const float *queries;       // [nq][dim]
+  const void *queries;        // [nq][dim], the rows' element type
   const uint32_t *exclude;    // nullable, 1 bit per position
   uint32_t topk, ef, max_scan;
   float threshold;
@@ -44,6 +50,16 @@ struct HnswArgs {
 __host__ __device__ inline size_t hnsw_lds_bytes(uint32_t dpad, uint32_t ef) {
   return (size_t)dpad * 4 + (size_t)ef * 8 + (size_t)HNSW_C_LDS * 8 + 64 * 4 + 64 * 4;
 }
+
+// what differs between the two element types: the element itself, and the four elements a lane loads per step
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <bool H> struct HnswElem { typedef float type; typedef f32x4 step; };
+template <> struct HnswElem<true> { typedef _Float16 type; typedef f16x4 step; };
+__device__ __forceinline__ f32x4 hnsw_widen(f32x4 v) { return v; }
+__device__ __forceinline__ f32x4 hnsw_widen(f16x4 v) { return __builtin_convertvector(v, f32x4); }
+// element i of an array of rows or queries, as fp32
+template <bool H>
+__device__ __forceinline__ float hnsw_elem(const void *p, size_t i) { return (float)static_cast<const typename HnswElem<H>::type *>(p)[i]; }
 
 // what one lane wrote to LDS (or, glob, to the query's workspace region) is visible to the other lanes of its wave afterwards
 __device__ __forceinline__ void hnsw_sync(bool glob) {
@@ -92,17 +108,20 @@ __device__ __forceinline__ uint32_t hnsw_put(uint64_t *A, uint32_t size, uint32_
   return end + 1;
 }
 
-// cdist[r] = the score of row coll[r] for r < nc (nc <= 64).  Sixteen lanes take a row, 16 bytes each per step, four rows in flight
-// per wave; the first step of the next four rows is requested before the current four are reduced across their lanes.
+// cdist[r] = the score of row coll[r] for r < nc (nc <= 64).  Sixteen lanes take a row, four elements each per step (16 bytes of
+// fp32, 8 bytes of fp16), four rows in flight per wave; the first step of the next four rows is requested before the current four are
+// reduced across their lanes.  Element e is component e % 4 of lane (e / 4) % 16 under either type: one summation order.
+template <bool H>
 __device__ __forceinline__ void hnsw_distances(const HnswArgs &a, const float *qv, const uint32_t *coll, float *cdist, uint32_t nc, int lane) {
   const uint32_t grp = (uint32_t)lane >> 4, sub = (uint32_t)lane & 15u;
   const uint32_t nv = a.dpad >> 2;
   const f32x4 *q4 = reinterpret_cast<const f32x4 *>(qv);
-  const f32x4 *rows4 = reinterpret_cast<const f32x4 *>(a.rows);
+  typedef typename HnswElem<H>::step step;
+  const step *rows4 = static_cast<const step *>(a.rows);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   uint32_t r = grp;
-  const f32x4 *row = rows4 + (size_t)coll[r < nc ? r : 0] * nv;
-  f32x4 b0 = sub < nv ? row[sub] : zero;
+  const step *row = rows4 + (size_t)coll[r < nc ? r : 0] * nv;
+  f32x4 b0 = sub < nv ? hnsw_widen(row[sub]) : zero;
   for (uint32_t g = 0; g < nc; g += 4) {
     f32x4 acc = zero;
     if (sub < nv) {
@@ -112,7 +131,7 @@ __device__ __forceinline__ void hnsw_distances(const HnswArgs &a, const float *q
     }
 #pragma unroll 4
     for (uint32_t t = sub + 16; t < nv; t += 16) {
-      const f32x4 b = row[t], x = q4[t];
+      const f32x4 b = hnsw_widen(row[t]), x = q4[t];
       if (a.ip) {
         acc.x = fmaf(b.x, x.x, acc.x); acc.y = fmaf(b.y, x.y, acc.y); acc.z = fmaf(b.z, x.z, acc.z); acc.w = fmaf(b.w, x.w, acc.w);
       } else {
@@ -123,7 +142,7 @@ __device__ __forceinline__ void hnsw_distances(const HnswArgs &a, const float *q
     const uint32_t rcur = r;
     r += 4;
     row = rows4 + (size_t)coll[r < nc ? r : 0] * nv;
-    if (g + 4 < nc) b0 = sub < nv ? row[sub] : zero;     // the next rows' first loads go out before the reduction below
+    if (g + 4 < nc) b0 = sub < nv ? hnsw_widen(row[sub]) : zero;     // the next rows' first loads go out before the reduction below
     float s = (acc.x + acc.y) + (acc.z + acc.w);
     s += __shfl_xor(s, 8, 16);
     s += __shfl_xor(s, 4, 16);
@@ -150,6 +169,7 @@ __device__ __forceinline__ const uint32_t *hnsw_list(const HnswArgs &a, uint32_t
 }
 
 // step 2 of the rule on level l >= 1: greedy, no visited set, no scan limit; moves ep / dist
+template <bool H>
 __device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const float *qv, uint32_t *coll, float *cdist, uint32_t &ep,
                                             float &dist, uint32_t &scanned, int lane) {
   bool changed = true;
@@ -162,7 +182,7 @@ __device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const
       uint32_t id = 0;
       if ((uint32_t)lane < nc) { id = lst[c0 + lane]; coll[lane] = id; }
       hnsw_sync(false);
-      hnsw_distances(a, qv, coll, cdist, nc, lane);
+      hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
       scanned += nc;
       const float d = (uint32_t)lane < nc ? cdist[lane] : __builtin_inff();
       float mn = d;
@@ -183,6 +203,7 @@ __device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const
 // step 3 of the rule on level l from ep (at distance dist): fills R (capacity a.ef, ascending) and returns its size.  C is the
 // HNSW_C_LDS words in LDS, G the walk's region of a.ccap words in the workspace (null when a.ccap fits LDS); vis is the walk's
 // visited bits, zero on entry.  The search kernel calls it on level 0, the build (zvk_hnsw_build.hip.h) on every level.
+template <bool H>
 __device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, const float *qv, uint64_t *R, uint64_t *C, uint64_t *G,
                                               uint32_t *coll, float *cdist, uint32_t *vis, uint32_t ep, float dist, uint32_t &scanned,
                                               uint32_t &hops, int lane) {
@@ -214,7 +235,7 @@ __device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, con
       if (nc == 0) continue;
       if (fresh) coll[__popcll(fm & ((1ull << lane) - 1ull))] = id;
       hnsw_sync(false);
-      hnsw_distances(a, qv, coll, cdist, nc, lane);
+      hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
       scanned += nc;
       // a row that fails `distance < worst(R)` against a full R fails it for good (the worst of a full R never grows): skip those
       uint64_t todo = nc == 64 ? ~0ull : ((1ull << nc) - 1ull);
@@ -262,6 +283,7 @@ __device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, con
   return rsize;
 }
 
+template <bool H>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
   const int lane = (int)threadIdx.x;
@@ -271,21 +293,21 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
   uint64_t *C = R + a.ef;
   uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
   float *cdist = reinterpret_cast<float *>(coll + 64);
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? a.queries[(size_t)q * a.dim + i] : 0.f;
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? hnsw_elem<H>(a.queries, (size_t)q * a.dim + i) : 0.f;
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
 
   // 1. the entry point
   uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances(a, qv, coll, cdist, 1, lane);
+  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
   float dist = cdist[0];
   hnsw_sync(false);
 
   // 2. the upper levels
-  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, qv, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy<H>(a, l, qv, coll, cdist, ep, dist, scanned, lane);
 
   // 3. level 0
-  const uint32_t rsize = hnsw_beam(a, 0, qv, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
+  const uint32_t rsize = hnsw_beam<H>(a, 0, qv, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
                                    a.visited + (size_t)q * a.vis_words, ep, dist, scanned, hops, lane);
 
   // 4. the first topk of R within the threshold

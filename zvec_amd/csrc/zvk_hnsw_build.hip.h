@@ -8,7 +8,8 @@
 //   hnsw_reverse_kernel  one wave per group applies its requests in ascending source
 //   hnsw_reverse_one_kernel  a round of ONE node: every used request word is a group of one, no sort and no grouping
 //   hnsw_restride_kernel the upper table under a larger stride (zvec_hip_hnsw_add, api_entry_hnsw_add.inc.h)
-// The walk is the search's own (hnsw_greedy, hnsw_beam, hnsw_put, hnsw_distances of zvk_hnsw.hip.h).
+// The walk is the search's own (hnsw_greedy, hnsw_beam, hnsw_put, hnsw_distances of zvk_hnsw.hip.h), and so is the template parameter
+// H (rows are halves): a row copied into LDS is widened on the way and kept there as fp32.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 #pragma once
 #include <hipcub/hipcub.hpp>
@@ -47,6 +48,7 @@ __host__ __device__ inline size_t hnsw_reverse_lds_bytes(uint32_t dpad) {
 // c unless some kept s has d(c, s) <= d(c, base); stop at cap.  The candidate's row goes into cv, its distances to the kept ids are
 // computed 64 at a time and one ballot decides.  kept[] receives the ids, mask (nullable) the bit of every kept place of S; ndist
 // grows by the kept ids each candidate was compared with.  Returns the number kept.
+template <bool H>
 __device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t *S, uint32_t ns, uint32_t cap, float *cv, uint32_t *kept,
                                               uint32_t *mask, float *cdist, uint32_t &ndist, int lane) {
   uint32_t nk = 0;
@@ -56,11 +58,11 @@ __device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t 
     const float dc = fkey_inv((uint32_t)(w >> 32));
     bool bad = false;
     if (nk > 0) {
-      for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) cv[t] = a.rows[(size_t)c * a.dpad + t];
+      for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) cv[t] = hnsw_elem<H>(a.rows, (size_t)c * a.dpad + t);
       hnsw_sync(false);
       for (uint32_t k0 = 0; k0 < nk; k0 += 64) {
         const uint32_t nc = min(64u, nk - k0);
-        hnsw_distances(a, cv, kept + k0, cdist, nc, lane);
+        hnsw_distances<H>(a, cv, kept + k0, cdist, nc, lane);
         bad = bad || __ballot((uint32_t)lane < nc && cdist[lane] <= dc) != 0;
         hnsw_sync(false);
       }
@@ -78,6 +80,7 @@ __device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t 
   return nk;
 }
 
+template <bool H>
 __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
   const HnswArgs &a = b.g;
@@ -92,16 +95,16 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
   uint32_t *kept = reinterpret_cast<uint32_t *>(cdist + 64);
   uint32_t *mask = kept + HNSW_BUILD_MAX_M0;
   const uint32_t li = hnsw_uni(b.levels[i - b.node_base]);
-  for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) qv[t] = a.rows[(size_t)i * a.dpad + t];
+  for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) qv[t] = hnsw_elem<H>(a.rows, (size_t)i * a.dpad + t);
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
 
   // 1. the entry point, then greedy on the levels above the node's own
   uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances(a, qv, coll, cdist, 1, lane);
+  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
   float dist = cdist[0];
   hnsw_sync(false);
-  for (uint32_t l = b.top; l > li; --l) hnsw_greedy(a, l, qv, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = b.top; l > li; --l) hnsw_greedy<H>(a, l, qv, coll, cdist, ep, dist, scanned, lane);
 
   uint32_t *vis = a.visited + (size_t)wv * a.vis_words;
   uint64_t *G = a.cand_ws != nullptr ? a.cand_ws + (size_t)wv * a.ccap : nullptr;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
     // 2. W = the beam search's result list on this level; its nearest is the next level's entry point
     for (uint32_t t = (uint32_t)lane; t < a.vis_words; t += 64) vis[t] = 0;
     hnsw_sync(true);
-    const uint32_t rsize = hnsw_beam(a, (uint32_t)l, qv, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
+    const uint32_t rsize = hnsw_beam<H>(a, (uint32_t)l, qv, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
     {
       const uint64_t w0 = hnsw_uni64(R[0]);
       ep = (uint32_t)w0;
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
     } else {
       if (lane < 16) mask[lane] = 0;
       hnsw_sync(false);
-      nk = hnsw_keep(a, R, rsize, cap, cv, kept, mask, cdist, scanned, lane);
+      nk = hnsw_keep<H>(a, R, rsize, cap, cv, kept, mask, cdist, scanned, lane);
       for (uint32_t j = 0; j < rsize && nk < b.min_neighbors; ++j) {
         if ((hnsw_uni(mask[j >> 5]) >> (j & 31u)) & 1u) continue;
         if (lane == 0) kept[nk] = (uint32_t)R[j];
@@ -193,6 +196,7 @@ struct HnswReverseLds {
 // ascending source.  A list with room takes the source at its end; a full list plus the source is sorted by (distance to the target,
 // id) and goes through the keep rule, no shortcut and no fill, and the places the prune emptied are zeroed, so that a list never keeps
 // anything behind its count.  Returns the prunes run.
+template <bool H>
 __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, const HnswReverseLds &m, const uint64_t *req, uint64_t j0,
                                                        uint64_t jend, int lane) {
   const HnswArgs &a = b.g;
@@ -221,7 +225,7 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
       continue;
     }
     if (!have_row) {
-      for (uint32_t x = (uint32_t)lane; x < a.dpad; x += 64) m.qv[x] = a.rows[(size_t)t * a.dpad + x];
+      for (uint32_t x = (uint32_t)lane; x < a.dpad; x += 64) m.qv[x] = hnsw_elem<H>(a.rows, (size_t)t * a.dpad + x);
       have_row = true;
       hnsw_sync(false);
     }
@@ -230,7 +234,7 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
       const uint32_t nc = min(64u, cap + 1 - c0);
       if ((uint32_t)lane < nc) m.coll[lane] = c0 + (uint32_t)lane < cap ? lst[c0 + lane] : src;
       hnsw_sync(false);
-      hnsw_distances(a, m.qv, m.coll, m.cdist, nc, lane);
+      hnsw_distances<H>(a, m.qv, m.coll, m.cdist, nc, lane);
       for (uint32_t jj = 0; jj < nc; ++jj) {
         const uint64_t word = hnsw_pack(__builtin_bit_cast(float, hnsw_uni(__builtin_bit_cast(uint32_t, m.cdist[jj]))), hnsw_uni(m.coll[jj]));
         ssize = hnsw_put(m.S, ssize, cap + 1, word, lane, false);
@@ -238,7 +242,7 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
       hnsw_sync(false);
     }
     uint32_t unused = 0;
-    const uint32_t nk = hnsw_keep(a, m.S, ssize, cap, m.cv, m.kept, nullptr, m.cdist, unused, lane);
+    const uint32_t nk = hnsw_keep<H>(a, m.S, ssize, cap, m.cv, m.kept, nullptr, m.cdist, unused, lane);
     for (uint32_t x = (uint32_t)lane; x < cap; x += 64) lst[x] = x < nk ? m.kept[x] : 0u;
     cnt = nk;
     ++nprune;
@@ -250,6 +254,7 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
 
 // One wave per (level, target) group of the sorted round buffer, grid-stride.  Targets are older than the round and every
 // (level, target) is one group, so no two waves touch one list.
+template <bool H>
 __global__ __launch_bounds__(64) void hnsw_reverse_kernel(HnswBuildArgs b, const uint64_t *req, uint64_t slots, const uint32_t *gstart,
                                                           const uint32_t *ngroups) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
@@ -257,13 +262,14 @@ __global__ __launch_bounds__(64) void hnsw_reverse_kernel(HnswBuildArgs b, const
   const HnswReverseLds m(hnsw_smem, b.g.dpad);
   const uint32_t ng = hnsw_uni(*ngroups);
   uint32_t nprune = 0;
-  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) nprune += hnsw_reverse_group(b, m, req, hnsw_uni(gstart[g]), slots, lane);
+  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) nprune += hnsw_reverse_group<H>(b, m, req, hnsw_uni(gstart[g]), slots, lane);
   if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
 }
 
 // The reverse phase of a round of ONE node, on the round buffer as the insert kernel left it: one wave per request slot, grid-stride.
 // The selection of one node on one level holds distinct targets, so the used words are distinct (level, target) pairs with one source
 // each: every used word is a whole group, and no two waves touch one list.
+template <bool H>
 __global__ __launch_bounds__(64) void hnsw_reverse_one_kernel(HnswBuildArgs b, uint64_t slots) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
   const int lane = (int)threadIdx.x;
@@ -271,7 +277,7 @@ __global__ __launch_bounds__(64) void hnsw_reverse_one_kernel(HnswBuildArgs b, u
   uint32_t nprune = 0;
   for (uint64_t j = blockIdx.x; j < slots; j += gridDim.x) {
     if (hnsw_uni64(b.req[j]) == HNSW_REQ_NONE) continue;
-    nprune += hnsw_reverse_group(b, m, b.req, j, j + 1, lane);
+    nprune += hnsw_reverse_group<H>(b, m, b.req, j, j + 1, lane);
   }
   if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
 }

@@ -1831,15 +1831,19 @@ class HipHammingIVFSearcher:
 
 class HipHnswSearcher:
     """Batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*): what HnswSearcher::search_impl is above its brute-force
-    hand-over.  fp32 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays, or built from rows (build)."""
+    hand-over.  fp32 or fp16 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays, or built from rows
+    (build).  dtype="fp16" (zvec_hip_hnsw_create_typed): rows and queries are stored and passed as IEEE binary16; load / build / add /
+    search take float16 arrays as they are and round float32 arrays to nearest even (astype(float16), what HalfFloatConverter does);
+    the _dev variants take raw pointers to halves; get_vectors_by_ids returns float16.  Scores are fp32."""
 
     def __init__(self, dim, metric="SquaredEuclidean", device=0, dtype="fp32"):
         self.dim = int(dim)
         self.metric = metric_from_name(metric) if isinstance(metric, str) else int(metric)
         self.device = device
-        self.dtype, _ = _dtype_of(dtype)
+        self.dtype, self.np_dtype = _dtype_of(dtype)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().zvec_hip_hnsw_create(self.dim, self.dtype, self.metric, device, C.byref(self._h)), "zvec_hip_hnsw_create")
+        create = "zvec_hip_hnsw_create_typed" if self.dtype == DT_FP16 else "zvec_hip_hnsw_create"
+        _lib.check(getattr(_lib.lib(), create)(self.dim, self.dtype, self.metric, device, C.byref(self._h)), create)
 
     def __del__(self):
         try:
@@ -1855,7 +1859,7 @@ class HipHnswSearcher:
     def load(self, rows, nbr0, cnt0, entry_point=0, keys=None, upper_of=None, nbr_up=None, cnt_up=None):
         """rows [n][dim]; nbr0 [n][m0] with cnt0 [n]; upper levels (all three or none): upper_of [n], nbr_up [n_upper][max_level][m],
         cnt_up [n_upper][max_level]"""
-        rows = np.ascontiguousarray(rows, np.float32)
+        rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
         if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
             return IndexError_.Mismatch
@@ -1890,7 +1894,7 @@ class HipHnswSearcher:
         """HnswBuilder::build: rows [n][dim] in, searchable graph out, by the rounds of DESIGN §3c.  An argument left 0 takes the
         reference's default (m 50, m0 2m, ef_construction 500, prune_cnt m, scaling_factor m); levels [n] or None = generated
         (hnsw_levels).  Returns 0 or a negative IndexError value."""
-        rows = np.ascontiguousarray(rows, np.float32)
+        rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
         if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
             return IndexError_.Mismatch
@@ -1902,7 +1906,7 @@ class HipHnswSearcher:
 
     def build_dev(self, d_rows, n, keys=None, levels=None, m=0, m0=0, ef_construction=0, prune_cnt=0, min_neighbors=0, scaling_factor=0,
                   seed=0):
-        """build with rows [n][dim] fp32 in device memory (a raw device pointer); keys and levels stay host arrays"""
+        """build with rows [n][dim] of the searcher's dtype in device memory (a raw device pointer); keys and levels stay host arrays"""
         args = self._build_args(int(n), keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed)
         if args is None:
             return IndexError_.InvalidArgument
@@ -1933,7 +1937,7 @@ class HipHnswSearcher:
         rounds of DESIGN §3c "Appending".  params (m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed): one left
         out or 0 takes the value of the last build (the reference's default on a loaded handle).  Returns 0 or a negative
         IndexError value."""
-        rows = np.ascontiguousarray(rows, np.float32)
+        rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
         if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
             return IndexError_.Mismatch
@@ -1944,7 +1948,7 @@ class HipHnswSearcher:
         return _lib.lib().zvec_hip_hnsw_add(self._h, n, _np_ptr(rows), _np_ptr(k), C.byref(p) if p is not None else None, _np_ptr(lv))
 
     def add_dev(self, d_rows, n, keys=None, levels=None, **params):
-        """add with rows [n][dim] fp32 in device memory (a raw device pointer); keys and levels stay host arrays"""
+        """add with rows [n][dim] of the searcher's dtype in device memory (a raw device pointer); keys and levels stay host arrays"""
         args = self._add_args(int(n), keys, levels, params)
         if args is None:
             return IndexError_.InvalidArgument
@@ -1974,7 +1978,7 @@ class HipHnswSearcher:
 
     def get_vectors_by_ids(self, positions):
         pos = np.ascontiguousarray(positions, np.uint64)
-        out = np.zeros((pos.size, self.dim), np.float32)
+        out = np.zeros((pos.size, self.dim), self.np_dtype)
         _lib.check(_lib.lib().zvec_hip_hnsw_get_vectors(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_hnsw_get_vectors")
         return out
 
@@ -1996,7 +2000,7 @@ class HipHnswSearcher:
         HnswContext's.  Fills ctx like search_impl of the other searchers and returns 0 or a negative IndexError value."""
         if ctx is None or ctx.topk() == 0:
             return IndexError_.InvalidArgument
-        q = np.ascontiguousarray(query, np.float32).reshape(int(count), -1)
+        q = np.ascontiguousarray(query, self.np_dtype).reshape(int(count), -1)
         if q.shape[1] != self.dim:
             return IndexError_.Mismatch
         k = ctx.topk()
@@ -2011,7 +2015,7 @@ class HipHnswSearcher:
 
     def search_dev(self, d_queries, count, topk, ef, max_scan, d_out_keys, d_out_scores, d_out_counts, ctx, threshold=FLT_MAX,
                    d_exclude=None, stream=None):
-        """device-pointer form (async): all arguments are raw device pointers (ints)"""
+        """device-pointer form (async): all arguments are raw device pointers (ints); the queries are of the searcher's dtype"""
         return _lib.lib().zvec_hip_hnsw_search_dev(
             self._h, ctx._h, C.c_void_p(d_queries), count, topk, int(ef), int(max_scan), threshold, C.c_void_p(d_exclude) if d_exclude else None,
             C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
