@@ -1,6 +1,7 @@
 // test_hnsw_add_plan_cpu.cc — zvec_amd/csrc/host/hnsw_add_plan.h without a GPU and without HIP: the rounds from a base against a
 // restatement, the request offsets of the new nodes, the levels of a range, the capacity steps, the stride decision, the refusals,
-// and a few thousand random call sequences in which the plan of a graph grown call by call is held to DESIGN §3c "Appending".
+// a few thousand random call sequences in which the plan of a graph grown call by call is held to DESIGN §3c "Appending", and the
+// one plan of both entries (hnsw_insert_plan) against the composition of the small functions, in those sequences and in fixed cases.
 // Built by tests/test_hnsw_add_plan_cpu.py with -fsanitize=address,undefined.
 #include <cstdio>
 #include <cstdlib>
@@ -61,6 +62,141 @@ void check_call(const std::vector<uint32_t> &lv, uint32_t base, uint32_t count, 
   }
   EXPECT(count == 0 || next == base + count || (base == 0 && count == 1));
   if (base == 0 && count) EXPECT(off[1] == 0);                                                         // the seed asks for nothing
+}
+
+bool same_shape(const HnswShape &a, const HnswShape &b) {
+  return a.n == b.n && a.cap_rows == b.cap_rows && a.cap_upper == b.cap_upper && a.m0 == b.m0 && a.m == b.m && a.stride == b.stride &&
+         a.n_upper == b.n_upper && a.entry == b.entry;
+}
+bool same_params(const zvec_hip_hnsw_build_params &a, const zvec_hip_hnsw_build_params &b) {
+  return a.m == b.m && a.m0 == b.m0 && a.ef_construction == b.ef_construction && a.prune_cnt == b.prune_cnt &&
+         a.min_neighbors == b.min_neighbors && a.scaling_factor == b.scaling_factor && a.seed == b.seed;
+}
+
+// hnsw_insert_plan against the small functions composed by hand, as the two entries composed them before there was one plan
+void check_plan(const HnswShape &found, const zvec_hip_hnsw_build_params &rem, uint64_t want_rows, uint64_t want_upper, const uint32_t *lv,
+                uint32_t count, const zvec_hip_hnsw_build_params *p, uint32_t div, uint32_t mx, uint64_t budget, bool append, HnswInsertPlan &pl) {
+  EXPECT(hnsw_insert_plan(found, rem, want_rows, want_upper, count, true, p, lv, div, mx, budget, append, pl) == 0);
+  zvec_hip_hnsw_build_params q{};
+  EXPECT(hnsw_add_params(p, rem, found.n, found.m0, found.m, q) == 0 && same_params(q, pl.q));
+  std::vector<uint32_t> levels;
+  EXPECT(hnsw_add_levels(found.n, count, lv, q, levels) == 0 && levels == pl.lv);
+  std::vector<HnswRound> rounds;
+  std::vector<uint64_t> off;
+  uint32_t entry = found.entry, top = found.stride;
+  hnsw_plan_rounds((uint32_t)found.n, levels.data(), count, div, mx, q.m0, q.m, entry, top, rounds, off);
+  EXPECT(pl.base == found.n && pl.count == count && pl.top == top && pl.after.entry == entry && off == pl.req_off && rounds.size() == pl.rounds.size());
+  for (size_t r = 0; r < rounds.size(); ++r)
+    EXPECT(rounds[r].first == pl.rounds[r].first && rounds[r].end == pl.rounds[r].end && rounds[r].entry == pl.rounds[r].entry && rounds[r].top == pl.rounds[r].top);
+  std::vector<uint32_t> upper_of(count);
+  const HnswAddShape sh = hnsw_add_shape(found.stride, found.n_upper, levels.data(), count, upper_of.data());
+  EXPECT(upper_of == pl.upper_of && sh.restride == pl.restride && sh.stride == pl.after.stride && sh.n_upper == pl.after.n_upper);
+  const HnswRoundsNeed need = hnsw_rounds_need(rounds, off, (uint32_t)found.n, budget);
+  EXPECT(need.max_slots == pl.need.max_slots && need.max_ws == pl.need.max_ws && need.multi == pl.need.multi && pl.budget == budget);
+  EXPECT(pl.after.n == found.n + count && pl.after.m0 == q.m0 && pl.after.m == (sh.stride ? q.m : 0));
+  EXPECT(pl.after.cap_rows == hnsw_grow(found.cap_rows, found.n + count, want_rows));
+  EXPECT(pl.after.cap_upper == (sh.stride ? hnsw_grow(found.cap_upper, sh.n_upper, want_upper) : 0));
+  EXPECT(same_shape(hnsw_shape_kept(pl.after), pl.after));                             // what a plan leaves needs no tidying
+}
+
+void insert_plan_cases() {
+  const zvec_hip_hnsw_build_params none{};
+  zvec_hip_hnsw_build_params p{};
+  p.m = 4; p.m0 = 8; p.ef_construction = 16; p.scaling_factor = 5; p.seed = 77;
+  std::vector<uint32_t> lv(600);
+  EXPECT(hnsw_levels_range(0, 600, 5, 77, lv.data()) == 0);
+  uint32_t n_upper = 0;
+  for (uint32_t v : lv) n_upper += v >= 1;
+  EXPECT(n_upper > 60 && n_upper < 300);
+  const HnswShape empty;
+  HnswInsertPlan build, add, gen;
+  // a build: empty shape, nothing remembered, nothing wanted; the capacities are exactly (n, n_upper)
+  check_plan(empty, none, 0, 0, lv.data(), 600, &p, 16, 64, 1 << 20, false, build);
+  EXPECT(build.after.cap_rows == 600 && build.after.cap_upper == n_upper && build.after.n_upper == n_upper && build.restride && build.base == 0);
+  // the same rows as an add on an empty handle that a reserve(600, 300) went before
+  check_plan(empty, none, 600, 300, lv.data(), 600, &p, 16, 64, 1 << 20, true, add);
+  EXPECT(add.after.cap_rows == 600 && add.after.cap_upper == 300 && add.restride && add.rounds.size() == build.rounds.size());
+  add.after.cap_upper = n_upper;
+  EXPECT(same_shape(add.after, build.after) && add.req_off == build.req_off && add.upper_of == build.upper_of);
+  // generated levels are the given ones
+  EXPECT(hnsw_insert_plan(empty, none, 0, 0, 600, true, &p, nullptr, 16, 64, 1 << 20, false, gen) == 0 && gen.lv == lv && same_shape(gen.after, build.after));
+  // count == 0 on a graph: an empty plan, the shape as found
+  HnswShape g = build.after;
+  HnswInsertPlan zero;
+  zero.count = 9;
+  EXPECT(hnsw_insert_plan(g, p, 1000, 1000, 0, false, nullptr, nullptr, 16, 64, 1 << 20, true, zero) == 0);
+  EXPECT(zero.rounds.empty() && zero.lv.empty() && zero.count == 0 && same_shape(zero.after, g) && !zero.restride && zero.q.m0 == 8 && zero.q.seed == 77);
+  // ... and an add of no rows does not ask whether levels could be generated, a build of no rows does (scaling_factor 4)
+  zvec_hip_hnsw_build_params p4 = p;
+  p4.scaling_factor = 4;
+  EXPECT(hnsw_insert_plan(empty, none, 0, 0, 0, false, &p4, nullptr, 16, 64, 1 << 20, true, zero) == 0);
+  EXPECT(hnsw_insert_plan(empty, none, 0, 0, 0, false, &p4, nullptr, 16, 64, 1 << 20, false, zero) == ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  EXPECT(hnsw_insert_plan(empty, none, 0, 0, 0, false, &p, nullptr, 16, 64, 1 << 20, false, zero) == 0);       // a build of no rows
+  EXPECT(zero.rounds.empty() && zero.after.n == 0 && zero.after.m0 == 8 && zero.after.m == 0 && zero.after.cap_rows == 0 && zero.top == 0);
+  // one row on an empty shape: the seed, no round
+  check_plan(empty, none, 0, 0, lv.data(), 1, &p, 16, 64, 1 << 20, false, zero);
+  EXPECT(zero.rounds.empty() && zero.after.n == 1 && zero.after.cap_rows == 1 && zero.after.entry == 0);
+  // a first upper node sets restride, and makes room for the upper table; level-0 rows alone do neither
+  HnswShape flat;
+  flat.n = flat.cap_rows = 10; flat.m0 = 8;
+  const uint32_t first_upper[3] = {0, 2, 0}, level0[3] = {0, 0, 0};
+  HnswInsertPlan up;
+  check_plan(flat, none, 0, 0, first_upper, 3, &p, 16, 64, 1 << 20, true, up);
+  EXPECT(up.restride && up.after.stride == 2 && up.after.n_upper == 1 && up.after.cap_upper == 1 && up.after.m == 4 && up.after.entry == 11 && up.top == 2);
+  EXPECT(up.after.cap_rows == 20);
+  check_plan(flat, none, 0, 0, level0, 3, &p, 16, 64, 1 << 20, true, up);
+  EXPECT(!up.restride && up.after.stride == 0 && up.after.cap_upper == 0 && up.after.m == 0);
+
+  // refusals: the codes of hnsw_add_params and hnsw_add_levels come back as they are, and a refused plan leaves its output alone
+  HnswInsertPlan keep = build;
+  auto refused = [&](int rc, int want) {
+    EXPECT(rc == want);
+    EXPECT(same_shape(keep.after, build.after) && same_params(keep.q, build.q) && keep.lv == build.lv && keep.rounds.size() == build.rounds.size() &&
+           keep.req_off == build.req_off && keep.upper_of == build.upper_of && keep.count == build.count && keep.top == build.top);
+  };
+  auto plan = [&](const HnswShape &found, uint64_t count, bool have_rows, const zvec_hip_hnsw_build_params &pp, const uint32_t *levels, bool append,
+                  uint32_t mx = 64) { return hnsw_insert_plan(found, none, 0, 0, count, have_rows, &pp, levels, 16, mx, 1 << 20, append, keep); };
+  zvec_hip_hnsw_build_params bad = p;
+  bad.m0 = 16;
+  refused(plan(g, 3, true, bad, level0, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);          // m0 disagrees with the graph
+  bad = p; bad.m = 8;
+  refused(plan(g, 3, true, bad, level0, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);          // m disagrees with the upper lists
+  bad = p; bad.ef_construction = 513;
+  refused(plan(g, 3, true, bad, level0, true), ZVEC_HIP_ERR_UNSUPPORTED);
+  refused(plan(empty, 3, true, bad, level0, false), ZVEC_HIP_ERR_UNSUPPORTED);
+  bad = p; bad.m0 = 257;
+  refused(plan(empty, 3, true, bad, level0, false), ZVEC_HIP_ERR_UNSUPPORTED);
+  bad = p; bad.m = 129;
+  refused(plan(empty, 3, true, bad, level0, false), ZVEC_HIP_ERR_UNSUPPORTED);
+  bad = p; bad.min_neighbors = 5;
+  refused(plan(g, 3, true, bad, level0, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  HnswShape no_lists = flat;
+  no_lists.m0 = 0;
+  refused(plan(no_lists, 3, true, none, level0, true), ZVEC_HIP_ERR_UNSUPPORTED);       // a loaded graph without level-0 lists
+  const uint32_t high[3] = {0, 16, 0};
+  refused(plan(g, 3, true, p, high, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);              // a level of 16
+  refused(plan(empty, 3, true, p, high, false), ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  refused(plan(g, 3, true, p4, nullptr, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);          // generated levels want 5 .. 1000
+  refused(plan(g, 0xfffffff0ull, true, p, level0, true), ZVEC_HIP_ERR_OUT_OF_RANGE);
+  refused(plan(g, ~0ull, true, p, level0, true), ZVEC_HIP_ERR_OUT_OF_RANGE);
+  refused(plan(g, 3, false, p, level0, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);           // no rows
+  refused(plan(empty, 3, false, p, level0, false), ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  // where two faults coincide each entry keeps its order: a build tests the range before the rows, an add the rows before the range;
+  // the parameters come first in both
+  refused(plan(empty, 0xfffffff0ull, false, p, level0, false), ZVEC_HIP_ERR_OUT_OF_RANGE);
+  refused(plan(g, 0xfffffff0ull, false, p, level0, true), ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  refused(plan(empty, 0xfffffff0ull, false, bad, level0, false), ZVEC_HIP_ERR_INVALID_ARGUMENT);
+  bad = p; bad.ef_construction = 513;
+  refused(plan(g, 0, false, bad, nullptr, true), ZVEC_HIP_ERR_UNSUPPORTED);             // an add of no rows still reads its parameters
+  // one round of 986896 nodes with 256 + 15 * 128 = 2176 request slots each is 2^31 + 2048 slots, which the sort and the group starts do
+  // not count; one node fewer is 2^31 - 128
+  zvec_hip_hnsw_build_params wide = none;
+  wide.m = 128; wide.m0 = 256; wide.ef_construction = 16;
+  HnswShape big;
+  big.n = big.cap_rows = 1u << 24; big.m0 = 256; big.m = 128; big.stride = 15; big.n_upper = big.cap_upper = 1;
+  std::vector<uint32_t> l15(1u << 20, 15);
+  refused(plan(big, 986896, true, wide, l15.data(), true, 1u << 20), ZVEC_HIP_ERR_UNSUPPORTED);
+  EXPECT(plan(big, 986895, true, wide, l15.data(), true, 1u << 20) == 0 && keep.need.max_slots == (1ull << 31) - 128 && keep.rounds.size() == 1);
 }
 
 void fixed_cases() {
@@ -198,6 +334,10 @@ void random_sequences() {
     size_t rounds = 0;
     uint64_t cap = 0;
     std::vector<uint32_t> upper_of(n);
+    HnswShape shape;                                                                    // of the graph grown by hnsw_insert_plan
+    zvec_hip_hnsw_build_params p{};
+    p.m = m; p.m0 = m0; p.ef_construction = 16;
+    const uint64_t want_rows = it % 4 == 2 ? n / 2 : 0, want_upper = it % 4 == 2 ? 7 : 0;
     while (base < n) {
       const uint32_t count = single ? 1 : 1 + (uint32_t)(rng() % std::min<uint32_t>(n - base, 150));
       const uint32_t e0 = entry, t0 = top;
@@ -222,8 +362,15 @@ void random_sequences() {
       EXPECT(sh.stride == mxl && sh.restride == (mxl > stride));
       stride = sh.stride; n_upper = sh.n_upper;
       EXPECT(top == stride || base + count == 0);                                       // the entry point is on the largest level
-      cap = hnsw_grow(cap, (uint64_t)base + count, 0);
+      cap = hnsw_grow(cap, (uint64_t)base + count, want_rows);
       EXPECT(cap >= (uint64_t)base + count);
+      // the one plan, from the shape the last call left: the same rounds, ranks, stride and capacity as the pieces above
+      EXPECT(shape.n == base && shape.entry == e0 && shape.stride == t0);
+      HnswInsertPlan pl;
+      check_plan(shape, p, want_rows, want_upper, lv.data() + base, count, base ? nullptr : &p, div, mx, 4096, true, pl);
+      EXPECT(pl.rounds.size() == plan.size() && pl.after.entry == entry && pl.top == top && pl.after.stride == stride && pl.after.n_upper == n_upper);
+      EXPECT(pl.after.cap_rows == cap && pl.after.cap_upper >= n_upper && std::equal(pl.upper_of.begin(), pl.upper_of.end(), upper_of.begin() + base));
+      shape = pl.after;
       base += count;
     }
     uint32_t rank = 0;
@@ -244,6 +391,7 @@ int main() {
   fixed_cases();
   levels_and_params();
   capacity_and_stride();
+  insert_plan_cases();
   random_sequences();
   printf("ok\n");
   return 0;

@@ -219,6 +219,51 @@ def test_add_on_an_empty_handle_equals_build():
     _same_graph(se, g._replace(keys=_keys(600)), "after an add of no rows")
 
 
+def test_add_after_a_build_of_no_rows_equals_build():
+    """a handle that built zero rows holds no nodes: the add is the build of its rows, and build_info keeps the empty build"""
+    fx, g, c, _ = B.model_of("l2-div16-max64")
+    fxa = A.Fixture(fx.rows, fx.params, fx.levels, (600,), fx.round_div, fx.round_max, fx.metric)
+    se = _searcher(fx)
+    assert se.add(np.zeros((0, 24), np.float32)) == 0                       # no rows on a fresh handle: nothing happens
+    with pytest.raises(Exception):
+        se.add_info()
+    assert se.info()["n"] == 0
+    # (no levels are passed for no rows, so the build asks for a scaling_factor levels could be generated with)
+    assert se.build(np.zeros((0, 24), np.float32), **dict(_params(fx.params), scaling_factor=5)) == 0
+    empty = se.build_info()
+    assert (empty["rounds"], empty["dists"], empty["requests"], empty["prunes"]) == (0, 0, 0, 0)
+    se, infos = _run(fxa, [A.Call(0, 600, None, None, None, None)], se=se, first_is_build=False)
+    _same_graph(se, g._replace(keys=_keys(600)), "add after a build of no rows")
+    assert _counters(infos[0]) == c and infos[0]["restrided"] == 1 and infos[0]["grew_rows"] == 1
+    assert se.build_info() == empty
+
+
+def _grow(cap, need, reserved):
+    """hnsw_grow (host/hnsw_add_plan.h)"""
+    return cap if need <= cap else max(need, reserved, 2 * cap)
+
+
+def test_a_build_keeps_exact_capacity_even_after_a_reserve():
+    """build(200) leaves room for 200 rows and its own upper nodes, whatever a reserve said before; the add of one row shows it"""
+    fx = B.base("l2", 16, 64)
+    lv = fx.levels
+    nu0, nu1 = int((lv[:200] >= 1).sum()), int((lv[:201] >= 1).sum())
+    assert nu0 > 0
+    for reserve, want_rows, want_upper in ((False, 0, 0), (True, 600, min(600, 600 // 49 + 64))):      # (no build yet: scaling_factor 50)
+        se = _searcher(fx)
+        if reserve:
+            assert se.reserve(600) == 0
+        with _options(hnsw_build_round_div=fx.round_div, hnsw_build_round_max=fx.round_max):
+            assert se.build(fx.rows[:200], levels=lv[:200], **_params(fx.params)) == 0
+            assert se.add(fx.rows[200:201], levels=lv[200:201]) == 0
+        i = se.add_info()
+        assert (i["grew_rows"], i["cap_rows"]) == (1, _grow(200, 201, want_rows)) and i["cap_rows"] == (600 if reserve else 400)
+        cap_upper = _grow(nu0, nu1, want_upper)
+        assert (i["grew_upper"], i["cap_upper"]) == (int(cap_upper > nu0), cap_upper)
+        if lv[200] == 0:
+            assert (i["grew_upper"], i["cap_upper"]) == (0, nu0)
+
+
 def test_generated_levels_do_not_depend_on_the_calls():
     import zvec_amd as zv
     fx = B.base()

@@ -160,6 +160,36 @@ def test_refusals():
 H_MAX_EF = 512
 
 
+def test_a_refused_build_over_a_graph_changes_nothing():
+    """a build replaces the graph only when it succeeds: after two refused builds the handle still holds the first 200 rows of
+    the append model's "cut" fixture, its build info, and answers as before"""
+    import hnsw_add_ref as A
+    fx, calls = A.model_of("cut")
+    g, c = calls[0].graph, calls[0].counters
+    n = g.rows.shape[0]
+    first = B.Fixture(fx.rows[:n], fx.params, fx.levels[:n], fx.round_div, fx.round_max, fx.metric)
+    se = _build(first)
+    before = (se.info(), se.build_info(), se.export())
+    bad = fx.levels[:n].copy()
+    bad[n // 2] = 16
+    p = fx.params
+    assert se.build(fx.rows[:n], levels=bad, m=p.m, m0=p.m0, ef_construction=p.ef_construction) == INVALID
+    assert se.build(fx.rows[:n], levels=fx.levels[:n], m=p.m, m0=p.m0, ef_construction=H_MAX_EF + 1) == UNSUPPORTED
+    assert (se.info(), se.build_info()) == before[:2]
+    for x, y in zip(se.export(), before[2]):
+        assert np.array_equal(x, y)
+    _same(se, g, c, "after two refused builds")
+    q = H.exact_queries(g, np.random.default_rng(9), 8)
+    ctx = se.create_context()
+    ctx.set_topk(10)
+    assert se.search(q, 8, ctx, 16) == 0
+    scanned, hops, _ = se.last_stats(ctx, 8)
+    for i in range(8):
+        r = H.search_model(g, q[i], 10, 16, metric=fx.metric)
+        assert ctx.counts[i] == r.keys.size and np.array_equal(ctx.keys[i, :r.keys.size], r.keys)
+        assert np.array_equal(ctx.scores[i, :r.keys.size], r.scores) and (scanned[i], hops[i]) == (r.scanned, r.hops)
+
+
 @pytest.mark.parametrize("name", ["l2-div16-max64", "ip-div1-max64"])
 def test_search_on_the_built_graph_equals_the_model(name):
     fx, g, c, _ = B.model_of(name)

@@ -1,10 +1,12 @@
 // hnsw_add_plan.h — the host's share of inserting nodes into an HNSW graph, for the build (zvec_hip_hnsw_build, base 0) and the append
 // (zvec_hip_hnsw_add, base = the nodes already there): the levels of a range of positions, the parameters a call runs with, the rounds
-// from a base with the request offsets of the new nodes only, the capacity steps and the stride of the upper table.  DESIGN §3c
-// "Building" and "Appending".  Nothing of HIP: tests/cpp/test_hnsw_add_plan_cpu.cc.
+// from a base with the request offsets of the new nodes only, the capacity steps and the stride of the upper table; and all of them
+// in the order both entries run them, as one plan (hnsw_insert_plan).  DESIGN §3c "Building" and "Appending".  Nothing of HIP:
+// tests/cpp/test_hnsw_add_plan_cpu.cc.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../../include/zvec_hip.h"      // (the error codes, zvec_hip_hnsw_build_params)
@@ -161,4 +163,76 @@ inline HnswAddShape hnsw_add_shape(uint32_t old_stride, uint32_t old_n_upper, co
   }
   sh.restride = sh.stride > old_stride;
   return sh;
+}
+
+// The plain numbers of a graph: what the arrays hold and what they have room for.  stride: of the upper table, the largest level
+// (zvec_hip_hnsw_info's max_level), 0 without upper lists; cap_rows / cap_upper: rows / nodes of level >= 1 the arrays take before
+// they must move.  All zero: no graph.
+struct HnswShape {
+  uint64_t n = 0, cap_rows = 0, cap_upper = 0;
+  uint32_t m0 = 0, m = 0, stride = 0, n_upper = 0, entry = 0;
+};
+
+// A shape as a handle keeps it: without rows no entry point and no upper lists; without upper lists no m, no stride, no upper nodes
+// and no room for any.
+inline HnswShape hnsw_shape_kept(HnswShape s) {
+  if (s.n == 0) s.entry = s.stride = 0;
+  if (s.stride == 0) { s.m = s.n_upper = 0; s.cap_upper = 0; }
+  return s;
+}
+
+// Everything the host decides about one insertion of `count` nodes behind the `base` a graph holds, before the device is touched.
+struct HnswInsertPlan {
+  zvec_hip_hnsw_build_params q{};       // what the call runs with
+  uint32_t base = 0, count = 0;
+  std::vector<uint32_t> lv, upper_of;   // [count] levels and ranks in the upper table of the new nodes
+  std::vector<HnswRound> rounds;
+  std::vector<uint64_t> req_off;        // [count + 1]
+  HnswRoundsNeed need;
+  uint64_t budget = 0;                  // the workspace the slices of a round stay within
+  HnswShape after;                      // the graph after the call; cap_*: what the arrays grow to (hnsw_grow)
+  uint32_t top = 0;                     // the entry point's level after the call
+  bool restride = false;                // the upper table is made, or re-strided, before the first round
+};
+
+// The prelude of zvec_hip_hnsw_build (found: all zero, rem: all zero, want_*: 0, append: false) and of zvec_hip_hnsw_add (found: the
+// graph, or all zero on a handle without nodes; rem: the handle's remembered parameters; want_*: what a reserve asked for; append:
+// true).  The two entries order their refusals differently where two faults coincide, and each keeps its order: a build tests the
+// node range before the rows and plans an empty call like any other (so it still refuses a scaling_factor no level can be generated
+// with); an add tests the rows first, the range with the levels, and answers count == 0 with an empty plan once the parameters stand.
+// A refused call leaves `out` as it was.
+inline int hnsw_insert_plan(const HnswShape &found, const zvec_hip_hnsw_build_params &rem, uint64_t want_rows, uint64_t want_upper,
+                            uint64_t count, bool have_rows, const zvec_hip_hnsw_build_params *p, const uint32_t *levels, uint32_t round_div,
+                            uint32_t round_max, uint64_t budget, bool append, HnswInsertPlan &out) {
+  HnswInsertPlan pl;
+  int rc = hnsw_add_params(p, rem, found.n, found.m0, found.m, pl.q);
+  if (rc) return rc;
+  if (pl.q.m0 == 0) return ZVEC_HIP_ERR_UNSUPPORTED;       // (a loaded graph without level-0 lists takes no node)
+  if (!append && count >= HNSW_PLAN_MAX_NODES) return ZVEC_HIP_ERR_OUT_OF_RANGE;
+  if (count && !have_rows) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  pl.after = found;
+  pl.top = found.stride;                // (the entry point of a graph is on its largest level)
+  pl.budget = budget;
+  if (append && count == 0) { out = std::move(pl); return 0; }
+  rc = hnsw_add_levels(found.n, count, levels, pl.q, pl.lv);
+  if (rc) return rc;
+  pl.base = (uint32_t)found.n;
+  pl.count = (uint32_t)count;
+  uint32_t entry = found.entry;
+  hnsw_plan_rounds(pl.base, pl.lv.data(), pl.count, round_div, round_max, pl.q.m0, pl.q.m, entry, pl.top, pl.rounds, pl.req_off);
+  pl.upper_of.resize(pl.count);
+  const HnswAddShape sh = hnsw_add_shape(found.stride, found.n_upper, pl.lv.data(), pl.count, pl.upper_of.data());
+  pl.need = hnsw_rounds_need(pl.rounds, pl.req_off, pl.base, budget);
+  if (pl.need.max_slots >= (1ull << 31)) return ZVEC_HIP_ERR_UNSUPPORTED;       // (group starts are 32-bit, the sort counts in int)
+  pl.restride = sh.restride;
+  pl.after.n = found.n + count;
+  pl.after.m0 = pl.q.m0;
+  pl.after.m = sh.stride ? pl.q.m : 0;
+  pl.after.stride = sh.stride;
+  pl.after.n_upper = sh.n_upper;
+  pl.after.entry = entry;
+  pl.after.cap_rows = hnsw_grow(found.cap_rows, pl.after.n, want_rows);
+  pl.after.cap_upper = sh.stride ? hnsw_grow(found.cap_upper, sh.n_upper, want_upper) : 0;
+  out = std::move(pl);
+  return 0;
 }
