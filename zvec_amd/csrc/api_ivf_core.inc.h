@@ -381,7 +381,11 @@ __global__ void done_word_kernel(volatile uint32_t *word, uint32_t epoch) {
 // A host-pointer call waits for its stream here (RuntimeOpts::wait).  Everything the call enqueued is on `stream`.
 int host_wait(zvec_hip_ctx_s *ctx, hipStream_t stream) {
   const int policy = ropts().wait.load(std::memory_order_relaxed);
+  const bool fresh_word = ctx->done_word.p == nullptr;
   if (policy == 1 && ctx->done_word.ensure(64) == 0 && ctx->done_word.dev) {
+    // hipHostMalloc does not clear what it hands out: a block that a destroyed context gave back still holds that context's last
+    // epoch, and the wait of this context's call of the same number would end before its kernels had run
+    if (fresh_word) memset(ctx->done_word.p, 0, 64);
     // a plain word in pinned memory: no runtime call (and none of its locks) per poll; a short spin for the single caller's
     // latency, then the CPU is handed on between polls — with more callers than CPUs the waiting threads no longer hold the
     // time slices the launching ones need
