@@ -1056,7 +1056,8 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
  * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below), and takes more rows
  * afterwards (zvec_hip_hnsw_add, below); deleting nodes, reading the
- * reference's dumped HNSW segments (hnsw_searcher_entity.cc), the cosine metric and group-by are not served.  Small indexes
+ * reference's dumped HNSW segments (hnsw_searcher_entity.cc), the cosine metric and group-by are not served; graphs over sparse
+ * rows (src/core/algorithm/hnsw_sparse/) are searched by the zvec_hip_hnsw_sparse_* family at the end of this file.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
  *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
@@ -1200,6 +1201,62 @@ int zvec_hip_hnsw_add_dev(zvec_hip_hnsw_t h, uint64_t count, const void *d_rows,
 int zvec_hip_hnsw_reserve(zvec_hip_hnsw_t h, uint64_t rows, uint64_t upper_nodes);
 /* what the last add of `h` did; NoReady (-21) before the first one.  zvec_hip_hnsw_last_build_info keeps describing the last build. */
 int zvec_hip_hnsw_last_add_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_add_info *out);
+
+/* ---- HNSW over sparse rows: search on a built graph ------------------------------------------
+ * stands behind HnswSparseSearcher::search_impl (src/core/algorithm/hnsw_sparse/hnsw_sparse_searcher.cc:208) above its brute-force
+ * hand-over: the walk of HnswSparseAlgorithm::search, select_entry_point and search_neighbors (hnsw_sparse_algorithm.cc:85-279),
+ * which is the dense walk line for line — the rule of DESIGN §3c unchanged, ties by (distance, node), the largest by (distance, node)
+ * leaving a full set — with dc.dist(..) on a sparse row (:138, :263) as the distance.  A handle family of its own beside
+ * zvec_hip_hnsw_*: it loads a graph that is already built and searches it.  Building or appending on the device, SquaredEuclideanSparse,
+ * deleting nodes, the reference's dumped segments (hnsw_sparse_searcher_entity.cc) and group-by are not served.  Speed: not measured.
+ *   - Metric and value type: ZVEC_HIP_METRIC_IP (InnerProductSparse) over ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16 values; every other
+ *     metric (ZVEC_HIP_METRIC_L2 included) or type returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
+ *   - Score: MinusInnerProductSparseMatrix<T>::Compute (src/ailego/math/inner_product_matrix.h:2781-2862) as on the sparse flat
+ *     index: minus the sum of value products over shared indices, exactly +0.0 when no index is shared.  Halves are stored as halves
+ *     and widened where they are read, sums are fp32 fma; no half arithmetic.  The order in which a (row, query) pair's products are
+ *     summed depends on that pair alone (DESIGN §3c "Sparse rows"), so an fp16 handle answers bit for bit as an fp32 handle given the
+ *     widened values and the same graph.
+ *   - Rows and queries are runs as zvec_hip_sparse_append / zvec_hip_sparse_search take them: counts, then the runs back to back,
+ *     indices strictly ascending inside a run, at most 4096 pairs each; `values` pointers are elements of the handle's type.
+ *   - exclude_bitset, threshold, ef, max_scan, out_counts, the fill past out_counts[q] and the "hnsw_ws_bytes" slices are those of
+ *     zvec_hip_hnsw_search. */
+typedef struct zvec_hip_hnsw_sparse_s *zvec_hip_hnsw_sparse_t;
+int zvec_hip_hnsw_sparse_create(int dtype, int metric, int device, zvec_hip_hnsw_sparse_t *out);
+/* the value type the handle was created with */
+int zvec_hip_hnsw_sparse_dtype(zvec_hip_hnsw_sparse_t h, int *dtype);
+int zvec_hip_hnsw_sparse_destroy(zvec_hip_hnsw_sparse_t h);
+/* HnswSparseSearcher::load (hnsw_sparse_searcher.cc:119) in the shape of plain host arrays — what HnswSparseEntity serves the
+ * algorithm: get_sparse_vector_by_id (hnsw_sparse_entity.h:470; counts [n], indices, values), get_key (keys [n], NULL = the position)
+ * and the graph arrays exactly as zvec_hip_hnsw_load takes them, with the same checks.  Also InvalidArgument (-31), the handle
+ * untouched, for a count above 4096 or indices that are not strictly ascending inside a row.  A second load replaces the first;
+ * n == 0 is a valid empty index. */
+int zvec_hip_hnsw_sparse_load(zvec_hip_hnsw_sparse_t h, uint64_t n, const uint32_t *counts, const uint32_t *indices, const void *values,
+                              const uint64_t *keys, uint32_t m0, const uint32_t *nbr0, const uint32_t *cnt0, uint32_t max_level,
+                              uint32_t m, uint32_t n_upper, const uint32_t *upper_of, const uint32_t *nbr_up, const uint32_t *cnt_up,
+                              uint32_t entry_point);
+/* what load took, read back (every pointer nullable but `count`): the shape and the stored pairs, one row by position
+ * (ZVEC_HIP_ERR_NO_EXIST beyond the last row; indices / values need room for *count entries, at most 4096), the graph arrays as
+ * zvec_hip_hnsw_export returns them */
+int zvec_hip_hnsw_sparse_info(zvec_hip_hnsw_sparse_t h, uint64_t *n, uint64_t *elements, uint32_t *m0, uint32_t *max_level, uint32_t *m,
+                              uint32_t *n_upper, uint32_t *entry_point);
+int zvec_hip_hnsw_sparse_get_vector(zvec_hip_hnsw_sparse_t h, uint64_t position, uint32_t *count, uint32_t *indices, void *values);
+int zvec_hip_hnsw_sparse_export(zvec_hip_hnsw_sparse_t h, uint64_t *keys, uint32_t *nbr0, uint32_t *cnt0, uint32_t *upper_of,
+                                uint32_t *nbr_up, uint32_t *cnt_up);
+/* HnswSparseSearcher::search_impl(sparse_count, sparse_indices, sparse_query, qmeta, count, ctx): the queries as
+ * zvec_hip_sparse_search takes them (a run it refuses is refused here with the same code), everything else as zvec_hip_hnsw_search:
+ * the walk runs with max(ef, topk), above 512 Unsupported (-12); max_scan counts distances computed, 0 = n. */
+int zvec_hip_hnsw_sparse_search(zvec_hip_hnsw_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *q_indices,
+                                const void *q_values, uint32_t count, uint32_t topk, uint32_t ef, uint32_t max_scan, float threshold,
+                                const uint64_t *exclude_bitset, uint64_t *out_keys, float *out_scores, uint32_t *out_counts);
+/* the same with q_counts on the host and the query pairs, the bitset and the outputs in device memory, queued on `stream` (NULL: the
+ * context's), shaped like zvec_hip_sparse_search_dev */
+int zvec_hip_hnsw_sparse_search_dev(zvec_hip_hnsw_sparse_t h, zvec_hip_ctx_t ctx, const uint32_t *q_counts, const uint32_t *d_q_indices,
+                                    const void *d_q_values, uint32_t count, uint32_t topk, uint32_t ef, uint32_t max_scan,
+                                    float threshold, const uint64_t *d_exclude_bitset, uint64_t *d_out_keys, float *d_out_scores,
+                                    uint32_t *d_out_counts, void *stream);
+/* as zvec_hip_hnsw_last_stats, with the same NoReady (-21) rule */
+int zvec_hip_hnsw_sparse_last_stats(zvec_hip_hnsw_sparse_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned,
+                                    uint32_t *out_hops, uint32_t *out_slices);
 
 #ifdef __cplusplus
 }

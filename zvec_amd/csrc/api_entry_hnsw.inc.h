@@ -70,6 +70,12 @@ struct HnswGraph : HnswShape {
     unsigned char *dst = arr.rows.p + (size_t)first * pad_bytes;
     if (pad_bytes != row_bytes) ZCHK(hipMemset(dst, 0, (size_t)count * pad_bytes));
     ZCHK(hipMemcpy2D(dst, pad_bytes, rows, row_bytes, row_bytes, count, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    return put_keys(first, count, keys);
+  }
+
+  // the keys of the places first .. first + count - 1 (host), or their positions when keys is NULL
+  int put_keys(uint64_t first, uint64_t count, const uint64_t *keys) {
+    if (count == 0) return 0;
     std::vector<uint64_t> id;
     if (!keys) {
       id.resize(count);
@@ -77,6 +83,40 @@ struct HnswGraph : HnswShape {
       keys = id.data();
     }
     ZCHK(hipMemcpy(arr.keys.p + first, keys, (size_t)count * 8, hipMemcpyHostToDevice));
+    return 0;
+  }
+
+  // A fresh graph made for a caller's whole one (zvec_hip_hnsw_load and its sparse twin): exactly the room of `to` (rows pad_bytes
+  // apart), the lists and counts copied in from the host, `to` its shape.  Rows and keys are the caller's to put.
+  int load_lists(const HnswShape &to, size_t pad_bytes, hipStream_t s, const uint32_t *nbr0, const uint32_t *cnt0, const uint32_t *upper_of,
+                 const uint32_t *nbr_up, const uint32_t *cnt_up) {
+    if (to.n) {
+      bool grew_rows, grew_upper;
+      ZRET(resize(to, pad_bytes, s, grew_rows, grew_upper));
+      const size_t slots = (size_t)to.n_upper * to.stride;
+      ZCHK(hipMemcpy(arr.cnt0, cnt0, (size_t)to.n * 4, hipMemcpyHostToDevice));
+      if (to.m0) ZCHK(hipMemcpy(arr.nbr0, nbr0, (size_t)to.n * to.m0 * 4, hipMemcpyHostToDevice));
+      if (to.stride) {
+        ZCHK(hipMemcpy(arr.upper_of, upper_of, (size_t)to.n * 4, hipMemcpyHostToDevice));
+        ZCHK(hipMemcpy(arr.cnt_up, cnt_up, slots * 4, hipMemcpyHostToDevice));
+        if (to.m) ZCHK(hipMemcpy(arr.nbr_up, nbr_up, slots * to.m * 4, hipMemcpyHostToDevice));
+      }
+    }
+    static_cast<HnswShape &>(*this) = to;
+    return 0;
+  }
+
+  // keys and lists back to the host as load took them (each pointer nullable); the caller holds the handle's lock and has set the device
+  int export_lists(uint64_t *keys, uint32_t *nbr0, uint32_t *cnt0, uint32_t *upper_of, uint32_t *nbr_up, uint32_t *cnt_up) const {
+    if (n == 0) return 0;
+    const size_t rows = n, slots = (size_t)n_upper * stride;
+    if (keys) ZCHK(hipMemcpy(keys, arr.keys, rows * 8, hipMemcpyDeviceToHost));
+    if (nbr0 && m0) ZCHK(hipMemcpy(nbr0, arr.nbr0, rows * m0 * 4, hipMemcpyDeviceToHost));
+    if (cnt0) ZCHK(hipMemcpy(cnt0, arr.cnt0, rows * 4, hipMemcpyDeviceToHost));
+    if (stride == 0) return 0;
+    if (upper_of) ZCHK(hipMemcpy(upper_of, arr.upper_of, rows * 4, hipMemcpyDeviceToHost));
+    if (nbr_up && m) ZCHK(hipMemcpy(nbr_up, arr.nbr_up, slots * m * 4, hipMemcpyDeviceToHost));
+    if (cnt_up) ZCHK(hipMemcpy(cnt_up, arr.cnt_up, slots * 4, hipMemcpyDeviceToHost));
     return 0;
   }
 
@@ -131,10 +171,12 @@ struct zvec_hip_hnsw_s {
 #define HNSW_KERNEL(h, k) ((h)->f16() ? k<true> : k<false>)
 
 // One change of an HNSW handle (IvfWrite's twin): h->mu, the built-in context's mutex (the rounds use its stream and workspace) and
-// h->rw exclusively, in the handle's lock order, while it lives.
-struct HnswWrite {
-  zvec_hip_hnsw_s *const h;
-  explicit HnswWrite(zvec_hip_hnsw_s *h_) : h(h_), g(h_->mu), gc(h_->defctx->mu), w(h_->rw) {}
+// h->rw exclusively, in the handle's lock order, while it lives.  Hd: zvec_hip_hnsw_s, or the sparse family's handle, which keeps
+// the same three locks in the same order.
+extern "C++" template <typename Hd>
+struct HnswWriteOf {
+  Hd *const h;
+  explicit HnswWriteOf(Hd *h_) : h(h_), g(h_->mu), gc(h_->defctx->mu), w(h_->rw) {}
   int open() { ZCHK(hipSetDevice(h->device)); return 0; }
   // before the first touch of the arrays: searches enqueued on other contexts have finished with them
   int quiesce() { ZCHK(hipDeviceSynchronize()); return 0; }
@@ -143,6 +185,7 @@ struct HnswWrite {
   std::lock_guard<std::mutex> g, gc;
   std::unique_lock<FairSharedMutex> w;
 };
+typedef HnswWriteOf<zvec_hip_hnsw_s> HnswWrite;
 
 // The one place a graph becomes the handle's: g is h->graph itself (an add in place) or a fresh one that takes its place, the old
 // arrays going with `g`.  The shape is normalised here and nowhere else (hnsw_shape_kept).
@@ -230,20 +273,8 @@ int zvec_hip_hnsw_load(zvec_hip_hnsw_t h, uint64_t n, const void *rows, const ui
   HnswGraph g;                                   // a fresh graph with exactly the room of the caller's
   HnswShape to;
   to.n = to.cap_rows = n; to.m0 = m0; to.m = m; to.stride = max_level; to.n_upper = n_upper; to.cap_upper = n_upper; to.entry = entry_point;
-  if (n) {
-    bool grew_rows, grew_upper;
-    ZRET(g.resize(to, h->pad_bytes(), h->defctx->cur, grew_rows, grew_upper));
-    ZRET(g.put_rows(0, n, rows, false, keys, h->row_bytes(), h->pad_bytes()));
-    const size_t slots = (size_t)n_upper * max_level;
-    ZCHK(hipMemcpy(g.arr.cnt0, cnt0, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (m0) ZCHK(hipMemcpy(g.arr.nbr0, nbr0, (size_t)n * m0 * 4, hipMemcpyHostToDevice));
-    if (max_level) {
-      ZCHK(hipMemcpy(g.arr.upper_of, upper_of, (size_t)n * 4, hipMemcpyHostToDevice));
-      ZCHK(hipMemcpy(g.arr.cnt_up, cnt_up, slots * 4, hipMemcpyHostToDevice));
-      if (m) ZCHK(hipMemcpy(g.arr.nbr_up, nbr_up, slots * m * 4, hipMemcpyHostToDevice));
-    }
-  }
-  static_cast<HnswShape &>(g) = to;
+  ZRET(g.load_lists(to, h->pad_bytes(), h->defctx->cur, nbr0, cnt0, upper_of, nbr_up, cnt_up));
+  ZRET(g.put_rows(0, n, rows, false, keys, h->row_bytes(), h->pad_bytes()));
   hnsw_commit(h, g);                             // the old arrays go with the local
   h->params = zvec_hip_hnsw_build_params();
   return 0;
@@ -283,38 +314,31 @@ int zvec_hip_hnsw_export(zvec_hip_hnsw_t h, uint64_t *keys, uint32_t *nbr0, uint
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   std::shared_lock<FairSharedMutex> r(h->rw);
   if (!h->loaded) return ZVEC_HIP_ERR_NO_INDEX_LOADED;
-  const HnswGraph &g = h->graph;
-  if (g.n == 0) return 0;
+  if (h->graph.n == 0) return 0;
   ZCHK(hipSetDevice(h->device));
-  const size_t n = g.n, slots = (size_t)g.n_upper * g.stride;
-  if (keys) ZCHK(hipMemcpy(keys, g.arr.keys, n * 8, hipMemcpyDeviceToHost));
-  if (nbr0 && g.m0) ZCHK(hipMemcpy(nbr0, g.arr.nbr0, n * g.m0 * 4, hipMemcpyDeviceToHost));
-  if (cnt0) ZCHK(hipMemcpy(cnt0, g.arr.cnt0, n * 4, hipMemcpyDeviceToHost));
-  if (g.stride == 0) return 0;
-  if (upper_of) ZCHK(hipMemcpy(upper_of, g.arr.upper_of, n * 4, hipMemcpyDeviceToHost));
-  if (nbr_up && g.m) ZCHK(hipMemcpy(nbr_up, g.arr.nbr_up, slots * g.m * 4, hipMemcpyDeviceToHost));
-  if (cnt_up) ZCHK(hipMemcpy(cnt_up, g.arr.cnt_up, slots * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return h->graph.export_lists(keys, nbr0, cnt0, upper_of, nbr_up, cnt_up);
 }
 
-// The search proper; the caller holds c->mu and h->rw (shared) and has validated the arguments.  A batch goes in slices of queries so
-// that the visited bits (ceil(n / 32) words per query) and the candidate regions (min(max_scan, n) words of 8 bytes per query, only
-// when that is more than the kernel holds in LDS) stay within the "hnsw_ws_bytes" option; a query's walk does not depend on its slice.
-static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
-                                  uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
-                                  uint32_t *d_out_counts, hipStream_t s) {
+// The search proper of both HNSW families on graph `g` of handle `owner`; the caller holds c->mu and the handle's rw (shared) and has
+// validated the arguments.  A batch goes in slices of queries so that the visited bits (ceil(n / 32) words per query) and the
+// candidate regions (min(max_scan, n) words of 8 bytes per query, only when that is more than the kernel holds in LDS) stay within
+// the "hnsw_ws_bytes" option; a query's walk does not depend on its slice.  `a`: g.args(..) of the family; launch(a, q0, mq) starts
+// the family's kernel for the queries q0 .. q0 + mq - 1 of the batch, `a` holding the slice's workspace, outputs and statistics.
+extern "C++" template <typename Launch>
+static int hnsw_search_sliced(const void *owner, const HnswGraph &g, HnswArgs a, zvec_hip_ctx_s *c, uint32_t count, uint32_t topk, uint32_t ef,
+                              uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
+                              uint32_t *d_out_counts, hipStream_t s, Launch &&launch) {
   c->sh.count = 0;              // (no certify step is pending, no flat route and no IVF plan to read back)
   c->route = 0;
   c->ivf_plan.route = 0;
   c->hnsw_count = 0;
   ZRET(c->hnsw_stats.ensure((size_t)count * 8));
   uint32_t slices = 0;
-  if (h->graph.n == 0) {
+  if (g.n == 0) {
     hipLaunchKernelGGL(hnsw_empty_kernel, dim3((count * std::max(topk, 2u) + 255) / 256), dim3(256), 0, s, d_out_keys, d_out_scores,
                        d_out_counts, c->hnsw_stats.as<uint32_t>(), count, topk);
     ZCHK(hipGetLastError());
   } else {
-    HnswArgs a = h->graph.args(h->dim, h->dpad, h->metric);
     const uint32_t n = a.n;
     a.exclude = reinterpret_cast<const uint32_t *>(d_exclude);
     a.topk = topk; a.ef = std::max(ef, topk); a.max_scan = max_scan ? max_scan : n; a.threshold = threshold;
@@ -330,21 +354,31 @@ static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const v
     for (uint32_t q0 = 0; q0 < count; q0 += slice, ++slices) {
       const uint32_t mq = std::min(slice, count - q0);
       ZCHK(hipMemsetAsync(vis, 0, (size_t)mq * a.vis_words * 4, s));
-      a.queries = static_cast<const unsigned char *>(d_queries) + (size_t)q0 * h->row_bytes();
       a.visited = vis; a.cand_ws = cand;
       a.out_keys = d_out_keys + (size_t)q0 * topk; a.out_scores = d_out_scores + (size_t)q0 * topk; a.out_counts = d_out_counts + q0;
       a.stats = c->hnsw_stats.as<uint32_t>() + 2 * (size_t)q0;
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_search_kernel), dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
-      ZCHK(hipGetLastError());
+      ZRET(launch(a, q0, mq));
     }
   }
-  c->hnsw_owner = h;
+  c->hnsw_owner = owner;
   c->hnsw_count = count;
   c->hnsw_slices = slices;
   return 0;
 }
 
-static int hnsw_search_args(zvec_hip_hnsw_t h, const void *queries, uint32_t count, uint32_t topk, uint32_t ef, const void *keys,
+static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const void *d_queries, uint32_t count, uint32_t topk, uint32_t ef,
+                                  uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
+                                  uint32_t *d_out_counts, hipStream_t s) {
+  return hnsw_search_sliced(h, h->graph, h->graph.args(h->dim, h->dpad, h->metric), c, count, topk, ef, max_scan, threshold, d_exclude,
+                            d_out_keys, d_out_scores, d_out_counts, s, [&](HnswArgs &a, uint32_t q0, uint32_t mq) -> int {
+    a.queries = static_cast<const unsigned char *>(d_queries) + (size_t)q0 * h->row_bytes();
+    hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_search_kernel), dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
+    ZCHK(hipGetLastError());
+    return 0;
+  });
+}
+
+static int hnsw_search_args(const void *h, const void *queries, uint32_t count, uint32_t topk, uint32_t ef, const void *keys,
                             const void *scores, const void *counts) {
   if (!h || !queries || !keys || !scores || !counts) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   if (count && topk == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -385,13 +419,12 @@ int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *quer
   return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
 }
 
-int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
-                             uint32_t *out_slices) {
-  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
+// the statistics hnsw_search_sliced left on context c for handle `owner` (of either family)
+static int hnsw_last_stats_of(const void *owner, int device, zvec_hip_ctx_s *c, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
+                              uint32_t *out_slices) {
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->hnsw_owner != h || c->hnsw_count == 0 || count > c->hnsw_count) return ZVEC_HIP_ERR_NO_READY;
-  ZCHK(hipSetDevice(h->device));
+  if (c->hnsw_owner != owner || c->hnsw_count == 0 || count > c->hnsw_count) return ZVEC_HIP_ERR_NO_READY;
+  ZCHK(hipSetDevice(device));
   ZCHK(hipStreamSynchronize(c->cur));
   std::vector<uint32_t> st((size_t)count * 2);
   ZCHK(hipMemcpy(st.data(), c->hnsw_stats.p, st.size() * 4, hipMemcpyDeviceToHost));
@@ -401,4 +434,10 @@ int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t cou
   }
   if (out_slices) *out_slices = c->hnsw_slices;
   return 0;
+}
+
+int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
+                             uint32_t *out_slices) {
+  if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  return hnsw_last_stats_of(h, h->device, ctx ? ctx : h->defctx, count, out_scanned, out_hops, out_slices);
 }

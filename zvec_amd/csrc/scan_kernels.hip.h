@@ -42,3 +42,4 @@
 #include "zvk_sparse_ingest.hip.h"
 #include "zvk_hnsw.hip.h"
 #include "zvk_hnsw_build.hip.h"
+#include "zvk_hnsw_sparse.hip.h"

@@ -59,5 +59,6 @@ extern "C" {
 #include "api_entry_hnsw.inc.h"
 #include "api_entry_hnsw_build.inc.h"
 #include "api_entry_hnsw_add.inc.h"
+#include "api_entry_hnsw_sparse.inc.h"
 
 }  // extern "C"

@@ -153,6 +153,18 @@ __device__ __forceinline__ void hnsw_distances(const HnswArgs &a, const float *q
   hnsw_sync(false);
 }
 
+// The distance step of the walk is a template parameter S of hnsw_greedy and hnsw_beam: a small scorer, passed by value, whose call
+// score(a, coll, cdist, nc, lane) leaves the scores of rows coll[0 .. nc) in cdist (nc <= 64, whole wave, visible to every lane on
+// return).  The dense one is hnsw_distances against the query (or the build's candidate row) at qv in LDS; zvk_hnsw_sparse.hip.h
+// has the one for sparse rows.
+template <bool H>
+struct HnswDenseScorer {
+  const float *qv;
+  __device__ __forceinline__ void operator()(const HnswArgs &a, const uint32_t *coll, float *cdist, uint32_t nc, int lane) const {
+    hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
+  }
+};
+
 __device__ __forceinline__ bool hnsw_excluded(const HnswArgs &a, uint32_t id) {
   return a.exclude != nullptr && ((a.exclude[id >> 5] >> (id & 31u)) & 1u) != 0;
 }
@@ -169,8 +181,8 @@ __device__ __forceinline__ const uint32_t *hnsw_list(const HnswArgs &a, uint32_t
 }
 
 // step 2 of the rule on level l >= 1: greedy, no visited set, no scan limit; moves ep / dist
-template <bool H>
-__device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const float *qv, uint32_t *coll, float *cdist, uint32_t &ep,
+template <typename S>
+__device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, S score, uint32_t *coll, float *cdist, uint32_t &ep,
                                             float &dist, uint32_t &scanned, int lane) {
   bool changed = true;
   while (changed) {
@@ -182,7 +194,7 @@ __device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const
       uint32_t id = 0;
       if ((uint32_t)lane < nc) { id = lst[c0 + lane]; coll[lane] = id; }
       hnsw_sync(false);
-      hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
+      score(a, coll, cdist, nc, lane);
       scanned += nc;
       const float d = (uint32_t)lane < nc ? cdist[lane] : __builtin_inff();
       float mn = d;
@@ -203,8 +215,8 @@ __device__ __forceinline__ void hnsw_greedy(const HnswArgs &a, uint32_t l, const
 // step 3 of the rule on level l from ep (at distance dist): fills R (capacity a.ef, ascending) and returns its size.  C is the
 // HNSW_C_LDS words in LDS, G the walk's region of a.ccap words in the workspace (null when a.ccap fits LDS); vis is the walk's
 // visited bits, zero on entry.  The search kernel calls it on level 0, the build (zvk_hnsw_build.hip.h) on every level.
-template <bool H>
-__device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, const float *qv, uint64_t *R, uint64_t *C, uint64_t *G,
+template <typename S>
+__device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, S score, uint64_t *R, uint64_t *C, uint64_t *G,
                                               uint32_t *coll, float *cdist, uint32_t *vis, uint32_t ep, float dist, uint32_t &scanned,
                                               uint32_t &hops, int lane) {
   if (lane == 0) atomicOr(&vis[ep >> 5], 1u << (ep & 31u));
@@ -235,7 +247,7 @@ __device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, con
       if (nc == 0) continue;
       if (fresh) coll[__popcll(fm & ((1ull << lane) - 1ull))] = id;
       hnsw_sync(false);
-      hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
+      score(a, coll, cdist, nc, lane);
       scanned += nc;
       // a row that fails `distance < worst(R)` against a full R fails it for good (the worst of a full R never grows): skip those
       uint64_t todo = nc == 64 ? ~0ull : ((1ull << nc) - 1ull);
@@ -283,34 +295,9 @@ __device__ __forceinline__ uint32_t hnsw_beam(const HnswArgs &a, uint32_t l, con
   return rsize;
 }
 
-template <bool H>
-__global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  const int lane = (int)threadIdx.x;
-  const uint32_t q = blockIdx.x;
-  float *qv = reinterpret_cast<float *>(hnsw_smem);
-  uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
-  uint64_t *C = R + a.ef;
-  uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
-  float *cdist = reinterpret_cast<float *>(coll + 64);
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? hnsw_elem<H>(a.queries, (size_t)q * a.dim + i) : 0.f;
-  if (lane == 0) coll[0] = a.entry;
-  hnsw_sync(false);
-
-  // 1. the entry point
-  uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
-  float dist = cdist[0];
-  hnsw_sync(false);
-
-  // 2. the upper levels
-  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy<H>(a, l, qv, coll, cdist, ep, dist, scanned, lane);
-
-  // 3. level 0
-  const uint32_t rsize = hnsw_beam<H>(a, 0, qv, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
-                                   a.visited + (size_t)q * a.vis_words, ep, dist, scanned, hops, lane);
-
-  // 4. the first topk of R within the threshold
+// Step 4 of the rule for query q of the launch: the first topk of R (rsize words) within the threshold, and the two statistics.
+__device__ __forceinline__ void hnsw_emit(const HnswArgs &a, uint32_t q, const uint64_t *R, uint32_t rsize, uint32_t scanned, uint32_t hops,
+                                          int lane) {
   const uint32_t lim = min(a.topk, rsize);
   uint32_t outc = 0;
   for (uint32_t j0 = 0; j0 < a.topk; j0 += 64) {
@@ -334,6 +321,37 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
     a.stats[2 * (size_t)q] = scanned;
     a.stats[2 * (size_t)q + 1] = hops;
   }
+}
+
+template <bool H>
+__global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+  const int lane = (int)threadIdx.x;
+  const uint32_t q = blockIdx.x;
+  float *qv = reinterpret_cast<float *>(hnsw_smem);
+  uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
+  uint64_t *C = R + a.ef;
+  uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
+  float *cdist = reinterpret_cast<float *>(coll + 64);
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? hnsw_elem<H>(a.queries, (size_t)q * a.dim + i) : 0.f;
+  if (lane == 0) coll[0] = a.entry;
+  hnsw_sync(false);
+
+  // 1. the entry point
+  uint32_t scanned = 1, hops = 0, ep = a.entry;
+  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
+  float dist = cdist[0];
+  hnsw_sync(false);
+
+  // 2. the upper levels
+  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, HnswDenseScorer<H>{qv}, coll, cdist, ep, dist, scanned, lane);
+
+  // 3. level 0
+  const uint32_t rsize = hnsw_beam(a, 0, HnswDenseScorer<H>{qv}, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
+                                   a.visited + (size_t)q * a.vis_words, ep, dist, scanned, hops, lane);
+
+  // 4. the first topk of R within the threshold
+  hnsw_emit(a, q, R, rsize, scanned, hops, lane);
 }
 
 // an index without rows: every list is empty and nothing was walked

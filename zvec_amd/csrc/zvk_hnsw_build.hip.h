@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
   hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
   float dist = cdist[0];
   hnsw_sync(false);
-  for (uint32_t l = b.top; l > li; --l) hnsw_greedy<H>(a, l, qv, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = b.top; l > li; --l) hnsw_greedy(a, l, HnswDenseScorer<H>{qv}, coll, cdist, ep, dist, scanned, lane);
 
   uint32_t *vis = a.visited + (size_t)wv * a.vis_words;
   uint64_t *G = a.cand_ws != nullptr ? a.cand_ws + (size_t)wv * a.ccap : nullptr;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
     // 2. W = the beam search's result list on this level; its nearest is the next level's entry point
     for (uint32_t t = (uint32_t)lane; t < a.vis_words; t += 64) vis[t] = 0;
     hnsw_sync(true);
-    const uint32_t rsize = hnsw_beam<H>(a, (uint32_t)l, qv, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
+    const uint32_t rsize = hnsw_beam(a, (uint32_t)l, HnswDenseScorer<H>{qv}, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
     {
       const uint64_t w0 = hnsw_uni64(R[0]);
       ep = (uint32_t)w0;

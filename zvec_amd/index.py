@@ -2030,6 +2030,135 @@ class HipHnswSearcher:
         return scanned, hops, int(slices.value)
 
 
+class HipHnswSparseSearcher:
+    """Batched k-NN search on a built HNSW graph over sparse rows (zvec_hip_hnsw_sparse_*): what HnswSparseSearcher::search_impl is
+    above its brute-force hand-over.  metric "InnerProductSparse" (scores are minus the inner product), dtype "fp32" or "fp16" values.
+    Rows and queries are CSR-like as for HipFlatSparseStreamer: counts[n], then the runs back to back in indices (uint32, strictly
+    ascending inside a run, at most 4096) and values; the graph arrays are HipHnswSearcher.load's."""
+
+    MAX_COUNT = 4096
+
+    def __init__(self, device=0, dtype="fp32", metric="InnerProductSparse"):
+        if metric not in _SPARSE_METRIC_NAMES:
+            raise ValueError("zvec_amd: a sparse index serves %s, not %r" % (" and ".join(sorted(_SPARSE_METRIC_NAMES)), metric))
+        self.device = device
+        self.metric = metric
+        self.dtype, self.np_dtype = _dtype_of(dtype)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().zvec_hip_hnsw_sparse_create(self.dtype, _SPARSE_METRIC_NAMES[metric], device, C.byref(self._h)),
+                   "zvec_hip_hnsw_sparse_create")
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().zvec_hip_hnsw_sparse_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def create_context(self):
+        return IndexContext(self.device)
+
+    _runs = HipFlatSparseStreamer._runs
+
+    def load(self, counts, indices, values, nbr0, cnt0, entry_point=0, keys=None, upper_of=None, nbr_up=None, cnt_up=None):
+        """rows as runs (counts [n], indices, values); nbr0 [n][m0] with cnt0 [n]; upper levels (all three or none): upper_of [n],
+        nbr_up [n_upper][max_level][m], cnt_up [n_upper][max_level]"""
+        runs = self._runs(counts, indices, values)
+        if runs is None:
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        n = c.size
+        nbr0 = np.ascontiguousarray(nbr0, np.uint32).reshape(n, -1) if n else np.zeros((0, 1), np.uint32)
+        cnt0 = np.ascontiguousarray(cnt0, np.uint32)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint64)
+        if cnt0.size != n or (k is not None and k.size != n):
+            return IndexError_.InvalidArgument
+        max_level = m = n_upper = 0
+        if nbr_up is not None and n:
+            upper_of = np.ascontiguousarray(upper_of, np.uint32)
+            nbr_up = np.ascontiguousarray(nbr_up, np.uint32)
+            cnt_up = np.ascontiguousarray(cnt_up, np.uint32)
+            if nbr_up.ndim != 3 or cnt_up.shape != nbr_up.shape[:2] or upper_of.size != n:
+                return IndexError_.InvalidArgument
+            n_upper, max_level, m = nbr_up.shape
+        if max_level == 0:
+            upper_of = nbr_up = cnt_up = None
+        return _lib.lib().zvec_hip_hnsw_sparse_load(self._h, n, _np_ptr(c), _np_ptr(i), _np_ptr(v), _np_ptr(k), nbr0.shape[1], _np_ptr(nbr0),
+                                                    _np_ptr(cnt0), max_level, m, n_upper, _np_ptr(upper_of), _np_ptr(nbr_up),
+                                                    _np_ptr(cnt_up), int(entry_point))
+
+    def info(self):
+        """{n, elements, m0, max_level, m, n_upper, entry_point}"""
+        n, e = C.c_uint64(0), C.c_uint64(0)
+        v = [C.c_uint32(0) for _ in range(5)]
+        _lib.check(_lib.lib().zvec_hip_hnsw_sparse_info(self._h, C.byref(n), C.byref(e), *[C.byref(x) for x in v]),
+                   "zvec_hip_hnsw_sparse_info")
+        names = ("m0", "max_level", "m", "n_upper", "entry_point")
+        return dict([("n", int(n.value)), ("elements", int(e.value))] + [(k, int(x.value)) for k, x in zip(names, v)])
+
+    def get_vector_by_id(self, pos):
+        """(indices, values) of the row at position `pos` as stored, or None beyond the last row"""
+        n = C.c_uint32(0)
+        idx = np.zeros(self.MAX_COUNT, np.uint32)
+        val = np.zeros(self.MAX_COUNT, self.np_dtype)
+        rc = _lib.lib().zvec_hip_hnsw_sparse_get_vector(self._h, int(pos), C.byref(n), _np_ptr(idx), _np_ptr(val))
+        return (idx[:n.value].copy(), val[:n.value].copy()) if rc == 0 else None
+
+    def export(self):
+        """keys, nbr0, cnt0, upper_of, nbr_up, cnt_up as load took them (the upper three None without upper levels)"""
+        i = self.info()
+        n = i["n"]
+        keys, nbr0, cnt0 = np.zeros(n, np.uint64), np.zeros((n, i["m0"]), np.uint32), np.zeros(n, np.uint32)
+        up = i["max_level"] > 0
+        upper_of = np.zeros(n, np.uint32) if up else None
+        nbr_up = np.zeros((i["n_upper"], i["max_level"], i["m"]), np.uint32) if up else None
+        cnt_up = np.zeros((i["n_upper"], i["max_level"]), np.uint32) if up else None
+        _lib.check(_lib.lib().zvec_hip_hnsw_sparse_export(self._h, _np_ptr(keys), _np_ptr(nbr0), _np_ptr(cnt0), _np_ptr(upper_of),
+                                                          _np_ptr(nbr_up), _np_ptr(cnt_up)), "zvec_hip_hnsw_sparse_export")
+        return keys, nbr0, cnt0, upper_of, nbr_up, cnt_up
+
+    def search(self, counts, indices, values, count, ctx, ef, max_scan=0):
+        """HnswSparseSearcher::search_impl: topk, threshold and the exclude bitset (1 bit per node) come from ctx; ef and max_scan are
+        the HNSW context's.  Fills ctx like search_impl of the other searchers and returns 0 or a negative IndexError value."""
+        if ctx is None or ctx.topk() == 0:
+            return IndexError_.InvalidArgument
+        runs = self._runs(counts, indices, values)
+        if runs is None or runs[0].size != int(count):
+            return IndexError_.InvalidArgument
+        c, i, v = runs
+        k = ctx.topk()
+        keys = np.zeros((count, k), np.uint64)
+        scores = np.zeros((count, k), np.float32)
+        cnts = np.zeros(count, np.uint32)
+        rc = _lib.lib().zvec_hip_hnsw_sparse_search(self._h, ctx._h, _np_ptr(c), _np_ptr(i), _np_ptr(v), count, k, int(ef), int(max_scan),
+                                                    ctx.threshold(), _np_ptr(ctx._exclude), _np_ptr(keys), _np_ptr(scores), _np_ptr(cnts))
+        if rc == 0:
+            ctx._set_results(keys, scores, cnts)
+        return rc
+
+    def search_dev(self, counts, d_indices, d_values, count, topk, ef, max_scan, d_out_keys, d_out_scores, d_out_counts, ctx,
+                   threshold=FLT_MAX, d_exclude=None, stream=None):
+        """device-pointer form (async): `counts` is a HOST array, everything else raw device pointers (ints); d_values holds elements
+        of the index's value type"""
+        c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if c.size != int(count):
+            return IndexError_.InvalidArgument
+        return _lib.lib().zvec_hip_hnsw_sparse_search_dev(
+            self._h, ctx._h, _np_ptr(c), C.c_void_p(d_indices), C.c_void_p(d_values), count, topk, int(ef), int(max_scan), threshold,
+            C.c_void_p(d_exclude) if d_exclude else None, C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts),
+            C.c_void_p(stream) if stream else None)
+
+    def last_stats(self, ctx, count):
+        """(distances computed [count], nodes expanded on level 0 [count], slices) of the last search of this index on ctx"""
+        scanned = np.zeros(count, np.uint32)
+        hops = np.zeros(count, np.uint32)
+        slices = C.c_uint32(0)
+        _lib.check(_lib.lib().zvec_hip_hnsw_sparse_last_stats(self._h, ctx._h, count, _np_ptr(scanned), _np_ptr(hops), C.byref(slices)),
+                   "zvec_hip_hnsw_sparse_last_stats")
+        return scanned, hops, int(slices.value)
+
+
 def hnsw_levels(n, scaling_factor, seed=0):
     """the levels zvec_hip_hnsw_build gives n nodes when it is passed none (zvec_hip_hnsw_build_levels; host only)"""
     out = np.zeros(int(n), np.uint32)
