@@ -364,8 +364,10 @@ int zvec_hip_ivf_add_dev(zvec_hip_ivf_t h, const void *d_rows, uint64_t n, const
                          const uint64_t *keys, uint64_t first_row, void *stream);
 /* NoReady (-21) while any owned list is short of its announced size; the index is searchable afterwards */
 int zvec_hip_ivf_end_lists(zvec_hip_ivf_t h);
-/* per-query statistics of the last search on ctx (IndexContext::Stats, index_context.h:67-111):
- * scanned[q] = total_scan_count, probes[q] = lists actually probed.  Host arrays, nullable. */
+/* per-query statistics of the last search of `h` on ctx (IndexContext::Stats, index_context.h:67-111), for its first `count`
+ * queries (a batch that went in slices: of its last slice): scanned[q] = total_scan_count, probes[q] = lists actually probed.  Host
+ * arrays, nullable.  Waits for the context's stream.  NoReady (-21) when the context's last search was not one of `h` or was
+ * shorter, or took the large-k route, which counts neither. */
 int zvec_hip_ivf_last_stats(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, uint32_t count,
                             uint32_t *scanned, uint32_t *probes);
 
@@ -565,9 +567,9 @@ int zvec_hip_ctx_profile_read(zvec_hip_ctx_t ctx, uint64_t *launches, double *sc
                               double *algorithmic_bytes, double *algorithmic_flops, int reset);
 /* Which route the last flat search on ctx took (zvec_hip_flat_search / _search_dev over fp rows): the profile above names a
  * launch by its duration only, this names it by what the host dispatched.  Cleared when such a search starts; a search that
- * went in slices ORs them.  Host bookkeeping, no device call.  Defined only straight after such a search: every other
- * search kind on the context (IVF, whose coarse pass is a flat scan; k-means labelling; group-by, by-ids, Hamming and
- * sparse searches) leaves the word undefined — they may OR bits into it and never clear it.
+ * went in slices ORs them.  Host bookkeeping, no device call.  Reports 0 when the context's last search was not a flat one (an IVF,
+ * Hamming IVF, HNSW or sparse search) or before any search; the flat group-by and by-ids searches and batch_distance clear the word
+ * too and report what they launched of the scans below, if anything.
  *   bits 0..8    shape of the main scan: 0 dense-score path, 1 / 2 / 3 the 4-wave tile with 1 / 2 / 4 query groups, 4 the 16-row
  *                shape, 5 the 8-wave 128 x 128 tile, 6 the 256 x 256 fp16 tile, 7 the gathering 8-wave tile (sparse keep-set),
  *                8 the kept rows were copied to a compacted store first (the scan of the copy sets its own shape bit as well)
@@ -587,8 +589,7 @@ int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route);
  *             list_count, list_tpc [nlist], list_qoff, item_off [nlist + 1] (item_off in the deal order: lists largest first),
  *             csr_q, csr_slot [csr_len <= nq x nprobe] (list-major; the order inside a list is not defined)
  * Returns 0 for the tile route, ZVEC_HIP_ERR_NO_READY ("nothing to report", info->route says why) when the last search took the
- * direct or the large-k route, was cut short by an error, or was not an IVF search (a flat, group-by or by-ids search on the
- * context in between; other search kinds leave the plan of the last IVF search readable). */
+ * direct or the large-k route, was cut short by an error, or was not an IVF search (any other search on the context in between). */
 #define ZVEC_HIP_IVF_ROUTE_NONE 0u
 #define ZVEC_HIP_IVF_ROUTE_DIRECT_BLOCK_TOPK 1u /* a few queries, wave per row: the scoring blocks keep their own top-k lists */
 #define ZVEC_HIP_IVF_ROUTE_DIRECT_SELECT 2u     /* a few queries, wave per row: score matrix, selected in one run or two steps */

@@ -557,9 +557,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
   ZRET(effective_exclude(h->holes, h->st.n, c, d_exclude_bitset, s, &d_exclude_bitset));
   // the kernels address the padded query matrix with 32-bit word offsets: very large batches go in slices
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(h->st.dpad, 1u));
-  c->sh.count = 0;
-  c->route = 0;                 // (zvec_hip_ctx_last_route: what this search launches)
-  c->ivf_plan.route = 0;        // (zvec_hip_ctx_last_ivf_plan: not an IVF search)
+  c->last.begin(LastSearch::FLAT, h);
   // Half-width pre-selection (zvk_shadow.hip.h, as for the IVF lists): the scan streams the fp16 twin of the store for k' rows per
   // query — half the bytes of a small batch's HBM-bound scan, and fp16 matrix work instead of fp32 for a wide one —, those are
   // re-scored on the fp32 rows, the k best certified; zvec_hip_flat_shadow_certify re-runs what fails.
@@ -580,6 +578,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
       std::swap(c->qpad, c->sh.q16);
       std::swap(c->qnorm, c->sh.qn16);
       ZRET(rc);
+      c->last.count = count;
       return shadow_rescore_select(c, h->st, tw, count, kp, topk, SearchOut{d_out_keys, d_out_scores, nullptr, d_out_counts}, s);
     }
   }
@@ -589,6 +588,7 @@ static int flat_search_dev_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, const v
     SearchOut out{d_out_keys + (size_t)q0 * topk, d_out_scores + (size_t)q0 * topk, nullptr, d_out_counts + q0};
     ZRET(flat_scan_prepared(c, h->st, m, topk, threshold, d_exclude_bitset, out, s, ScanRole::user));
   }
+  c->last.count = count;
   return 0;
 }
 
@@ -599,8 +599,8 @@ static int flat_shadow_certify_locked(zvec_hip_flat_s *h, zvec_hip_ctx_s *c, con
   auto search = [&](ShadowMode mode, const void *q, const void *, uint32_t m, uint64_t *keys, float *scores, uint32_t *counts) {
     return flat_search_dev_locked(h, c, q, m, topk, FLT_MAX, d_exclude, keys, scores, counts, s, mode);
   };
-  return shadow_certify(c, h->shadow, d_queries, h->st.row_bytes(), nullptr, 0, count, topk, d_out_keys, d_out_scores, d_out_counts, s,
-                        rerun_out, 0, search);
+  return shadow_certify(c, LastSearch::FLAT, h, h->shadow, d_queries, h->st.row_bytes(), nullptr, 0, count, topk, d_out_keys, d_out_scores,
+                        d_out_counts, s, rerun_out, 0, search);
 }
 
 int zvec_hip_flat_set_shadow(zvec_hip_flat_t h, int enable, uint32_t preselect) {
@@ -678,7 +678,7 @@ int zvec_hip_flat_search(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const void *quer
     ZRET(host_search_wrap_begin(c, queries, (size_t)count * h->st.row_bytes(), exclude_bitset, h->st.n, count, topk, c->cur));
     ZRET(flat_search_dev_locked(h, c, c->io_qp, count, topk, threshold, exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr,
                                 c->io_keys.as<uint64_t>(), c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur));
-    if (c->sh.count)       // shadow rows: the queries whose result could not be certified are re-run on the fp32 rows
+    if (c->last.certify.count)       // shadow rows: the queries whose result could not be certified are re-run on the fp32 rows
       ZRET(flat_shadow_certify_locked(h, c, c->io_qp, count, topk, exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr,
                                       c->io_keys.as<uint64_t>(), c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur, nullptr));
   }
@@ -696,7 +696,7 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
-  c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
+  c->last.begin(LastSearch::FLAT, h);
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
   const StoreView &st = h->st;
@@ -717,7 +717,6 @@ int zvec_hip_flat_search_by_ids(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const voi
   }
   ZRET(host_search_wrap_begin(c, queries, (size_t)count * st.row_bytes(), nullptr, 0, count, topk, s));
   ZRET(prep_queries(c, st, c->io_qp, count, threshold, s));
-  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(((size_t)total + count + 8) * sizeof(uint32_t)));
   uint32_t *d_pos = c->plan.as<uint32_t>();
   uint32_t *d_off = d_pos + std::max<uint32_t>(total, 1);
@@ -743,7 +742,7 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);
-  c->sh.count = 0;                                     // (no step of this call goes through the twin: no certify step is pending)
+  c->last.begin(LastSearch::FLAT, h);
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
   const StoreView &st = h->st;
@@ -754,7 +753,6 @@ int zvec_hip_flat_batch_distance(zvec_hip_flat_t h, zvec_hip_ctx_t ctx, const vo
   ZRET(c->io_q.ensure(st.row_bytes()));
   ZCHK(hipMemcpyAsync(c->io_q.p, query, st.row_bytes(), hipMemcpyHostToDevice, s));
   ZRET(prep_queries(c, st, c->io_q.p, 1, FLT_MAX, s));
-  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(((size_t)n + 8) * sizeof(uint32_t)));
   uint32_t *d_pos = c->plan.as<uint32_t>(), *d_off = d_pos + n;
   ZCHK(hipMemcpyAsync(d_pos, clean.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));

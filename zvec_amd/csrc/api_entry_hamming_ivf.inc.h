@@ -116,8 +116,7 @@ struct BivfWrite {
     const hipError_t he = hipStreamSynchronize(s);
     if (rc == 0 && he != hipSuccess) rc = ZVEC_HIP_ERR_RUNTIME;
     h->loaded = rc == 0;
-    h->defctx->bivf_count = 0;
-    h->defctx->bivf_cand_count = 0;
+    h->defctx->last.begin(LastSearch::NONE, nullptr);     // (the probes and candidates of a search of the rows that went)
     return rc;
   }
 
@@ -386,11 +385,7 @@ static int bivf_search_dev_locked(zvec_hip_bivf_s *h, zvec_hip_ctx_s *c, const v
                                   const BivfRerank *rr = nullptr) {
   const StoreView &st = h->lists;
   const uint32_t nlist = h->nlist, np = std::min(nprobe, nlist);
-  c->sh.count = 0;              // (no certify step is pending, no flat route and no fp IVF plan to read back)
-  c->route = 0;
-  c->ivf_plan.route = 0;
-  c->bivf_count = 0;
-  c->bivf_cand_count = 0;
+  c->last.begin(LastSearch::HAMMING_IVF, h);
   const int cus = device_cus(c);
   const BivfSlices cutq = bivf_slices(count, np, topk, h->max_tiles, nlist, st.bin_chunks(), cus, (uint64_t)ropts().bivf_part_bytes.load(std::memory_order_relaxed));
   const uint32_t nsplit = cutq.nsplit;
@@ -459,13 +454,11 @@ static int bivf_search_dev_locked(zvec_hip_bivf_s *h, zvec_hip_ctx_s *c, const v
     hipLaunchKernelGGL(bivf_rerank_kernel, dim3(m), dim3(256), bivf_rerank_lds_bytes(rr->dim), s, r);
     ZCHK(hipGetLastError());
   }
-  c->bivf_owner = h;
-  c->bivf_count = count;
-  c->bivf_np = np;
+  c->last.count = count;
+  c->last.bivf_np = np;
   if (rr) {
-    c->bivf_cand_count = count;
-    c->bivf_cand_kc = topk;
-    c->bivf_cand_slice = cutq.slice;
+    c->last.bivf_cand_kc = topk;
+    c->last.bivf_cand_slice = cutq.slice;
   }
   return 0;
 }
@@ -515,11 +508,12 @@ int zvec_hip_bivf_last_probes(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, uint32_t co
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->bivf_owner != h || c->bivf_count == 0 || count > c->bivf_count) return ZVEC_HIP_ERR_NO_READY;
+  if (!c->last.admits(LastSearch::HAMMING_IVF, h, count)) return ZVEC_HIP_ERR_NO_READY;
+  const uint32_t nq = c->last.count, np = c->last.bivf_np;
   ZCHK(hipSetDevice(h->device));
   ZCHK(hipStreamSynchronize(c->cur));
-  const uint32_t *pidx = c->bivf_probe.as<uint32_t>(), *pcnt = pidx + (size_t)c->bivf_count * c->bivf_np, *pscan = pcnt + c->bivf_count;
-  if (probe_idx) ZCHK(hipMemcpy(probe_idx, pidx, (size_t)count * c->bivf_np * 4, hipMemcpyDeviceToHost));
+  const uint32_t *pidx = c->bivf_probe.as<uint32_t>(), *pcnt = pidx + (size_t)nq * np, *pscan = pcnt + nq;
+  if (probe_idx) ZCHK(hipMemcpy(probe_idx, pidx, (size_t)count * np * 4, hipMemcpyDeviceToHost));
   if (probe_cnt) ZCHK(hipMemcpy(probe_cnt, pcnt, (size_t)count * 4, hipMemcpyDeviceToHost));
   if (scanned) ZCHK(hipMemcpy(scanned, pscan, (size_t)count * 4, hipMemcpyDeviceToHost));
   return 0;

@@ -226,10 +226,11 @@ int zvec_hip_bivf_last_candidates(zvec_hip_bivf_t h, zvec_hip_ctx_t ctx, uint32_
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->bivf_owner != h || c->bivf_cand_count == 0 || count > c->bivf_cand_count || kc != c->bivf_cand_kc) return ZVEC_HIP_ERR_NO_READY;
+  if (!c->last.admits(LastSearch::HAMMING_IVF, h, count) || c->last.bivf_cand_kc == 0 || kc != c->last.bivf_cand_kc)
+    return ZVEC_HIP_ERR_NO_READY;
   ZCHK(hipSetDevice(h->device));
   ZCHK(hipStreamSynchronize(c->cur));
-  const BivfCand b = bivf_cand_arrays(c, c->bivf_cand_count, kc, c->bivf_cand_slice);
+  const BivfCand b = bivf_cand_arrays(c, c->last.count, kc, c->last.bivf_cand_slice);
   if (positions) ZCHK(hipMemcpy(positions, b.pos, (size_t)count * kc * 4, hipMemcpyDeviceToHost));
   if (hamming_scores) ZCHK(hipMemcpy(hamming_scores, b.scores, (size_t)count * kc * 4, hipMemcpyDeviceToHost));
   if (counts) ZCHK(hipMemcpy(counts, b.counts, (size_t)count * 4, hipMemcpyDeviceToHost));

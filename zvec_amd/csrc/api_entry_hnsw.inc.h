@@ -193,7 +193,7 @@ static void hnsw_commit(zvec_hip_hnsw_s *h, HnswGraph &g) {
   if (&g != &h->graph) std::swap(h->graph, g);
   static_cast<HnswShape &>(h->graph) = hnsw_shape_kept(h->graph);
   h->loaded = true;
-  h->defctx->hnsw_count = 0;
+  h->defctx->last.begin(LastSearch::NONE, nullptr);       // (the statistics of a search of the graph that went)
 }
 
 int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
@@ -328,10 +328,7 @@ extern "C++" template <typename Launch>
 static int hnsw_search_sliced(const void *owner, const HnswGraph &g, HnswArgs a, zvec_hip_ctx_s *c, uint32_t count, uint32_t topk, uint32_t ef,
                               uint32_t max_scan, float threshold, const uint64_t *d_exclude, uint64_t *d_out_keys, float *d_out_scores,
                               uint32_t *d_out_counts, hipStream_t s, Launch &&launch) {
-  c->sh.count = 0;              // (no certify step is pending, no flat route and no IVF plan to read back)
-  c->route = 0;
-  c->ivf_plan.route = 0;
-  c->hnsw_count = 0;
+  c->last.begin(LastSearch::HNSW, owner);
   ZRET(c->hnsw_stats.ensure((size_t)count * 8));
   uint32_t slices = 0;
   if (g.n == 0) {
@@ -360,9 +357,8 @@ static int hnsw_search_sliced(const void *owner, const HnswGraph &g, HnswArgs a,
       ZRET(launch(a, q0, mq));
     }
   }
-  c->hnsw_owner = owner;
-  c->hnsw_count = count;
-  c->hnsw_slices = slices;
+  c->last.count = count;
+  c->last.hnsw_slices = slices;
   return 0;
 }
 
@@ -423,7 +419,7 @@ int zvec_hip_hnsw_search(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *quer
 static int hnsw_last_stats_of(const void *owner, int device, zvec_hip_ctx_s *c, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
                               uint32_t *out_slices) {
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->hnsw_owner != owner || c->hnsw_count == 0 || count > c->hnsw_count) return ZVEC_HIP_ERR_NO_READY;
+  if (!c->last.admits(LastSearch::HNSW, owner, count)) return ZVEC_HIP_ERR_NO_READY;
   ZCHK(hipSetDevice(device));
   ZCHK(hipStreamSynchronize(c->cur));
   std::vector<uint32_t> st((size_t)count * 2);
@@ -432,7 +428,7 @@ static int hnsw_last_stats_of(const void *owner, int device, zvec_hip_ctx_s *c, 
     if (out_scanned) out_scanned[q] = st[2 * (size_t)q];
     if (out_hops) out_hops[q] = st[2 * (size_t)q + 1];
   }
-  if (out_slices) *out_slices = c->hnsw_slices;
+  if (out_slices) *out_slices = c->last.hnsw_slices;
   return 0;
 }
 

@@ -88,7 +88,7 @@ int zvec_hip_hnsw_sparse_load(zvec_hip_hnsw_sparse_t h, uint64_t n, const uint32
   std::swap(h->row_off, row_off); std::swap(h->idx, idx); std::swap(h->val, val);
   h->elems = total;
   h->loaded = true;
-  h->defctx->hnsw_count = 0;
+  h->defctx->last.begin(LastSearch::NONE, nullptr);       // (the statistics of a search of the graph that went)
   return 0;
 }
 

@@ -614,7 +614,7 @@ static int ivf_search_dev_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const voi
   const uint32_t maxq = std::max<uint32_t>(1u, 0x7fffffffu / std::max<uint32_t>(std::max(h->lists.dpad, h->cent.dpad), 1u));
   // (the flags of a shadow search belong to ONE call of the core: a sliced batch reads the fp32 lists)
   if (count > maxq) mode = ShadowMode{ShadowMode::fp32_only};
-  c->sh.count = 0;
+  c->last.begin(LastSearch::IVF, h);
   for (uint32_t q0 = 0; q0 < count; q0 += maxq) {
     const uint32_t m = std::min(maxq, count - q0);
     SearchOut out{d_out_keys ? d_out_keys + (size_t)q0 * topk : nullptr, d_out_scores ? d_out_scores + (size_t)q0 * topk : nullptr, nullptr,
@@ -693,8 +693,8 @@ static int ivf_shadow_certify_locked(zvec_hip_ivf_s *h, zvec_hip_ctx_s *c, const
     return ivf_search_dev_locked(h, c, q, m, topk, FLT_MAX, nprobe, max_scan_count, 0, d_exclude, keys, scores, counts, s, cq,
                                  CoarseSplit(), mode);
   };
-  return shadow_certify(c, h->shadow, d_queries, h->lists.row_bytes(), d_coarse_queries, h->cent.row_bytes(), count, topk, d_out_keys,
-                        d_out_scores, d_out_counts, s, rerun_out, 0, search);
+  return shadow_certify(c, LastSearch::IVF, h, h->shadow, d_queries, h->lists.row_bytes(), d_coarse_queries, h->cent.row_bytes(), count,
+                        topk, d_out_keys, d_out_scores, d_out_counts, s, rerun_out, 0, search);
 }
 
 int zvec_hip_ivf_set_shadow(zvec_hip_ivf_t h, int enable, uint32_t preselect) {
@@ -765,7 +765,7 @@ static int ivf_search_host_impl(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, const void
   ZRET(ivf_search_dev_locked(h, c, c->io_qp, count, topk, threshold, nprobe, max_scan_count, brute_force,
                              exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr, c->io_keys.as<uint64_t>(),
                              c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur, d_cq));
-  if (c->sh.count)       // shadow lists: the queries whose result could not be certified are re-run on the fp32 lists
+  if (c->last.certify.count)       // shadow lists: the queries whose result could not be certified are re-run on the fp32 lists
     ZRET(ivf_shadow_certify_locked(h, c, c->io_qp, count, topk, nprobe, max_scan_count, exclude_bitset ? c->io_ex.as<uint64_t>() : nullptr,
                                    c->io_keys.as<uint64_t>(), c->io_scores.as<float>(), c->io_counts.as<uint32_t>(), c->cur, d_cq, nullptr));
   return host_search_wrap_end(c, count, topk, out_keys, out_scores, out_counts, c->cur);
@@ -816,10 +816,12 @@ int zvec_hip_ivf_last_stats(zvec_hip_ivf_t h, zvec_hip_ctx_t ctx, uint32_t count
   if (!h) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
-  if (!c->q_scanned || count > c->last_count) return ZVEC_HIP_ERR_NO_READY;
+  const IvfPlanMark &m = c->last.ivf;
+  if (!c->last.admits(LastSearch::IVF, h, count) || !m.has_stats()) return ZVEC_HIP_ERR_NO_READY;
   ZCHK(hipSetDevice(h->device));
   ZCHK(hipStreamSynchronize(c->cur));
-  if (scanned) ZCHK(hipMemcpy(scanned, c->q_scanned, (size_t)count * 4, hipMemcpyDeviceToHost));
-  if (probes) ZCHK(hipMemcpy(probes, c->q_nprobe, (size_t)count * 4, hipMemcpyDeviceToHost));
+  const uint32_t *pb = c->plan.as<uint32_t>();           // (nothing but this search has touched the buffer: it would have begun the record)
+  if (scanned) ZCHK(hipMemcpy(scanned, pb + m.o_qscanned, (size_t)count * 4, hipMemcpyDeviceToHost));
+  if (probes) ZCHK(hipMemcpy(probes, pb + m.o_qnprobe, (size_t)count * 4, hipMemcpyDeviceToHost));
   return 0;
 }

@@ -90,7 +90,7 @@ int zvec_hip_ctx_profile(zvec_hip_ctx_t ctx, int enable) {
 int zvec_hip_ctx_last_route(zvec_hip_ctx_t ctx, uint32_t *route) {
   if (!ctx || !route) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> g(ctx->mu);
-  *route = ctx->route;
+  *route = ctx->last.flat_route();
   return 0;
 }
 
@@ -101,7 +101,7 @@ int zvec_hip_ctx_last_ivf_plan(zvec_hip_ctx_t ctx, zvec_hip_ivf_plan_info *info,
                                uint32_t *item_off, uint32_t *list_tpc, uint32_t *csr_q, uint32_t *csr_slot) {
   if (!ctx || !info) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> g(ctx->mu);
-  const IvfPlanMark &m = ctx->ivf_plan;
+  const IvfPlanMark m = ctx->last.ivf_plan();
   *info = zvec_hip_ivf_plan_info();
   info->route = m.route; info->nq = m.nq; info->nlist = m.nlist; info->nprobe = m.nprobe; info->brute_force = m.brute_force;
   if (m.route != ZVEC_HIP_IVF_ROUTE_TILE) return ZVEC_HIP_ERR_NO_READY;

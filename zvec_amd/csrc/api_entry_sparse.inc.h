@@ -180,6 +180,7 @@ int sparse_search_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t
                          uint32_t *d_counts, hipStream_t s) {
   if (!merge_fits(topk)) return ZVEC_HIP_ERR_UNSUPPORTED;
   const SparseStore &st = h->st;
+  c->last.begin(LastSearch::SPARSE, h);
   if (st.n == 0) return empty_results(d_keys, d_counts, count, topk, s);
   ZRET(effective_exclude(h->holes, st.n, c, d_exclude, s, &d_exclude));      // (the caller's pointer untouched while the store has no hole)
   const SearchOut out{d_keys, d_scores, nullptr, d_counts};
@@ -229,6 +230,7 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
                        uint32_t count, const uint32_t *ids, const uint32_t *offsets, const uint64_t *d_exclude,
                        const uint32_t **d_list_off, hipStream_t s, uint32_t row_stride = 0) {
   const SparseStore &st = h->st;
+  c->last.begin(LastSearch::SPARSE, h);          // (no marks of its own; the plan buffer is reused)
   ZRET(effective_exclude(h->holes, st.n, c, d_exclude, s, &d_exclude));      // (a hole is never scored: +inf, as any excluded position)
   const uint32_t total = offsets[count];
   const uint64_t want = (uint64_t)device_cus(c) * 16;
@@ -249,7 +251,6 @@ int sparse_rows_locked(zvec_hip_sparse_s *h, zvec_hip_ctx_s *c, const uint32_t *
   const uint32_t items = (uint32_t)item_e0.size();
   plan.insert(plan.end(), item_e0.begin(), item_e0.end());
   ZRET(sparse_upload_plan(c, plan, s));
-  c->ivf_plan.route = 0;        // (the plan buffer is reused: no IVF plan to read back any more)
   ZRET(c->plan.ensure(std::max<size_t>(total, 1) * 4));
   const size_t cells = row_stride ? (size_t)count * row_stride : std::max<size_t>(total, 1);
   ZRET(c->part_s.ensure(cells * 4));

@@ -67,6 +67,7 @@ int zvec_hip_sparse_search_grouped(zvec_hip_sparse_t h, zvec_hip_ctx_t ctx, cons
   zvec_hip_ctx_s *c = ctx ? ctx : h->defctx;
   std::lock_guard<std::mutex> g(c->mu);
   std::shared_lock<FairSharedMutex> r(h->rw);          // the row count the bitset and group_of_position are sized for == the rows scanned
+  c->last.begin(LastSearch::SPARSE, h);
   ZCHK(hipSetDevice(h->device));
   hipStream_t s = c->cur;
   const SparseStore &st = h->st;

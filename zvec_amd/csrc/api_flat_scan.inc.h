@@ -358,8 +358,9 @@ int empty_results(uint64_t *keys, uint32_t *counts, uint32_t count, uint32_t top
   return 0;
 }
 
-// Route read-back (zvec_hip_ctx_last_route, include/zvec_hip.h): a user-facing flat search clears ctx->route, flat_scan_prepared and
-// flat_scan_gather OR in what they launch.  Written on the host only; nothing reads it to decide anything.
+// Route read-back (zvec_hip_ctx_last_route, include/zvec_hip.h): a user-facing search begins the context's record (ctx->last, which
+// clears the word), flat_scan_prepared and flat_scan_gather OR in what they launch; only a flat search's word can be read.  Written on
+// the host only; nothing reads it to decide anything.
 //   bits 0..8   the main scan's shape, bit 9 whether its exclusion variant ran
 //   bits 10..11 how the shared bounds were seeded (ROUTE_SEED_*)
 //   bits 16..25 shape (and exclusion bit) of the seeding prefix's own scan, where that is a scan with lists: the recursive
@@ -392,9 +393,9 @@ int flat_scan_gather(zvec_hip_ctx_s *ctx, const StoreView &st, const uint32_t *d
     hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
                        so.scores, so.idx, d_pos, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk, threshold);
     ZCHK(hipGetLastError());
-    ctx->route |= ROUTE_SEED_GTAU | (ROUTE_GATHER << ROUTE_PREFIX_SHIFT);
+    ctx->last.route |= ROUTE_SEED_GTAU | (ROUTE_GATHER << ROUTE_PREFIX_SHIFT);
   }
-  ctx->route |= ROUTE_GATHER;
+  ctx->last.route |= ROUTE_GATHER;
   int occ8 = 1;
   a.k = topk;
   ZRET(launch_scan8(a, st.f16, 0, cus, stream, &occ8));
@@ -571,7 +572,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
       tmp.base = ctx->cmp_base.as<float>(); tmp.bnorm = ctx->cmp_norm.as<float>();
       tmp.extra = st.extra ? ctx->cmp_extra.as<float>() : nullptr; tmp.keys = ctx->cmp_keys.as<uint64_t>();
       tmp.n = kept;
-      ctx->route |= ROUTE_COMPACT;
+      ctx->last.route |= ROUTE_COMPACT;
       return flat_scan_prepared(ctx, tmp, count, topk, threshold, nullptr, out_in, stream, role);
     }
   }
@@ -593,7 +594,7 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
     const bool want_b = pick_ng(count, topk) < 1;
     if (want_b && !k_fits_merge) return ZVEC_HIP_ERR_UNSUPPORTED;
     if ((want_a || want_b) && k_fits_merge) {
-      ctx->route |= ROUTE_DENSE | (d_exclude ? ROUTE_EXCL : 0u);
+      ctx->last.route |= ROUTE_DENSE | (d_exclude ? ROUTE_EXCL : 0u);
       // sub-batches so that the score matrix stays <= 1 GiB
       const uint32_t sub = dense_sub_batch(count, ntiles_d * TILE_N);
       ZRET(ctx->part_s.ensure((size_t)ntiles_d * TILE_N * 4 * sub));
@@ -639,16 +640,16 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
       hipLaunchKernelGGL(seed_bound_kernel, dim3(count), dim3(256), 0, stream, dump, dump_stride, (uint32_t)SEED_ROWS, ctx->gtau.as<uint32_t>(),
                          ctx->qnorm.as<float>(), st.bnorm, st.metric, topk);
       ZCHK(hipGetLastError());
-      ctx->route |= ROUTE_SEED_BOUND;
+      ctx->last.route |= ROUTE_SEED_BOUND;
     } else {
       // The prefix scan is a fused scan of its own: its work-groups publish their full lists' k-th scores into ctx->gtau as they
       // go, WITHOUT slack, and in the summation order of ITS tile shape.  None of that may reach the main scan: seed_gtau_kernel
       // STORES the bound (the slacked k-th score under the threshold, or the threshold alone for a short list), it does not fold
       // it into what the prefix scan left behind.
-      const uint32_t outer = ctx->route;
-      ctx->route = 0;
+      const uint32_t outer = ctx->last.route;
+      ctx->last.route = 0;
       ZRET(flat_scan_prepared(ctx, view, count, topk, threshold, d_exclude, so, stream, ScanRole::internal));
-      ctx->route = outer | ROUTE_SEED_GTAU | ((ctx->route & ROUTE_SHAPE_MASK) << ROUTE_PREFIX_SHIFT);
+      ctx->last.route = outer | ROUTE_SEED_GTAU | ((ctx->last.route & ROUTE_SHAPE_MASK) << ROUTE_PREFIX_SHIFT);
       hipLaunchKernelGGL(seed_gtau_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, ctx->gtau.as<uint32_t>(),
                          so.scores, so.idx, (const uint32_t *)nullptr, so.counts, ctx->qnorm.as<float>(), st.bnorm, st.metric, count, topk,
                          threshold);
@@ -700,8 +701,8 @@ int flat_scan_prepared(zvec_hip_ctx_s *ctx, const StoreView &st, uint32_t count,
   prof_end(ctx, stream, pi);
   if (profile_it) gate_leave(ctx, stream);
   ZRET(lrc);
-  ctx->route |= (wide256 ? ROUTE_SCAN256 : wide ? ROUTE_SCAN8 : m16_small ? ROUTE_M16 : ng == 4 ? ROUTE_NG4 : ng == 2 ? ROUTE_NG2 : ROUTE_NG1) |
-                (d_exclude ? ROUTE_EXCL : 0u);
+  ctx->last.route |= (d_exclude ? ROUTE_EXCL : 0u) |
+                     (wide256 ? ROUTE_SCAN256 : wide ? ROUTE_SCAN8 : m16_small ? ROUTE_M16 : ng == 4 ? ROUTE_NG4 : ng == 2 ? ROUTE_NG2 : ROUTE_NG1);
 
   ZRET(launch_merge(merge_partials(a.part_s, a.part_i, nchunks, a.gtau, topk, threshold, st.keys, out), count, merge_threads(count), stream));
   if (user_facing) ZRET(refine_l2(ctx, st, count, topk, threshold, out.keys, out.scores, out.idx, out.counts, stream));
@@ -815,10 +816,9 @@ int shadow_rescore_select(zvec_hip_ctx_s *ctx, const StoreView &rows, const Shad
   sa.flags = sh.flags.as<uint32_t>(); sa.nflag = sa.flags + count;
   hipLaunchKernelGGL(shadow_select_kernel, dim3(count), dim3(64), 0, stream, sa);
   ZCHK(hipGetLastError());
-  sh.count = count;
-  sh.kp = kp;
-  sh.topk = topk;
-  sh.owner = &twin;
+  ctx->last.certify.count = count;
+  ctx->last.certify.kp = kp;
+  ctx->last.certify.topk = topk;
   return 0;
 }
 
@@ -826,19 +826,21 @@ int shadow_rescore_select(zvec_hip_ctx_s *ctx, const StoreView &rows, const Shad
 // their results replacing the uncertified ones.  `search(mode, queries, coarse_queries, m, keys, scores, counts)` searches m gathered
 // query rows the way the index searched the batch (same probe rule, same exclude set).  `d_coarse`: the batch's coarse-space rows
 // of `crb` bytes (an IVF index with a coarse space of its own; nullptr otherwise).  `tier` 1: inside the second pass, whose own flagged
-// queries go to the fp32 rows.  The caller holds c->mu (and whatever lock its search needs).
+// queries go to the fp32 rows.  `family`, `owner`: the index whose twin `twin` is, as its searches begin the context's record; the
+// step is taken from the record before anything is searched again (the re-runs begin it anew).  The caller holds c->mu (and whatever
+// lock its search needs).
 template <typename Search>
-int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, size_t rb, const void *d_coarse, size_t crb,
-                   uint32_t count, uint32_t topk, uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, hipStream_t s,
-                   uint32_t *rerun_out, int tier, const Search &search) {
+int shadow_certify(zvec_hip_ctx_s *c, LastSearch::Family family, const void *owner, ShadowTwin &twin, const void *d_queries, size_t rb,
+                   const void *d_coarse, size_t crb, uint32_t count, uint32_t topk, uint64_t *d_out_keys, float *d_out_scores,
+                   uint32_t *d_out_counts, hipStream_t s, uint32_t *rerun_out, int tier, const Search &search) {
   if (rerun_out) *rerun_out = 0;
-  if (c->sh.count == 0) return 0;                      // the last search on this context did not use the twin
-  if (c->sh.count != count || c->sh.owner != &twin || c->sh.topk != topk) return ZVEC_HIP_ERR_INVALID_ARGUMENT;   // not this search's step
-  c->sh.count = 0;
+  if (c->last.certify.count == 0) return 0;            // the last search on this context did not use the twin
+  if (!c->last.admits(family, owner, count) || c->last.certify.count != count || c->last.certify.topk != topk)
+    return ZVEC_HIP_ERR_INVALID_ARGUMENT;              // not this search's step
+  const uint32_t used_kp = c->last.take_certify().kp;
   uint32_t nflag = 0;
   ZCHK(hipMemcpyAsync(&nflag, c->sh.flags.as<uint32_t>() + count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   ZCHK(hipStreamSynchronize(s));
-  const uint32_t used_kp = c->sh.kp;
   if (tier == 0) {
     twin.gov.report(nflag, count);
     if (twin.kp == 0) twin.gov.report_width(nflag, count);
@@ -873,8 +875,8 @@ int shadow_certify(zvec_hip_ctx_s *c, ShadowTwin &twin, const void *d_queries, s
   if (tier == 0 && used_kp < 64) {
     const ShadowMode wide{ShadowMode::forced, std::min<uint32_t>(64, std::max<uint32_t>(32, 2 * used_kp))};   // (wide lists are dear to keep: twice the first pass)
     rc = search(wide, tq.p, tcq.p, m, tk.p, ts.p, tc.p);
-    if (rc == 0 && c->sh.count)
-      rc = shadow_certify(c, twin, tq.p, rb, tcq.p, crb, m, topk, tk.p, ts.p, tc.p, s, &answered_by_fp32, 1, search);
+    if (rc == 0 && c->last.certify.count)
+      rc = shadow_certify(c, family, owner, twin, tq.p, rb, tcq.p, crb, m, topk, tk.p, ts.p, tc.p, s, &answered_by_fp32, 1, search);
   } else {
     rc = search(ShadowMode{ShadowMode::fp32_only}, tq.p, tcq.p, m, tk.p, ts.p, tc.p);
   }

@@ -25,7 +25,11 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   if (h->coarse_sep && !brute_force && !given && d_coarse_queries == nullptr) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
   const int cus = device_cus(ctx);
   const uint32_t nlist = h->lay.nlist;
-  ctx->ivf_plan = IvfPlanMark();       // (zvec_hip_ctx_last_ivf_plan: set again where a route has enqueued all of its work)
+  // (ivf_search_dev_locked has begun the context's record; a sliced batch reports its last slice: the IVF marks are set again where a
+  // route has enqueued all of its work)
+  ctx->last.count = 0;
+  IvfPlanMark &mark = ctx->last.ivf;
+  mark = IvfPlanMark();
   if (nprobe < 1) nprobe = 1;
   if (nprobe > nlist) nprobe = nlist;
 
@@ -150,8 +154,9 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
       // (equal scores: list order, then entry order = the order of the candidate stream, as below)
       ZRET(launch_merge(merge_stream(ctx->direct_scores.as<float>(), ctx->direct_idx.as<uint32_t>(), bpq, topk, true, topk, threshold,
                                      h->lists.keys, out), count, 256, stream));
-      ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
-      ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_DIRECT_BLOCK_TOPK; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist; ctx->ivf_plan.nprobe = nprobe;
+      mark.route = ZVEC_HIP_IVF_ROUTE_DIRECT_BLOCK_TOPK; mark.nq = count; mark.nlist = nlist; mark.nprobe = nprobe;
+      mark.o_qscanned = count;             // (q_nprobe | q_scanned at the head of the plan buffer, as laid out above)
+      ctx->last.count = count;
       return 0;
     }
     // equal scores keep the reference's order — probe rank, then position in the list — which here is the ORDER of the
@@ -172,8 +177,9 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     } else {
       ZRET(launch_merge(merge_stream(ps, ppos, 1, stride, true, topk, threshold, h->lists.keys, out), count, 64, stream));
     }
-    ctx->q_nprobe = dp.q_nprobe; ctx->q_scanned = dp.q_scanned; ctx->last_count = count; ctx->last_list_count = nullptr;
-    ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_DIRECT_SELECT; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist; ctx->ivf_plan.nprobe = nprobe;
+    mark.route = ZVEC_HIP_IVF_ROUTE_DIRECT_SELECT; mark.nq = count; mark.nlist = nlist; mark.nprobe = nprobe;
+    mark.o_qscanned = count;               // (q_nprobe | q_scanned at the head of the plan buffer, as laid out above)
+    ctx->last.count = count;
     return 0;
   }
 
@@ -223,9 +229,9 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
     ZRET(launch_merge(merge_stream(ctx->part_s.as<float>(), ctx->part_i.as<uint32_t>(), 1, (uint32_t)maxlen, false, topk, threshold,
                                    h->lists.keys, out), count, 64, stream));
     ZCHK(hipStreamSynchronize(stream));    // d_pos is freed on return
-    ctx->q_nprobe = nullptr; ctx->q_scanned = nullptr; ctx->last_count = 0;
-    ctx->ivf_plan.route = ZVEC_HIP_IVF_ROUTE_LARGE_K; ctx->ivf_plan.nq = count; ctx->ivf_plan.nlist = nlist;
-    ctx->ivf_plan.nprobe = brute_force ? nlist : nprobe; ctx->ivf_plan.brute_force = brute_force ? 1u : 0u;
+    mark.route = ZVEC_HIP_IVF_ROUTE_LARGE_K; mark.nq = count; mark.nlist = nlist;
+    mark.nprobe = brute_force ? nlist : nprobe; mark.brute_force = brute_force ? 1u : 0u;
+    ctx->last.count = count;
     return 0;
   }
   // Half-width pre-selection (zvk_shadow.hip.h): the scan reads the fp16 twin of the lists and keeps k' > k rows per query, which
@@ -239,7 +245,6 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   }
   const bool use_shadow = kp != 0;
   const uint32_t ks = use_shadow ? kp : topk;                            // k of the list scan and of its merge
-  ctx->sh.count = 0;
   const uint32_t rows_per_group = 32;
   const uint64_t npairs = (uint64_t)count * (brute_force ? nlist : nprobe);
   // layout of the plan buffer (u32 words)
@@ -285,8 +290,6 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   p.q_nprobe = pb + o_qnprobe; p.q_scanned = pb + o_qscanned; p.q_nslots = pb + o_qnslots; p.slot_begin = pb + o_slotbegin;
   p.list_count = pb + o_lcount; p.list_fill = pb + o_lfill; p.list_qoff = pb + o_lqoff; p.item_off = pb + o_itemoff;
   p.total_items = pb + o_total; p.csr_q = pb + o_csrq; p.csr_slot = pb + o_csrslot;
-  ctx->q_nprobe = p.q_nprobe; ctx->q_scanned = p.q_scanned; ctx->last_count = count;
-  ctx->last_list_count = p.list_count;
   if (ctx->profile && ctx->nprof < PROFILE_MAX && ctx->stats.p)      // the slot prof_begin will take for this launch
     p.work_stats = ctx->stats.as<unsigned long long>() + 2 * (size_t)ctx->nprof;
   hipLaunchKernelGGL(plan_wave_kernel<false>, dim3((count + 3) / 4), dim3(256), 0, stream, p);
@@ -341,12 +344,13 @@ int ivf_search_core(zvec_hip_ivf_s *h, zvec_hip_ctx_s *ctx, const void *d_querie
   ZRET(lrc);
   {
     // the plan is complete on the stream from here on: remember where its arrays lie (host words only, nothing enqueued)
-    IvfPlanMark &m = ctx->ivf_plan;
+    IvfPlanMark &m = mark;
     m.route = ZVEC_HIP_IVF_ROUTE_TILE; m.scan_threads = scan_threads; m.nq = count; m.nlist = nlist;
     m.nprobe = brute_force ? nlist : nprobe; m.tpc = tpc; m.rows_per_group = rows_per_group; m.brute_force = brute_force ? 1u : 0u;
     m.slots_bound = slots_bound; m.npairs = npairs; m.words = off;
     m.o_qnprobe = o_qnprobe; m.o_qscanned = o_qscanned; m.o_qnslots = o_qnslots; m.o_slotbegin = o_slotbegin; m.o_lcount = o_lcount;
     m.o_lqoff = o_lqoff; m.o_itemoff = o_itemoff; m.o_ltpc = o_ltpc; m.o_total = o_total; m.o_csrq = o_csrq; m.o_csrslot = o_csrslot;
+    ctx->last.count = count;
   }
 
   // 4. merge the per-(query, probe, chunk) partial lists in probe order

@@ -388,10 +388,6 @@ struct ShadowMode {
 // of every query (keys | shadow scores | true scores | positions | counts), flags [count] + the flagged count [1]
 struct ShadowScratch {
   DevBuf q16, qn16, qinfo, keys, scores, rescored, idx, counts, flags;
-  uint32_t count = 0;                  // queries of the last search that went through the twin (0: none)
-  uint32_t kp = 0;                     // width that search used
-  uint32_t topk = 0;                   // its k
-  const ShadowTwin *owner = nullptr;   // the twin it went through: a certify step of another index (or another k) is refused
 };
 
 }  // namespace
@@ -404,20 +400,6 @@ struct zvec_hip_gate_s {
   hipEvent_t ev = nullptr;
   bool armed = false;
   std::mutex mu;
-};
-
-// What the last IVF search on a context planned (zvec_hip_ctx_last_ivf_plan): the route it took and, for the tile route, where
-// its arrays lie inside ctx->plan (u32 word offsets: the buffer may be reallocated, the offsets hold).  Host bookkeeping only.
-struct IvfPlanMark {
-  uint32_t route = 0;                      // ZVEC_HIP_IVF_ROUTE_*; 0 = the last search planned nothing that can be read back
-  uint32_t scan_threads = 0;               // threads of plan_scan_kernel (tile route)
-  uint32_t nq = 0, nlist = 0, nprobe = 0;  // nprobe: probe ranks per query (nlist under brute force)
-  uint32_t tpc = 0, rows_per_group = 0, brute_force = 0;
-  uint64_t slots_bound = 0;                // what part_s / part_i were sized from
-  uint64_t npairs = 0;                     // capacity of csr_q / csr_slot
-  size_t words = 0;                        // words of the plan buffer in use
-  size_t o_qnprobe = 0, o_qscanned = 0, o_qnslots = 0, o_slotbegin = 0, o_lcount = 0, o_lqoff = 0, o_itemoff = 0, o_ltpc = 0,
-         o_total = 0, o_csrq = 0, o_csrslot = 0;
 };
 
 struct zvec_hip_ctx_s {
@@ -445,17 +427,12 @@ struct zvec_hip_ctx_s {
   // Hamming IVF (api_entry_hamming_ivf.inc.h): probe lists [count][np] | probed lists [count] | rows scanned [count] of the last
   // search, kept for zvec_hip_bivf_last_probes; the plan arrays of its current slice
   DevBuf bivf_probe, bivf_plan;
-  const void *bivf_owner = nullptr;                    // the index of that search
-  uint32_t bivf_count = 0, bivf_np = 0;
   // ... and stage 1 of the last zvec_hip_bivf_search_fp32 (zvec_hip_bivf_last_candidates): a slice's scratch keys [slice][kc] u64 |
   // positions [count][kc] | Hamming scores [count][kc] | counts [count]
   DevBuf bivf_cand;
-  uint32_t bivf_cand_count = 0, bivf_cand_kc = 0, bivf_cand_slice = 0;
   // HNSW search (api_entry_hnsw.inc.h): candidate regions | visited bits of the current slice; {distances computed, nodes expanded}
   // per query of the last search, kept for zvec_hip_hnsw_last_stats
   DevBuf hnsw_ws, hnsw_stats;
-  const void *hnsw_owner = nullptr;
-  uint32_t hnsw_count = 0, hnsw_slices = 0;
   DevBuf benc;                                         // sign bits of the fp32 queries of zvec_hip_flat_search_fp32[_dev] (api_entry_binary_quant.inc.h)
   DevBuf holes_ex;                                     // caller's exclude set OR the store's holes                      // group-by search: per-group bests / lists, group of every position, results
   PinnedBuf pin_in, pin_out;                           // (transfers up to PIN_LIMIT bytes go through pinned memory)
@@ -466,10 +443,7 @@ struct zvec_hip_ctx_s {
   uint64_t last_wait_ns = 0;                           // how long the previous call waited: spin (short) or sleep (long) next time
   hipEvent_t block_ev = nullptr;                       // wait policy 2: hipEventBlockingSync
   DevBuf stats;       // per-launch {distinct_rows, pair_rows} u64 x PROFILE_MAX
-  uint32_t *q_scanned = nullptr, *q_nprobe = nullptr;  // inside plan
-  uint32_t *last_list_count = nullptr;                 // inside plan
-  uint32_t last_count = 0;
-  IvfPlanMark ivf_plan;                                // the last IVF search's route and plan layout (zvec_hip_ctx_last_ivf_plan)
+  LastSearch last;                                     // what the last user-facing search left to be read back (host/last_search.h)
   // profiling
   bool profile = false;
   std::vector<hipEvent_t> ev0, ev1;
@@ -478,7 +452,6 @@ struct zvec_hip_ctx_s {
   std::vector<uint32_t> prof_dscan;
   int nprof = 0;
   int cus = 0;
-  uint32_t route = 0;                                  // which flat scan route the last user-facing flat search took (ROUTE_*, api_flat_scan.inc.h)
   // (the workspace members free themselves afterwards)
   ~zvec_hip_ctx_s() {
     (void)hipSetDevice(device);

@@ -28,6 +28,7 @@
 #include "host/sparse_put_plan.h"
 #include "host/ivf_layout.h"
 #include "host/hnsw_add_plan.h"
+#include "host/last_search.h"
 
 using namespace zvk;
 
