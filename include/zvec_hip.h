@@ -1058,7 +1058,7 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below), and takes more rows
  * afterwards (zvec_hip_hnsw_add, below); deleting nodes, reading the
  * reference's dumped HNSW segments (hnsw_searcher_entity.cc), the cosine metric and group-by are not served; graphs over sparse
- * rows (src/core/algorithm/hnsw_sparse/) are searched by the zvec_hip_hnsw_sparse_* family at the end of this file.  Small indexes
+ * rows (src/core/algorithm/hnsw_sparse/) are built and searched by the zvec_hip_hnsw_sparse_* family at the end of this file.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
  *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
@@ -1203,13 +1203,14 @@ int zvec_hip_hnsw_reserve(zvec_hip_hnsw_t h, uint64_t rows, uint64_t upper_nodes
 /* what the last add of `h` did; NoReady (-21) before the first one.  zvec_hip_hnsw_last_build_info keeps describing the last build. */
 int zvec_hip_hnsw_last_add_info(zvec_hip_hnsw_t h, zvec_hip_hnsw_add_info *out);
 
-/* ---- HNSW over sparse rows: search on a built graph ------------------------------------------
+/* ---- HNSW over sparse rows: search on a built graph, and building one ------------------------
  * stands behind HnswSparseSearcher::search_impl (src/core/algorithm/hnsw_sparse/hnsw_sparse_searcher.cc:208) above its brute-force
  * hand-over: the walk of HnswSparseAlgorithm::search, select_entry_point and search_neighbors (hnsw_sparse_algorithm.cc:85-279),
  * which is the dense walk line for line — the rule of DESIGN §3c unchanged, ties by (distance, node), the largest by (distance, node)
  * leaving a full set — with dc.dist(..) on a sparse row (:138, :263) as the distance.  A handle family of its own beside
- * zvec_hip_hnsw_*: it loads a graph that is already built and searches it.  Building or appending on the device, SquaredEuclideanSparse,
- * deleting nodes, the reference's dumped segments (hnsw_sparse_searcher_entity.cc) and group-by are not served.  Speed: not measured.
+ * zvec_hip_hnsw_*: it loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_sparse_build, below), and searches
+ * it.  Appending on the device (add), SquaredEuclideanSparse, deleting nodes, the reference's dumped segments
+ * (hnsw_sparse_searcher_entity.cc) and group-by are not served.  Speed: not measured.
  *   - Metric and value type: ZVEC_HIP_METRIC_IP (InnerProductSparse) over ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16 values; every other
  *     metric (ZVEC_HIP_METRIC_L2 included) or type returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
  *   - Score: MinusInnerProductSparseMatrix<T>::Compute (src/ailego/math/inner_product_matrix.h:2781-2862) as on the sparse flat
@@ -1258,6 +1259,27 @@ int zvec_hip_hnsw_sparse_search_dev(zvec_hip_hnsw_sparse_t h, zvec_hip_ctx_t ctx
 /* as zvec_hip_hnsw_last_stats, with the same NoReady (-21) rule */
 int zvec_hip_hnsw_sparse_last_stats(zvec_hip_hnsw_sparse_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned,
                                     uint32_t *out_hops, uint32_t *out_slices);
+/* HnswSparseBuilder::train / build (src/core/algorithm/hnsw_sparse/hnsw_sparse_builder.cc): the rows as zvec_hip_hnsw_sparse_load takes
+ * them (counts [n], indices, values; at most 4096 pairs a row, indices strictly ascending inside a row), keys [n] or NULL = the
+ * position, levels [n] (each <= 15) or NULL = generated.  Parameters, their defaults and limits, the levels, the rounds and their two
+ * options and the "hnsw_ws_bytes" slices are those of zvec_hip_hnsw_build, and the rule is DESIGN §3c "Building" unchanged, with the
+ * handle's distance (InnerProductSparse over fp32 or fp16 values).  In the keep rule d(c, s) is scored with c's row staged and s's
+ * streamed, and compared with d(c, base) scored with the base's row staged: on real values the two roles may differ in the last bit,
+ * integer-valued data is exact either way (DESIGN §3c "Sparse rows", "Building").  A build replaces the handle's rows and graph
+ * whole, and only on success: a refused build leaves the handle exactly as it found it.  Afterwards search, info, get_vector,
+ * export and last_stats serve the built graph as after a load.  n == 0 and n == 1 are valid.  InvalidArgument (-31): a count above
+ * 4096, indices that are not strictly ascending inside a row, min_neighbors above m or m0, a level above 15, a generated level asked
+ * for with scaling_factor outside 5 .. 1000.  Unsupported (-12): ef_construction > 512, m0 > 256, m > 128.  No row length is refused
+ * for want of LDS.  The handle remembers the parameters. */
+int zvec_hip_hnsw_sparse_build(zvec_hip_hnsw_sparse_t h, uint64_t n, const uint32_t *counts, const uint32_t *indices, const void *values,
+                               const uint64_t *keys, const zvec_hip_hnsw_build_params *p, const uint32_t *levels);
+/* the same with the pairs in device memory (counts, keys and levels stay host arrays); synchronous.  Only the counts are checked:
+ * strictly ascending indices are the caller's contract, as in zvec_hip_hnsw_sparse_search_dev. */
+int zvec_hip_hnsw_sparse_build_dev(zvec_hip_hnsw_sparse_t h, uint64_t n, const uint32_t *counts, const uint32_t *d_indices,
+                                   const void *d_values, const uint64_t *keys, const zvec_hip_hnsw_build_params *p,
+                                   const uint32_t *levels);
+/* what the last build of `h` did (the counters count what zvec_hip_hnsw_build's count); NoReady (-21) before the first one */
+int zvec_hip_hnsw_sparse_last_build_info(zvec_hip_hnsw_sparse_t h, zvec_hip_hnsw_build_info *out);
 
 #ifdef __cplusplus
 }

@@ -284,6 +284,9 @@ SYMBOLS = {
     "zvec_hip_hnsw_sparse_search_dev": (C.c_int, [_h, _h, _u32p, _u32p, _valp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                                   _u64p, _u64p, _f32p, _u32p, C.c_void_p]),
     "zvec_hip_hnsw_sparse_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "zvec_hip_hnsw_sparse_build": (C.c_int, [_h, C.c_uint64, _u32p, _u32p, _valp, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_sparse_build_dev": (C.c_int, [_h, C.c_uint64, _u32p, _u32p, _valp, _u64p, C.c_void_p, _u32p]),
+    "zvec_hip_hnsw_sparse_last_build_info": (C.c_int, [_h, C.c_void_p]),
     "zvec_hip_ctx_profile": (C.c_int, [_h, C.c_int]),
     "zvec_hip_ctx_profile_read": (C.c_int, [_h, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),

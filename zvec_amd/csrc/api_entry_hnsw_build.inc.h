@@ -3,6 +3,8 @@
 // api_entry_hnsw.inc.h then answers search, info, export and get_vectors as after a load.  The rule is DESIGN §3c "Building":
 // HnswAlgorithm::add_node, update_neighbors and reverse_update_neighbors (hnsw_algorithm.cc:31-81, 394-515) applied in rounds.
 // hnsw_plan_call and hnsw_insert_apply are shared with the append (api_entry_hnsw_add.inc.h): plan, then prepare, then mutate.
+// The plan, HnswRoundsScratch and hnsw_run_rounds also serve the build over sparse rows (api_entry_hnsw_sparse_build.inc.h), which
+// hands hnsw_run_rounds its own three launches.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 static_assert(HNSW_PLAN_MAX_LEVEL == HNSW_BUILD_MAX_LEVEL && HNSW_PLAN_MAX_EF == HNSW_MAX_EF && HNSW_PLAN_MAX_M0 == HNSW_BUILD_MAX_M0 &&
@@ -47,23 +49,28 @@ struct HnswRoundsScratch {
   }
 };
 
+// the three kernels of a family's build, in the order a round launches them
+enum HnswRoundStep { HNSW_STEP_INSERT, HNSW_STEP_REVERSE_ONE, HNSW_STEP_REVERSE };
+
 // The rounds of `pl` on the graph g: resized for the plan's shape, the new rows and their upper_of in place, n still the old count.
-// A round of one node applies its requests straight from the round buffer (hnsw_reverse_one_kernel); a round of more sorts and groups
-// them first.  The caller holds an HnswWrite and has synchronised the device.
-static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const HnswGraph &g, const HnswInsertPlan &pl, HnswRoundsScratch &w, HnswInsertDone &done) {
+// A round of one node applies its requests straight from the round buffer (the family's reverse-one kernel); a round of more sorts
+// and groups them first.  args: g.args(..) of the family; launch(step, b, grid, slots, s) starts the family's kernel for that step
+// with `grid` waves on stream s (the grouped reverse step reads w.req_b, w.gstart and w.ngroups).  c: the handle's built-in
+// context.  The caller holds the handle's write scope and has synchronised the device.
+extern "C++" template <typename Launch>
+static int hnsw_run_rounds(zvec_hip_ctx_s *c, const HnswArgs &args, const HnswGraph &g, const HnswInsertPlan &pl, HnswRoundsScratch &w,
+                           HnswInsertDone &done, Launch &&launch) {
   if (pl.rounds.empty()) return 0;
-  zvec_hip_ctx_s *c = h->defctx;
   hipStream_t s = c->cur;
   const zvec_hip_hnsw_build_params &q = pl.q;
   HnswBuildArgs b{};
   HnswArgs &a = b.g;
-  a = g.args(h->dim, h->dpad, h->metric);
+  a = args;
   a.n = pl.rounds.back().end; a.m = q.m;
   a.ef = q.ef_construction; a.max_scan = 0xffffffffu; a.threshold = 0.f;
   b.nbr0 = g.arr.nbr0; b.cnt0 = g.arr.cnt0; b.nbr_up = g.arr.nbr_up; b.cnt_up = g.arr.cnt_up;
   b.node_base = pl.base; b.levels = w.levels; b.req_off = w.req_off; b.req = w.req_a;
   b.prune_cnt = q.prune_cnt; b.min_neighbors = q.min_neighbors; b.counters = w.counters;
-  const size_t lds_ins = hnsw_insert_lds_bytes(a.dpad, a.ef), lds_rev = hnsw_reverse_lds_bytes(a.dpad);
   for (const HnswRound &r : pl.rounds) {
     const bool spill = r.first > HNSW_C_LDS;
     a.entry = r.entry; a.ccap = r.first; a.vis_words = (r.first + 31) / 32;
@@ -75,16 +82,14 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const HnswGraph &g, const HnswIns
     uint32_t slices = 0;
     for (uint32_t f = r.first; f < r.end; f += slice, ++slices) {     // (the graph is frozen: a slice sees what every slice sees)
       b.first = f;
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_insert_kernel), dim3(std::min(slice, r.end - f)), dim3(64), lds_ins, s, b);
-      ZCHK(hipGetLastError());
+      ZRET(launch(HNSW_STEP_INSERT, b, std::min(slice, r.end - f), (uint64_t)0, s));
     }
     done.slices = std::max(done.slices, slices);
     ZCHK(hipEventRecord(w.ev[1].e, s));
     const uint64_t slots = pl.req_off[r.end - pl.base] - pl.req_off[r.first - pl.base];
     if (r.end - r.first == 1) {
       // the reverse phase of one node: every used request word is a (level, target) group of its own
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_one_kernel), dim3((uint32_t)std::min<uint64_t>(slots, 4096)), dim3(64), lds_rev, s, b, slots);
-      ZCHK(hipGetLastError());
+      ZRET(launch(HNSW_STEP_REVERSE_ONE, b, (uint32_t)std::min<uint64_t>(slots, 4096), slots, s));
       ++done.one;
     } else {
       // the reverse phase: group the round's requests by (level, target, source), then one wave per (level, target)
@@ -92,9 +97,7 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const HnswGraph &g, const HnswIns
       ZCHK(hipMemsetAsync(w.ngroups, 0, 4, s));
       hipLaunchKernelGGL(hnsw_groups_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, w.req_b.p, slots, w.gstart.p, w.ngroups.p);
       ZCHK(hipGetLastError());
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_kernel), dim3((uint32_t)std::min<uint64_t>(slots, 4096)), dim3(64), lds_rev, s, b,
-                         w.req_b.p, slots, w.gstart.p, w.ngroups.p);
-      ZCHK(hipGetLastError());
+      ZRET(launch(HNSW_STEP_REVERSE, b, (uint32_t)std::min<uint64_t>(slots, 4096), slots, s));
     }
     ZCHK(hipEventRecord(w.ev[2].e, s));
     ZCHK(hipEventSynchronize(w.ev[2].e));
@@ -111,7 +114,8 @@ static int hnsw_run_rounds(zvec_hip_hnsw_s *h, const HnswGraph &g, const HnswIns
   return 0;
 }
 
-// What both entries hand hnsw_insert_plan beside their own arguments: the two round options and the workspace budget.
+// What both entries hand hnsw_insert_plan beside their own arguments: the two round options and the workspace budget.  h is read
+// for an append alone.
 static int hnsw_plan_call(const HnswShape &found, const zvec_hip_hnsw_s *h, bool append, uint64_t count, const void *rows,
                           const zvec_hip_hnsw_build_params *p, const uint32_t *levels, HnswInsertPlan &pl) {
   const zvec_hip_hnsw_build_params none{};
@@ -119,6 +123,14 @@ static int hnsw_plan_call(const HnswShape &found, const zvec_hip_hnsw_s *h, bool
                           levels, (uint32_t)ropts().hnsw_build_round_div.load(std::memory_order_relaxed),
                           (uint32_t)ropts().hnsw_build_round_max.load(std::memory_order_relaxed),
                           (uint64_t)ropts().hnsw_ws_bytes.load(std::memory_order_relaxed), append, pl);
+}
+
+// After the last round of `pl` on g: the graph takes the plan's shape, and `done` what the plan and the arrays say of the call.
+static void hnsw_insert_finish(HnswGraph &g, const HnswInsertPlan &pl, HnswInsertDone &done) {
+  static_cast<HnswShape &>(g) = pl.after;
+  done.rounds = (uint32_t)pl.rounds.size(); done.top = pl.top; done.entry = pl.after.entry;
+  done.first = pl.base; done.count = pl.count; done.restrided = pl.restride;
+  done.cap_rows = g.cap_rows; done.cap_upper = g.cap_upper;
 }
 
 // Carries a plan out on g, the handle's graph or a fresh one: prepare, then mutate.  Everything that can be refused for want of
@@ -136,11 +148,19 @@ static int hnsw_insert_apply(zvec_hip_hnsw_s *h, HnswGraph &g, const HnswInsertP
   if (pl.after.stride)                                                                             //    and counts are zero already
     ZCHK(hipMemcpy(g.arr.upper_of.p + pl.base, pl.upper_of.data(), (size_t)pl.count * 4, hipMemcpyHostToDevice));
   ZCHK(hipDeviceSynchronize());                  // (a device-to-device copy of rows may still be in flight on the null stream)
-  ZRET(hnsw_run_rounds(h, g, pl, w, done));                                                        // 4
-  static_cast<HnswShape &>(g) = pl.after;                                                          // 5
-  done.rounds = (uint32_t)pl.rounds.size(); done.top = pl.top; done.entry = pl.after.entry;
-  done.first = pl.base; done.count = pl.count; done.restrided = pl.restride;
-  done.cap_rows = g.cap_rows; done.cap_upper = g.cap_upper;
+  ZRET(hnsw_run_rounds(h->defctx, g.args(h->dim, h->dpad, h->metric), g, pl, w, done,              // 4
+                       [&](HnswRoundStep step, const HnswBuildArgs &b, uint32_t grid, uint64_t slots, hipStream_t s) -> int {
+    const size_t lds_rev = hnsw_reverse_lds_bytes(b.g.dpad);
+    if (step == HNSW_STEP_INSERT)
+      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_insert_kernel), dim3(grid), dim3(64), hnsw_insert_lds_bytes(b.g.dpad, b.g.ef), s, b);
+    else if (step == HNSW_STEP_REVERSE_ONE)
+      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_one_kernel), dim3(grid), dim3(64), lds_rev, s, b, slots);
+    else
+      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_kernel), dim3(grid), dim3(64), lds_rev, s, b, w.req_b.p, slots, w.gstart.p, w.ngroups.p);
+    ZCHK(hipGetLastError());
+    return 0;
+  }));
+  hnsw_insert_finish(g, pl, done);                                                                 // 5
   return 0;
 }
 

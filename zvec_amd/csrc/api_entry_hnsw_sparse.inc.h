@@ -3,7 +3,7 @@
 // HnswSparseSearcher (src/core/algorithm/hnsw_sparse/hnsw_sparse_searcher.cc): the graph arrays, their validation, the sliced search,
 // the statistics and the write scope are that file's (HnswGraph, hnsw_validate, hnsw_search_sliced, hnsw_last_stats_of,
 // HnswWriteOf); the rows are CSR as the sparse flat store keeps them, and the run checks and the query staging are
-// api_entry_sparse.inc.h's.  Loads a graph somebody else built; building one on the device is not served.
+// api_entry_sparse.inc.h's.  Loads a graph somebody else built; api_entry_hnsw_sparse_build.inc.h builds one.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 // the dynamic LDS a kernel may take without having its limit raised: a walk needs hnsw_sparse_lds_bytes, 46.25 KiB at the most
@@ -19,11 +19,47 @@ struct zvec_hip_hnsw_sparse_s {
   Scoped<uint32_t> idx;                // [elems]
   Scoped<unsigned char> val;           // [elems] values of `width` bytes
   uint64_t elems = 0;
+  zvec_hip_hnsw_build_params params{};           // of the last build; all zero after a load
+  bool built = false;                  // bdone is the last build's
+  HnswInsertDone bdone;
   zvec_hip_ctx_s *defctx = nullptr;
   std::mutex mu;                       // lock order and meaning as zvec_hip_hnsw_s
   FairSharedMutex rw;
   ~zvec_hip_hnsw_sparse_s() { delete defctx; }
 };
+
+// The rows of a graph in fresh blocks of their own, CSR as the sparse flat store keeps them: what a load or a build makes whole
+// before the handle changes.  counts [n] on the host (total = their sum); the pairs on the host, or on the device.
+struct HnswSparseRows {
+  Scoped<uint64_t> row_off;
+  Scoped<uint32_t> idx;
+  Scoped<unsigned char> val;
+  uint64_t elems = 0;
+  int put(const uint32_t *counts, uint64_t n, uint64_t total, const uint32_t *indices, const void *values, uint32_t width, bool on_device) {
+    std::vector<uint64_t> off((size_t)n + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + counts[i];
+    ZRET(upload(row_off, off.data(), off.size()));
+    ZRET(idx.alloc(std::max<size_t>(total, 1)));
+    ZRET(val.alloc(std::max<size_t>(total, 1) * width));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (total) {
+      ZCHK(hipMemcpy(idx.p, indices, (size_t)total * 4, kind));
+      ZCHK(hipMemcpy(val.p, values, (size_t)total * width, kind));
+    }
+    elems = total;
+    return 0;
+  }
+};
+
+// The one place a graph and its rows become the handle's (hnsw_commit's twin); the old arrays go with g and rows.
+static void hnsw_sparse_commit(zvec_hip_hnsw_sparse_s *h, HnswGraph &g, HnswSparseRows &rows) {
+  std::swap(h->graph, g);
+  static_cast<HnswShape &>(h->graph) = hnsw_shape_kept(h->graph);
+  std::swap(h->row_off, rows.row_off); std::swap(h->idx, rows.idx); std::swap(h->val, rows.val);
+  h->elems = rows.elems;
+  h->loaded = true;
+  h->defctx->last.begin(LastSearch::NONE, nullptr);       // (the statistics of a search of the graph that went)
+}
 
 int zvec_hip_hnsw_sparse_create(int dtype, int metric, int device, zvec_hip_hnsw_sparse_t *out) {
   if (!out) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
@@ -70,25 +106,10 @@ int zvec_hip_hnsw_sparse_load(zvec_hip_hnsw_sparse_t h, uint64_t n, const uint32
   to.n = to.cap_rows = n; to.m0 = m0; to.m = m; to.stride = max_level; to.n_upper = n_upper; to.cap_upper = n_upper; to.entry = entry_point;
   ZRET(g.load_lists(to, 0, h->defctx->cur, nbr0, cnt0, upper_of, nbr_up, cnt_up));
   ZRET(g.put_keys(0, n, keys));
-  Scoped<uint64_t> row_off;
-  Scoped<uint32_t> idx;
-  Scoped<unsigned char> val;
-  std::vector<uint64_t> off((size_t)n + 1, 0);
-  for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + counts[i];
-  ZRET(row_off.alloc(off.size()));
-  ZRET(idx.alloc(std::max<size_t>(total, 1)));
-  ZRET(val.alloc(std::max<size_t>(total, 1) * h->width));
-  ZCHK(hipMemcpy(row_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-  if (total) {
-    ZCHK(hipMemcpy(idx.p, indices, (size_t)total * 4, hipMemcpyHostToDevice));
-    ZCHK(hipMemcpy(val.p, values, (size_t)total * h->width, hipMemcpyHostToDevice));
-  }
-  std::swap(h->graph, g);                        // the old arrays go with the locals
-  static_cast<HnswShape &>(h->graph) = hnsw_shape_kept(h->graph);
-  std::swap(h->row_off, row_off); std::swap(h->idx, idx); std::swap(h->val, val);
-  h->elems = total;
-  h->loaded = true;
-  h->defctx->last.begin(LastSearch::NONE, nullptr);       // (the statistics of a search of the graph that went)
+  HnswSparseRows rows;
+  ZRET(rows.put(counts, n, total, indices, values, h->width, false));
+  hnsw_sparse_commit(h, g, rows);                // the old arrays go with the locals
+  h->params = zvec_hip_hnsw_build_params();
   return 0;
 }
 

@@ -43,3 +43,4 @@
 #include "zvk_hnsw.hip.h"
 #include "zvk_hnsw_build.hip.h"
 #include "zvk_hnsw_sparse.hip.h"
+#include "zvk_hnsw_sparse_build.hip.h"

@@ -61,5 +61,6 @@ extern "C" {
 #include "api_entry_hnsw_build.inc.h"
 #include "api_entry_hnsw_add.inc.h"
 #include "api_entry_hnsw_sparse.inc.h"
+#include "api_entry_hnsw_sparse_build.inc.h"
 
 }  // extern "C"

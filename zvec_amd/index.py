@@ -2034,7 +2034,8 @@ class HipHnswSparseSearcher:
     """Batched k-NN search on a built HNSW graph over sparse rows (zvec_hip_hnsw_sparse_*): what HnswSparseSearcher::search_impl is
     above its brute-force hand-over.  metric "InnerProductSparse" (scores are minus the inner product), dtype "fp32" or "fp16" values.
     Rows and queries are CSR-like as for HipFlatSparseStreamer: counts[n], then the runs back to back in indices (uint32, strictly
-    ascending inside a run, at most 4096) and values; the graph arrays are HipHnswSearcher.load's."""
+    ascending inside a run, at most 4096) and values; the graph arrays are HipHnswSearcher.load's.  The graph is loaded as plain
+    arrays, or built from the rows (build)."""
 
     MAX_COUNT = 4096
 
@@ -2087,6 +2088,38 @@ class HipHnswSparseSearcher:
         return _lib.lib().zvec_hip_hnsw_sparse_load(self._h, n, _np_ptr(c), _np_ptr(i), _np_ptr(v), _np_ptr(k), nbr0.shape[1], _np_ptr(nbr0),
                                                     _np_ptr(cnt0), max_level, m, n_upper, _np_ptr(upper_of), _np_ptr(nbr_up),
                                                     _np_ptr(cnt_up), int(entry_point))
+
+    _build_args = HipHnswSearcher._build_args
+
+    def build(self, counts, indices, values, keys=None, levels=None, m=0, m0=0, ef_construction=0, prune_cnt=0, min_neighbors=0,
+              scaling_factor=0, seed=0):
+        """HnswSparseBuilder::build: rows as runs (counts [n], indices, values) in, searchable graph out, by the rounds of DESIGN
+        §3c.  keys, levels and the parameters are HipHnswSearcher.build's.  Returns 0 or a negative IndexError value."""
+        runs = self._runs(counts, indices, values)
+        args = None if runs is None else self._build_args(runs[0].size, keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors,
+                                                          scaling_factor, seed)
+        if args is None:
+            return IndexError_.InvalidArgument
+        (c, i, v), (k, lv, p) = runs, args
+        return _lib.lib().zvec_hip_hnsw_sparse_build(self._h, c.size, _np_ptr(c), _np_ptr(i), _np_ptr(v), _np_ptr(k), C.byref(p), _np_ptr(lv))
+
+    def build_dev(self, counts, d_indices, d_values, keys=None, levels=None, m=0, m0=0, ef_construction=0, prune_cnt=0, min_neighbors=0,
+                  scaling_factor=0, seed=0):
+        """build with the pairs in device memory (raw device pointers; d_values holds elements of the index's value type, the
+        indices ascend inside a row); counts, keys and levels stay host arrays"""
+        c = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        args = self._build_args(c.size, keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed)
+        if args is None:
+            return IndexError_.InvalidArgument
+        k, lv, p = args
+        return _lib.lib().zvec_hip_hnsw_sparse_build_dev(self._h, c.size, _np_ptr(c), C.c_void_p(d_indices), C.c_void_p(d_values),
+                                                         _np_ptr(k), C.byref(p), _np_ptr(lv))
+
+    def build_info(self):
+        """{rounds, slices, top, entry_point, dists, requests, prunes, insert_ms, reverse_ms} of the last build"""
+        out = _lib.HnswBuildInfo()
+        _lib.check(_lib.lib().zvec_hip_hnsw_sparse_last_build_info(self._h, C.byref(out)), "zvec_hip_hnsw_sparse_last_build_info")
+        return {k: getattr(out, k) for k, _ in out._fields_}
 
     def info(self):
         """{n, elements, m0, max_level, m, n_upper, entry_point}"""
