@@ -1057,7 +1057,7 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  * HnswAlgorithm::search, select_entry_point and search_neighbors (hnsw_algorithm.cc:83-278), restated in DESIGN §3c, one wave per
  * query.  The handle loads a graph that is already built, or builds one from rows (zvec_hip_hnsw_build, below), and takes more rows
  * afterwards (zvec_hip_hnsw_add, below); deleting nodes, reading the
- * reference's dumped HNSW segments (hnsw_searcher_entity.cc), the cosine metric and group-by are not served; graphs over sparse
+ * reference's dumped HNSW segments (hnsw_searcher_entity.cc) and the cosine metric are not served; graphs over sparse
  * rows (src/core/algorithm/hnsw_sparse/) are built and searched by the zvec_hip_hnsw_sparse_* family at the end of this file.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
@@ -1118,6 +1118,36 @@ int zvec_hip_hnsw_search_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *
  * Waits for the context's stream.  NoReady (-21) when the context's last search was not one of `h` or was shorter. */
 int zvec_hip_hnsw_last_stats(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, uint32_t count, uint32_t *out_scanned, uint32_t *out_hops,
                              uint32_t *out_slices);
+
+/* Group-by search on the graph: HnswAlgorithm::search with expand_neighbors_by_group (hnsw_algorithm.cc:102-104, 280-392) and
+ * HnswContext::topk_to_group_result (hnsw_context.h:188-250); the rule is "Group-by" of DESIGN §3c.  The arguments are those of
+ * zvec_hip_hnsw_search with topk replaced by group_of_node [n] (the caller's group_by(key) as dense numbers, one per node; a value
+ * >= ngroups: the node has no group, it is walked like any other and never returned), ngroups, group_num >= 1 and group_topk >= 1.
+ *   G1 the walk of zvec_hip_hnsw_search with ef_eff = max(ef, group_num * group_topk) (HnswContext::set_group_params);
+ *   G2 its result list, ascending by (score, node), is dealt to the groups of its members;
+ *   G3 only when that gave fewer than group_num groups: the visited bits are cleared, the members of the list marked and made the
+ *      candidates, and the smallest candidate is expanded on level 0 (each unvisited neighbour scored in stored order, offered to
+ *      its group unless excluded or without one, then made a candidate) until the node that brings the group_num-th group, which
+ *      ends the walk at once, or until no candidate is left or max_scan distances have been computed in all;
+ *   G4 a group keeps its group_topk best documents by (score, node); the groups come best document first.
+ * Candidates are popped in (score, node) order and G3 ends with the group_num-th group; the reference pops its refilled heap in
+ * array order and goes on popping (DESIGN §3c says why this differs).  The five outputs are those of zvec_hip_flat_search_grouped
+ * in the same layout and with the same fill: out_groups [count][group_num] (0xffffffff past out_ngroups[q]), out_ngroups [count],
+ * out_keys / out_scores [count][group_num][group_topk] (2^64 - 1 / +inf past a group's documents), out_counts [count][group_num]
+ * = the documents of the group with score <= threshold (a group whose best document lies beyond it is listed with 0).
+ * InvalidArgument (-31), no output written: group_num == 0, group_topk == 0, group_of_node NULL with n > 0.  Unsupported (-12):
+ * ef > 512 or group_num * group_topk > 512.  n == 0: out_ngroups[q] = 0.  Slicing and workspace are zvec_hip_hnsw_search's, and
+ * zvec_hip_hnsw_last_stats serves these searches too (G3's distances and expansions included).  The host form uploads
+ * group_of_node; the _dev form takes device pointers throughout and is asynchronous on `stream`. */
+int zvec_hip_hnsw_search_grouped(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *queries, uint32_t count, const uint32_t *group_of_node,
+                                 uint32_t ngroups, uint32_t group_num, uint32_t group_topk, uint32_t ef, uint32_t max_scan, float threshold,
+                                 const uint64_t *exclude_bitset, uint32_t *out_groups, uint32_t *out_ngroups, uint64_t *out_keys,
+                                 float *out_scores, uint32_t *out_counts);
+int zvec_hip_hnsw_search_grouped_dev(zvec_hip_hnsw_t h, zvec_hip_ctx_t ctx, const void *d_queries, uint32_t count,
+                                     const uint32_t *d_group_of_node, uint32_t ngroups, uint32_t group_num, uint32_t group_topk,
+                                     uint32_t ef, uint32_t max_scan, float threshold, const uint64_t *d_exclude_bitset,
+                                     uint32_t *d_out_groups, uint32_t *d_out_ngroups, uint64_t *d_out_keys, float *d_out_scores,
+                                     uint32_t *d_out_counts, void *stream);
 
 /* ---- HNSW: building a graph from rows --------------------------------------------------------
  * stands behind HnswBuilder::train / build (hnsw_builder.cc) and HnswAlgorithm::add_node (hnsw_algorithm.cc:31-81).  The reference

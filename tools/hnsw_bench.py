@@ -28,6 +28,12 @@ fp16 beside fp32 in the same run.
     python tools/hnsw_bench.py --dtype fp16 [--n 100000 --dim 128] [--out profiles/hnsw_1m_fp16.json]
     python tools/hnsw_bench.py --dtype fp16 --build [--out profiles/hnsw_build_1m_fp16.json]
     python tools/hnsw_bench.py --dtype fp16 --append [--out profiles/hnsw_append_1m_fp16.json]
+
+With --grouped the same corpus and graph go through the group-by search (zvec_hip_hnsw_search_grouped_dev): 1000 groups
+(node % 1000), group_num 10 x group_topk 10, at batches 1 / 64 / 1024, beside the plain search with topk = 100 and the same ef (128)
+in the same process: both times, their ratio, and the distances computed per query of each.
+
+    python tools/hnsw_bench.py --grouped [--n 100000 --dim 128] [--out profiles/hnsw_grouped.json]
 """
 import time
 import argparse
@@ -177,6 +183,40 @@ def append_bench(args, torch, zvec_amd, rows, g, stream, dtype="fp32"):
             "build_of_the_first_rows_seconds": part_seconds, "one_build_of_all_rows": one_build, "legs": legs}
 
 
+def grouped_bench(args, torch, se, n, dim, g, ts, stream):
+    """--grouped: the group-by search (1000 groups, 10 x 10) beside the plain search of 100 documents at the same ef"""
+    dev = torch.device("cuda:0")
+    ngroups, gnum, gk, ef = 1000, 10, 10, 128
+    group_of = (torch.arange(n, device=dev) % ngroups).to(torch.int32)
+    legs = []
+    for batch in (1, 64, 1024):
+        q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
+        keys = torch.empty((batch, gnum * gk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, gnum * gk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch, gnum), dtype=torch.int32, device=dev)
+        groups = torch.empty((batch, gnum), dtype=torch.int32, device=dev)
+        found = torch.empty((batch,), dtype=torch.int32, device=dev)
+        ctx = se.create_context()
+        torch.cuda.synchronize()
+
+        def plain():
+            assert se.search_dev(q.data_ptr(), batch, gnum * gk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx,
+                                 stream=stream) == 0
+
+        def grouped():
+            assert se.search_grouped_dev(q.data_ptr(), batch, group_of.data_ptr(), ngroups, gnum, gk, ef, 0, groups.data_ptr(),
+                                         found.data_ptr(), keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), ctx, stream=stream) == 0
+        leg = {"batch": batch, "ef": ef}
+        for name, step in (("plain", plain), ("grouped", grouped)):
+            leg[name + "_ms_per_step"] = _timed(torch, ts, args.steps, args.warmup, step)
+            leg[name + "_mean_scanned"] = float(se.last_stats(ctx, batch)[0].mean())
+        leg["grouped_over_plain"] = leg["grouped_ms_per_step"] / leg["plain_ms_per_step"]
+        leg["mean_groups_found"] = float(found.float().mean())
+        legs.append(leg)
+    return {"workload": "hnsw group-by search %d x %d fp32, k-NN graph, %d groups (node %% %d), %d x %d, beside plain topk %d"
+                        % (n, dim, ngroups, ngroups, gnum, gk, gnum * gk), "steps": args.steps, "warmup": args.warmup, "legs": legs}
+
+
 def _emit(args, res):
     print(json.dumps(res))
     if args.out:
@@ -195,6 +235,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--grouped", action="store_true", help="group-by search (1000 groups, 10 x 10) beside plain topk 100 at the same ef")
     ap.add_argument("--build", action="store_true", help="build the graph with zvec_hip_hnsw_build_dev instead of the k-NN stand-in")
     ap.add_argument("--ef-construction", type=int, default=200)
     ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32",
@@ -254,6 +295,8 @@ def main():
         assert se16.load(rows.half().cpu().numpy(), nbr0_, cnt0_, se.info()["entry_point"], k_, upper_of_, nbr_up_, cnt_up_) == 0
         handles.append(("fp16", se16, 2))
         del k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_
+    if args.grouped:
+        return _emit(args, grouped_bench(args, torch, se, n, dim, g, ts, stream))
     fctx = flat.create_context()
     legs = []
     for batch in (1, 64, 1024):

@@ -262,6 +262,10 @@ SYMBOLS = {
                                        _u32p]),
     "zvec_hip_hnsw_search_dev": (C.c_int, [_h, _h, _valp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u64p, _u64p, _f32p,
                                            _u32p, C.c_void_p]),
+    "zvec_hip_hnsw_search_grouped": (C.c_int, [_h, _h, _valp, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
+    "zvec_hip_hnsw_search_grouped_dev": (C.c_int, [_h, _h, _valp, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p, C.c_void_p]),
     "zvec_hip_hnsw_last_stats": (C.c_int, [_h, _h, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "zvec_hip_hnsw_build_levels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, _u32p]),
     "zvec_hip_hnsw_build": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_void_p, _u32p]),

@@ -58,6 +58,7 @@ extern "C" {
 #include "api_entry_sparse_put_dev.inc.h"
 #include "api_entry_sparse_group.inc.h"
 #include "api_entry_hnsw.inc.h"
+#include "api_entry_hnsw_group.inc.h"
 #include "api_entry_hnsw_build.inc.h"
 #include "api_entry_hnsw_add.inc.h"
 #include "api_entry_hnsw_sparse.inc.h"

@@ -2020,6 +2020,45 @@ class HipHnswSearcher:
             self._h, ctx._h, C.c_void_p(d_queries), count, topk, int(ef), int(max_scan), threshold, C.c_void_p(d_exclude) if d_exclude else None,
             C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None)
 
+    def group_by_search_impl(self, query, count, ctx, ef, max_scan=0):
+        """the group-by branch of HnswSearcher::search_impl (HnswAlgorithm::search with expand_neighbors_by_group,
+        hnsw_algorithm.cc:102-104, 280-392; HnswContext::topk_to_group_result, hnsw_context.h:188-250) through
+        zvec_hip_hnsw_search_grouped: group_num, group_topk, the group_by function, the threshold and the exclude bitset come from
+        ctx; ef and max_scan are HnswContext's.  Results in ctx.group_result(q).  Called directly: search itself keeps its
+        behaviour under a group context."""
+        if ctx is None or not ctx.group_by_search() or ctx._group_topk <= 0 or ctx._group_by is None:
+            return IndexError_.InvalidArgument
+        q = np.ascontiguousarray(query, self.np_dtype).reshape(int(count), -1)
+        if q.shape[1] != self.dim:
+            return IndexError_.Mismatch
+        n = self.info()["n"]
+        allk = np.zeros(n, np.uint64)
+        if n:
+            _lib.check(_lib.lib().zvec_hip_hnsw_export(self._h, _np_ptr(allk), None, None, None, None, None), "zvec_hip_hnsw_export")
+        of, ids = ctx._groups_for(allk)
+        gnum, gk = ctx._group_num, ctx._group_topk
+        groups = np.zeros((count, gnum), np.uint32)
+        ngroups = np.zeros(count, np.uint32)
+        keys = np.zeros((count, gnum, gk), np.uint64)
+        scores = np.zeros((count, gnum, gk), np.float32)
+        cnts = np.zeros((count, gnum), np.uint32)
+        rc = _lib.lib().zvec_hip_hnsw_search_grouped(self._h, ctx._h, _np_ptr(q), count, _np_ptr(of) if n else None, max(len(ids), 1), gnum,
+                                                     gk, int(ef), int(max_scan), ctx.threshold(), _np_ptr(ctx._exclude), _np_ptr(groups),
+                                                     _np_ptr(ngroups), _np_ptr(keys), _np_ptr(scores), _np_ptr(cnts))
+        if rc == 0:
+            ctx._set_group_results(ids, groups, ngroups, keys, scores, cnts)
+        return rc
+
+    def search_grouped_dev(self, d_queries, count, d_group_of_node, ngroups, group_num, group_topk, ef, max_scan, d_out_groups, d_out_ngroups,
+                           d_out_keys, d_out_scores, d_out_counts, ctx, threshold=FLT_MAX, d_exclude=None, stream=None):
+        """device-pointer form of the group-by search (async): all arguments are raw device pointers (ints); the queries are of the
+        searcher's dtype, d_group_of_node one uint32 per node"""
+        return _lib.lib().zvec_hip_hnsw_search_grouped_dev(
+            self._h, ctx._h, C.c_void_p(d_queries), count, C.c_void_p(d_group_of_node) if d_group_of_node else None, int(ngroups),
+            int(group_num), int(group_topk), int(ef), int(max_scan), threshold, C.c_void_p(d_exclude) if d_exclude else None,
+            C.c_void_p(d_out_groups), C.c_void_p(d_out_ngroups), C.c_void_p(d_out_keys), C.c_void_p(d_out_scores), C.c_void_p(d_out_counts),
+            C.c_void_p(stream) if stream else None)
+
     def last_stats(self, ctx, count):
         """(distances computed [count], nodes expanded on level 0 [count], slices) of the last search of this index on ctx"""
         scanned = np.zeros(count, np.uint32)
