@@ -1061,7 +1061,8 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  * rows (src/core/algorithm/hnsw_sparse/) are built and searched by the zvec_hip_hnsw_sparse_* family at the end of this file.  Small indexes
  * (doc_cnt <= bruteforce_threshold) are the caller's to hand to a flat handle.
  *   - ZVEC_HIP_METRIC_L2 (score = squared distance) or ZVEC_HIP_METRIC_IP (score = MINUS the dot product, as on the flat
- *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED;
+ *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED.  Binary rows under the Hamming distance have a
+ *     creator of their own, zvec_hip_hnsw_create_binary (up to 32768 bits); the two creators below keep refusing binary types;
  *   - Element type.  A handle serves ONE element type: ZVEC_HIP_DT_FP32 (float) or, through zvec_hip_hnsw_create_typed,
  *     ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes) — the reference's HNSW after HalfFloatConverter / HalfFloatReformer.  Every `rows`,
  *     `queries` and get_vectors `out` pointer below, host or device, is a `const void *` / `void *` read as elements of the handle's
@@ -1083,6 +1084,16 @@ int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_h
 /* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16.  Any other type or metric returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
  * With ZVEC_HIP_DT_FP32 this is zvec_hip_hnsw_create. */
 int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
+/* Binary rows under the Hamming distance (hamming_metric.cc over DT_BINARY32 / DT_BINARY64; the reference's HNSW takes its metric
+ * from IndexFactory::CreateMetric, hnsw_searcher.cc:133, hnsw_builder.cc:101): score = (float) popcount(row ^ query), an exact
+ * integer.  dtype: ZVEC_HIP_DT_BINARY32 or ZVEC_HIP_DT_BINARY64, every other type ZVEC_HIP_ERR_UNSUPPORTED; the metric is Hamming by
+ * construction.  InvalidArgument (-31): out == NULL, dim_bits == 0, dim_bits not a multiple of 32 (BINARY32) / 64 (BINARY64), the
+ * flat index's rules; Unsupported (-12) above 32768 bits (the query's words are kept in LDS).  *out is untouched on every refusal.
+ * The handle is served by every zvec_hip_hnsw_* entry: `rows`, `queries` and get_vectors `out` are dim_bits / 32 uint32_t resp.
+ * dim_bits / 64 uint64_t words a row (the same bytes on a little-endian host), zvec_hip_hnsw_info reports dim in bits, and the
+ * limits (ef, m0, m, the workspace slicing, the options) are those of the other types.  Rows are stored as bits: 1/32 of the
+ * bytes of the same rows unpacked to 0/1 floats, whose squared L2 distance is the same number.  DESIGN §3c "Binary rows". */
+int zvec_hip_hnsw_create_binary(uint32_t dim_bits, int dtype, int device, zvec_hip_hnsw_t *out);
 /* the element type the handle was created with */
 int zvec_hip_hnsw_dtype(zvec_hip_hnsw_t h, int *dtype);
 int zvec_hip_hnsw_destroy(zvec_hip_hnsw_t h);

@@ -34,6 +34,13 @@ With --grouped the same corpus and graph go through the group-by search (zvec_hi
 in the same process: both times, their ratio, and the distances computed per query of each.
 
     python tools/hnsw_bench.py --grouped [--n 100000 --dim 128] [--out profiles/hnsw_grouped.json]
+
+With --dtype binary32 the corpus is n rows of --dim uniform random bits.  The binary handle (zvec_hip_hnsw_create_binary) builds the
+graph on the device, and the same queries go through it, through an fp32 SquaredEuclidean handle that holds the same graph over the
+rows unpacked to 0/1 (the same walk and scores, 32 times the bytes), and through the flat Hamming scan of the same rows: ms per step
+of each, distances computed, and recall@10 counted on the scores (Hamming scores tie).
+
+    python tools/hnsw_bench.py --dtype binary32 [--n 100000 --dim 768] [--out profiles/hnsw_hamming_100k_768b.json]
 """
 import time
 import argparse
@@ -217,6 +224,65 @@ def grouped_bench(args, torch, se, n, dim, g, ts, stream):
                         % (n, dim, ngroups, ngroups, gnum, gk, gnum * gk), "steps": args.steps, "warmup": args.warmup, "legs": legs}
 
 
+def binary_bench(args, torch, zvec_amd, g, ts, stream):
+    """--dtype binary32: n rows of --dim uniform random bits; the binary handle builds the graph (zvec_hip_hnsw_build_dev), and three
+    paths answer the same queries: the binary handle, an fp32 SquaredEuclidean handle holding the same graph over the rows unpacked
+    to 0/1 (the same walk and the same scores, 32 times the bytes), and the flat Hamming scan of the same rows (the exact answer,
+    which recall is counted against)."""
+    dev = torch.device("cuda:0")
+    n, bits, m0, m = args.n, args.dim, 32, 16
+    words = bits // 32
+
+    def random_words(count):
+        return torch.randint(-2**31, 2**31 - 1, (count, words), generator=g, device=dev, dtype=torch.int32)
+
+    def unpacked(w):                               # bit i of a word -> element i, as np.unpackbits(bitorder="little") of its bytes
+        return ((w.unsqueeze(-1) >> torch.arange(32, device=dev, dtype=torch.int32)) & 1).reshape(w.shape[0], bits).float()
+    rows = random_words(n)
+    torch.cuda.synchronize()
+    hb = zvec_amd.HipHnswSearcher(bits, "Hamming", dtype="binary32")
+    t0 = time.perf_counter()
+    assert hb.build_dev(rows.data_ptr(), n, m=m, m0=m0, ef_construction=args.ef_construction, seed=1) == 0
+    built = dict(hb.build_info(), build_seconds=time.perf_counter() - t0, ef_construction=args.ef_construction)
+    hf = zvec_amd.HipHnswSearcher(bits, "SquaredEuclidean")
+    k_, nbr0, cnt0, upper_of, nbr_up, cnt_up = hb.export()
+    assert hf.load(unpacked(rows).cpu().numpy(), nbr0, cnt0, hb.info()["entry_point"], k_, upper_of, nbr_up, cnt_up) == 0
+    flat = zvec_amd.HipFlatSearcher(bits, "Hamming", dtype="binary32")
+    assert flat.add_batch_dev(rows.data_ptr(), n) == 0
+    fctx = flat.create_context()
+    legs = []
+    for batch in (1, 64, 1024):
+        q = random_words(batch)
+        qf = unpacked(q)
+        keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
+        scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
+        counts = torch.empty((batch,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+
+        def flat_step():
+            assert flat.search_dev(q.data_ptr(), batch, args.topk, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), fctx, stream=stream) == 0
+        flat_ms = _timed(torch, ts, args.steps, args.warmup, flat_step)
+        truth = scores.cpu().numpy()               # (Hamming scores tie: recall is counted on the scores, place by place)
+        for ef in (64, 128, 256):
+            leg = {"batch": batch, "ef": ef, "flat_hamming_ms_per_step": flat_ms}
+            for name, hs, hq in (("binary32", hb, q), ("fp32_unpacked", hf, qf)):
+                hctx = hs.create_context()
+
+                def step():
+                    assert hs.search_dev(hq.data_ptr(), batch, args.topk, ef, 0, keys.data_ptr(), scores.data_ptr(), counts.data_ptr(), hctx,
+                                         stream=stream) == 0
+                leg[name + "_ms_per_step"] = _timed(torch, ts, args.steps, args.warmup, step)
+                scanned = hs.last_stats(hctx, batch)[0]
+                leg[name + "_mean_scanned"] = float(scanned.mean())
+                leg[name + "_recall_at_%d" % args.topk] = float((scores.cpu().numpy() <= truth[:, -1:]).mean())
+            leg["fp32_unpacked_over_binary32"] = leg["fp32_unpacked_ms_per_step"] / leg["binary32_ms_per_step"]
+            legs.append(leg)
+    return {"workload": "hnsw search %d x %d bits, uniform random, graph built on the device by the binary handle m0=%d m=%d, k=%d: "
+                        "binary32 handle, fp32 L2 handle over the rows unpacked to 0/1 (same graph), flat Hamming scan" % (n, bits, m0, m, args.topk),
+            "row_bytes_held": {"binary32": n * ((words + 3) // 4 * 4) * 4, "fp32_unpacked": n * bits * 4},
+            "steps": args.steps, "warmup": args.warmup, "build": built, "legs": legs}
+
+
 def _emit(args, res):
     print(json.dumps(res))
     if args.out:
@@ -238,8 +304,9 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="group-by search (1000 groups, 10 x 10) beside plain topk 100 at the same ef")
     ap.add_argument("--build", action="store_true", help="build the graph with zvec_hip_hnsw_build_dev instead of the k-NN stand-in")
     ap.add_argument("--ef-construction", type=int, default=200)
-    ap.add_argument("--dtype", choices=("fp32", "fp16"), default="fp32",
-                    help="fp16: a binary16-representable corpus through the fp32 handle and the fp16 handle, side by side")
+    ap.add_argument("--dtype", choices=("fp32", "fp16", "binary32"), default="fp32",
+                    help="fp16: a binary16-representable corpus through the fp32 handle and the fp16 handle, side by side; "
+                         "binary32: --dim random bits through the binary handle, the fp32 handle over the unpacked rows and the flat scan")
     args = ap.parse_args()
     import torch
     import zvec_amd
@@ -247,6 +314,10 @@ def main():
     n, dim, m0, m = args.n, args.dim, 32, 16
     g = torch.Generator(device=dev)
     g.manual_seed(1)
+    if args.dtype == "binary32":
+        ts = torch.cuda.Stream(device=dev)
+        ts.wait_stream(torch.cuda.current_stream(dev))
+        return _emit(args, binary_bench(args, torch, zvec_amd, g, ts, ts.cuda_stream))
     rows = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
     f16 = args.dtype == "fp16"
     if f16:

@@ -251,6 +251,7 @@ SYMBOLS = {
                                                         C.c_uint32, C.c_uint32, C.c_float, _u64p, _u32p, _u32p, _u64p, _f32p, _u32p]),
     "zvec_hip_hnsw_create": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
     "zvec_hip_hnsw_create_typed": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_h)]),
+    "zvec_hip_hnsw_create_binary": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(_h)]),
     "zvec_hip_hnsw_dtype": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "zvec_hip_hnsw_destroy": (C.c_int, [_h]),
     "zvec_hip_hnsw_load": (C.c_int, [_h, C.c_uint64, _valp, _u64p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p,

@@ -145,7 +145,9 @@ struct HnswInsertDone {
 struct zvec_hip_hnsw_s {
   int device = 0;
   int metric = 0;
-  int dtype = ZVEC_HIP_DT_FP32;        // of rows and queries: fp32, or fp16 (zvec_hip_hnsw_create_typed); halves are stored as halves
+  int dtype = ZVEC_HIP_DT_FP32;        // of rows and queries: fp32, or fp16 (zvec_hip_hnsw_create_typed); halves are stored as halves;
+                                       // or BINARY32 / BINARY64 (zvec_hip_hnsw_create_binary), whose element is a uint32_t word of 32
+                                       // bits under either type (the same bytes on a little-endian host)
   uint32_t esz = 4;                    // bytes per element
   uint32_t dim = 0, dpad = 0;          // dpad: elements per stored row, dim rounded up to 4 (a lane of the kernel loads four elements)
   bool loaded = false;
@@ -161,14 +163,15 @@ struct zvec_hip_hnsw_s {
   // mutex of the context it works through, then rw shared (as zvec_hip_flat_s); info, export and get_vectors hold rw shared alone.
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;
-  bool f16() const { return dtype == ZVEC_HIP_DT_FP16; }
+  HnswKind kind() const { return dtype == ZVEC_HIP_DT_FP32 ? HNSW_F32 : dtype == ZVEC_HIP_DT_FP16 ? HNSW_F16 : HNSW_BITS; }
+  uint32_t callers_dim() const { return kind() == HNSW_BITS ? dim * 32 : dim; }       // bits of a binary handle
   size_t row_bytes() const { return (size_t)dim * esz; }           // of a row as callers pass it
   size_t pad_bytes() const { return (size_t)dpad * esz; }          // of a row as it is stored
   ~zvec_hip_hnsw_s() { delete defctx; }
 };
 
-// the instantiation of a kernel template for the handle's element type
-#define HNSW_KERNEL(h, k) ((h)->f16() ? k<true> : k<false>)
+// the instantiation of a kernel template for the kind of the handle's rows
+#define HNSW_KERNEL(h, k) ((h)->kind() == HNSW_BITS ? k<HNSW_BITS> : (h)->kind() == HNSW_F16 ? k<HNSW_F16> : k<HNSW_F32>)
 
 // One change of an HNSW handle (IvfWrite's twin): h->mu, the built-in context's mutex (the rounds use its stream and workspace) and
 // h->rw exclusively, in the handle's lock order, while it lives.  Hd: zvec_hip_hnsw_s, or the sparse family's handle, which keeps
@@ -196,19 +199,34 @@ static void hnsw_commit(zvec_hip_hnsw_s *h, HnswGraph &g) {
   h->defctx->last.begin(LastSearch::NONE, nullptr);       // (the statistics of a search of the graph that went)
 }
 
-int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
-  if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (metric != ZVEC_HIP_METRIC_L2 && metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS)
+// a handle of `dim` elements of `esz` bytes, every argument checked by the caller
+static int hnsw_new(uint32_t dim, uint32_t esz, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
   zvec_hip_ctx_s *c = nullptr;
   ZRET(ctx_new(device, &c));
   zvec_hip_hnsw_s *h = new (std::nothrow) zvec_hip_hnsw_s();
   if (!h) { ctx_free(c); return ZVEC_HIP_ERR_NO_MEMORY; }
   h->device = device; h->metric = metric; h->dim = dim; h->dpad = (dim + 3) / 4 * 4; h->defctx = c;
-  h->dtype = dtype; h->esz = dtype == ZVEC_HIP_DT_FP16 ? 2 : 4;
+  h->dtype = dtype; h->esz = esz;
   *out = h;
   return 0;
+}
+
+int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
+  if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (metric != ZVEC_HIP_METRIC_L2 && metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS)
+  return hnsw_new(dim, dtype == ZVEC_HIP_DT_FP16 ? 2 : 4, dtype, metric, device, out);
+}
+
+// Binary rows under the Hamming distance (HNSW_BITS): the handle counts uint32_t words, 32 bits each, whichever of the two types
+// its callers pass, and dpad is the words of a stored row: a whole number of 16-byte chunks.
+int zvec_hip_hnsw_create_binary(uint32_t dim_bits, int dtype, int device, zvec_hip_hnsw_t *out) {
+  if (!out || dim_bits == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dtype != ZVEC_HIP_DT_BINARY32 && dtype != ZVEC_HIP_DT_BINARY64) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dim_bits % (dtype == ZVEC_HIP_DT_BINARY64 ? 64 : 32) != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
+  if (dim_bits > HNSW_MAX_BITS) return ZVEC_HIP_ERR_UNSUPPORTED;    // (the query's words are kept in LDS)
+  return hnsw_new(dim_bits / 32, 4, dtype, ZVEC_HIP_METRIC_HAMMING, device, out);
 }
 
 // the fp32 creator: every other type stays Unsupported here, fp16 included (zvec_hip_hnsw_create_typed takes it)
@@ -286,7 +304,7 @@ int zvec_hip_hnsw_info(zvec_hip_hnsw_t h, uint64_t *n, uint32_t *dim, uint32_t *
   std::shared_lock<FairSharedMutex> r(h->rw);
   const HnswShape &g = h->graph;
   if (n) *n = g.n;
-  if (dim) *dim = h->dim;
+  if (dim) *dim = h->callers_dim();
   if (m0) *m0 = g.m0;
   if (max_level) *max_level = g.stride;
   if (m) *m = g.m;

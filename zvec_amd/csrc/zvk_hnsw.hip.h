@@ -9,10 +9,13 @@
 // region of the context workspace when more than that many candidates are alive at the same time (rows excluded by the caller's
 // bitset are traversed but never fill R, so nothing bounds C below the row count then).
 //
-// Rows and queries are fp32 or IEEE binary16 (template parameter H of everything that touches their memory: H = true, halves).  A half
-// is widened to fp32 where it is read, which is exact (subnormals included, nothing flushed); from there on the arithmetic is the
-// fp32 kernel's own, operation for operation and in the same order, so an fp16 handle answers bit for bit as an fp32 handle given the
-// widened values would (DESIGN §3c "fp16 rows").  LDS holds the query, and the build's candidate row, as fp32 either way.
+// Rows and queries are of one of three kinds (HnswKind, the template parameter K of every kernel): fp32, IEEE binary16, or words of
+// bits under the Hamming distance (zvk_hnsw_hamming.hip.h).  HnswRows<K> says what a kernel needs of its kind: the 4-byte word a
+// query, or the build's candidate or base row, is kept as in LDS, how one is read, and the scorer.  The dense code below it keeps its
+// own parameter H (H = true, halves).  A half is widened to fp32 where it is read, which is exact (subnormals included, nothing
+// flushed); from there on the arithmetic is the fp32 kernel's own, operation for operation and in the same order, so an fp16 handle
+// answers bit for bit as an fp32 handle given the widened values would (DESIGN §3c "fp16 rows").  LDS holds a dense query, and the
+// build's candidate row, as fp32 either way.
 #pragma once
 #include "zvk_common.hip.h"
 
@@ -21,10 +24,14 @@ namespace zvk {
 constexpr uint32_t HNSW_MAX_EF = 512;      // words of R: 4 KiB of LDS per query
 constexpr uint32_t HNSW_C_LDS = 1024;      // words of C held in LDS: 8 KiB per query
 constexpr uint32_t HNSW_MAX_DIM = 4096;    // the query row is kept in LDS
+constexpr uint32_t HNSW_MAX_BITS = 32768;  // of a binary row: 1024 words, the LDS bytes of a 1024-d fp32 query
+
+enum HnswKind : int { HNSW_F32 = 0, HNSW_F16 = 1, HNSW_BITS = 2 };
 
 struct HnswArgs {
   const void *rows;           // [n][dpad] row-major, zero padded; dpad is a multiple of 4 elements (a lane loads 16 bytes of
-                              // fp32, 8 bytes of fp16: the same four elements; an fp16 row is 8-byte aligned and no more)
+                              // fp32, 8 bytes of fp16: the same four elements; an fp16 row is 8-byte aligned and no more).
+                              // Binary rows: an element is a uint32_t word of 32 bits, dim and dpad count words
   const uint64_t *keys;       // [n]
   const uint32_t *nbr0;       // [n][m0]
   const uint32_t *cnt0;       // [n]
@@ -163,6 +170,16 @@ struct HnswDenseScorer {
   __device__ __forceinline__ void operator()(const HnswArgs &a, const uint32_t *coll, float *cdist, uint32_t nc, int lane) const {
     hnsw_distances<H>(a, qv, coll, cdist, nc, lane);
   }
+};
+
+// Kind K as the kernels see it (the primary template: fp32 and fp16; zvk_hnsw_hamming.hip.h specialises it for HNSW_BITS).  lds: what
+// a query, or the build's candidate or base row, is kept as in LDS, 4 bytes under every kind; word(p, i): element i of an array of
+// rows or queries as that; Scorer: constructed from the row in LDS.
+template <HnswKind K>
+struct HnswRows {
+  typedef float lds;
+  typedef HnswDenseScorer<K == HNSW_F16> Scorer;
+  static __device__ __forceinline__ float word(const void *p, size_t i) { return hnsw_elem<K == HNSW_F16>(p, i); }
 };
 
 __device__ __forceinline__ bool hnsw_excluded(const HnswArgs &a, uint32_t id) {
@@ -323,31 +340,33 @@ __device__ __forceinline__ void hnsw_emit(const HnswArgs &a, uint32_t q, const u
   }
 }
 
-template <bool H>
+template <HnswKind K>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+  typedef typename HnswRows<K>::lds lds_t;
   const int lane = (int)threadIdx.x;
   const uint32_t q = blockIdx.x;
-  float *qv = reinterpret_cast<float *>(hnsw_smem);
+  lds_t *qv = reinterpret_cast<lds_t *>(hnsw_smem);
   uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
   uint64_t *C = R + a.ef;
   uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
   float *cdist = reinterpret_cast<float *>(coll + 64);
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? hnsw_elem<H>(a.queries, (size_t)q * a.dim + i) : 0.f;
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswRows<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
+  const typename HnswRows<K>::Scorer score{qv};
 
   // 1. the entry point
   uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
+  score(a, coll, cdist, 1, lane);
   float dist = cdist[0];
   hnsw_sync(false);
 
   // 2. the upper levels
-  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, HnswDenseScorer<H>{qv}, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, score, coll, cdist, ep, dist, scanned, lane);
 
   // 3. level 0
-  const uint32_t rsize = hnsw_beam(a, 0, HnswDenseScorer<H>{qv}, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
+  const uint32_t rsize = hnsw_beam(a, 0, score, R, C, a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr, coll, cdist,
                                    a.visited + (size_t)q * a.vis_words, ep, dist, scanned, hops, lane);
 
   // 4. the first topk of R within the threshold

@@ -198,12 +198,13 @@ __device__ __forceinline__ void hnsw_group_emit(const HnswArgs &a, const HnswGro
   }
 }
 
-template <bool H>
+template <HnswKind K>
 __global__ __launch_bounds__(64) void hnsw_group_search_kernel(HnswArgs a, HnswGroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+  typedef typename HnswRows<K>::lds lds_t;
   const int lane = (int)threadIdx.x;
   const uint32_t q = blockIdx.x;
-  float *qv = reinterpret_cast<float *>(hnsw_smem);
+  lds_t *qv = reinterpret_cast<lds_t *>(hnsw_smem);
   uint64_t *R = reinterpret_cast<uint64_t *>(qv + a.dpad);
   uint64_t *C = R + a.ef;
   uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
@@ -213,19 +214,20 @@ __global__ __launch_bounds__(64) void hnsw_group_search_kernel(HnswArgs a, HnswG
   s.group = reinterpret_cast<uint32_t *>(s.docs + (size_t)ga.gnum * ga.gk);
   s.size = s.group + ga.gnum;
   s.used = 0;
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? hnsw_elem<H>(a.queries, (size_t)q * a.dim + i) : 0.f;
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswRows<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
+  const typename HnswRows<K>::Scorer score{qv};
 
   // G1: steps 1-3 of the plain rule under ef_eff
   uint32_t scanned = 1, hops = 0, ep = a.entry;
-  hnsw_distances<H>(a, qv, coll, cdist, 1, lane);
+  score(a, coll, cdist, 1, lane);
   float dist = cdist[0];
   hnsw_sync(false);
-  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, HnswDenseScorer<H>{qv}, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = a.max_level; l >= 1; --l) hnsw_greedy(a, l, score, coll, cdist, ep, dist, scanned, lane);
   uint64_t *G = a.cand_ws != nullptr ? a.cand_ws + (size_t)q * a.ccap : nullptr;
   uint32_t *vis = a.visited + (size_t)q * a.vis_words;
-  const uint32_t rsize = hnsw_beam(a, 0, HnswDenseScorer<H>{qv}, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
+  const uint32_t rsize = hnsw_beam(a, 0, score, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
 
   // G2: R ascending, each member offered to its group; 64 group numbers are fetched at a time
   for (uint32_t i0 = 0; i0 < rsize; i0 += 64) {
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(64) void hnsw_group_search_kernel(HnswArgs a, HnswG
   }
 
   // G3: fewer groups than asked for: walk on
-  if (s.used < ga.gnum) hnsw_group_expand(a, ga, HnswDenseScorer<H>{qv}, s, R, rsize, C, G, coll, cdist, vis, scanned, hops, lane);
+  if (s.used < ga.gnum) hnsw_group_expand(a, ga, score, s, R, rsize, C, G, coll, cdist, vis, scanned, hops, lane);
 
   // G4 (C's place in LDS is free now: it holds the order of the slots)
   hnsw_sync(false);

@@ -1831,7 +1831,9 @@ class HipHammingIVFSearcher:
 
 class HipHnswSearcher:
     """Batched k-NN search on a built HNSW graph (zvec_hip_hnsw_*): what HnswSearcher::search_impl is above its brute-force
-    hand-over.  fp32 or fp16 rows, "SquaredEuclidean" or "InnerProduct".  The graph is loaded as plain arrays, or built from rows
+    hand-over.  fp32 or fp16 rows, "SquaredEuclidean" or "InnerProduct"; or, with metric "Hamming", dtype="binary32" / "binary64"
+    (zvec_hip_hnsw_create_binary): dim counts bits, rows and queries are dim // 32 uint32 resp. dim // 64 uint64 words as on
+    HipHammingIVFSearcher, scores are (float) popcount(row ^ query).  The graph is loaded as plain arrays, or built from rows
     (build).  dtype="fp16" (zvec_hip_hnsw_create_typed): rows and queries are stored and passed as IEEE binary16; load / build / add /
     search take float16 arrays as they are and round float32 arrays to nearest even (astype(float16), what HalfFloatConverter does);
     the _dev variants take raw pointers to halves; get_vectors_by_ids returns float16.  Scores are fp32."""
@@ -1842,8 +1844,16 @@ class HipHnswSearcher:
         self.device = device
         self.dtype, self.np_dtype = _dtype_of(dtype)
         self._h = C.c_void_p()
+        if self.dtype in (DT_BINARY32, DT_BINARY64) and self.metric == METRIC_HAMMING:
+            _lib.check(_lib.lib().zvec_hip_hnsw_create_binary(self.dim, self.dtype, device, C.byref(self._h)), "zvec_hip_hnsw_create_binary")
+            return
         create = "zvec_hip_hnsw_create_typed" if self.dtype == DT_FP16 else "zvec_hip_hnsw_create"
         _lib.check(getattr(_lib.lib(), create)(self.dim, self.dtype, self.metric, device, C.byref(self._h)), create)
+
+    @property
+    def row_words(self):
+        """words of np_dtype per row: dim for fp rows, dim // 32 resp. dim // 64 for bit rows"""
+        return _row_words(self.dim, self.dtype)
 
     def __del__(self):
         try:
@@ -1861,7 +1871,7 @@ class HipHnswSearcher:
         cnt_up [n_upper][max_level]"""
         rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
-        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+        if rows.ndim != 2 or (n and rows.shape[1] != self.row_words):
             return IndexError_.Mismatch
         nbr0 = np.ascontiguousarray(nbr0, np.uint32).reshape(n, -1) if n else np.zeros((0, 1), np.uint32)
         cnt0 = np.ascontiguousarray(cnt0, np.uint32)
@@ -1896,7 +1906,7 @@ class HipHnswSearcher:
         (hnsw_levels).  Returns 0 or a negative IndexError value."""
         rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
-        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+        if rows.ndim != 2 or (n and rows.shape[1] != self.row_words):
             return IndexError_.Mismatch
         args = self._build_args(n, keys, levels, m, m0, ef_construction, prune_cnt, min_neighbors, scaling_factor, seed)
         if args is None:
@@ -1939,7 +1949,7 @@ class HipHnswSearcher:
         IndexError value."""
         rows = np.ascontiguousarray(rows, self.np_dtype)
         n = rows.shape[0]
-        if rows.ndim != 2 or (n and rows.shape[1] != self.dim):
+        if rows.ndim != 2 or (n and rows.shape[1] != self.row_words):
             return IndexError_.Mismatch
         args = self._add_args(n, keys, levels, params)
         if args is None:
@@ -1978,7 +1988,7 @@ class HipHnswSearcher:
 
     def get_vectors_by_ids(self, positions):
         pos = np.ascontiguousarray(positions, np.uint64)
-        out = np.zeros((pos.size, self.dim), self.np_dtype)
+        out = np.zeros((pos.size, self.row_words), self.np_dtype)
         _lib.check(_lib.lib().zvec_hip_hnsw_get_vectors(self._h, _np_ptr(pos), pos.size, _np_ptr(out)), "zvec_hip_hnsw_get_vectors")
         return out
 
@@ -2001,7 +2011,7 @@ class HipHnswSearcher:
         if ctx is None or ctx.topk() == 0:
             return IndexError_.InvalidArgument
         q = np.ascontiguousarray(query, self.np_dtype).reshape(int(count), -1)
-        if q.shape[1] != self.dim:
+        if q.shape[1] != self.row_words:
             return IndexError_.Mismatch
         k = ctx.topk()
         keys = np.zeros((count, k), np.uint64)
@@ -2029,7 +2039,7 @@ class HipHnswSearcher:
         if ctx is None or not ctx.group_by_search() or ctx._group_topk <= 0 or ctx._group_by is None:
             return IndexError_.InvalidArgument
         q = np.ascontiguousarray(query, self.np_dtype).reshape(int(count), -1)
-        if q.shape[1] != self.dim:
+        if q.shape[1] != self.row_words:
             return IndexError_.Mismatch
         n = self.info()["n"]
         allk = np.zeros(n, np.uint64)
