@@ -170,8 +170,18 @@ struct zvec_hip_hnsw_s {
   ~zvec_hip_hnsw_s() { delete defctx; }
 };
 
-// the instantiation of a kernel template for the kind of the handle's rows
-#define HNSW_KERNEL(h, k) ((h)->kind() == HNSW_BITS ? k<HNSW_BITS> : (h)->kind() == HNSW_F16 ? k<HNSW_F16> : k<HNSW_F32>)
+// the dynamic LDS a kernel may take without having its limit raised (raise_dynamic_lds)
+constexpr size_t HNSW_LDS_UNRAISED = 64 * 1024;
+
+// f(the model of the handle's rows): the kernel instantiations a dense or binary handle launches are picked here
+extern "C++" template <typename F>
+static int hnsw_with_rows(const zvec_hip_hnsw_s *h, F &&f) {
+  switch (h->kind()) {
+    case HNSW_BITS: return f(HnswRows<HNSW_BITS>());
+    case HNSW_F16: return f(HnswRows<HNSW_F16>());
+    default: return f(HnswRows<HNSW_F32>());
+  }
+}
 
 // One change of an HNSW handle (IvfWrite's twin): h->mu, the built-in context's mutex (the rounds use its stream and workspace) and
 // h->rw exclusively, in the handle's lock order, while it lives.  Hd: zvec_hip_hnsw_s, or the sparse family's handle, which keeps
@@ -386,9 +396,11 @@ static int hnsw_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, const v
   return hnsw_search_sliced(h, h->graph, h->graph.args(h->dim, h->dpad, h->metric), c, count, topk, ef, max_scan, threshold, d_exclude,
                             d_out_keys, d_out_scores, d_out_counts, s, [&](HnswArgs &a, uint32_t q0, uint32_t mq) -> int {
     a.queries = static_cast<const unsigned char *>(d_queries) + (size_t)q0 * h->row_bytes();
-    hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_search_kernel), dim3(mq), dim3(64), hnsw_lds_bytes(a.dpad, a.ef), s, a);
-    ZCHK(hipGetLastError());
-    return 0;
+    return hnsw_with_rows(h, [&](auto rows) -> int {
+      hipLaunchKernelGGL(hnsw_search_kernel<decltype(rows)::KIND>, dim3(mq), dim3(64), hnsw_search_lds_bytes(rows.slot_bytes(a), a.ef, 0), s, a);
+      ZCHK(hipGetLastError());
+      return 0;
+    });
   });
 }
 

@@ -3,8 +3,8 @@
 // api_entry_hnsw.inc.h then answers search, info, export and get_vectors as after a load.  The rule is DESIGN §3c "Building":
 // HnswAlgorithm::add_node, update_neighbors and reverse_update_neighbors (hnsw_algorithm.cc:31-81, 394-515) applied in rounds.
 // hnsw_plan_call and hnsw_insert_apply are shared with the append (api_entry_hnsw_add.inc.h): plan, then prepare, then mutate.
-// The plan, HnswRoundsScratch and hnsw_run_rounds also serve the build over sparse rows (api_entry_hnsw_sparse_build.inc.h), which
-// hands hnsw_run_rounds its own three launches.
+// The plan, HnswRoundsScratch and hnsw_rounds_of also serve the build over sparse rows (api_entry_hnsw_sparse_build.inc.h), which
+// brings its own model of the rows.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
 static_assert(HNSW_PLAN_MAX_LEVEL == HNSW_BUILD_MAX_LEVEL && HNSW_PLAN_MAX_EF == HNSW_MAX_EF && HNSW_PLAN_MAX_M0 == HNSW_BUILD_MAX_M0 &&
@@ -49,14 +49,14 @@ struct HnswRoundsScratch {
   }
 };
 
-// the three kernels of a family's build, in the order a round launches them
+// the three kernels of a build, in the order a round launches them
 enum HnswRoundStep { HNSW_STEP_INSERT, HNSW_STEP_REVERSE_ONE, HNSW_STEP_REVERSE };
 
 // The rounds of `pl` on the graph g: resized for the plan's shape, the new rows and their upper_of in place, n still the old count.
-// A round of one node applies its requests straight from the round buffer (the family's reverse-one kernel); a round of more sorts
-// and groups them first.  args: g.args(..) of the family; launch(step, b, grid, slots, s) starts the family's kernel for that step
-// with `grid` waves on stream s (the grouped reverse step reads w.req_b, w.gstart and w.ngroups).  c: the handle's built-in
-// context.  The caller holds the handle's write scope and has synchronised the device.
+// A round of one node applies its requests straight from the round buffer (the reverse-one kernel); a round of more sorts and groups
+// them first.  args: g.args(..) of the family; launch(step, b, grid, slots, s) starts the kernel for that step with `grid` waves on
+// stream s (the grouped reverse step reads w.req_b, w.gstart and w.ngroups): hnsw_rounds_of, below, is the caller.  c: the handle's
+// built-in context.  The caller holds the handle's write scope and has synchronised the device.
 extern "C++" template <typename Launch>
 static int hnsw_run_rounds(zvec_hip_ctx_s *c, const HnswArgs &args, const HnswGraph &g, const HnswInsertPlan &pl, HnswRoundsScratch &w,
                            HnswInsertDone &done, Launch &&launch) {
@@ -114,6 +114,33 @@ static int hnsw_run_rounds(zvec_hip_ctx_s *c, const HnswArgs &args, const HnswGr
   return 0;
 }
 
+// hnsw_run_rounds for rows of the model's kind (`args`: g.args(..) of the family): the LDS of an insert wave and of a reverse wave
+// from the function the kernels lay theirs out by, the dynamic-LDS limit of the instantiations raised where a launch needs more than
+// the default (only CSR rows can: two 4096-pair fp32 runs are 64 KiB), and the three launches.
+extern "C++" template <typename Rows>
+static int hnsw_rounds_of(zvec_hip_ctx_s *c, const HnswArgs &args, const Rows &rows, const HnswGraph &g, const HnswInsertPlan &pl,
+                          HnswRoundsScratch &w, HnswInsertDone &done) {
+  const size_t slot = rows.slot_bytes(args);
+  const size_t lds_ins = hnsw_walk_lds_bytes(2, slot, pl.q.ef_construction, true, Rows::SCRATCH, true, true);
+  const size_t lds_rev = hnsw_walk_lds_bytes(2, slot, HNSW_REVERSE_WORDS, false, Rows::SCRATCH, true, false);
+  if (lds_ins > LDS_LIMIT) return ZVEC_HIP_ERR_UNSUPPORTED;          // (no valid input gets here: 78.3 KiB at 4096 pairs, ef 512)
+  if (lds_ins > HNSW_LDS_UNRAISED) ZRET(raise_dynamic_lds<&hnsw_insert_kernel<Rows>>(LDS_LIMIT));
+  if (lds_rev > HNSW_LDS_UNRAISED) {
+    ZRET(raise_dynamic_lds<&hnsw_reverse_kernel<Rows>>(LDS_LIMIT));
+    ZRET(raise_dynamic_lds<&hnsw_reverse_one_kernel<Rows>>(LDS_LIMIT));
+  }
+  return hnsw_run_rounds(c, args, g, pl, w, done, [&](HnswRoundStep step, const HnswBuildArgs &b, uint32_t grid, uint64_t slots, hipStream_t s) -> int {
+    if (step == HNSW_STEP_INSERT)
+      hipLaunchKernelGGL(hnsw_insert_kernel<Rows>, dim3(grid), dim3(64), lds_ins, s, b, rows);
+    else if (step == HNSW_STEP_REVERSE_ONE)
+      hipLaunchKernelGGL(hnsw_reverse_one_kernel<Rows>, dim3(grid), dim3(64), lds_rev, s, b, rows, slots);
+    else
+      hipLaunchKernelGGL(hnsw_reverse_kernel<Rows>, dim3(grid), dim3(64), lds_rev, s, b, rows, w.req_b.p, slots, w.gstart.p, w.ngroups.p);
+    ZCHK(hipGetLastError());
+    return 0;
+  });
+}
+
 // What both entries hand hnsw_insert_plan beside their own arguments: the two round options and the workspace budget.  h is read
 // for an append alone.
 static int hnsw_plan_call(const HnswShape &found, const zvec_hip_hnsw_s *h, bool append, uint64_t count, const void *rows,
@@ -148,17 +175,8 @@ static int hnsw_insert_apply(zvec_hip_hnsw_s *h, HnswGraph &g, const HnswInsertP
   if (pl.after.stride)                                                                             //    and counts are zero already
     ZCHK(hipMemcpy(g.arr.upper_of.p + pl.base, pl.upper_of.data(), (size_t)pl.count * 4, hipMemcpyHostToDevice));
   ZCHK(hipDeviceSynchronize());                  // (a device-to-device copy of rows may still be in flight on the null stream)
-  ZRET(hnsw_run_rounds(h->defctx, g.args(h->dim, h->dpad, h->metric), g, pl, w, done,              // 4
-                       [&](HnswRoundStep step, const HnswBuildArgs &b, uint32_t grid, uint64_t slots, hipStream_t s) -> int {
-    const size_t lds_rev = hnsw_reverse_lds_bytes(b.g.dpad);
-    if (step == HNSW_STEP_INSERT)
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_insert_kernel), dim3(grid), dim3(64), hnsw_insert_lds_bytes(b.g.dpad, b.g.ef), s, b);
-    else if (step == HNSW_STEP_REVERSE_ONE)
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_one_kernel), dim3(grid), dim3(64), lds_rev, s, b, slots);
-    else
-      hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_reverse_kernel), dim3(grid), dim3(64), lds_rev, s, b, w.req_b.p, slots, w.gstart.p, w.ngroups.p);
-    ZCHK(hipGetLastError());
-    return 0;
+  ZRET(hnsw_with_rows(h, [&](auto rows) -> int {                                                   // 4
+    return hnsw_rounds_of(h->defctx, g.args(h->dim, h->dpad, h->metric), rows, g, pl, w, done);
   }));
   hnsw_insert_finish(g, pl, done);                                                                 // 5
   return 0;

@@ -24,9 +24,12 @@ static int hnsw_group_search_dev_locked(zvec_hip_hnsw_s *h, zvec_hip_ctx_s *c, c
     a.out_counts = o.counts + (size_t)q0 * gnum;
     ga.out_groups = o.groups + (size_t)q0 * gnum;
     ga.out_ngroups = o.ngroups + q0;
-    hipLaunchKernelGGL(HNSW_KERNEL(h, hnsw_group_search_kernel), dim3(mq), dim3(64), hnsw_group_lds_bytes(a.dpad, a.ef, gnum, gk), s, a, ga);
-    ZCHK(hipGetLastError());
-    return 0;
+    return hnsw_with_rows(h, [&](auto rows) -> int {
+      hipLaunchKernelGGL(hnsw_group_search_kernel<decltype(rows)::KIND>, dim3(mq), dim3(64),
+                         hnsw_group_lds_bytes(hnsw_search_lds_bytes(rows.slot_bytes(a), a.ef, 0), gnum, gk), s, a, ga);
+      ZCHK(hipGetLastError());
+      return 0;
+    });
   }));
   if (h->graph.n == 0) {
     ga.out_groups = o.groups; ga.out_ngroups = o.ngroups;

@@ -6,9 +6,6 @@
 // api_entry_sparse.inc.h's.  Loads a graph somebody else built; api_entry_hnsw_sparse_build.inc.h builds one.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
 
-// the dynamic LDS a kernel may take without having its limit raised: a walk needs hnsw_sparse_lds_bytes, 46.25 KiB at the most
-constexpr size_t HNSW_SPARSE_LDS_LIMIT = 64 * 1024;
-
 struct zvec_hip_hnsw_sparse_s {
   int device = 0;
   int dtype = ZVEC_HIP_DT_FP32;        // of the values of rows and queries; halves are stored as halves
@@ -170,19 +167,19 @@ static int hnsw_sparse_search_dev_locked(zvec_hip_hnsw_sparse_s *h, zvec_hip_ctx
       max_run = std::max(max_run, q_counts[q]);
     }
     // (never truncated: a walk whose run, R and C do not fit is refused whole)
-    if (hnsw_sparse_lds_bytes(max_run, h->width, std::max(ef, topk)) > HNSW_SPARSE_LDS_LIMIT) return ZVEC_HIP_ERR_UNSUPPORTED;
+    if (hnsw_search_lds_bytes(hnsw_sparse_run_bytes(max_run, h->width), std::max(ef, topk), HnswCsrRows<float>::SCRATCH) > HNSW_LDS_UNRAISED)
+      return ZVEC_HIP_ERR_UNSUPPORTED;
     ZRET(sparse_upload_plan(c, plan, s));
     sa.op = SparseOperands{h->row_off, h->idx, h->val, nullptr, c->sp_plan.as<uint32_t>(), d_qidx, d_qval};
     sa.run_bytes = (uint32_t)hnsw_sparse_run_bytes(max_run, h->width);
   }
   const size_t run_bytes = sa.run_bytes;
-  const uint32_t width = h->width;
   return hnsw_search_sliced(h, h->graph, h->graph.args(0, 0, ZVEC_HIP_METRIC_IP), c, count, topk, ef, max_scan, threshold, d_exclude,
                             d_out_keys, d_out_scores, d_out_counts, s, [&](HnswArgs &a, uint32_t q0, uint32_t mq) -> int {
     sa.g = a;
     sa.q0 = q0;
-    const size_t lds = run_bytes + hnsw_sparse_lds_bytes(0, width, a.ef);
-    if (width == 2) hipLaunchKernelGGL(hnsw_sparse_search_kernel<_Float16>, dim3(mq), dim3(64), lds, s, sa);
+    const size_t lds = hnsw_search_lds_bytes(run_bytes, a.ef, HnswCsrRows<float>::SCRATCH);
+    if (h->width == 2) hipLaunchKernelGGL(hnsw_sparse_search_kernel<_Float16>, dim3(mq), dim3(64), lds, s, sa);
     else hipLaunchKernelGGL(hnsw_sparse_search_kernel<float>, dim3(mq), dim3(64), lds, s, sa);
     ZCHK(hipGetLastError());
     return 0;

@@ -1,38 +1,10 @@
 // api_entry_hnsw_sparse_build.inc.h — C ABI entry points: building an HNSW graph over SPARSE rows on the device
-// (zvec_hip_hnsw_sparse_build*; inside extern "C").  Device code: zvk_hnsw_sparse_build.hip.h.  Stands behind HnswSparseBuilder
-// (src/core/algorithm/hnsw_sparse/hnsw_sparse_builder.cc).  The rule is DESIGN §3c "Building" unchanged, and so is the host's share:
-// the plan (hnsw_plan_call, host/hnsw_add_plan.h), the rounds' scratch and the rounds themselves (HnswRoundsScratch,
-// hnsw_run_rounds of api_entry_hnsw_build.inc.h, given this family's three launches).  Runs in, searchable graph out: the handle of
-// api_entry_hnsw_sparse.inc.h then answers search, info, get_vector and export as after a load.
+// (zvec_hip_hnsw_sparse_build*; inside extern "C").  Device code: the build kernels of zvk_hnsw_build.hip.h on the model of
+// zvk_hnsw_sparse.hip.h.  Stands behind HnswSparseBuilder (src/core/algorithm/hnsw_sparse/hnsw_sparse_builder.cc).  The rule is
+// DESIGN §3c "Building" unchanged, and so is the host's share: the plan (hnsw_plan_call, host/hnsw_add_plan.h), the rounds' scratch
+// and the rounds themselves (HnswRoundsScratch, hnsw_rounds_of of api_entry_hnsw_build.inc.h).  Runs in, searchable graph out: the
+// handle of api_entry_hnsw_sparse.inc.h then answers search, info, get_vector and export as after a load.
 // Part of zvec_hip_api.hip (one translation unit; included in order, not standalone).
-
-// The launches of one build: the three kernels for the handle's value type, their LDS, and the limit raised where a launch needs it.
-extern "C++" template <typename VT>
-static int hnsw_sparse_rounds(zvec_hip_hnsw_sparse_s *h, const HnswGraph &g, const HnswSparseRows &rows, uint32_t longest,
-                              const HnswInsertPlan &pl, HnswRoundsScratch &w, HnswInsertDone &done) {
-  HnswSparseBuildArgs sa{};
-  sa.row_off = rows.row_off; sa.idx = rows.idx; sa.val = rows.val; sa.run_elems = longest;
-  const size_t lds_ins = hnsw_sparse_build_lds_bytes(longest, sizeof(VT), pl.q.ef_construction, true);
-  const size_t lds_rev = hnsw_sparse_build_lds_bytes(longest, sizeof(VT), HNSW_BUILD_MAX_M0 + 2, false);
-  if (lds_ins > LDS_LIMIT) return ZVEC_HIP_ERR_UNSUPPORTED;          // (no valid input gets here: 78.3 KiB at 4096 pairs, ef 512)
-  if (lds_ins > HNSW_SPARSE_LDS_LIMIT) ZRET(raise_dynamic_lds<&hnsw_sparse_insert_kernel<VT>>(LDS_LIMIT));
-  if (lds_rev > HNSW_SPARSE_LDS_LIMIT) {
-    ZRET(raise_dynamic_lds<&hnsw_sparse_reverse_kernel<VT>>(LDS_LIMIT));
-    ZRET(raise_dynamic_lds<&hnsw_sparse_reverse_one_kernel<VT>>(LDS_LIMIT));
-  }
-  return hnsw_run_rounds(h->defctx, g.args(0, 0, ZVEC_HIP_METRIC_IP), g, pl, w, done,
-                         [&](HnswRoundStep step, const HnswBuildArgs &b, uint32_t grid, uint64_t slots, hipStream_t s) -> int {
-    sa.b = b;
-    if (step == HNSW_STEP_INSERT)
-      hipLaunchKernelGGL(hnsw_sparse_insert_kernel<VT>, dim3(grid), dim3(64), lds_ins, s, sa);
-    else if (step == HNSW_STEP_REVERSE_ONE)
-      hipLaunchKernelGGL(hnsw_sparse_reverse_one_kernel<VT>, dim3(grid), dim3(64), lds_rev, s, sa, slots);
-    else
-      hipLaunchKernelGGL(hnsw_sparse_reverse_kernel<VT>, dim3(grid), dim3(64), lds_rev, s, sa, w.req_b.p, slots, w.gstart.p, w.ngroups.p);
-    ZCHK(hipGetLastError());
-    return 0;
-  });
-}
 
 // A build is an insertion from base 0 into a fresh graph over fresh rows; both take the old ones' place on success.  Everything that
 // can be refused is refused, and everything that is allocated is allocated, on locals: a refused build leaves the handle as it was.
@@ -59,8 +31,10 @@ static int hnsw_sparse_build_entry(zvec_hip_hnsw_sparse_t h, uint64_t n, const u
   if (pl.after.stride) ZCHK(hipMemcpy(g.arr.upper_of.p, pl.upper_of.data(), (size_t)pl.count * 4, hipMemcpyHostToDevice));
   ZCHK(hipDeviceSynchronize());                  // (a device-to-device copy of pairs may still be in flight on the null stream)
   const uint32_t longest = n ? *std::max_element(counts, counts + n) : 0u;
-  if (h->width == 2) ZRET(hnsw_sparse_rounds<_Float16>(h, g, rows, longest, pl, ws, done));
-  else ZRET(hnsw_sparse_rounds<float>(h, g, rows, longest, pl, ws, done));
+  ZRET(sparse_dispatch(h->width, [&](auto vt) -> int {     // (both slots of a wave are sized by the longest row)
+    const HnswCsrRows<decltype(vt)> model{SparseOperands{rows.row_off, rows.idx, rows.val, nullptr, nullptr, nullptr, nullptr}, longest};
+    return hnsw_rounds_of(h->defctx, g.args(0, 0, ZVEC_HIP_METRIC_IP), model, g, pl, ws, done);
+  }));
   hnsw_insert_finish(g, pl, done);
   hnsw_sparse_commit(h, g, rows);                // the old arrays go with the locals
   h->params = pl.q;

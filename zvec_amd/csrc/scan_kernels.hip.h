@@ -45,4 +45,3 @@
 #include "zvk_hnsw_group.hip.h"
 #include "zvk_hnsw_build.hip.h"
 #include "zvk_hnsw_sparse.hip.h"
-#include "zvk_hnsw_sparse_build.hip.h"

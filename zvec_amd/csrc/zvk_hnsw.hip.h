@@ -9,13 +9,14 @@
 // region of the context workspace when more than that many candidates are alive at the same time (rows excluded by the caller's
 // bitset are traversed but never fill R, so nothing bounds C below the row count then).
 //
-// Rows and queries are of one of three kinds (HnswKind, the template parameter K of every kernel): fp32, IEEE binary16, or words of
-// bits under the Hamming distance (zvk_hnsw_hamming.hip.h).  HnswRows<K> says what a kernel needs of its kind: the 4-byte word a
-// query, or the build's candidate or base row, is kept as in LDS, how one is read, and the scorer.  The dense code below it keeps its
-// own parameter H (H = true, halves).  A half is widened to fp32 where it is read, which is exact (subnormals included, nothing
-// flushed); from there on the arithmetic is the fp32 kernel's own, operation for operation and in the same order, so an fp16 handle
-// answers bit for bit as an fp32 handle given the widened values would (DESIGN §3c "fp16 rows").  LDS holds a dense query, and the
-// build's candidate row, as fp32 either way.
+// Rows and queries are of one of five kinds.  The build kernels (zvk_hnsw_build.hip.h) are templates on the MODEL of their kind, a
+// small struct passed by value (see "The model of a row kind" below): HnswRows<K> for dense fp32 rows, IEEE binary16 rows and words
+// of bits under the Hamming distance (zvk_hnsw_hamming.hip.h), HnswCsrRows<VT> for sparse rows with float or _Float16 values
+// (zvk_hnsw_sparse.hip.h).  The search kernels stage their query themselves: hnsw_search_kernel<K> and hnsw_group_search_kernel<K>
+// for the dense kinds, hnsw_sparse_search_kernel<VT>.  The dense distance code keeps its own parameter H (H = true, halves).
+// A half is widened to fp32 where it is read, which is exact (subnormals included, nothing flushed); from there on the arithmetic is
+// the fp32 kernel's own, operation for operation and in the same order, so an fp16 handle answers bit for bit as an fp32 handle
+// given the widened values would (DESIGN §3c "fp16 rows").  LDS holds a dense query, and the build's candidate row, as fp32 either way.
 #pragma once
 #include "zvk_common.hip.h"
 
@@ -25,6 +26,7 @@ constexpr uint32_t HNSW_MAX_EF = 512;      // words of R: 4 KiB of LDS per query
 constexpr uint32_t HNSW_C_LDS = 1024;      // words of C held in LDS: 8 KiB per query
 constexpr uint32_t HNSW_MAX_DIM = 4096;    // the query row is kept in LDS
 constexpr uint32_t HNSW_MAX_BITS = 32768;  // of a binary row: 1024 words, the LDS bytes of a 1024-d fp32 query
+constexpr uint32_t HNSW_BUILD_MAX_M0 = 256; // the kept ids of one selection of the build are held in LDS
 
 enum HnswKind : int { HNSW_F32 = 0, HNSW_F16 = 1, HNSW_BITS = 2 };
 
@@ -54,9 +56,45 @@ struct HnswArgs {
   uint32_t *stats;            // [nq][2]: distances computed, nodes expanded
 };
 
-__host__ __device__ inline size_t hnsw_lds_bytes(uint32_t dpad, uint32_t ef) {
-  return (size_t)dpad * 4 + (size_t)ef * 8 + (size_t)HNSW_C_LDS * 8 + 64 * 4 + 64 * 4;
+// The LDS of one wave of any kernel of the walk, search or build, of any row kind; the host sizes a launch with the function the
+// kernel lays its arrays out by.  slots: the staged rows (1: the query; 2: the build's base row and the keep rule's candidate), each
+// slot_bytes, a multiple of 8; words: of R (or of the reverse phase's sorted list S); cand: C is there; scratch: what the kind's
+// scorer keeps beside coll and cdist, a multiple of 8; kept, mask: the selection's kept ids, and its bits over the places of R.
+// slots | R [words] | C [HNSW_C_LDS] | scorer scratch | coll [64] | cdist [64] | kept [HNSW_BUILD_MAX_M0] | mask [16]
+// The search kernels lay out the same bytes with slots = 1 and neither kept nor mask.
+__host__ __device__ inline size_t hnsw_walk_lds_bytes(uint32_t slots, size_t slot_bytes, uint32_t words, bool cand, uint32_t scratch, bool kept,
+                                                      bool mask) {
+  return slots * slot_bytes + (size_t)words * 8 + (cand ? (size_t)HNSW_C_LDS * 8 : 0) + scratch + 64 * 4 + 64 * 4 +
+         (kept ? HNSW_BUILD_MAX_M0 * 4 : 0) + (mask ? 16 * 4 : 0);
 }
+
+// a search wave's: the query's slot, R of ef words, C, and the kind's scorer scratch
+__host__ __device__ inline size_t hnsw_search_lds_bytes(size_t slot_bytes, uint32_t ef, uint32_t scratch) {
+  return hnsw_walk_lds_bytes(1, slot_bytes, ef, true, scratch, false, false);
+}
+
+// The arrays of a build wave.  Only what the launch was sized for may be touched: slot1 with two slots, C with cand, kept with kept,
+// mask with mask; the other pointers lie beyond the allocation.  A reverse wave's sorted list S is R.
+struct HnswLds {
+  unsigned char *slot0, *slot1, *scratch;
+  uint64_t *R, *C;
+  uint32_t *coll, *kept, *mask;
+  float *cdist;
+  // Off: the integer the slots' offsets are computed in, size_t or uint32_t (LDS offsets fit either).  The choice changes no value,
+  // only the code the compiler makes of the kernel around it: the insert kernel takes uint32_t (zvk_hnsw_build.hip.h says why).
+  template <typename Off>
+  __device__ __forceinline__ HnswLds(unsigned char *smem, uint32_t slots, Off slot_bytes, uint32_t words, bool cand, uint32_t scratch_bytes) {
+    slot0 = smem;
+    slot1 = smem + slot_bytes;
+    R = reinterpret_cast<uint64_t *>(smem + slots * slot_bytes);
+    C = R + words;
+    scratch = reinterpret_cast<unsigned char *>(C + (cand ? HNSW_C_LDS : 0u));
+    coll = reinterpret_cast<uint32_t *>(scratch + scratch_bytes);
+    cdist = reinterpret_cast<float *>(coll + 64);
+    kept = reinterpret_cast<uint32_t *>(cdist + 64);
+    mask = kept + HNSW_BUILD_MAX_M0;
+  }
+};
 
 // what differs between the two element types: the element itself, and the four elements a lane loads per step
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -172,14 +210,38 @@ struct HnswDenseScorer {
   }
 };
 
-// Kind K as the kernels see it (the primary template: fp32 and fp16; zvk_hnsw_hamming.hip.h specialises it for HNSW_BITS).  lds: what
-// a query, or the build's candidate or base row, is kept as in LDS, 4 bytes under every kind; word(p, i): element i of an array of
-// rows or queries as that; Scorer: constructed from the row in LDS.
+// The model of a row kind: all a kernel of the walk knows of its rows, and the only thing a new kind has to supply.  A plain struct
+// passed to the kernel by value, with
+//   Scorer                                   the kind's scorer
+//   SCRATCH                                  the bytes of LDS the scorer needs beside coll and cdist (a multiple of 8)
+//   slot_bytes(a)                            the bytes one staged row takes in LDS (host and device; a multiple of 8)
+//   stage_row(a, slot, scratch, node, lane)  the whole wave copies stored row `node` into the slot
+// The stager ends in hnsw_sync(false) and returns the scorer of other rows against the slot; whoever read the slot's last occupant
+// has finished (every scorer call ends in hnsw_sync).  A Scorer is trivially default-constructible and assignable: a reverse group
+// declares one before it knows whether it will stage the row (hnsw_reverse_group).
+//
+// HnswRows<K>: the dense kinds, which carry nothing beside HnswArgs (the primary template: fp32 and fp16; zvk_hnsw_hamming.hip.h
+// specialises Scorer and word for HNSW_BITS through HnswDenseKind).  A slot is dpad words of 4 bytes under every kind.
 template <HnswKind K>
-struct HnswRows {
+struct HnswDenseKind {
   typedef float lds;
   typedef HnswDenseScorer<K == HNSW_F16> Scorer;
   static __device__ __forceinline__ float word(const void *p, size_t i) { return hnsw_elem<K == HNSW_F16>(p, i); }
+};
+
+template <HnswKind K>
+struct HnswRows {
+  typedef typename HnswDenseKind<K>::lds lds_t;
+  typedef typename HnswDenseKind<K>::Scorer Scorer;
+  static constexpr HnswKind KIND = K;
+  static constexpr uint32_t SCRATCH = 0;
+  __host__ __device__ __forceinline__ size_t slot_bytes(const HnswArgs &a) const { return (size_t)a.dpad * 4; }
+  __device__ __forceinline__ Scorer stage_row(const HnswArgs &a, unsigned char *slot, unsigned char *, uint32_t node, int lane) const {
+    lds_t *s = reinterpret_cast<lds_t *>(slot);
+    for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) s[t] = HnswDenseKind<K>::word(a.rows, (size_t)node * a.dpad + t);
+    hnsw_sync(false);
+    return Scorer{s};
+  }
 };
 
 __device__ __forceinline__ bool hnsw_excluded(const HnswArgs &a, uint32_t id) {
@@ -340,10 +402,11 @@ __device__ __forceinline__ void hnsw_emit(const HnswArgs &a, uint32_t q, const u
   }
 }
 
+// one wave per query, one wave per work-group (the dense kinds; zvk_hnsw_sparse.hip.h has the sparse rows' kernel)
 template <HnswKind K>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  typedef typename HnswRows<K>::lds lds_t;
+  typedef typename HnswDenseKind<K>::lds lds_t;
   const int lane = (int)threadIdx.x;
   const uint32_t q = blockIdx.x;
   lds_t *qv = reinterpret_cast<lds_t *>(hnsw_smem);
@@ -351,7 +414,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
   uint64_t *C = R + a.ef;
   uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
   float *cdist = reinterpret_cast<float *>(coll + 64);
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswRows<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswDenseKind<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
   const typename HnswRows<K>::Scorer score{qv};

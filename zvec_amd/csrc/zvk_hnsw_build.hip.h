@@ -8,19 +8,22 @@
 //   hnsw_reverse_kernel  one wave per group applies its requests in ascending source
 //   hnsw_reverse_one_kernel  a round of ONE node: every used request word is a group of one, no sort and no grouping
 //   hnsw_restride_kernel the upper table under a larger stride (zvec_hip_hnsw_add, api_entry_hnsw_add.inc.h)
-// The walk is the search's own (hnsw_greedy, hnsw_beam, hnsw_put and the scorer of zvk_hnsw.hip.h), and so is the template parameter
-// K (the kind of the rows): a row of halves copied into LDS is widened on the way and kept there as fp32, a row of bits is copied as
-// it is.
+// The walk is the search's own (hnsw_greedy, hnsw_beam, hnsw_put of zvk_hnsw.hip.h), and so is the template parameter Rows, the model
+// of the rows' kind: it stages a stored row into an LDS slot and hands back the scorer against it, and nothing else here knows what a
+// row is.  Dense, binary and sparse builds (zvec_hip_hnsw_sparse_build, api_entry_hnsw_sparse_build.inc.h) are instantiations.
+// Two slots: slot 0 is the BASE of the wave's work, the new node's row in the insert kernel and the target's row in a reverse group
+// (staged only when the group's first prune is due); slot 1 is the keep rule's current candidate.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 #pragma once
+#include <type_traits>
 #include <hipcub/hipcub.hpp>
 #include "zvk_hnsw.hip.h"
 
 namespace zvk {
 
 constexpr uint32_t HNSW_BUILD_MAX_LEVEL = 15;
-constexpr uint32_t HNSW_BUILD_MAX_M0 = 256;      // the kept ids of one selection are held in LDS
-constexpr uint32_t HNSW_BUILD_MAX_M = 128;
+constexpr uint32_t HNSW_BUILD_MAX_M = 128;       // (HNSW_BUILD_MAX_M0: zvk_hnsw.hip.h, beside the LDS layout)
+constexpr uint32_t HNSW_REVERSE_WORDS = HNSW_BUILD_MAX_M0 + 2;       // of a reverse wave's sorted list S: a full list, the source, a pad
 constexpr uint32_t HNSW_REQ_SRC_BITS = 28;       // a request word: level << 60 | target << 28 | source - first node of the round
 constexpr uint64_t HNSW_REQ_NONE = ~0ull;        // (no target is 2^32 - 1: sorts behind every request, belongs to no group)
 
@@ -38,20 +41,13 @@ struct HnswBuildArgs {
   unsigned long long *counters; // distances computed by the insert kernels, requests raised, prunes run
 };
 
-__host__ __device__ inline size_t hnsw_insert_lds_bytes(uint32_t dpad, uint32_t ef) {
-  return (size_t)dpad * 8 + (size_t)ef * 8 + (size_t)HNSW_C_LDS * 8 + 64 * 4 + 64 * 4 + HNSW_BUILD_MAX_M0 * 4 + 16 * 4;
-}
-__host__ __device__ inline size_t hnsw_reverse_lds_bytes(uint32_t dpad) {
-  return (size_t)dpad * 8 + (size_t)(HNSW_BUILD_MAX_M0 + 1) * 8 + 8 + 64 * 4 + 64 * 4 + HNSW_BUILD_MAX_M0 * 4;
-}
-
 // The keep rule of update_neighbors / reverse_update_neighbors: walk the ns words of S (ascending by (distance to the base, id)) and keep
-// c unless some kept s has d(c, s) <= d(c, base); stop at cap.  The candidate's row goes into cv, its distances to the kept ids are
-// computed 64 at a time and one ballot decides.  kept[] receives the ids, mask (nullable) the bit of every kept place of S; ndist
+// c unless some kept s has d(c, s) <= d(c, base); stop at cap.  The candidate's row goes into slot 1, its distances to the kept ids
+// are computed 64 at a time and one ballot decides.  m.kept receives the ids, mask (nullable) the bit of every kept place of S; ndist
 // grows by the kept ids each candidate was compared with.  Returns the number kept.
-template <HnswKind K>
-__device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t *S, uint32_t ns, uint32_t cap, typename HnswRows<K>::lds *cv, uint32_t *kept,
-                                              uint32_t *mask, float *cdist, uint32_t &ndist, int lane) {
+template <typename Rows>
+__device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const Rows &rows, const HnswLds &m, const uint64_t *S, uint32_t ns, uint32_t cap,
+                                              uint32_t *mask, uint32_t &ndist, int lane) {
   uint32_t nk = 0;
   for (uint32_t j = 0; j < ns && nk < cap; ++j) {
     const uint64_t w = hnsw_uni64(S[j]);
@@ -59,20 +55,18 @@ __device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t 
     const float dc = fkey_inv((uint32_t)(w >> 32));
     bool bad = false;
     if (nk > 0) {
-      for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) cv[t] = HnswRows<K>::word(a.rows, (size_t)c * a.dpad + t);
-      hnsw_sync(false);
-      const typename HnswRows<K>::Scorer score{cv};
+      const typename Rows::Scorer to_c = rows.stage_row(a, m.slot1, m.scratch, c, lane);
       for (uint32_t k0 = 0; k0 < nk; k0 += 64) {
         const uint32_t nc = min(64u, nk - k0);
-        score(a, kept + k0, cdist, nc, lane);
-        bad = bad || __ballot((uint32_t)lane < nc && cdist[lane] <= dc) != 0;
+        to_c(a, m.kept + k0, m.cdist, nc, lane);
+        bad = bad || __ballot((uint32_t)lane < nc && m.cdist[lane] <= dc) != 0;
         hnsw_sync(false);
       }
       ndist += nk;
     }
     if (!bad) {
       if (lane == 0) {
-        kept[nk] = c;
+        m.kept[nk] = c;
         if (mask != nullptr) mask[j >> 5] |= 1u << (j & 31u);
       }
       ++nk;
@@ -82,33 +76,35 @@ __device__ __forceinline__ uint32_t hnsw_keep(const HnswArgs &a, const uint64_t 
   return nk;
 }
 
-template <HnswKind K>
-__global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  typedef typename HnswRows<K>::lds lds_t;
+// the writable list of node t on level l and its count
+__device__ __forceinline__ uint32_t *hnsw_own_list(const HnswBuildArgs &b, uint32_t l, uint32_t t, uint32_t *&cnt) {
+  if (l == 0) {
+    cnt = b.cnt0 + t;
+    return b.nbr0 + (size_t)t * b.g.m0;
+  }
+  const size_t slot = (size_t)hnsw_uni(b.g.upper_of[t]) * b.g.max_level + (l - 1);
+  cnt = b.cnt_up + slot;
+  return b.nbr_up + slot * b.g.m;
+}
+
+template <typename Rows>
+__global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b, Rows rows) {
+  extern __shared__ f32x4 zvk_smem4[];
   const HnswArgs &a = b.g;
   const int lane = (int)threadIdx.x;
   const uint32_t wv = blockIdx.x, i = b.first + wv;
-  lds_t *qv = reinterpret_cast<lds_t *>(hnsw_smem);
-  lds_t *cv = qv + a.dpad;
-  uint64_t *R = reinterpret_cast<uint64_t *>(cv + a.dpad);
-  uint64_t *C = R + a.ef;
-  uint32_t *coll = reinterpret_cast<uint32_t *>(C + HNSW_C_LDS);
-  float *cdist = reinterpret_cast<float *>(coll + 64);
-  uint32_t *kept = reinterpret_cast<uint32_t *>(cdist + 64);
-  uint32_t *mask = kept + HNSW_BUILD_MAX_M0;
+  // (slot offsets in 32 bits: with 64-bit offsets the binary and the CSR fp32 instantiations measure 1.7 % slower)
+  const HnswLds m(reinterpret_cast<unsigned char *>(zvk_smem4), 2, (uint32_t)rows.slot_bytes(a), a.ef, true, Rows::SCRATCH);
   const uint32_t li = hnsw_uni(b.levels[i - b.node_base]);
-  for (uint32_t t = (uint32_t)lane; t < a.dpad; t += 64) qv[t] = HnswRows<K>::word(a.rows, (size_t)i * a.dpad + t);
-  if (lane == 0) coll[0] = a.entry;
-  hnsw_sync(false);
-  const typename HnswRows<K>::Scorer score{qv};
+  if (lane == 0) m.coll[0] = a.entry;
+  const typename Rows::Scorer score = rows.stage_row(a, m.slot0, m.scratch, i, lane);
 
   // 1. the entry point, then greedy on the levels above the node's own
   uint32_t scanned = 1, hops = 0, ep = a.entry;
-  score(a, coll, cdist, 1, lane);
-  float dist = cdist[0];
+  score(a, m.coll, m.cdist, 1, lane);
+  float dist = m.cdist[0];
   hnsw_sync(false);
-  for (uint32_t l = b.top; l > li; --l) hnsw_greedy(a, l, score, coll, cdist, ep, dist, scanned, lane);
+  for (uint32_t l = b.top; l > li; --l) hnsw_greedy(a, l, score, m.coll, m.cdist, ep, dist, scanned, lane);
 
   uint32_t *vis = a.visited + (size_t)wv * a.vis_words;
   uint64_t *G = a.cand_ws != nullptr ? a.cand_ws + (size_t)wv * a.ccap : nullptr;
@@ -119,43 +115,36 @@ __global__ __launch_bounds__(64) void hnsw_insert_kernel(HnswBuildArgs b) {
     // 2. W = the beam search's result list on this level; its nearest is the next level's entry point
     for (uint32_t t = (uint32_t)lane; t < a.vis_words; t += 64) vis[t] = 0;
     hnsw_sync(true);
-    const uint32_t rsize = hnsw_beam(a, (uint32_t)l, score, R, C, G, coll, cdist, vis, ep, dist, scanned, hops, lane);
+    const uint32_t rsize = hnsw_beam(a, (uint32_t)l, score, m.R, m.C, G, m.coll, m.cdist, vis, ep, dist, scanned, hops, lane);
     {
-      const uint64_t w0 = hnsw_uni64(R[0]);
+      const uint64_t w0 = hnsw_uni64(m.R[0]);
       ep = (uint32_t)w0;
       dist = fkey_inv((uint32_t)(w0 >> 32));
     }
     // 3. selection
     uint32_t nk;
     if (rsize <= min(b.prune_cnt, cap)) {
-      for (uint32_t j = (uint32_t)lane; j < rsize; j += 64) kept[j] = (uint32_t)R[j];
+      for (uint32_t j = (uint32_t)lane; j < rsize; j += 64) m.kept[j] = (uint32_t)m.R[j];
       nk = rsize;
       hnsw_sync(false);
     } else {
-      if (lane < 16) mask[lane] = 0;
+      if (lane < 16) m.mask[lane] = 0;
       hnsw_sync(false);
-      nk = hnsw_keep<K>(a, R, rsize, cap, cv, kept, mask, cdist, scanned, lane);
+      nk = hnsw_keep(a, rows, m, m.R, rsize, cap, m.mask, scanned, lane);
       for (uint32_t j = 0; j < rsize && nk < b.min_neighbors; ++j) {
-        if ((hnsw_uni(mask[j >> 5]) >> (j & 31u)) & 1u) continue;
-        if (lane == 0) kept[nk] = (uint32_t)R[j];
+        if ((hnsw_uni(m.mask[j >> 5]) >> (j & 31u)) & 1u) continue;
+        if (lane == 0) m.kept[nk] = (uint32_t)m.R[j];
         ++nk;
       }
       hnsw_sync(false);
     }
     // 4. the node's own list, and one request per selected neighbour
-    uint32_t *own, *ocnt;
-    if (l == 0) {
-      own = b.nbr0 + (size_t)i * a.m0;
-      ocnt = b.cnt0 + i;
-    } else {
-      const size_t slot = (size_t)hnsw_uni(a.upper_of[i]) * a.max_level + (uint32_t)(l - 1);
-      own = b.nbr_up + slot * a.m;
-      ocnt = b.cnt_up + slot;
-    }
+    uint32_t *ocnt;
+    uint32_t *own = hnsw_own_list(b, (uint32_t)l, i, ocnt);
     for (uint32_t j = (uint32_t)lane; j < cap; j += 64) {
       uint64_t word = HNSW_REQ_NONE;
       if (j < nk) {
-        const uint32_t t = kept[j];
+        const uint32_t t = m.kept[j];
         own[j] = t;
         word = ((uint64_t)(uint32_t)l << 60) | ((uint64_t)t << HNSW_REQ_SRC_BITS) | (uint64_t)(i - b.round_first);
       }
@@ -181,46 +170,32 @@ __global__ void hnsw_groups_kernel(const uint64_t *req, uint64_t slots, uint32_t
   if (j == 0 || (req[j - 1] >> HNSW_REQ_SRC_BITS) != (w >> HNSW_REQ_SRC_BITS)) gstart[atomicAdd(ngroups, 1u)] = (uint32_t)j;
 }
 
-// The LDS of a reverse wave (hnsw_reverse_lds_bytes); T: the word its kind keeps a row as (HnswRows<K>::lds)
-template <typename T>
-struct HnswReverseLds {
-  T *qv, *cv;
-  float *cdist;
-  uint64_t *S;
-  uint32_t *coll, *kept;
-  __device__ explicit HnswReverseLds(unsigned char *smem, uint32_t dpad) {
-    qv = reinterpret_cast<T *>(smem);
-    cv = qv + dpad;
-    S = reinterpret_cast<uint64_t *>(cv + dpad);
-    coll = reinterpret_cast<uint32_t *>(S + HNSW_BUILD_MAX_M0 + 2);
-    cdist = reinterpret_cast<float *>(coll + 64);
-    kept = reinterpret_cast<uint32_t *>(cdist + 64);
-  }
-};
+// The LDS of a wave of either reverse kernel: the sorted list S where an insert wave has R, no C, no mask
+template <typename Rows>
+__device__ __forceinline__ HnswLds hnsw_reverse_lds(const HnswBuildArgs &b, const Rows &rows) {
+  extern __shared__ f32x4 zvk_smem4[];
+  return HnswLds(reinterpret_cast<unsigned char *>(zvk_smem4), 2, rows.slot_bytes(b.g), HNSW_REVERSE_WORDS, false, Rows::SCRATCH);
+}
 
 // One (level, target) group, by one wave: the words req[j0 .. ) that share req[j0]'s level and target, at most up to jend, in
-// ascending source.  A list with room takes the source at its end; a full list plus the source is sorted by (distance to the target,
-// id) and goes through the keep rule, no shortcut and no fill, and the places the prune emptied are zeroed, so that a list never keeps
-// anything behind its count.  Returns the prunes run.
-template <HnswKind K>
-__device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, const HnswReverseLds<typename HnswRows<K>::lds> &m, const uint64_t *req, uint64_t j0,
+// ascending source.  A list with room takes the source at its end; a full list plus the source is scored against the target's row
+// (slot 0, staged at the group's first prune), sorted into m.R by (distance to the target, id) and put through the keep rule, no
+// shortcut and no fill, and the places the prune emptied are zeroed, so that a list never keeps anything behind its count.  Returns
+// the prunes run.
+template <typename Rows>
+__device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, const Rows &rows, const HnswLds &m, const uint64_t *req, uint64_t j0,
                                                        uint64_t jend, int lane) {
   const HnswArgs &a = b.g;
-  const typename HnswRows<K>::Scorer score{m.qv};          // against the target's row, once it is in LDS
   const uint64_t head = hnsw_uni64(req[j0]) >> HNSW_REQ_SRC_BITS;
   const uint32_t l = (uint32_t)(head >> 32), t = (uint32_t)head;
   const uint32_t cap = l == 0 ? a.m0 : a.m;
-  uint32_t *lst, *lcnt;
-  if (l == 0) {
-    lst = b.nbr0 + (size_t)t * a.m0;
-    lcnt = b.cnt0 + t;
-  } else {
-    const size_t slot = (size_t)hnsw_uni(a.upper_of[t]) * a.max_level + (l - 1);
-    lst = b.nbr_up + slot * a.m;
-    lcnt = b.cnt_up + slot;
-  }
+  uint32_t *lcnt;
+  uint32_t *lst = hnsw_own_list(b, l, t, lcnt);
   uint32_t cnt = hnsw_uni(*lcnt), nprune = 0;
   bool have_row = false;
+  static_assert(std::is_trivially_default_constructible<typename Rows::Scorer>::value &&
+                std::is_trivially_copy_assignable<typename Rows::Scorer>::value, "the model's contract (zvk_hnsw.hip.h)");
+  typename Rows::Scorer to_t;                    // (set at the group's first prune, before its first use)
   for (uint64_t j = j0; j < jend; ++j) {
     const uint64_t w = hnsw_uni64(req[j]);
     if ((w >> HNSW_REQ_SRC_BITS) != head) break;
@@ -232,24 +207,23 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
       continue;
     }
     if (!have_row) {
-      for (uint32_t x = (uint32_t)lane; x < a.dpad; x += 64) m.qv[x] = HnswRows<K>::word(a.rows, (size_t)t * a.dpad + x);
+      to_t = rows.stage_row(a, m.slot0, m.scratch, t, lane);
       have_row = true;
-      hnsw_sync(false);
     }
     uint32_t ssize = 0;
     for (uint32_t c0 = 0; c0 < cap + 1; c0 += 64) {
       const uint32_t nc = min(64u, cap + 1 - c0);
       if ((uint32_t)lane < nc) m.coll[lane] = c0 + (uint32_t)lane < cap ? lst[c0 + lane] : src;
       hnsw_sync(false);
-      score(a, m.coll, m.cdist, nc, lane);
+      to_t(a, m.coll, m.cdist, nc, lane);
       for (uint32_t jj = 0; jj < nc; ++jj) {
         const uint64_t word = hnsw_pack(__builtin_bit_cast(float, hnsw_uni(__builtin_bit_cast(uint32_t, m.cdist[jj]))), hnsw_uni(m.coll[jj]));
-        ssize = hnsw_put(m.S, ssize, cap + 1, word, lane, false);
+        ssize = hnsw_put(m.R, ssize, cap + 1, word, lane, false);
       }
       hnsw_sync(false);
     }
     uint32_t unused = 0;
-    const uint32_t nk = hnsw_keep<K>(a, m.S, ssize, cap, m.cv, m.kept, nullptr, m.cdist, unused, lane);
+    const uint32_t nk = hnsw_keep(a, rows, m, m.R, ssize, cap, nullptr, unused, lane);
     for (uint32_t x = (uint32_t)lane; x < cap; x += 64) lst[x] = x < nk ? m.kept[x] : 0u;
     cnt = nk;
     ++nprune;
@@ -261,30 +235,28 @@ __device__ __forceinline__ uint32_t hnsw_reverse_group(const HnswBuildArgs &b, c
 
 // One wave per (level, target) group of the sorted round buffer, grid-stride.  Targets are older than the round and every
 // (level, target) is one group, so no two waves touch one list.
-template <HnswKind K>
-__global__ __launch_bounds__(64) void hnsw_reverse_kernel(HnswBuildArgs b, const uint64_t *req, uint64_t slots, const uint32_t *gstart,
+template <typename Rows>
+__global__ __launch_bounds__(64) void hnsw_reverse_kernel(HnswBuildArgs b, Rows rows, const uint64_t *req, uint64_t slots, const uint32_t *gstart,
                                                           const uint32_t *ngroups) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
   const int lane = (int)threadIdx.x;
-  const HnswReverseLds<typename HnswRows<K>::lds> m(hnsw_smem, b.g.dpad);
+  const HnswLds m = hnsw_reverse_lds(b, rows);
   const uint32_t ng = hnsw_uni(*ngroups);
   uint32_t nprune = 0;
-  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) nprune += hnsw_reverse_group<K>(b, m, req, hnsw_uni(gstart[g]), slots, lane);
+  for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) nprune += hnsw_reverse_group(b, rows, m, req, hnsw_uni(gstart[g]), slots, lane);
   if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
 }
 
 // The reverse phase of a round of ONE node, on the round buffer as the insert kernel left it: one wave per request slot, grid-stride.
 // The selection of one node on one level holds distinct targets, so the used words are distinct (level, target) pairs with one source
 // each: every used word is a whole group, and no two waves touch one list.
-template <HnswKind K>
-__global__ __launch_bounds__(64) void hnsw_reverse_one_kernel(HnswBuildArgs b, uint64_t slots) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
+template <typename Rows>
+__global__ __launch_bounds__(64) void hnsw_reverse_one_kernel(HnswBuildArgs b, Rows rows, uint64_t slots) {
   const int lane = (int)threadIdx.x;
-  const HnswReverseLds<typename HnswRows<K>::lds> m(hnsw_smem, b.g.dpad);
+  const HnswLds m = hnsw_reverse_lds(b, rows);
   uint32_t nprune = 0;
   for (uint64_t j = blockIdx.x; j < slots; j += gridDim.x) {
     if (hnsw_uni64(b.req[j]) == HNSW_REQ_NONE) continue;
-    nprune += hnsw_reverse_group<K>(b, m, b.req, j, j + 1, lane);
+    nprune += hnsw_reverse_group(b, rows, m, b.req, j, j + 1, lane);
   }
   if (lane == 0 && nprune != 0) atomicAdd(&b.counters[2], (unsigned long long)nprune);
 }

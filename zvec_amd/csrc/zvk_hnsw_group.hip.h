@@ -20,8 +20,9 @@ struct HnswGroupArgs {
   uint32_t *out_ngroups;      // [nq]
 };                            // (HnswArgs: out_keys / out_scores [nq][gnum][gk], out_counts [nq][gnum], ef = ef_eff; topk is not read)
 
-__host__ __device__ inline size_t hnsw_group_lds_bytes(uint32_t dpad, uint32_t ef, uint32_t gnum, uint32_t gk) {
-  return hnsw_lds_bytes(dpad, ef) + (size_t)gnum * gk * 8 + (size_t)gnum * 8;
+// the search's LDS (hnsw_search_lds_bytes), then the slots
+__host__ __device__ inline size_t hnsw_group_lds_bytes(size_t walk_bytes, uint32_t gnum, uint32_t gk) {
+  return walk_bytes + (size_t)gnum * gk * 8 + (size_t)gnum * 8;
 }
 
 // the slots of one query, in LDS
@@ -201,7 +202,7 @@ __device__ __forceinline__ void hnsw_group_emit(const HnswArgs &a, const HnswGro
 template <HnswKind K>
 __global__ __launch_bounds__(64) void hnsw_group_search_kernel(HnswArgs a, HnswGroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_smem[];
-  typedef typename HnswRows<K>::lds lds_t;
+  typedef typename HnswDenseKind<K>::lds lds_t;
   const int lane = (int)threadIdx.x;
   const uint32_t q = blockIdx.x;
   lds_t *qv = reinterpret_cast<lds_t *>(hnsw_smem);
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64) void hnsw_group_search_kernel(HnswArgs a, HnswG
   s.group = reinterpret_cast<uint32_t *>(s.docs + (size_t)ga.gnum * ga.gk);
   s.size = s.group + ga.gnum;
   s.used = 0;
-  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswRows<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
+  for (uint32_t i = (uint32_t)lane; i < a.dpad; i += 64) qv[i] = i < a.dim ? HnswDenseKind<K>::word(a.queries, (size_t)q * a.dim + i) : lds_t(0);
   if (lane == 0) coll[0] = a.entry;
   hnsw_sync(false);
   const typename HnswRows<K>::Scorer score{qv};

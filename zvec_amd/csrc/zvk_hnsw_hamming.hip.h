@@ -1,7 +1,7 @@
 // zvk_hnsw_hamming.hip.h — the distance step of the HNSW walk over binary rows under the Hamming distance (zvec_hip_hnsw_create_binary,
 // api_entry_hnsw.inc.h): score = (float) popcount(row ^ query), an exact integer.  The walk, the build and the group-by stages are
-// those of zvk_hnsw.hip.h, zvk_hnsw_build.hip.h and zvk_hnsw_group.hip.h, instantiated for HNSW_BITS; this file is the scorer they
-// take and HnswRows<HNSW_BITS>, which tells them that a row in LDS is words, copied as they are.  DESIGN §3c "Binary rows".
+// those of zvk_hnsw.hip.h, zvk_hnsw_build.hip.h and zvk_hnsw_group.hip.h, instantiated for HnswRows<HNSW_BITS>; this file is the scorer
+// they take and HnswDenseKind<HNSW_BITS>, which tells that model that a row in LDS is words, copied as they are.  DESIGN §3c "Binary rows".
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
 //
 // Stored rows are [n][wpad] uint32_t words, words = bits / 32 rounded up to 4 and zero padded, so every row is 16-byte aligned and a
@@ -86,7 +86,7 @@ struct HnswHammingScorer {
 };
 
 template <>
-struct HnswRows<HNSW_BITS> {
+struct HnswDenseKind<HNSW_BITS> {
   typedef uint32_t lds;
   typedef HnswHammingScorer Scorer;
   static __device__ __forceinline__ uint32_t word(const void *p, size_t i) { return static_cast<const uint32_t *>(p)[i]; }

@@ -1,7 +1,8 @@
-// zvk_hnsw_sparse.hip.h — batched beam search on a built HNSW graph over SPARSE rows (zvec_hip_hnsw_sparse_*,
-// api_entry_hnsw_sparse.inc.h): the walk of zvk_hnsw.hip.h (hnsw_greedy, hnsw_beam, hnsw_put, hnsw_list, hnsw_emit, none of it
-// copied) with another distance step.  Reference: src/core/algorithm/hnsw_sparse/hnsw_sparse_algorithm.cc, which is
-// hnsw_algorithm.cc line for line but for dc.dist(...) on a sparse row; under InnerProductSparse that is
+// zvk_hnsw_sparse.hip.h — SPARSE rows in the HNSW kernels (zvec_hip_hnsw_sparse_*, api_entry_hnsw_sparse.inc.h and
+// api_entry_hnsw_sparse_build.inc.h): the scorer; the search kernel, which is the walk of zvk_hnsw.hip.h (hnsw_greedy, hnsw_beam,
+// hnsw_emit, none of it copied) behind a query staged as a run; and HnswCsrRows<VT>, the model that the build kernels of
+// zvk_hnsw_build.hip.h are instantiated for.  Reference: src/core/algorithm/hnsw_sparse/hnsw_sparse_algorithm.cc,
+// which is hnsw_algorithm.cc line for line but for dc.dist(...) on a sparse row; under InnerProductSparse that is
 // MinusInnerProductSparseMatrix<T>::Compute (src/ailego/math/inner_product_matrix.h:2781-2862): minus the sum of value products over
 // shared indices, exactly +0.0 when no index is shared.
 // Part of the device code of libzvec_hip (included through scan_kernels.hip.h).
@@ -22,6 +23,12 @@
 // starting from +0; the sixteen accumulators are then added by the fixed butterfly __shfl_xor 8, 4, 2, 1 inside the group, and the
 // score is 0.f - sum.  Neither the group, the slot in `coll`, nor the other rows of the batch enter.  A query run of length 0 reads
 // neither LDS nor a row and scores every node 0.f - 0.f = +0; an empty row reads nothing either and scores +0.
+//
+// Roles in the build.  The scorer wants one operand staged in LDS and streams the other from CSR.  Slot 0 holds the BASE of the
+// wave's work: the new node's row in the insert kernel, the target's row in a reverse group.  Slot 1 holds the keep rule's current
+// candidate c.  A score's bits depend on the (staged run, streamed row) pair alone, as in the search.  d(c, s) of the keep rule is
+// (c staged, s streamed); it is compared with d(c, base), which came out of the walk or the sort as (base staged, c streamed).  On
+// real values the two roles may differ in the last bit; integer-valued data is exact either way.
 #pragma once
 #include "zvk_hnsw.hip.h"
 #include "zvk_sparse.hip.h"
@@ -35,13 +42,9 @@ struct HnswSparseArgs {
   uint32_t run_bytes;         // LDS set aside for the run: hnsw_sparse_run_bytes of the batch's longest
 };
 
-// the run's part of LDS, the words of R behind it 8-byte aligned
+// a run's slot in LDS, the next slot or the words of R behind it 8-byte aligned
 __host__ __device__ inline size_t hnsw_sparse_run_bytes(uint32_t run_elems, uint32_t width) {
   return (sparse_run_lds_bytes(run_elems, width) + 7) & ~(size_t)7;
-}
-// run | R [ef] | C [HNSW_C_LDS] | row begins [64] (u64) | coll [64] | cdist [64] | row lengths [64]
-__host__ __device__ inline size_t hnsw_sparse_lds_bytes(uint32_t run_elems, uint32_t width, uint32_t ef) {
-  return hnsw_sparse_run_bytes(run_elems, width) + (size_t)ef * 8 + (size_t)HNSW_C_LDS * 8 + 64 * 8 + 3 * 64 * 4;
 }
 
 template <typename VT>
@@ -106,7 +109,37 @@ struct HnswSparseScorer {
   }
 };
 
-// one wave per query, one wave per work-group, as hnsw_search_kernel
+// The model of CSR rows for the build kernels (zvk_hnsw.hip.h, "The model of a row kind"); of the HnswArgs beside it rows, dim, dpad,
+// ip and queries are not read.  A slot is a run as sparse_stage_run lays it out: indices, then values as stored.
+template <typename VT>
+struct HnswCsrRows {
+  typedef HnswSparseScorer<VT> Scorer;
+  static constexpr uint32_t SCRATCH = 64 * 8 + 64 * 4;      // the begins (u64) and the lengths of the collected rows
+  SparseOperands op;          // the stored rows
+  uint32_t run_elems;         // what a slot has room for: the longest row of the build
+
+  __host__ __device__ __forceinline__ size_t slot_bytes(const HnswArgs &) const { return hnsw_sparse_run_bytes(run_elems, sizeof(VT)); }
+
+  // (rows are read with u64 offsets; sparse_stage_run reads query arrays with u32 offsets)
+  __device__ __forceinline__ Scorer stage_row(const HnswArgs &, unsigned char *slot, unsigned char *scratch, uint32_t node, int lane) const {
+    const VT *val = static_cast<const VT *>(op.val);
+    const uint64_t rb = hnsw_uni64(op.row_off[node]);
+    const uint32_t len = (uint32_t)min((uint64_t)run_elems, hnsw_uni64(op.row_off[(size_t)node + 1]) - rb);
+    uint32_t *qi = reinterpret_cast<uint32_t *>(slot);
+    VT *qv = reinterpret_cast<VT *>(qi + len);
+    for (uint32_t e = (uint32_t)lane; e < len; e += 64) {
+      qi[e] = op.idx[rb + e];
+      qv[e] = val[rb + e];
+    }
+    hnsw_sync(false);
+    uint64_t *rbeg = reinterpret_cast<uint64_t *>(scratch);
+    return Scorer{op.row_off, op.idx, val, qi, qv, len, sparse_halvings(len), rbeg, reinterpret_cast<uint32_t *>(rbeg + 64)};
+  }
+};
+
+// One wave per query, one wave per work-group, as hnsw_search_kernel, whose steps these are; a kernel of its own because the folded
+// one is slower on the dense kinds.  run | R [ef] | C [HNSW_C_LDS] | row begins [64] (u64) | coll [64] | cdist [64] |
+// row lengths [64]: hnsw_walk_lds_bytes of one slot of s.run_bytes and HnswCsrRows<VT>::SCRATCH.
 template <typename VT>
 __global__ __launch_bounds__(64) void hnsw_sparse_search_kernel(HnswSparseArgs s) {
   extern __shared__ f32x4 zvk_smem4[];
