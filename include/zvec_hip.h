@@ -34,7 +34,8 @@ enum {
   ZVEC_HIP_DT_FP32 = 0,
   ZVEC_HIP_DT_FP16 = 1,
   ZVEC_HIP_DT_BINARY32 = 2, /* IndexMeta::DT_BINARY32 = 7 (index_meta.h:39): a row is dim / 32 uint32_t words */
-  ZVEC_HIP_DT_BINARY64 = 3  /* IndexMeta::DT_BINARY64 = 8 (index_meta.h:40): a row is dim / 64 uint64_t words */
+  ZVEC_HIP_DT_BINARY64 = 3, /* IndexMeta::DT_BINARY64 = 8 (index_meta.h:40): a row is dim / 64 uint64_t words */
+  ZVEC_HIP_DT_INT8 = 4      /* IndexMeta::DT_INT8 = 4: a row is dim int8_t values; HNSW handles only (zvec_hip_hnsw_create_typed) */
 };
 
 /* IndexMetric names served: "SquaredEuclidean" (src/core/metric/euclidean_metric.cc:743),
@@ -711,6 +712,25 @@ int zvec_hip_binary_encode_dev(zvec_hip_ctx_t ctx, const float *d_in, uint64_t c
                                float threshold, uint32_t *d_out, void *stream);
 int zvec_hip_binary_encode(zvec_hip_ctx_t ctx, const float *in, uint64_t count, uint32_t dim, uint32_t encode_dims,
                            float threshold, uint32_t *out);
+/* ---- fp32 -> int8 (integer quantisation) ---------------------------------------------------------------------
+ * The two transforms of Int8QuantizerReformer (src/core/quantizer/integer_quantizer_reformer.cc) on the device: what turns fp32 rows
+ * and queries into those of a ZVEC_HIP_DT_INT8 HNSW handle.  d_in / in: [count][dim] fp32; d_out / out: [count][dim] int8_t.
+ *   ZVEC_HIP_INT8_SCALE_BIAS: EntropyInt8Quantizer::encode (src/ailego/algorithm/integer_quantizer.cc:348-354), what convert and
+ *   transform do under SquaredEuclidean: out = (int8) round(clamp((v + bias) * scale, -127, 127)), -127 and 127 being the reference's
+ *   MIN_VALUE and MAX_VALUE (integer_quantizer.h:171), so -128 is never written.  One fp32 add, one fp32 multiply, nothing fused;
+ *   round is std::round, halves away from zero.  scale (> 0) and bias are the caller's: training the histogram is not served.
+ *   ZVEC_HIP_INT8_PER_ROW: the inner-product query transform (integer_quantizer_reformer.cc:236-246): per row s = 127 / max|v|,
+ *   out = (int8) round(v * s); scale and bias are ignored.  out_factors (NULL, or [count] floats) receives max|v| / 127, the factor
+ *   normalize multiplies the scores by.  A row of zeros divides by zero in the reference; here it gives zeros and the factor 0.
+ * Values must be finite; a nan gives 0.  zvec_hip_int8_encode_dev only enqueues work on `stream` (NULL: the context's);
+ * zvec_hip_int8_encode is the same through host pointers, staged through the device in bounded slices.  count == 0 returns 0 and
+ * writes nothing; a NULL context or pointer, dim == 0, dim > 2^20, another mode, or a scale that is not > 0 under SCALE_BIAS is
+ * ZVEC_HIP_ERR_INVALID_ARGUMENT and touches no output. */
+enum { ZVEC_HIP_INT8_SCALE_BIAS = 0, ZVEC_HIP_INT8_PER_ROW = 1 };
+int zvec_hip_int8_encode_dev(zvec_hip_ctx_t ctx, const float *d_in, uint64_t count, uint32_t dim, int mode, float scale, float bias,
+                             int8_t *d_out, float *d_out_factors, void *stream);
+int zvec_hip_int8_encode(zvec_hip_ctx_t ctx, const float *in, uint64_t count, uint32_t dim, int mode, float scale, float bias,
+                         int8_t *out, float *out_factors);
 /* IndexConverter::transform + IndexBuilder::build of a "BinaryConverter" index (binary_converter.cc:185-196; flat_builder.cc:188-276),
  * IndexStreamer::add_impl behind the converter: n fp32 rows of `dim` values are encoded on the device (encode_dims, threshold as
  * above) and stored exactly as zvec_hip_flat_append[_dev] stores the same words — positions, keys (NULL: key = position), all of
@@ -1064,7 +1084,7 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  *     index); every other metric, and a dim above 4096: ZVEC_HIP_ERR_UNSUPPORTED.  Binary rows under the Hamming distance have a
  *     creator of their own, zvec_hip_hnsw_create_binary (up to 32768 bits); the two creators below keep refusing binary types;
  *   - Element type.  A handle serves ONE element type: ZVEC_HIP_DT_FP32 (float) or, through zvec_hip_hnsw_create_typed,
- *     ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes) — the reference's HNSW after HalfFloatConverter / HalfFloatReformer.  Every `rows`,
+ *     ZVEC_HIP_DT_INT8 (next item) or ZVEC_HIP_DT_FP16 (IEEE binary16, 2 bytes) — the reference's HNSW after HalfFloatConverter / HalfFloatReformer.  Every `rows`,
  *     `queries` and get_vectors `out` pointer below, host or device, is a `const void *` / `void *` read as elements of the handle's
  *     type, the way zvec_hip_flat_* treats `vecs`; scores are fp32 for either type.  Halves are stored as halves (half the bytes
  *     held, half the bytes a distance fetches).  Each is widened to fp32 where it is read, which is exact (subnormals included,
@@ -1073,6 +1093,14 @@ int zvec_hip_sparse_search_grouped_by_ids(zvec_hip_sparse_t h, zvec_hip_ctx_t ct
  *     counts, statistics, built and appended graphs and their counters — bit for bit as an fp32 handle given the widened rows and
  *     queries would.  No half-precision arithmetic.  Values must be finite: inf and NaN are not checked for and give unspecified
  *     results.  DESIGN §3c "fp16 rows".
+ *   - int8 rows.  zvec_hip_hnsw_create_typed also takes ZVEC_HIP_DT_INT8 (the reference's HNSW behind its Int8 converter): `rows`,
+ *     `queries` and get_vectors `out` are int8_t[dim] a row, 4-byte aligned, values the full -128 .. 127; dim is a multiple of 4
+ *     (the reference aligns int8 rows to 4 bytes, index_meta.h:547).  Scores: L2 = (float)(int32) sum (row[i] - q[i])^2,
+ *     IP = (float)(int32)(-sum row[i] * q[i]).  The sum is an exact 32-bit integer (dim <= 4096: |sum| <= 4096 * 255^2 < 2^31) and
+ *     the only rounding is its conversion to fp32, to nearest even.  This is the project's rule: the reference's SIMD int8 L2 goes
+ *     through saturating 16-bit pair sums (euclidean_distance_matrix_int8.cc:40-59), where two adjacent -128 * -128 products
+ *     saturate; here nothing saturates.  Rows that come out of the quantiser (zvec_hip_int8_encode, values in [-127, 127]) never
+ *     reach that case.  A quarter of the fp32 bytes held and fetched.  DESIGN §3c "int8 rows".
  *   - a node is its position 0 .. n-1; exclude_bitset, threshold, out_counts and the fill of the places past out_counts[q]
  *     (key 2^64 - 1, score +inf) are those of zvec_hip_flat_search; an excluded node is walked through but never returned;
  *   - lists are ascending by (score, node); of two candidates or results at one distance the one with the smaller node comes first,
@@ -1081,8 +1109,9 @@ typedef struct zvec_hip_hnsw_s *zvec_hip_hnsw_t;
 /* the fp32 creator: dtype must be ZVEC_HIP_DT_FP32; every other type is ZVEC_HIP_ERR_UNSUPPORTED here, ZVEC_HIP_DT_FP16 included
  * (callers of this entry hand over float pointers; that behaviour is kept exactly) */
 int zvec_hip_hnsw_create(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
-/* dtype: ZVEC_HIP_DT_FP32 or ZVEC_HIP_DT_FP16.  Any other type or metric returns ZVEC_HIP_ERR_UNSUPPORTED and leaves *out untouched.
- * With ZVEC_HIP_DT_FP32 this is zvec_hip_hnsw_create. */
+/* dtype: ZVEC_HIP_DT_FP32, ZVEC_HIP_DT_FP16 or ZVEC_HIP_DT_INT8.  Any other type or metric, or a dim above 4096, returns
+ * ZVEC_HIP_ERR_UNSUPPORTED; dim == 0, or an int8 dim that is no multiple of 4, ZVEC_HIP_ERR_INVALID_ARGUMENT; *out is untouched on
+ * every refusal.  With ZVEC_HIP_DT_FP32 this is zvec_hip_hnsw_create. */
 int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out);
 /* Binary rows under the Hamming distance (hamming_metric.cc over DT_BINARY32 / DT_BINARY64; the reference's HNSW takes its metric
  * from IndexFactory::CreateMetric, hnsw_searcher.cc:133, hnsw_builder.cc:101): score = (float) popcount(row ^ query), an exact

@@ -41,6 +41,12 @@ rows unpacked to 0/1 (the same walk and scores, 32 times the bytes), and through
 of each, distances computed, and recall@10 counted on the scores (Hamming scores tie).
 
     python tools/hnsw_bench.py --dtype binary32 [--n 100000 --dim 768] [--out profiles/hnsw_hamming_100k_768b.json]
+
+With --dtype int8 (alone or with --build) the corpus and the queries are quantised once on the device (zvec_hip_int8_encode_dev, one
+scale, no bias), and the same values go through the fp32 handle (the int8 values widened) and the int8 handle
+(zvec_hip_hnsw_create_typed(ZVEC_HIP_DT_INT8)) holding the same graph, as --dtype fp16 does for halves.
+
+    python tools/hnsw_bench.py --dtype int8 --n 100000 --dim 768 --out profiles/hnsw_100k_768_int8.json
 """
 import time
 import argparse
@@ -283,6 +289,17 @@ def binary_bench(args, torch, zvec_amd, g, ts, stream):
             "steps": args.steps, "warmup": args.warmup, "build": built, "legs": legs}
 
 
+def _quantised(torch, zvec_amd, x, stream):
+    """x (fp32 on the device, standard normal) -> int8 on the device: 4 sigma onto 127, beyond that clamped"""
+    out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    torch.cuda.synchronize()
+    ctx = zvec_amd.IndexContext(x.device.index)
+    ctx.int8_encode_dev(x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), scale=127.0 / 4.0, stream=stream)
+    ctx.synchronize()
+    torch.cuda.synchronize()
+    return out
+
+
 def _emit(args, res):
     print(json.dumps(res))
     if args.out:
@@ -304,10 +321,13 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="group-by search (1000 groups, 10 x 10) beside plain topk 100 at the same ef")
     ap.add_argument("--build", action="store_true", help="build the graph with zvec_hip_hnsw_build_dev instead of the k-NN stand-in")
     ap.add_argument("--ef-construction", type=int, default=200)
-    ap.add_argument("--dtype", choices=("fp32", "fp16", "binary32"), default="fp32",
+    ap.add_argument("--dtype", choices=("fp32", "fp16", "binary32", "int8"), default="fp32",
                     help="fp16: a binary16-representable corpus through the fp32 handle and the fp16 handle, side by side; "
+                         "int8: the corpus quantised to int8 through the fp32 handle (widened) and the int8 handle, side by side; "
                          "binary32: --dim random bits through the binary handle, the fp32 handle over the unpacked rows and the flat scan")
     args = ap.parse_args()
+    if args.dtype == "int8" and (args.append or args.grouped):
+        ap.error("--dtype int8 goes with the plain search, alone or with --build")
     import torch
     import zvec_amd
     dev = torch.device("cuda:0")
@@ -319,12 +339,15 @@ def main():
         ts.wait_stream(torch.cuda.current_stream(dev))
         return _emit(args, binary_bench(args, torch, zvec_amd, g, ts, ts.cuda_stream))
     rows = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
-    f16 = args.dtype == "fp16"
+    f16, i8 = args.dtype == "fp16", args.dtype == "int8"
     if f16:
         rows = rows.half().float()                 # every value is a binary16 value: both handles see the same numbers
     ts = torch.cuda.Stream(device=dev)
     ts.wait_stream(torch.cuda.current_stream(dev))
     stream = ts.cuda_stream
+    if i8:
+        rows8 = _quantised(torch, zvec_amd, rows, stream)
+        rows = rows8.float()                       # every value is an int8 value
     torch.cuda.synchronize()
     if args.append:
         if not f16:
@@ -366,6 +389,12 @@ def main():
         assert se16.load(rows.half().cpu().numpy(), nbr0_, cnt0_, se.info()["entry_point"], k_, upper_of_, nbr_up_, cnt_up_) == 0
         handles.append(("fp16", se16, 2))
         del k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_
+    if i8:                                         # the same graph in an int8 handle, over the bytes
+        se8 = zvec_amd.HipHnswSearcher(dim, "SquaredEuclidean", dtype="int8")
+        k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_ = se.export()
+        assert se8.load(rows8.cpu().numpy(), nbr0_, cnt0_, se.info()["entry_point"], k_, upper_of_, nbr_up_, cnt_up_) == 0
+        handles.append(("int8", se8, 1))
+        del k_, nbr0_, cnt0_, upper_of_, nbr_up_, cnt_up_, rows8
     if args.grouped:
         return _emit(args, grouped_bench(args, torch, se, n, dim, g, ts, stream))
     fctx = flat.create_context()
@@ -374,6 +403,9 @@ def main():
         q = torch.randn((batch, dim), generator=g, device=dev, dtype=torch.float32)
         if f16:
             q = q.half().float()
+        if i8:
+            q8 = _quantised(torch, zvec_amd, q, stream)
+            q = q8.float()
         keys = torch.empty((batch, args.topk), dtype=torch.int64, device=dev)
         scores = torch.empty((batch, args.topk), dtype=torch.float32, device=dev)
         counts = torch.empty((batch,), dtype=torch.int32, device=dev)
@@ -384,7 +416,7 @@ def main():
         truth = exact.cpu().numpy()
         for ef in (64, 128, 256):
             for name, hs, esz in handles:
-                hq = q.half() if esz == 2 else q
+                hq = q.half() if esz == 2 else q8 if esz == 1 else q
                 hctx = hs.create_context()
 
                 def step():
@@ -397,7 +429,7 @@ def main():
                 gathered = float(scanned.sum()) * dim * esz
                 leg = {"batch": batch, "ef": ef, "ms_per_step": ms, "qps": batch / ms * 1e3, "recall_at_%d" % args.topk: recall,
                        "mean_scanned": float(scanned.mean()), "mean_hops": float(hops.mean()), "gathered_gbs": gathered / ms / 1e6}
-                if f16:
+                if f16 or i8:
                     leg = dict(dtype=name, row_bytes_held=n * ((dim + 3) // 4 * 4) * esz, **leg)
                 legs.append(leg)
     del rows, flat
@@ -410,7 +442,7 @@ def main():
     for leg in legs:
         leg["stream_fraction"] = leg["gathered_gbs"] / gbs.value
     graph = "graph built on the device m0=%d m=%d" % (m0, m) if args.build else "k-NN graph m0=%d (+ 1-in-32 level 1, m=%d)" % (m0, m)
-    what = "fp16 beside fp32 on one binary16-representable corpus" if f16 else "fp32"
+    what = "fp16 beside fp32 on one binary16-representable corpus" if f16 else "int8 beside fp32 on one corpus quantised to int8" if i8 else "fp32"
     res = {"workload": "hnsw search %d x %d %s, %s, k=%d" % (n, dim, what, graph, args.topk),
            "stream_gbs": gbs.value, "clock_mhz": mhz.value, "steps": args.steps, "warmup": args.warmup, "legs": legs}
     if built is not None:

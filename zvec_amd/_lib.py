@@ -58,6 +58,8 @@ ROARING_NONE, ROARING_32, ROARING_64MAP, ROARING_FILE = 0, 1, 2, 3
 
 # ZVEC_HIP_DT_* / ZVEC_HIP_METRIC_* (binary rows go with the Hamming metric and nothing else: flat indexes and zvec_hip_bivf_*)
 DT_FP32, DT_FP16, DT_BINARY32, DT_BINARY64 = 0, 1, 2, 3
+DT_INT8 = 4                                    # HNSW handles only (zvec_hip_hnsw_create_typed)
+INT8_SCALE_BIAS, INT8_PER_ROW = 0, 1           # ZVEC_HIP_INT8_*: the modes of zvec_hip_int8_encode
 METRIC_L2, METRIC_IP, METRIC_COSINE, METRIC_HAMMING = 0, 1, 2, 3
 # ZVEC_HIP_IVF_ROUTE_*
 IVF_ROUTE_NONE, IVF_ROUTE_DIRECT_BLOCK_TOPK, IVF_ROUTE_DIRECT_SELECT, IVF_ROUTE_TILE, IVF_ROUTE_LARGE_K = 0, 1, 2, 3, 4
@@ -203,6 +205,9 @@ SYMBOLS = {
     "zvec_hip_reform_queries_dev": (C.c_int, [_h, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "zvec_hip_binary_encode_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
     "zvec_hip_binary_encode": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
+    "zvec_hip_int8_encode_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "zvec_hip_int8_encode": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "zvec_hip_flat_append_fp32": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, _u64p]),
     "zvec_hip_flat_append_fp32_dev": (C.c_int, [_h, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, _u64p, C.c_void_p]),
     "zvec_hip_flat_search_fp32": (C.c_int, [_h, _h, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_float, _u64p,

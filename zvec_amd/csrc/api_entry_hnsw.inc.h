@@ -147,7 +147,8 @@ struct zvec_hip_hnsw_s {
   int metric = 0;
   int dtype = ZVEC_HIP_DT_FP32;        // of rows and queries: fp32, or fp16 (zvec_hip_hnsw_create_typed); halves are stored as halves;
                                        // or BINARY32 / BINARY64 (zvec_hip_hnsw_create_binary), whose element is a uint32_t word of 32
-                                       // bits under either type (the same bytes on a little-endian host)
+                                       // bits under either type (the same bytes on a little-endian host); or INT8
+                                       // (zvec_hip_hnsw_create_typed), whose element is a uint32_t word of four values
   uint32_t esz = 4;                    // bytes per element
   uint32_t dim = 0, dpad = 0;          // dpad: elements per stored row, dim rounded up to 4 (a lane of the kernel loads four elements)
   bool loaded = false;
@@ -163,8 +164,11 @@ struct zvec_hip_hnsw_s {
   // mutex of the context it works through, then rw shared (as zvec_hip_flat_s); info, export and get_vectors hold rw shared alone.
   std::mutex mu;                       // serialises the calls that change the index or use defctx's workspace
   FairSharedMutex rw;
-  HnswKind kind() const { return dtype == ZVEC_HIP_DT_FP32 ? HNSW_F32 : dtype == ZVEC_HIP_DT_FP16 ? HNSW_F16 : HNSW_BITS; }
-  uint32_t callers_dim() const { return kind() == HNSW_BITS ? dim * 32 : dim; }       // bits of a binary handle
+  HnswKind kind() const {
+    return dtype == ZVEC_HIP_DT_FP32 ? HNSW_F32 : dtype == ZVEC_HIP_DT_FP16 ? HNSW_F16 : dtype == ZVEC_HIP_DT_INT8 ? HNSW_I8 : HNSW_BITS;
+  }
+  // bits of a binary handle, values of an int8 handle
+  uint32_t callers_dim() const { return kind() == HNSW_BITS ? dim * 32 : kind() == HNSW_I8 ? dim * 4 : dim; }
   size_t row_bytes() const { return (size_t)dim * esz; }           // of a row as callers pass it
   size_t pad_bytes() const { return (size_t)dpad * esz; }          // of a row as it is stored
   ~zvec_hip_hnsw_s() { delete defctx; }
@@ -178,6 +182,7 @@ extern "C++" template <typename F>
 static int hnsw_with_rows(const zvec_hip_hnsw_s *h, F &&f) {
   switch (h->kind()) {
     case HNSW_BITS: return f(HnswRows<HNSW_BITS>());
+    case HNSW_I8: return f(HnswRows<HNSW_I8>());
     case HNSW_F16: return f(HnswRows<HNSW_F16>());
     default: return f(HnswRows<HNSW_F32>());
   }
@@ -223,9 +228,13 @@ static int hnsw_new(uint32_t dim, uint32_t esz, int dtype, int metric, int devic
 
 int zvec_hip_hnsw_create_typed(uint32_t dim, int dtype, int metric, int device, zvec_hip_hnsw_t *out) {
   if (!out || dim == 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;
-  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dtype != ZVEC_HIP_DT_FP32 && dtype != ZVEC_HIP_DT_FP16 && dtype != ZVEC_HIP_DT_INT8) return ZVEC_HIP_ERR_UNSUPPORTED;
+  if (dtype == ZVEC_HIP_DT_INT8 && dim % 4 != 0) return ZVEC_HIP_ERR_INVALID_ARGUMENT;       // (int8 rows are aligned to 4 bytes, index_meta.h:547)
   if (metric != ZVEC_HIP_METRIC_L2 && metric != ZVEC_HIP_METRIC_IP) return ZVEC_HIP_ERR_UNSUPPORTED;
-  if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS)
+  if (dim > HNSW_MAX_DIM) return ZVEC_HIP_ERR_UNSUPPORTED;          // (the query row is kept in LDS; an int8 sum stays below 2^31)
+  // int8 rows (HNSW_I8): the handle counts uint32_t words of four values, as the binary handle counts words of 32 bits, and dpad
+  // is the words of a stored row: a whole number of 16-byte chunks
+  if (dtype == ZVEC_HIP_DT_INT8) return hnsw_new(dim / 4, 4, dtype, metric, device, out);
   return hnsw_new(dim, dtype == ZVEC_HIP_DT_FP16 ? 2 : 4, dtype, metric, device, out);
 }
 

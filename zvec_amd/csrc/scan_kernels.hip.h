@@ -42,6 +42,7 @@
 #include "zvk_sparse_ingest.hip.h"
 #include "zvk_hnsw.hip.h"
 #include "zvk_hnsw_hamming.hip.h"
+#include "zvk_hnsw_i8.hip.h"
 #include "zvk_hnsw_group.hip.h"
 #include "zvk_hnsw_build.hip.h"
 #include "zvk_hnsw_sparse.hip.h"

@@ -46,6 +46,7 @@ extern "C" {
 #include "api_entry_merge_prof.inc.h"
 #include "api_entry_filter.inc.h"
 #include "api_entry_binary_quant.inc.h"
+#include "api_entry_int8_quant.inc.h"
 #include "api_entry_hamming_ivf.inc.h"
 #include "api_entry_hamming_ivf_fp32.inc.h"
 #include "api_entry_group.inc.h"

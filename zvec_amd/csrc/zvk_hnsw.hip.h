@@ -9,9 +9,10 @@
 // region of the context workspace when more than that many candidates are alive at the same time (rows excluded by the caller's
 // bitset are traversed but never fill R, so nothing bounds C below the row count then).
 //
-// Rows and queries are of one of five kinds.  The build kernels (zvk_hnsw_build.hip.h) are templates on the MODEL of their kind, a
-// small struct passed by value (see "The model of a row kind" below): HnswRows<K> for dense fp32 rows, IEEE binary16 rows and words
-// of bits under the Hamming distance (zvk_hnsw_hamming.hip.h), HnswCsrRows<VT> for sparse rows with float or _Float16 values
+// Rows and queries are of one of six kinds.  The build kernels (zvk_hnsw_build.hip.h) are templates on the MODEL of their kind, a
+// small struct passed by value (see "The model of a row kind" below): HnswRows<K> for dense fp32 rows, IEEE binary16 rows, words
+// of bits under the Hamming distance (zvk_hnsw_hamming.hip.h) and words of four int8 values (zvk_hnsw_i8.hip.h), HnswCsrRows<VT> for
+// sparse rows with float or _Float16 values
 // (zvk_hnsw_sparse.hip.h).  The search kernels stage their query themselves: hnsw_search_kernel<K> and hnsw_group_search_kernel<K>
 // for the dense kinds, hnsw_sparse_search_kernel<VT>.  The dense distance code keeps its own parameter H (H = true, halves).
 // A half is widened to fp32 where it is read, which is exact (subnormals included, nothing flushed); from there on the arithmetic is
@@ -28,7 +29,7 @@ constexpr uint32_t HNSW_MAX_DIM = 4096;    // the query row is kept in LDS
 constexpr uint32_t HNSW_MAX_BITS = 32768;  // of a binary row: 1024 words, the LDS bytes of a 1024-d fp32 query
 constexpr uint32_t HNSW_BUILD_MAX_M0 = 256; // the kept ids of one selection of the build are held in LDS
 
-enum HnswKind : int { HNSW_F32 = 0, HNSW_F16 = 1, HNSW_BITS = 2 };
+enum HnswKind : int { HNSW_F32 = 0, HNSW_F16 = 1, HNSW_BITS = 2, HNSW_I8 = 3 };
 
 struct HnswArgs {
   const void *rows;           // [n][dpad] row-major, zero padded; dpad is a multiple of 4 elements (a lane loads 16 bytes of
@@ -221,7 +222,8 @@ struct HnswDenseScorer {
 // declares one before it knows whether it will stage the row (hnsw_reverse_group).
 //
 // HnswRows<K>: the dense kinds, which carry nothing beside HnswArgs (the primary template: fp32 and fp16; zvk_hnsw_hamming.hip.h
-// specialises Scorer and word for HNSW_BITS through HnswDenseKind).  A slot is dpad words of 4 bytes under every kind.
+// specialises Scorer and word for HNSW_BITS through HnswDenseKind, zvk_hnsw_i8.hip.h for HNSW_I8).  A slot is dpad words of 4 bytes
+// under every kind.
 template <HnswKind K>
 struct HnswDenseKind {
   typedef float lds;

@@ -28,20 +28,26 @@ __host__ __device__ inline uint32_t hnsw_hamming_lanes_log2(uint32_t wpad) {
   return lg;
 }
 
-__device__ __forceinline__ uint32_t hnsw_popc4(u32x4 b, u32x4 x, uint32_t acc) {
-  acc += (uint32_t)__builtin_popcount(b.x ^ x.x);          // (v_bcnt_u32_b32 adds its second operand)
-  acc += (uint32_t)__builtin_popcount(b.y ^ x.y);
-  acc += (uint32_t)__builtin_popcount(b.z ^ x.z);
-  acc += (uint32_t)__builtin_popcount(b.w ^ x.w);
-  return acc;
-}
+// The per-chunk step of the Hamming distance (the Acc of hnsw_chunk_distances below): acc + popcount(b ^ x), scored as it stands
+struct HnswPopcAcc {
+  __device__ __forceinline__ uint32_t add(u32x4 b, u32x4 x, uint32_t acc) const {
+    acc += (uint32_t)__builtin_popcount(b.x ^ x.x);        // (v_bcnt_u32_b32 adds its second operand)
+    acc += (uint32_t)__builtin_popcount(b.y ^ x.y);
+    acc += (uint32_t)__builtin_popcount(b.z ^ x.z);
+    acc += (uint32_t)__builtin_popcount(b.w ^ x.w);
+    return acc;
+  }
+  __device__ __forceinline__ float score(uint32_t acc) const { return (float)acc; }
+};
 
-// cdist[r] = (float) popcount(row coll[r] ^ the wpad words at qw in LDS) for r < nc (nc <= 64).  G lanes take a row, one chunk each
-// per step, 64 / G rows in flight; the first chunk of the next 64 / G rows is requested before the current ones are reduced across
-// their G lanes.  Rows r >= nc of the last batch load row coll[0] and write nothing.  Integer sums: no order to pin.
-template <uint32_t G>
-__device__ __forceinline__ void hnsw_hamming_distances(const HnswArgs &a, const uint32_t *qw, const uint32_t *coll, float *cdist, uint32_t nc,
-                                                       int lane) {
+// cdist[r] = f.score(the sum over the 16-byte chunks of f.add(chunk of row coll[r], chunk of the wpad words at qw in LDS)) for
+// r < nc (nc <= 64): the loop of every kind whose rows are words and whose score is an integer sum (bits here, int8 values in
+// zvk_hnsw_i8.hip.h).  G lanes take a row, one chunk each per step, 64 / G rows in flight; the first chunk of the next 64 / G rows
+// is requested before the current ones are reduced across their G lanes.  Rows r >= nc of the last batch load row coll[0] and write
+// nothing.  Integer sums modulo 2^32: no order to pin.
+template <uint32_t G, typename Acc>
+__device__ __forceinline__ void hnsw_chunk_distances(const HnswArgs &a, const uint32_t *qw, const uint32_t *coll, float *cdist, uint32_t nc,
+                                                     int lane, Acc f) {
   static_assert(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "a row is taken by a power of two of lanes, at most 16");
   constexpr uint32_t ROWS = 64 / G;
   const uint32_t grp = (uint32_t)lane / G, sub = (uint32_t)lane % G;
@@ -54,10 +60,10 @@ __device__ __forceinline__ void hnsw_hamming_distances(const HnswArgs &a, const 
   u32x4 b0 = sub < nv ? row[sub] : zero;
   for (uint32_t g = 0; g < nc; g += ROWS) {
     uint32_t acc = 0;
-    if (sub < nv) acc = hnsw_popc4(b0, q4[sub], 0u);
+    if (sub < nv) acc = f.add(b0, q4[sub], 0u);
     if constexpr (G == 16) {
 #pragma unroll 4
-      for (uint32_t t = sub + 16; t < nv; t += 16) acc = hnsw_popc4(row[t], q4[t], acc);
+      for (uint32_t t = sub + 16; t < nv; t += 16) acc = f.add(row[t], q4[t], acc);
     }
     const uint32_t rcur = r;
     r += ROWS;
@@ -65,23 +71,29 @@ __device__ __forceinline__ void hnsw_hamming_distances(const HnswArgs &a, const 
     if (g + ROWS < nc) b0 = sub < nv ? row[sub] : zero;    // the next rows' first loads go out before the reduction below
 #pragma unroll
     for (uint32_t o = G >> 1; o >= 1; o >>= 1) acc += (uint32_t)__shfl_xor((int)acc, (int)o, (int)G);
-    if (sub == 0 && rcur < nc) cdist[rcur] = (float)acc;
+    if (sub == 0 && rcur < nc) cdist[rcur] = f.score(acc);
   }
   hnsw_sync(false);
 }
 
-// The scorer of the walk over binary rows (the contract of HnswDenseScorer, zvk_hnsw.hip.h) against the words at qw in LDS.  G
-// depends on the handle's dimension alone, so the switch is uniform over the wave and over the launch.
+// the lane split of a handle's row width, uniform over the wave and over the launch: G depends on a.dpad alone
+template <typename Acc>
+__device__ __forceinline__ void hnsw_chunk_distances_any(const HnswArgs &a, const uint32_t *qw, const uint32_t *coll, float *cdist, uint32_t nc,
+                                                         int lane, Acc f) {
+  switch (hnsw_hamming_lanes_log2(a.dpad)) {
+    case 0: hnsw_chunk_distances<1>(a, qw, coll, cdist, nc, lane, f); break;
+    case 1: hnsw_chunk_distances<2>(a, qw, coll, cdist, nc, lane, f); break;
+    case 2: hnsw_chunk_distances<4>(a, qw, coll, cdist, nc, lane, f); break;
+    case 3: hnsw_chunk_distances<8>(a, qw, coll, cdist, nc, lane, f); break;
+    default: hnsw_chunk_distances<16>(a, qw, coll, cdist, nc, lane, f); break;
+  }
+}
+
+// The scorer of the walk over binary rows (the contract of HnswDenseScorer, zvk_hnsw.hip.h) against the words at qw in LDS.
 struct HnswHammingScorer {
   const uint32_t *qw;
   __device__ __forceinline__ void operator()(const HnswArgs &a, const uint32_t *coll, float *cdist, uint32_t nc, int lane) const {
-    switch (hnsw_hamming_lanes_log2(a.dpad)) {
-      case 0: hnsw_hamming_distances<1>(a, qw, coll, cdist, nc, lane); break;
-      case 1: hnsw_hamming_distances<2>(a, qw, coll, cdist, nc, lane); break;
-      case 2: hnsw_hamming_distances<4>(a, qw, coll, cdist, nc, lane); break;
-      case 3: hnsw_hamming_distances<8>(a, qw, coll, cdist, nc, lane); break;
-      default: hnsw_hamming_distances<16>(a, qw, coll, cdist, nc, lane); break;
-    }
+    hnsw_chunk_distances_any(a, qw, coll, cdist, nc, lane, HnswPopcAcc());
   }
 };
 

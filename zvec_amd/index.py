@@ -44,7 +44,7 @@ def _dtype_of(dtype):
 
 
 def _row_words(dim, dt):
-    """row length in words of its numpy type: elements for fp rows, dim // 32 resp. dim // 64 words for bit rows"""
+    """row length in words of its numpy type: elements for fp and int8 rows, dim // 32 resp. dim // 64 words for bit rows"""
     return int(dim) // 32 if dt == DT_BINARY32 else int(dim) // 64 if dt == DT_BINARY64 else int(dim)
 
 
@@ -348,6 +348,31 @@ class IndexContext:
         _lib.check(_lib.lib().zvec_hip_binary_encode(self._h, _np_ptr(rows), count, dim, int(dim if encode_dims is None else encode_dims),
                                                      float(threshold), _np_ptr(out)), "zvec_hip_binary_encode")
         return out
+
+    def int8_encode_dev(self, d_in, count, dim, d_out, scale=None, bias=0.0, per_row=False, d_factors=None, stream=None):
+        """Int8QuantizerReformer on fp32 rows already in HBM (device pointers): [count][dim] fp32 -> [count][dim] int8, as int8_encode
+        below; d_factors (per_row only): [count] fp32 or None.  Only enqueues."""
+        mode = _lib.INT8_PER_ROW if per_row else _lib.INT8_SCALE_BIAS
+        _lib.check(_lib.lib().zvec_hip_int8_encode_dev(self._h, C.c_void_p(d_in), int(count), int(dim), mode, float(scale or 0.0), float(bias),
+                                                       C.c_void_p(d_out), C.c_void_p(d_factors or 0), C.c_void_p(stream or 0)),
+                   "zvec_hip_int8_encode_dev")
+
+    def int8_encode(self, rows, scale=None, bias=0.0, per_row=False):
+        """host rows ([count][dim], anything numpy turns into fp32) -> int8 [count][dim] (zvec_hip_int8_encode).  With scale (> 0) and
+        bias: round(clamp((v + bias) * scale, -127, 127)), what the reference's int8 converter does under SquaredEuclidean.  With
+        per_row=True: its inner-product query transform, round(v * (127 / max|v| of the row)); returns (int8 rows, factors), factors
+        fp32 [count] = max|v| / 127.  Halves round away from zero."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2:
+            raise ValueError("zvec_amd: int8_encode takes [count][dim] rows")
+        if not per_row and scale is None:
+            raise ValueError("zvec_amd: int8_encode takes a scale, or per_row=True")
+        count, dim = rows.shape
+        out = np.zeros((count, dim), np.int8)
+        fac = np.zeros(count, np.float32) if per_row else None
+        _lib.check(_lib.lib().zvec_hip_int8_encode(self._h, _np_ptr(rows), count, dim, _lib.INT8_PER_ROW if per_row else _lib.INT8_SCALE_BIAS,
+                                                   float(scale or 0.0), float(bias), _np_ptr(out), _np_ptr(fac)), "zvec_hip_int8_encode")
+        return (out, fac) if per_row else out
 
     def synchronize(self):
         _lib.check(_lib.lib().zvec_hip_ctx_synchronize(self._h), "zvec_hip_ctx_synchronize")
@@ -1836,18 +1861,23 @@ class HipHnswSearcher:
     HipHammingIVFSearcher, scores are (float) popcount(row ^ query).  The graph is loaded as plain arrays, or built from rows
     (build).  dtype="fp16" (zvec_hip_hnsw_create_typed): rows and queries are stored and passed as IEEE binary16; load / build / add /
     search take float16 arrays as they are and round float32 arrays to nearest even (astype(float16), what HalfFloatConverter does);
-    the _dev variants take raw pointers to halves; get_vectors_by_ids returns float16.  Scores are fp32."""
+    the _dev variants take raw pointers to halves; get_vectors_by_ids returns float16.  Scores are fp32.  dtype="int8" (or np.int8;
+    zvec_hip_hnsw_create_typed): dim is a multiple of 4, rows and queries are taken and returned as np.int8 arrays (int8_encode makes
+    them from fp32), the _dev variants take raw pointers to int8; scores are the exact integer sums as fp32."""
 
     def __init__(self, dim, metric="SquaredEuclidean", device=0, dtype="fp32"):
         self.dim = int(dim)
         self.metric = metric_from_name(metric) if isinstance(metric, str) else int(metric)
         self.device = device
-        self.dtype, self.np_dtype = _dtype_of(dtype)
+        if isinstance(dtype, (str, type, np.dtype)) and dtype in ("int8", np.int8):
+            self.dtype, self.np_dtype = _lib.DT_INT8, np.int8        # (this handle alone takes int8: _dtype_of does not know it)
+        else:
+            self.dtype, self.np_dtype = _dtype_of(dtype)
         self._h = C.c_void_p()
         if self.dtype in (DT_BINARY32, DT_BINARY64) and self.metric == METRIC_HAMMING:
             _lib.check(_lib.lib().zvec_hip_hnsw_create_binary(self.dim, self.dtype, device, C.byref(self._h)), "zvec_hip_hnsw_create_binary")
             return
-        create = "zvec_hip_hnsw_create_typed" if self.dtype == DT_FP16 else "zvec_hip_hnsw_create"
+        create = "zvec_hip_hnsw_create_typed" if self.dtype in (DT_FP16, _lib.DT_INT8) else "zvec_hip_hnsw_create"
         _lib.check(getattr(_lib.lib(), create)(self.dim, self.dtype, self.metric, device, C.byref(self._h)), create)
 
     @property
@@ -2247,6 +2277,12 @@ def hnsw_levels(n, scaling_factor, seed=0):
     _lib.check(_lib.lib().zvec_hip_hnsw_build_levels(int(n), int(scaling_factor), int(seed) & 0xffffffffffffffff, _np_ptr(out)),
                "zvec_hip_hnsw_build_levels")
     return out
+
+
+def int8_encode(x, scale=None, bias=0.0, per_row=False, device=0):
+    """fp32 rows -> the int8 rows of HipHnswSearcher(dtype="int8") on the device, through a context of its own
+    (IndexContext.int8_encode): int8_encode(x, scale=s, bias=b), or int8_encode(x, per_row=True) -> (rows, factors)"""
+    return IndexContext(device).int8_encode(x, scale, bias, per_row)
 
 
 def container_segments(image, checksum=False):
